@@ -11,7 +11,13 @@ KKT dim N = n + 2*mi + me = 32768.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29511 bench.py --gpus 8 --steps 3 --warmup 1
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (k_update<128>, the fp64-MFMA
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the --steps steps and prints the line (with
+--dump-outputs DIR it first writes the last timed step's direction there); --full adds what takes work of its own: the
+backward-error check, the measured MFMA peak and shader clock, the other BASELINE.json configurations and the CPU baseline.
+
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full
+
+`roofline` is for the dominant kernel (k_update<128>, the fp64-MFMA
 trailing update): algorithmic flops (sum over launches of 2*nb*#lower-triangle entries updated)
 divided by the summed HIP-event durations of those launches, against the 78.6 TFLOP/s fp64 matrix
 peak.  `cpu_baseline` times the oracle (the reference's CPU path restated) on this box's host cores
@@ -75,10 +81,13 @@ def cpu_baseline(target_N=32768, eig_shape=(4096, 1024, 1536), lu_probe_shape=(6
     from pyipm_amd.problems import make_qp
     import scipy.linalg
     ncpu = os.cpu_count() or 1
-    blas, limits = "unknown", None
+    blas, limits, pool = "unknown", None, ncpu
     try:
         from threadpoolctl import threadpool_info, threadpool_limits as limits
         blas = ";".join(sorted(set("%s %s" % (i.get("internal_api"), i.get("version")) for i in threadpool_info())))
+        # the BLAS thread pool as the process started it (OMP_NUM_THREADS / the CPUs it may use): OpenBLAS cannot grow its
+        # pool afterwards -- asking for more threads than it holds crashes it -- so the sweep stays inside it
+        pool = max([int(i.get("num_threads") or 1) for i in threadpool_info() if i.get("user_api") == "blas"] or [ncpu])
     except Exception:
         pass
     cpu_model = "unknown"
@@ -101,7 +110,7 @@ def cpu_baseline(target_N=32768, eig_shape=(4096, 1024, 1536), lu_probe_shape=(6
         def __enter__(self): return self
         def __exit__(self, *a): return False
     lim = limits if limits is not None else _nolimit
-    cands = sorted(set(t for t in (8, 16, 32, 64, 128, ncpu) if 1 <= t <= ncpu))
+    cands = sorted(set(t for t in (8, 16, 32, 64, 128, ncpu, pool) if 1 <= t <= min(ncpu, pool)))
     rng = np.random.default_rng(0)
     Mx = rng.standard_normal((6144, 6144))
     sweep = {}
@@ -387,11 +396,11 @@ def main():
     ap.add_argument("--config4", choices=("auto", "on", "off"), default="auto",
                     help="after the timed region also time BASELINE.json's config 4 (n=65536, mi=32768 -> N=131072; 1 warm-up + 2 "
                          "steps) on the same GPUs and attach it as `config4`: the >= 5x-at-8-GPUs target is stated on THAT size, so "
-                         "every 1-GPU and N-GPU line carries its leg of it.  auto = only with the default headline workload")
+                         "every 1-GPU and N-GPU line carries its leg of it.  auto = only with --full and the default headline workload")
     ap.add_argument("--configs", choices=("auto", "on", "off"), default="auto",
                     help="after the timed region also time BASELINE.json's configs 2, 3 and 5 (n=2048/mi=2048; n=16384/me=mi=8192; 512 "
                          "batched n=256 QPs) on one GPU and attach them as `config2` / `config3` / `config5`.  auto = only with the "
-                         "default headline workload on one GPU")
+                         "default headline workload on one GPU and --full")
     ap.add_argument("--no-clock", action="store_true",
                     help="skip the extra step that measures the shader clock of the update kernel (counter-collection runs: the "
                          "traced process then holds exactly warmup + steps steps)")
@@ -402,6 +411,15 @@ def main():
                     help="after the timed region also run and report (a) the all-dense factorisation (skip_zeros=0) with a "
                          "bitwise check of the direction and (b) one L-BFGS search direction (SURVEY 8f rank 4).  Off by "
                          "default so that a kernel trace of the default command holds the headline workload only")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure also run what takes work of its own: the backward-error check of the last "
+                         "timed step, the measured MFMA peak and shader clock, the other BASELINE.json configurations (--configs / "
+                         "--config4 auto) and the CPU baseline (unless --no-cpu-baseline).  Off: the run sets up, warms up, times "
+                         "--steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed to DIR (rank 0): dz.npy, the direction (float64; "
+                         "above %d entries a fixed seeded sample of them, their positions in dz_index.npy), and factor_stats.npy "
+                         "(float64: %s)" % (DUMP_MAX_ENTRIES, ", ".join(STATS_ORDER)))
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -550,6 +568,8 @@ def main():
                 dist_ms[k] = dist_ms.get(k, 0.0) + v
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dz, st)
     wd.watch("backward-error check / reductions after the timed region", 600)
     if use_dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if share_gpu else device)
@@ -558,21 +578,23 @@ def main():
 
     # correctness of the timed steps' direction, outside the timed region: |Hc dz - g| / |g| with Hc applied from the KKT
     # blocks (never from the factor); dz is the last timed step's output with the flip undone.  (All ranks take part.)
-    raw = dz.clone()
-    if me + mi:
-        raw[n + mi:] *= -1.0
-    if world > 1:
-        g_res = core.residual_dist()
-        berr = float((core.matvec_dist(raw) - g_res).norm() / g_res.norm())
-    else:
-        g_res = core.residual()
-        berr = float((core.matvec(raw) - g_res).norm() / g_res.norm())
+    raw = g_res = berr = None
+    if args.full:
+        raw = dz.clone()
+        if me + mi:
+            raw[n + mi:] *= -1.0
+        if world > 1:
+            g_res = core.residual_dist()
+            berr = float((core.matvec_dist(raw) - g_res).norm() / g_res.norm())
+        else:
+            g_res = core.residual()
+            berr = float((core.matvec(raw) - g_res).norm() / g_res.norm())
 
     # The shader clock the bulk update actually runs at (round 4): one more step with the update kernel's per-block stamps on
     # (diagnostics buffer: 100 MHz wall clock and shader cycle counter around each block's main loop).  78.6 TFLOP/s is 256 CUs x
     # 128 flop/clk at 2.4 GHz; under this load the part clocks lower, and cycles / time says by how much.
     clock = None
-    if world == 1 and not use_dist and not condensed and not args.no_clock:
+    if args.full and world == 1 and not use_dist and not condensed and not args.no_clock:
         try:
             nrec = (core.Npad // 128) ** 2 + 4096
             tl = torch.zeros(nrec * 8, dtype=torch.int64, device=device)
@@ -625,10 +647,12 @@ def main():
                     "algorithmic_bytes_per_kflop": (v["area"] / v["flops"] * 1e3) if (ok and v["flops"]) else None}
         dobj, oobj = inst_obj(dom), inst_obj(oth)
         ach = dobj["achieved"]
-        try:
-            peak_meas = mfma_f64_peak(local_rank, 20000)
-        except Exception:
-            peak_meas = None
+        peak_meas = None
+        if args.full:
+            try:
+                peak_meas = mfma_f64_peak(local_rank, 20000)
+            except Exception:
+                peak_meas = None
         out = {
             "metric": "newton_steps_per_sec", "value": K / elapsed, "unit": "steps/s", "n_gpus": world,
             "rccl_ranks": rccl_ranks,
@@ -750,13 +774,14 @@ def main():
                                                       "`value` skips tiles the KKT block pattern makes exact zeros"}
         if args.extras and world == 1 and not use_dist:
             out["lbfgs_direction"] = lbfgs_block(device)
-        out["backward_error"] = berr
-        out["backward_error_note"] = "|Hc dz - g|/|g| of the last timed step, Hc from the staged blocks (pyipm_newton_kkt_matvec)"
+        if args.full:
+            out["backward_error"] = berr
+            out["backward_error_note"] = "|Hc dz - g|/|g| of the last timed step, Hc from the staged blocks (pyipm_newton_kkt_matvec)"
 
     # ---- the other BASELINE.json configurations, outside the timed region of `value` ------------------------------------
     default_workload = (n, me, mi) == (16384, 4096, 6144) and not args.opt and not args.force_dist and not args.python_driver
-    want_c4 = args.config4 == "on" or (args.config4 == "auto" and default_workload)
-    want_legs = args.configs == "on" or (args.configs == "auto" and default_workload and world == 1)
+    want_c4 = args.config4 == "on" or (args.config4 == "auto" and args.full and default_workload)
+    want_legs = args.configs == "on" or (args.configs == "auto" and args.full and default_workload and world == 1)
     if want_c4 or want_legs:
         core.close()
         one_step = None                                      # (the closure holds the handle and its workspace)
@@ -775,7 +800,7 @@ def main():
             out["config4"] = c4
     if rank == 0:
         wd.watch("cpu baseline", 1800)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(target_N=N, target_shape=(n, me, mi))
         wd.clear()
         sys.stdout.flush()
@@ -785,6 +810,23 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     wd.done = True
+
+
+STATS_ORDER = ("n_neg", "n_zero", "n_2x2", "n_pos", "d_min", "d_max", "growth", "nonfinite")
+DUMP_MAX_ENTRIES = 1 << 22          # 32 MB of float64 direction at most
+
+
+def dump_outputs(out_dir, dz, st):
+    """--dump-outputs: the last timed step's result as a caller receives it -- the direction dz and the factorisation's
+    statistics -- as .npy files.  A direction longer than DUMP_MAX_ENTRIES is sampled at fixed seeded positions."""
+    os.makedirs(out_dir, exist_ok=True)
+    v = dz.detach().cpu().numpy().astype(np.float64)
+    if v.size > DUMP_MAX_ENTRIES:
+        idx = np.sort(np.random.default_rng(0).choice(v.size, DUMP_MAX_ENTRIES, replace=False))
+        np.save(os.path.join(out_dir, "dz_index.npy"), idx.astype(np.float64))
+        v = v[idx]
+    np.save(os.path.join(out_dir, "dz.npy"), v)
+    np.save(os.path.join(out_dir, "factor_stats.npy"), np.array([float(st.get(k, np.nan)) for k in STATS_ORDER], dtype=np.float64))
 
 
 def default_panel_width(world, kkt_dim):

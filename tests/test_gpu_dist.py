@@ -337,7 +337,7 @@ def test_bench_multi_rank_path_on_one_gpu():
     env = dict(os.environ, PYIPM_BENCH_SHARE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--nvar", "1536", "--neq", "256", "--nineq", "640", "--nb", "256", "--no-cpu-baseline"]
+           "--nvar", "1536", "--neq", "256", "--nineq", "640", "--nb", "256", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -430,7 +430,7 @@ def test_bench_self_launches_for_several_gpus():
     # (nb = 1024, the multi-GPU default from KKT dimension 65536 on -- five panels here, the last one 640 wide, each factored as a
     # block of sub-panels; below that size bench.py takes nb = 256: tools/rank_replay.py)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--nvar", "2560", "--neq", "384", "--nineq", "896", "--nb", "1024", "--no-cpu-baseline"]
+           "--nvar", "2560", "--neq", "384", "--nineq", "896", "--nb", "1024", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -4,7 +4,7 @@ set -u
 O=gpurun_out/r02z; mkdir -p $O
 ( timeout 2400 python -m pytest tests -m gpu -q --durations=5 > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log )
 tail -5 $O/pytest.log
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -c 600 $O/bench_default.json
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -c 600 $O/bench_default.json
 timeout 900 python bench.py --no-cpu-baseline --steps 5 --warmup 2 > $O/bench.json 2> $O/bench.err
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp

@@ -6,7 +6,7 @@ set -u
 TAG=$1; shift
 O=gpurun_out/$TAG; mkdir -p $O
 cd "$(dirname "$0")/.."
-B="timeout 600 python bench.py --no-cpu-baseline --config4 off --steps ${STEPS:-6} --warmup 2 ${EXTRA:-}"
+B="timeout 600 python bench.py --full --no-cpu-baseline --config4 off --steps ${STEPS:-6} --warmup 2 ${EXTRA:-}"
 for rep in $(seq 1 ${REPS:-3}); do
   i=0
   for o in "$@"; do

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
 ( timeout 3000 python -m pytest tests -m gpu -q --durations=5 > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log )
 tail -5 $O/pytest.log
-timeout 1200 python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -c 300 $O/bench_default.json
+timeout 1200 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -c 300 $O/bench_default.json
 timeout 900 python bench.py --no-cpu-baseline --config4 off --steps 5 --warmup 2 > $O/bench.json 2> $O/bench.err
 # kernel trace + stats of the headline workload (the default command without its config-4 leg and CPU leg)
 kstats() {   # name, bench args...

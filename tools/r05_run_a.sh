@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
 ( timeout 1500 python -m pytest tests/test_gpu_batched.py tests/test_gpu_pivoting.py tests/test_gpu_ipm.py tests/test_gpu_merit.py tests/test_gpu_qp.py -m gpu -q -x --durations=5 > $O/pytest_a.log 2>&1; echo "pytest rc=$?" >> $O/pytest_a.log )
 tail -15 $O/pytest_a.log
-timeout 1500 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"; tail -c 600 $O/bench_default.err
+timeout 1500 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"; tail -c 600 $O/bench_default.err
 python - <<'PY'
 import json
 d = json.load(open("gpurun_out/r05a/bench_default.json"))
