@@ -144,6 +144,28 @@ int pyipm_newton_solve(pyipm_newton_ctx* ctx, const double* rhs, double* dz, int
  * first step, out[2] = after the last, out[3] = 1 when the adaptive loop met its target (out[1..2] = -1 for a
  * fixed-count solve, which does not measure). */
 int pyipm_newton_solve_info(pyipm_newton_ctx* ctx, double out[4]);
+/* sym_solve_cmp with a matrix right-hand side (pyipm.py:18-20, 911-914): k systems against the factor of the last
+ * factor().  rhs: k vectors of N doubles, vector j at rhs + j*ld_rhs (ld_rhs >= N); dz likewise at ld_dz (entries N ..
+ * ld_dz-1 of each column are not written).  flip / refine / memkind as in pyipm_newton_solve, column by column.
+ *   Valid: a single-rank handle with a factor (full or condensed) -- after factor() and before the next assemble().
+ *   PYIPM_E_BADARG: world > 1, provider-only and batched handles, ld_rhs or ld_dz < N, no factor yet, k < 0.
+ *   k == 0 returns 0 and does nothing.
+ *   Column j of dz solves Hc x = rhs_j, flip applied to rows n+mi .. N-1 as in solve.  With refine >= 0 it is bit for bit
+ *   independent of k and of the other columns (rhs_j alone or at any position of any batch gives the same bits; no
+ *   atomics, fixed partitions) and equal to rounding -- not to the bit -- to pyipm_newton_solve of that column.  With
+ *   refine < 0 the step count follows the worst column of the batch, so a column's bits depend on the others (a NaN
+ *   column ends the refinement of all); two identical calls still give identical bits.
+ *   refine > 0: that many steps R = B - Hc X; X += solve_many(R), Hc from the staged blocks.  refine < 0: adaptive, stops
+ *   when EVERY column meets "refine_target", after "refine_max" steps or when the worst column gains less than 4x;
+ *   pyipm_newton_solve_info then reports the step count and the worst column's backward errors.  A condensed factor
+ *   takes at least "condensed_refine" steps, as solve does.
+ *   The call leaves the factor, the kept residual, the direction of the last solve()/step() (step_lengths / merit_info /
+ *   merit_ray with dz = NULL) and a pending fused forward pass alone: solve() after it returns the bits it would without it.
+ *   Asynchronous on the handle's stream for device outputs; synchronises for PYIPM_MEM_HOST, host inputs are staged.
+ *   Working memory for the column blocks is allocated by the library on first use and grown on demand (not part of
+ *   pyipm_newton_workspace_bytes). */
+int pyipm_newton_solve_many(pyipm_newton_ctx* ctx, int64_t k, const double* rhs, int64_t ld_rhs,
+                            double* dz, int64_t ld_dz, int flip, int refine, int memkind);
 /* Restates the quantity reghess tests (pyipm.py:1379-1381: rcond = min|w| / max|w| over the eigenvalues w of Hc, "singular"
  * when rcond <= eps) without the eigendecomposition: it_pow power iterations on Hc applied from the blocks give max|w|,
  * it_inv inverse iterations through the factor (one substitution sweep each) give min|w| (0 = defaults 6 / 3; negative =

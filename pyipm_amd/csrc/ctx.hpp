@@ -158,6 +158,8 @@ struct Ctx {
     int sweep_persist = 1;                // single rank, one right-hand side: the backward sweep as ONE device-driven launch (k_bwd_sweep)
     int64_t sweep_buf_n = 0;              // ... (allocated for this many rows)
     double* sweep_buf = nullptr;          // ... the near sums as the column owners hand them to workgroup 0 (Npad doubles, NaN = not there yet)
+    double* ms_buf = nullptr;             // solve_many: its column blocks, partials and refinement vectors (lazily hipMalloc'd, grown on demand)
+    size_t ms_buf_bytes = 0;
     unsigned* sweep_sync = nullptr;       // ... its flags and counters (3 npanels + 1 words, zeroed before every sweep)
     bool sweep_used = false;              // ... a sweep ran since the error word was last read (solve_info / factor_end look at it)
     int dist_head_split = 1;              // per-panel schedule: the owner's head in two launches -- the next panel's diagonal block (its chain waits for

@@ -7,6 +7,7 @@
 #include "kernels_panel.hpp"
 #include "kernels_chain.hpp"
 #include "kernels_solve.hpp"
+#include "kernels_msolve.hpp"
 #include "kernels_batched.hpp"
 #include "kernels_merit.hpp"
 
@@ -1355,6 +1356,170 @@ int solve_inplace(Ctx* ctx, double* v, bool forward_done) {
     return cond_expand(ctx, ctx->vc, v);
 }
 
+// ---- many right-hand sides: pyipm_newton_solve_many (kernels_msolve.hpp) --------------------------------------------
+// V := M^{-1} V in place for kpad columns at stride ldv (the current geometry's Npad), kpad a multiple of MS_KB, single
+// rank: the per-panel structure of solve_plain (wide_sub sub-panels, active_ranges) with every GEMV a product over
+// column blocks.  part: >= (ceil(Npad / MS_RCH) + 1) * kpad * MS_SUBW doubles (the partials, then their sums).
+int solve_many_plain(Ctx* ctx, double* V, int64_t ldv, int64_t kpad, double* part) {
+    const Geo& g = ctx->g;
+    const hipStream_t st = ctx->stream;
+    auto sub_width = [&](int pw) {                        // wide_sub as in fwd_panel, and never above MS_SUBW (the in-panel kernels' limit)
+        const int sw = (ctx->wide_sub >= TB && ctx->wide_sub % TB == 0 && pw > ctx->wide_sub) ? ctx->wide_sub : pw;
+        return sw > MS_SUBW ? MS_SUBW : sw;
+    };
+    for (int64_t p = 0; p < g.npanels; ++p) {
+        const int pw = (int)g.panel_w(p), sw = sub_width(pw);
+        for (int off = 0; off < pw; off += sw) {
+            const int64_t c0 = g.panel_c0(p) + off, lc0 = g.local_c0(p) + off;
+            const int nbw = pw - off < sw ? pw - off : sw;
+            hipLaunchKernelGGL(k_ms_fwd_diag, dim3((unsigned)(kpad / MS_CW)), dim3(512), 0, st,
+                               ctx->A, g.Npad, lc0, c0, nbw, V, ldv);
+            PYIPM_KCHECK();
+            const int64_t below = g.Npad - (c0 + nbw);
+            if (below > 0) {
+                int64_t a0, a1, b0, b1;
+                active_ranges(ctx, c0, c0 + nbw, &a0, &a1, &b0, &b1);
+                hipLaunchKernelGGL(k_ms_fwd_gemm, dim3((unsigned)(kpad / MS_KB), (unsigned)(below / TB)), dim3(256), 0, st,
+                                   ctx->A, g.Npad, lc0, c0, nbw, c0 + nbw, V, ldv, a0, a1, b0, b1);
+                PYIPM_KCHECK();
+            }
+        }
+    }
+    hipLaunchKernelGGL(k_ms_diag, dim3((unsigned)(kpad / MS_CW), (unsigned)(g.Npad / TB)), dim3(256), 0, st, ctx->Dinv, ctx->Tsv,
+                       ctx->Tflag, ctx->block_refine, V, ldv);
+    PYIPM_KCHECK();
+    for (int64_t p = g.npanels - 1; p >= 0; --p) {
+        const int pw = (int)g.panel_w(p), sw = sub_width(pw);
+        for (int off = ((pw - 1) / sw) * sw; off >= 0; off -= sw) {
+            const int64_t c0 = g.panel_c0(p) + off, lc0 = g.local_c0(p) + off;
+            const int nbw = pw - off < sw ? pw - off : sw;
+            const int64_t below = g.Npad - (c0 + nbw);
+            const double* sums = nullptr;
+            if (below > 0) {
+                const int nchunk = (int)((below + MS_RCH - 1) / MS_RCH);
+                int64_t a0, a1, b0, b1;
+                active_ranges(ctx, c0, c0 + nbw, &a0, &a1, &b0, &b1);
+                hipLaunchKernelGGL(k_ms_bwd_part, dim3((unsigned)(kpad / MS_KB), (unsigned)(nbw / TB), (unsigned)nchunk), dim3(256), 0, st,
+                                   ctx->A, g.Npad, lc0, nbw, c0 + nbw, g.Npad, V, ldv, part, kpad, a0, a1, b0, b1);
+                PYIPM_KCHECK();
+                const int64_t nelem = kpad * nbw;
+                double* red = part + (size_t)nchunk * (size_t)nelem;
+                hipLaunchKernelGGL(k_ms_bwd_reduce, dim3((unsigned)(nelem / 64)), dim3(256), 0, st, part, nchunk, nelem, red);
+                PYIPM_KCHECK();
+                sums = red;
+            }
+            hipLaunchKernelGGL(k_ms_bwd_diag, dim3((unsigned)(kpad / MS_CW)), dim3(512), 0, st,
+                               ctx->A, g.Npad, lc0, c0, nbw, sums, V, ldv);
+            PYIPM_KCHECK();
+        }
+    }
+    return 0;
+}
+
+// X := Hc^{-1} X for full-order columns (ld = Npad; k real columns, the rest of kpad zero).  With the condensed factor the
+// columns are reduced into Xc (ld = gc.Npad) one by one, solved together, expanded one by one (cond_reduce / cond_expand
+// are O(N) per column apart from the Ji products).
+int solve_many_inplace(Ctx* ctx, double* X, int64_t k, int64_t kpad, double* part, double* Xc) {
+    const Geo& g = ctx->g;
+    if (!ctx->cond_active) return solve_many_plain(ctx, X, g.Npad, kpad, part);
+    const int64_t ldc = ctx->gc.Npad;
+    int rc;
+    if (kpad > k) PYIPM_HIP(hipMemsetAsync(Xc + k * ldc, 0, (size_t)((kpad - k) * ldc) * sizeof(double), ctx->stream));
+    for (int64_t j = 0; j < k; ++j) { rc = cond_reduce(ctx, X + j * g.Npad, Xc + j * ldc); if (rc) return rc; }
+    { GeoSwap sw(ctx, ctx->gc); rc = solve_many_plain(ctx, Xc, ldc, kpad, part); }
+    if (rc) return rc;
+    for (int64_t j = 0; j < k; ++j) { rc = cond_expand(ctx, Xc + j * ldc, X + j * g.Npad); if (rc) return rc; }
+    return 0;
+}
+
+// The whole call after argument checks: stage, solve, refine, flip, copy out.  Every vector lives in ctx->ms_buf: v0 - v3,
+// vc, the kept residual and the factor are not touched, so a pending fused forward pass and the last direction survive.
+int solve_many(Ctx* ctx, int64_t k, const double* rhs, int64_t ld_rhs, double* dz, int64_t ld_dz, int flip, int refine,
+               int memkind) {
+    const Geo& g = ctx->g;
+    const hipStream_t st = ctx->stream;
+    if (ctx->cond_active && refine >= 0 && refine < ctx->cond_min_refine) refine = ctx->cond_min_refine;
+    const bool adaptive = refine < 0;
+    const int64_t kpad = (k + MS_KB - 1) / MS_KB * MS_KB, Np = g.Npad, Nc = ctx->cond_active ? ctx->gc.Npad : 0;
+    const size_t col = (size_t)Np * (size_t)kpad;
+    const size_t n_part = (size_t)((Np + MS_RCH - 1) / MS_RCH + 1) * (size_t)kpad * (size_t)MS_SUBW;   // partials + their sums
+    size_t need = col + (size_t)Nc * (size_t)kpad + n_part;                    // X, Xc, partials
+    if (refine != 0) need += 2 * col;                                           // B, R
+    if (adaptive) need += col + 2 * (size_t)kpad;                               // the spare iterate, per-column sums
+    if (ctx->ms_buf_bytes < need * sizeof(double)) {
+        if (ctx->ms_buf) { PYIPM_HIP(hipStreamSynchronize(st)); PYIPM_HIP(hipFree(ctx->ms_buf)); ctx->ms_buf = nullptr; ctx->ms_buf_bytes = 0; }
+        PYIPM_HIP(hipMalloc((void**)&ctx->ms_buf, need * sizeof(double)));
+        ctx->ms_buf_bytes = need * sizeof(double);
+        if (getenv("PYIPM_POISON_WORKSPACE")) PYIPM_HIP(hipMemsetAsync(ctx->ms_buf, 0xFF, ctx->ms_buf_bytes, st));   // as the workspace
+    }
+    double* X = ctx->ms_buf;
+    double* Xc = X + col;
+    double* part = Xc + (size_t)Nc * (size_t)kpad;
+    double* B = part + n_part;
+    double* R = B + col;
+    double* Xp = R + col;
+    double* ss_dev = Xp + col;
+    // right-hand sides into X: rows N .. Npad and columns k .. kpad zero
+    PYIPM_HIP(hipMemcpy2DAsync(X, (size_t)Np * sizeof(double), rhs, (size_t)ld_rhs * sizeof(double), (size_t)g.N * sizeof(double),
+                               (size_t)k, memkind == PYIPM_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
+    if (Np > g.N) PYIPM_HIP(hipMemset2DAsync(X + g.N, (size_t)Np * sizeof(double), 0, (size_t)(Np - g.N) * sizeof(double), (size_t)k, st));
+    if (kpad > k) PYIPM_HIP(hipMemsetAsync(X + k * Np, 0, (size_t)((kpad - k) * Np) * sizeof(double), st));
+    if (memkind == PYIPM_MEM_HOST) PYIPM_HIP(hipStreamSynchronize(st));      // host memory not retained
+    if (refine != 0) {
+        PYIPM_HIP(hipMemcpyAsync(B, X, col * sizeof(double), hipMemcpyDeviceToDevice, st));
+        PYIPM_HIP(hipMemsetAsync(R, 0, col * sizeof(double), st));             // (its pad columns stay zero)
+    }
+    int rc = solve_many_inplace(ctx, X, k, kpad, part, Xc); if (rc) return rc;
+    // refinement as in solve_finish, column by column for the product, all columns at once for the solve; the adaptive
+    // loop follows the WORST column's backward error
+    ctx->info_steps = 0; ctx->info_converged = 0; ctx->info_berr0 = -1.0; ctx->info_berr = -1.0;
+    const int maxit = adaptive ? ctx->refine_max : refine;
+    std::vector<double> ss(adaptive ? 2 * (size_t)k : 0);
+    double prev = -1.0;
+    for (int it = 0; it <= maxit; ++it) {
+        if (!adaptive && it == maxit) break;
+        for (int64_t j = 0; j < k; ++j) { rc = kkt_matvec_dev(ctx, X + j * Np, R + j * Np); if (rc) return rc; }
+        hipLaunchKernelGGL(k_axpby, grid1((int64_t)col), dim3(256), 0, st, R, B, R, 1.0, -1.0, (int64_t)col);
+        PYIPM_KCHECK();
+        if (adaptive) {
+            hipLaunchKernelGGL(k_ms_sumsq2, dim3((unsigned)k), dim3(1024), 0, st, ss_dev, R, B, Np, g.N);
+            PYIPM_KCHECK();
+            PYIPM_HIP(hipMemcpyAsync(ss.data(), ss_dev, 2 * (size_t)k * sizeof(double), hipMemcpyDeviceToHost, st));
+            PYIPM_HIP(hipStreamSynchronize(st));
+            double berr = 0.0;
+            for (int64_t j = 0; j < k; ++j) {
+                const double b = ss[2 * j + 1] > 0.0 ? sqrt(ss[2 * j] / ss[2 * j + 1]) : sqrt(ss[2 * j]);
+                if (!(b <= berr) && berr == berr) berr = b;                        // (a NaN column makes the worst NaN)
+            }
+            if (it == 0) ctx->info_berr0 = berr;
+            ctx->info_berr = berr;
+            if (prev >= 0.0 && !(berr <= prev)) {                                 // the last step made it worse (or NaN): take it back
+                PYIPM_HIP(hipMemcpyAsync(X, Xp, col * sizeof(double), hipMemcpyDeviceToDevice, st));
+                ctx->info_berr = prev; ctx->info_steps = it - 1;
+                break;
+            }
+            if (!(berr <= 1.0e300)) break;                                        // NaN / Inf: nothing to refine
+            if (berr <= ctx->refine_target) { ctx->info_converged = 1; break; }
+            if (it == maxit || (prev >= 0.0 && berr > 0.25 * prev)) break;        // out of budget / stagnating
+            prev = berr;
+            PYIPM_HIP(hipMemcpyAsync(Xp, X, col * sizeof(double), hipMemcpyDeviceToDevice, st));
+        }
+        rc = solve_many_inplace(ctx, R, k, kpad, part, Xc); if (rc) return rc;
+        hipLaunchKernelGGL(k_axpby, grid1((int64_t)col), dim3(256), 0, st, X, X, R, 1.0, 1.0, (int64_t)col);
+        PYIPM_KCHECK();
+        ctx->info_steps = it + 1;
+    }
+    const int64_t from = g.n + g.mi;
+    if (flip && g.N > from) {
+        hipLaunchKernelGGL(k_ms_flip, grid1((g.N - from) * k), dim3(256), 0, st, X, Np, from, g.N, k);
+        PYIPM_KCHECK();
+    }
+    PYIPM_HIP(hipMemcpy2DAsync(dz, (size_t)ld_dz * sizeof(double), X, (size_t)Np * sizeof(double), (size_t)g.N * sizeof(double),
+                               (size_t)k, memkind == PYIPM_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+    if (memkind == PYIPM_MEM_HOST) PYIPM_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
 // y = Hc v from the staged blocks (Npad vectors on the device).  With several ranks every rank adds the terms of the
 // KKT columns it owns (row j of triu(d2L) | Je | Ji is column j of the lower triangle), rank 0 the element-wise s /
 // multiplier part; the caller sums y over the ranks (dist_impl.hpp).
@@ -2241,6 +2406,7 @@ int pyipm_newton_destroy(pyipm_newton_ctx* h) try {
     if (ctx->sweep_sync) hipFree(ctx->sweep_sync);
     if (ctx->chain_sync) hipFree(ctx->chain_sync);
     if (ctx->sweep_buf) hipFree(ctx->sweep_buf);
+    if (ctx->ms_buf) hipFree(ctx->ms_buf);
     if (ctx->merit_buf) hipFree(ctx->merit_buf);
     if (ctx->rc_warm[0]) hipFree(ctx->rc_warm[0]);
     if (ctx->ray_buf) hipFree(ctx->ray_buf);
@@ -2460,6 +2626,23 @@ int pyipm_newton_solve_info(pyipm_newton_ctx* h, double out[4]) try {
     Ctx* ctx = C(h);
     out[0] = (double)ctx->info_steps; out[1] = ctx->info_berr0; out[2] = ctx->info_berr; out[3] = (double)ctx->info_converged;
     return PYIPM_OK;
+} PYIPM_CATCH_H(h)
+
+int pyipm_newton_solve_many(pyipm_newton_ctx* h, int64_t k, const double* rhs, int64_t ld_rhs, double* dz, int64_t ld_dz,
+                            int flip, int refine, int memkind) try {
+    if (check_ctx(h)) return PYIPM_E_BADARG;
+    Ctx* ctx = C(h); const Geo& g = ctx->g;
+    if (ctx->batched) return single_only(ctx);
+    if (ctx->provider_only) { ctx->err = "solve_many: a provider-only handle has no factor"; return PYIPM_E_BADARG; }
+    if (g.world != 1) { ctx->err = "solve_many(): single-rank entry point"; return PYIPM_E_BADARG; }
+    if (k < 0) { ctx->err = "solve_many: k < 0"; return PYIPM_E_BADARG; }
+    if (k == 0) return PYIPM_OK;
+    if (!ctx->factored) { ctx->err = "solve_many: factor first"; return PYIPM_E_BADARG; }
+    if (!rhs || !dz) { ctx->err = "solve_many: null right-hand side or output"; return PYIPM_E_BADARG; }
+    if (ld_rhs < g.N || ld_dz < g.N) { ctx->err = "solve_many: leading dimension below N"; return PYIPM_E_BADARG; }
+    if (memkind != PYIPM_MEM_DEVICE && memkind != PYIPM_MEM_HOST) { ctx->err = "solve_many: bad memkind"; return PYIPM_E_BADARG; }
+    PYIPM_HIP(hipSetDevice(ctx->device));
+    return solve_many(ctx, k, rhs, ld_rhs, dz, ld_dz, flip, refine, memkind);
 } PYIPM_CATCH_H(h)
 
 // Restates the quantity reghess tests, rcond = min|w| / max|w| over the eigenvalues of Hc (pyipm.py:1379-1381), without

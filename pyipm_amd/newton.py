@@ -82,6 +82,7 @@ def load_library(path: str | None = None):
         "pyipm_newton_factor": (c_int, [ctxp, POINTER(FactorStats)]),
         "pyipm_newton_solve": (c_int, [ctxp, c_void_p, c_void_p, c_int, c_int, c_int]),
         "pyipm_newton_solve_info": (c_int, [ctxp, POINTER(c_double)]),
+        "pyipm_newton_solve_many": (c_int, [ctxp, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int]),
         "pyipm_newton_anorm": (c_int, [ctxp, POINTER(c_void_p)]),
         "pyipm_newton_rcond": (c_int, [ctxp, c_int, c_int, POINTER(c_double)]),
         "pyipm_newton_kkt_matvec": (c_int, [ctxp, c_void_p, c_void_p, c_int]),
@@ -343,6 +344,28 @@ class NewtonCore(object):
         self._ck(self.lib.pyipm_newton_solve(self.h, self._ptr(r), self._ptr(dz), int(bool(flip)), int(refine),
                                              MEM_DEVICE))
         return dz
+
+    def solve_many(self, B, flip=True, refine=0):
+        """``sym_solve_cmp`` with a matrix ``b`` (pyipm.py:911-914): ``B`` of shape (N, k), numpy or torch (1-D = one
+        column), solved against the current factor.  Returns an (N, k) fp64 device tensor: the transposed view of a
+        contiguous (k, N) buffer.  Column j is bitwise independent of the other columns; see pyipm_newton_solve_many."""
+        self._use_current_stream()
+        torch = self.torch
+        if isinstance(B, torch.Tensor):
+            B = B.to(device=self.device, dtype=torch.float64)
+        else:
+            B = torch.from_numpy(np.ascontiguousarray(np.asarray(B, dtype=np.float64))).to(self.device)
+        if B.dim() == 1:
+            B = B.reshape(-1, 1)
+        if B.dim() != 2 or B.shape[0] != self.N:
+            raise ValueError("solve_many: B must have shape (N, k) with N = %d, got %s" % (self.N, tuple(B.shape)))
+        k = int(B.shape[1])
+        rhs = B.t().contiguous()                         # (k, N): column j of B at rhs + j * N
+        dz = torch.empty((k, self.N), dtype=torch.float64, device=self.device)
+        self._ck(self.lib.pyipm_newton_solve_many(self.h, k, self._ptr(rhs), self.N, self._ptr(dz), self.N,
+                                                  int(bool(flip)), int(refine), MEM_DEVICE))
+        self._keep_rhs_many = rhs                        # (the library reads it on the stream, after this returns)
+        return dz.t()
 
     def solve_info(self):
         """Outcome of the last solve: refinement steps, backward error before / after, converged flag."""
