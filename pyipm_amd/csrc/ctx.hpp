@@ -20,6 +20,29 @@ constexpr int BM = 128;             // MFMA update tile rows (i)
 constexpr int BKU = 16;             // MFMA update k-stage
 constexpr int ROWCHUNK = 2048;      // rows per block in the backward column dots
 
+// Tuning numbers of the schedules (measured on MI355X; constants, not per-handle state)
+constexpr int64_t TAIL_COLS = 24576;          // groups of tail_group panels once at most this many columns remain: there the panel chain
+                                              // outlasts the bulk update, and shorter groups move in-group update work off the chain
+constexpr int BULK_WAVES = 8;                 // waves per block of the BULK update tiles (8: 128 VGPRs each, 4 waves per SIMD;
+                                              // 4: 241 VGPRs, 2 per SIMD: 1.5 % slower); the short side-stream launches keep 4
+constexpr int HEAD_WAVES = 4;                 // waves per block of a lookahead head launched on the chain's stream (4: k_update<128,true,4>,
+                                              // its own line in a kernel trace; 8: the bulk instance)
+constexpr int SIDE_PRIO = 1;                  // panel-chain update launches raise their wave priority
+constexpr int64_t PENDING_LEFT_ROWS = 12288;  // group chain: left-looking in-group updates of the rows below the diagonal block while more
+                                              // rows than this remain below it
+constexpr int64_t PENDING32_ROWS = 24576;     // a panel's pending in-group update in 32 x 64 blocks (k_inpanel_update) while at most this many
+                                              // rows remain (128x128 tiles keep one CU busy for 27 us per 256 columns of K, on the chain)
+constexpr int64_t HEAD32_ROWS = 6144;         // ... and the lookahead HEAD update (next group's columns, on the critical path between two
+                                              // groups' chains: one 128x128 tile at K = 512 takes 132 us however few tiles there are)
+constexpr int64_t HEAD32_ROWS_DIST = 16384;   // per-panel (multi-GPU) schedule: single-panel launches (the owner's head update of the
+                                              // next panel, always on the critical path there) while at most this many rows remain
+constexpr int64_t BULK_BN_ROWS = 20480;       // 128 x 256 tiles only for launches over more rows than this (and than persist_rows): below it the
+                                              // next group's chain is no longer hidden behind the bulk launch, and beside the wide tiles (one
+                                              // block per CU, every register) its kernels wait twice as long for a slot -- exposed panel 6.0
+                                              // instead of 5.3 ms with the threshold at persist_rows, the step 0.8 % slower
+constexpr int BULK_BN_MIN_K = 512;            // ... and with at least this K (shorter ones keep 128 x 128: twice the blocks)
+constexpr int TILE_FREE_CUS = 64;             // k_tile_step8: CUs assumed free beside a persistent bulk launch (units per block: 1 while the launch fits)
+
 // Block-cyclic 1D column distribution by panels of width nb.
 struct Geo {
     int64_t n, me, mi, N, Npad;
@@ -40,7 +63,7 @@ struct Geo {
 inline int default_group(int world, int nb = 256) {
     if (world > 1) return 1;
     const char* e = getenv("PYIPM_NEWTON_GROUP");
-    // 8 panels of 256 since the end of round 3 (K = 2048 per bulk launch while more than tail_cols columns remain, then
+    // 8 panels of 256 since the end of round 3 (K = 2048 per bulk launch while more than TAIL_COLS columns remain, then
     // tail_group = 4): with the 128 x 256 bulk tiles -1.2 % at N = 32768, -2.7 % at N = 131072 (4 before: no difference with
     // 128 x 128 tiles).  A group's diagonal block is one chain of at most 32 tile steps: 8 x nb / 64 <= 32.
     int g = e ? atoi(e) : (nb <= 256 ? 8 : 4);
@@ -103,10 +126,9 @@ struct Ctx {
     int lookahead = 2;                    // 0 none, 1 one group (two groups on a dedicated stream measured no faster: removed), 2 = 1 + the
                                           // first group's update panel by panel under its own chain where the slack block follows it (factor_all)
     hipEvent_t ev_early = nullptr;
-    int s_fast = 1;                       // panels inside the slack block: closed-form elimination (k_s_panel)
-    std::vector<char> grp_fast;           // per group: every panel of it takes that path (built by factor_all)
+    std::vector<char> grp_fast;           // per group: every panel of it lies inside the slack block: closed-form elimination (k_s_panel; built by factor_all)
     std::vector<char> grp_x;              // per group: lies inside the x block (its chain kernels may skip the slack rows)
-    struct TileList { unsigned* dev = nullptr; unsigned count = 0; unsigned head_count = 0;
+    struct TileList { unsigned* dev = nullptr; unsigned count = 0;
                       hipEvent_t ready = nullptr; hipStream_t on = nullptr; bool seen_done = false; };   // the async upload: its event, its stream
     struct TlArena { unsigned* dev = nullptr; unsigned* host = nullptr; size_t cap = 0, used = 0; };    // device + pinned host memory of the lists
     std::vector<TlArena> tl_arenas;
@@ -114,45 +136,23 @@ struct Ctx {
     int skip_zeros = 1;                   // trailing updates skip tiles that the KKT block structure makes exact zeros
     int group = 1;                        // panels per bulk trailing update
     bool tail_group_user = false;         // set_option("tail_group") was called (else: 8 for systems of at most 8192 rows)
-    int tail_group = 4;                   // group size once at most tail_cols columns remain: there the panel chain outlasts
-    int64_t tail_cols = 24576;            // the bulk update, and shorter groups move in-group update work off the chain
+    int tail_group = 4;                   // group size once at most TAIL_COLS columns remain
     std::vector<int> grp_of, grp_off;     // per panel: group id and offset inside the group (built by factor_all)
     std::vector<int64_t> grp_first;       // per group: first panel (+ one past the last group)
-    int bulk_waves = 8;                   // waves per block of the BULK update tiles (8: 128 VGPRs each, 4 waves per SIMD;
-                                          // 4: 241 VGPRs, 2 per SIMD: 1.5 % slower); the short side-stream launches keep 4
-    int fuse_su = 1;                      // ... fused into the previous tile's scaling launch (k_panel_scale + NextUpd): two
-                                          // dependent launches per tile on the chain instead of three; same bits
-    double* Wnext = nullptr;              // 64 x 64: -S of the next diagonal tile's rows (handed from the tile kernel to that launch)
+    double* Wnext = nullptr;              // 64 x 64: -S of the next diagonal tile's rows, handed from the tile kernel to the scaling launch
+                                          // that carries the next tile's in-panel update (k_panel_scale + NextUpd, factor_panel)
     int group_chain = 1;                  // single rank: the panels of a group are chained tile to tile (factor_group), the rows
                                           // below the group's diagonal block follow on their own stream; same bits
-    hipStream_t rest = nullptr;           // ... that stream (high priority, created on first use)
+    hipStream_t rest = nullptr;           // ... that stream (high priority, created on first use: ensure_rest_stream)
     std::vector<hipEvent_t> ev_band;      // panel (by offset in its group): its tiles are inverted and applied inside the diagonal block
     hipEvent_t ev_join = nullptr, ev_main = nullptr, ev_split = nullptr, ev_sfast = nullptr;
-    int head_waves = 4;                   // waves per block of a lookahead head launched on the chain's stream (4: k_update<128,true,4>,
-                                          // its own line in a kernel trace; 8: the bulk instance)
-    int64_t pending_left_rows = 12288;    // group chain: left-looking in-group updates of the rows below the diagonal block while more
-                                          // rows than this remain below it (-1: never)
-    int asm_tri = 1;                      // K1 launches only the patches on or below the diagonal (single rank, Npad a multiple of 512)
     int keep_zeros = 1;                   // K1 does not store again the zeros nothing can fill in (k_assemble, zeros_in_place)
     bool zeros_clean = false;             // ... which requires that the last writer of those places was a full assembly
     bool storage_exported = false;        // kkt_storage() handed the pointer out: a holder may write into those zeros at any time,
                                           // so every assembly is a full one until set_option("keep_zeros") is called again
-    int rest_prio = 1;                    // ctx->rest is a high-priority stream (set before the first factorisation)
-    int fast_on_main = 1;                 // groups inside the slack block (closed form) run on the main stream, not through the lookahead
-    int head_on_side = 1;                 // the lookahead head runs on the stream of the chain it follows (no stream crossing between
-                                          // a group's chain, the head and the next chain); ordered against the main stream by an event
-    int bwd_diag4 = 1;                    // in-panel backward substitution on 1024 threads through shared memory (k_bwd_diag4)
     int tile_step = 1;                    // stepped panel schedule (kernels_panel.hpp): one launch per diagonal tile (the rows inside the
                                           // diagonal block), one for the rows below it; panels of at most 4 tiles; same bits
-    int64_t head32_rows = 6144;           // ... and the lookahead HEAD update (next group's columns, on the critical path between two
-                                          // groups' chains: one 128x128 tile at K = 512 takes 132 us however few tiles there are)
     bool per_panel_mode = false;          // the per-panel phases (pyipm_newton_factor_begin ...) drive this factorisation
-    int64_t head32_rows_dist = 16384;     // per-panel (multi-GPU) schedule: single-panel launches (the owner's head update of the
-                                          // next panel, always on the critical path there) while at most this many rows remain
-    int64_t bulk_bn_rows = 20480;         // 128 x 256 tiles only for launches over more rows than this (and than persist_rows): below it the
-                                          // next group's chain is no longer hidden behind the bulk launch, and beside the wide tiles (one
-                                          // block per CU, every register) its kernels wait twice as long for a slot -- exposed panel 6.0
-                                          // instead of 5.3 ms with the threshold at persist_rows, the step 0.8 % slower
     int sweep_max_blocks = 0;             // test hook: cap on the workgroups of the one-launch sweeps (0 = as many as the GPU holds)
     int occ_fwd_sweep = 0, occ_bwd_sweep = 0;   // resident workgroups per CU of the one-launch sweeps (occupancy query, cached)
     int sweep_persist = 1;                // single rank, one right-hand side: the backward sweep as ONE device-driven launch (k_bwd_sweep)
@@ -162,16 +162,12 @@ struct Ctx {
     size_t ms_buf_bytes = 0;
     unsigned* sweep_sync = nullptr;       // ... its flags and counters (3 npanels + 1 words, zeroed before every sweep)
     bool sweep_used = false;              // ... a sweep ran since the error word was last read (solve_info / factor_end look at it)
-    int dist_head_split = 1;              // per-panel schedule: the owner's head in two launches -- the next panel's diagonal block (its chain waits for
-                                          // that alone), then the rows below it on ctx->rest (round 4)
     int dist_slices = 2;                  // distributed schedule: the two-message protocol (slices ahead of the panel message: the next owner's tile
                                           // chain starts on an nb x nb message); 0 = one message per panel (rounds 1-4); collective
     double dist_timeout_s = 300.0;        // distributed step: bound on the host's wait for the device (dist_impl.hpp:bounded_wait); <= 0: none
     int dist_comm2 = 0;                   // RCCL transport: the slice messages on a second communicator of their own (set before comm_init; dist_impl.hpp:comm2_setup)
     int wide_sub = 256;                   // per-panel schedule: a panel wider than this is factored as a block of sub-panels this wide
                                           // (factor_wide_panel: the single-rank group chain inside one panel); 0 = all stages in one launch
-    int64_t pending32_rows = 24576;       // ... and a panel's pending in-group update too while at most this many rows remain
-                                          // (128x128 tiles keep one CU busy for 27 us per 256 columns of K, on the chain)
     int reserve_cus = 16;                 // chain-bound phases: bulk updates run as persistent launches that leave this many CUs
     int64_t persist_rows = 12288;         // free for the panel chain -- while at most this many rows remain (on one rank the per-panel schedule with it
     int num_cus = 256;                    // everywhere took 140 instead of 120 ms); 0 = ordinary launches everywhere.  num_cus: of this device
@@ -180,9 +176,6 @@ struct Ctx {
                                           // the slow ones (boxes differ in memory speed, not in MFMA rate); a chain kernel waits twice as
                                           // long for a slot beside it (tools/contention_probe.py), so the chain-bound phase keeps the
                                           // persistent 128 x 128 launches (bulk_bn_all = 0).  128: 128 x 128 everywhere (rounds 1-2)
-    int bulk_bn_min_k = 512;              // ... for launches with at least this K (shorter ones keep 128 x 128: twice the blocks)
-    int xcd_swizzle = 1;
-    int side_prio = 1;                    // raise wave priority in panel-chain update launches
     unsigned long long* dbg_buf = nullptr;   // diagnostics only
     // condensed KKT option: factor the (n+me)-dimensional system
     //   [[H + delta I + Ji Sigma Ji', Je], [Je', -delta_c I]]  instead of the full (n+2mi+me) one
@@ -259,11 +252,7 @@ struct Ctx {
     unsigned long long* chain_dbg = nullptr; int chain_dbg_launch = 0;   // diagnostics only (option debug_chain_ptr)
     bool chain_used = false;              // ... a chain launch ran since the error word was last read (factor_end)
     int64_t tile8_rows = 12288;           // ... used by the single-rank schedule for the first group and where at most this many rows are left
-    int tile_free_cus = 64;               // ... CUs assumed free beside a persistent bulk launch (units per block: 1 while the launch fits)
     int bc_per_problem = 1;               // batched condensed form: the Gram part by one workgroup per problem where n = 64 .. 256 allows it
-    int s_early = 1;                      // the slack block's closed-form panels enqueued up front on the rows stream (factor_all)
-    int tile8_dist = 0;                   // ... also in the per-panel (multi-GPU) schedule
-    int tile_upb = 0;                     // ... its other row tiles: (row tile, y) units per 512-thread block, 1 | 2; 0 = by the size of the launch
     int block_refine = 2;                 // refinement steps of L T = S in the panel scaling and of T z = y in the solves
     double refine_cond = 1.0e3;           // ... applied to tiles whose pivot spread dmax/dmin exceeds this
     int profile = 0;

@@ -545,7 +545,7 @@ int update_range(Ctx* ctx, int64_t p, int64_t first, int64_t count, hipStream_t 
     if (q >= last) return 0;
     int64_t n_lp = 0;
     for (int64_t qq = q; qq < last; qq += g.world) ++n_lp;
-    return timed_update(ctx, p, 1, q / g.world, n_lp, st);
+    return timed_update(ctx, p, 1, q / g.world, n_lp, {.stream = st});
 }
 
 // The factorisation across the ranks: one-panel lookahead.  As soon as panel p has arrived, the owner of p+1 updates
@@ -728,13 +728,13 @@ int factor_dist_geo(Ctx* ctx, pyipm_factor_stats* stats, const double* fwd_b) {
         const int K = (int)g.panel_w(p);
         const int64_t c0q = g.panel_c0(q), nbwq = g.panel_w(q);
         if (panel_in_s(ctx, p)) return 0;                              // (a slack-block source: handled by update_range, whole columns)
-        if (small || g.Npad - (c0q + nbwq) <= ctx->head32_rows_dist) {
+        if (small || g.Npad - (c0q + nbwq) <= HEAD32_ROWS_DIST) {
             int64_t pa0, pa1, pb0, pb1;
             active_ranges(ctx, g.panel_c0(p), g.panel_c0(p) + K, &pa0, &pa1, &pb0, &pb1);
             return launch_inpanel_update(ctx, st, dim3((unsigned)((r1 - r0) / 32), (unsigned)(nbwq / TB)), ctx->A, g.Npad, g.local_c0(q), Lop, ldl,
-                                         wbuf(ctx, p), g.Npad, c0q, K, r0, g.Npad, pa0, pa1, pb0, pb1, ctx->side_prio);
+                                         wbuf(ctx, p), g.Npad, c0q, K, r0, g.Npad, pa0, pa1, pb0, pb1, SIDE_PRIO);
         }
-        return launch_update128(ctx, st, Lop, ldl, wbuf(ctx, p), K, r0, q / W, 1, /*bulk=*/true, 0, r1, 0, g.panel_c0(p), 1, 0, ctx->head_waves);
+        return launch_update128(ctx, st, Lop, ldl, wbuf(ctx, p), K, r0, q / W, 1, {.row_end = r1, .src_c0 = g.panel_c0(p), .waves = HEAD_WAVES});
     };
     // the panel message of p: owner sends (its pack is behind ev_fact), everyone else joins
     auto bcast_big = [&](int64_t p) -> int {
@@ -902,7 +902,7 @@ int factor_dist_geo(Ctx* ctx, pyipm_factor_stats* stats, const double* fwd_b) {
             } else {
                 // classic: the whole head on the main stream, the whole panel on the side stream behind it
                 const int64_t nbwn = g.panel_w(nxt);
-                const bool wide_next = ctx->dist_head_split && ctx->tile_step && ctx->wide_sub >= 128 &&
+                const bool wide_next = ctx->tile_step && ctx->wide_sub >= 128 &&
                                        ctx->wide_sub % 128 == 0 && nbwn > ctx->wide_sub && nbwn / TB <= 32 && c1n + nbwn < g.Npad &&
                                        !panel_in_s(ctx, nxt) && !panel_in_s(ctx, k) && nbwn % 32 == 0;
                 if (panel_in_s(ctx, k) || panel_in_s(ctx, nxt)) {
@@ -1050,39 +1050,27 @@ int solve_dist(Ctx* ctx, const double* rhs, double* dz, int flip, int refine, in
     const bool fwd_done = D->fwd_done && rhs == nullptr;                // the staged right-hand side went forward under the factorisation
     D->fwd_done = false;
     rc = solve_dist_any(ctx, D, ctx->v1, ctx->v0, fwd_done); if (rc) return rc;
-    if (ctx->cond_active && refine >= 0 && refine < ctx->cond_min_refine) refine = ctx->cond_min_refine;
-    ctx->info_steps = 0; ctx->info_converged = 0; ctx->info_berr0 = -1.0; ctx->info_berr = -1.0;
-    const bool adaptive = refine < 0;
-    const int maxit = adaptive ? ctx->refine_max : refine;
-    double prev = -1.0;
-    for (int it = 0; it <= maxit; ++it) {
-        if (!adaptive && it == maxit) break;
-        rc = matvec_dist(ctx, D, ctx->v0, ctx->v2); if (rc) return rc;
-        { int r_ = launch_axpby(ctx, st, ctx->v2, ctx->v1, ctx->v2, 1.0, -1.0, g.Npad); if (r_) return r_; }
-        if (adaptive) {
+    const size_t vbytes = (size_t)g.Npad * sizeof(double);
+    rc = refine_loop(ctx, refine,
+        [&]() -> int {                                          // v2 = b - Hc v0 (the ranks' shares summed inside the product)
+            int r_ = matvec_dist(ctx, D, ctx->v0, ctx->v2); if (r_) return r_;
+            return launch_axpby(ctx, st, ctx->v2, ctx->v1, ctx->v2, 1.0, -1.0, g.Npad);
+        },
+        [&](double* berr) -> int {
             double ss[2];
             { int r_ = launch_sumsq2(ctx, st, ctx->partial, ctx->v2, ctx->v1, g.N); if (r_) return r_; }
             DIST_HIP(hipMemcpyAsync(ss, ctx->partial, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
             DIST_HIP(hipStreamSynchronize(st));
-            const double berr = ss[1] > 0.0 ? sqrt(ss[0] / ss[1]) : sqrt(ss[0]);     // identical on every rank: replicated vectors
-            if (it == 0) ctx->info_berr0 = berr;
-            ctx->info_berr = berr;
-            if (prev >= 0.0 && !(berr <= prev)) {                             // the last step made it worse: take it back
-                DIST_HIP(hipMemcpyAsync(ctx->v0, ctx->v3, g.Npad * sizeof(double), hipMemcpyDeviceToDevice, st));
-                ctx->info_berr = prev; ctx->info_steps = it - 1;
-                break;
-            }
-            if (!(berr <= 1.0e300)) break;
-            if (berr <= ctx->refine_target) { ctx->info_converged = 1; break; }
-            if (it == maxit || (prev >= 0.0 && berr > 0.25 * prev)) break;
-            prev = berr;
-            DIST_HIP(hipMemcpyAsync(ctx->v3, ctx->v0, g.Npad * sizeof(double), hipMemcpyDeviceToDevice, st));
-        }
-        // (the correction goes through v3's neighbour-free scratch: vc is the condensed solve's own vector)
-        rc = solve_dist_any(ctx, D, ctx->v2, ctx->v2, false); if (rc) return rc;
-        { int r_ = launch_axpby(ctx, st, ctx->v0, ctx->v0, ctx->v2, 1.0, 1.0, g.Npad); if (r_) return r_; }
-        ctx->info_steps = it + 1;
-    }
+            *berr = ss[1] > 0.0 ? sqrt(ss[0] / ss[1]) : sqrt(ss[0]);             // identical on every rank: replicated vectors
+            return 0;
+        },
+        [&]() -> int { DIST_HIP(hipMemcpyAsync(ctx->v3, ctx->v0, vbytes, hipMemcpyDeviceToDevice, st)); return 0; },
+        [&]() -> int { DIST_HIP(hipMemcpyAsync(ctx->v0, ctx->v3, vbytes, hipMemcpyDeviceToDevice, st)); return 0; },
+        [&]() -> int {                                          // v0 += Hc^{-1} v2 (vc is the condensed solve's own vector)
+            int r_ = solve_dist_any(ctx, D, ctx->v2, ctx->v2, false); if (r_) return r_;
+            return launch_axpby(ctx, st, ctx->v0, ctx->v0, ctx->v2, 1.0, 1.0, g.Npad);
+        });
+    if (rc) return rc;
     { int r_ = launch_copy_flip(ctx, st, ctx->v2, ctx->v0, (flip && (g.me + g.mi) > 0) ? 1 : 0); if (r_) return r_; }
     DIST_HIP(hipEventRecord(ctx->ev[5], st));
     rc = copy_out(ctx, dz, ctx->v2, g.N, memkind); if (rc) return rc;

@@ -46,17 +46,28 @@ int stage_block(Ctx* ctx, const double* src, int64_t rows, int64_t cols, int64_t
 void active_ranges(const Ctx* ctx, int64_t cA, int64_t cB, int64_t* a0, int64_t* a1, int64_t* b0, int64_t* b1);
 bool panel_in_s(const Ctx* ctx, int64_t p);
 void panel_hole(const Ctx* ctx, int64_t p, int64_t* h0, int64_t* h1);
+// What a call of launch_update128 may set beside its operands (designated initialisers, in this order).
+struct UpdLaunch {
+    bool bulk = true;            // tile-list order, bulk instances; false: a panel-chain launch (plain grid, raised wave priority)
+    int64_t ldw = 0;             // leading dimension of Wop;   0: the KKT storage's (Npad)
+    int64_t row_end = 0;         // rows [row_begin, row_end);  0: Npad
+    int64_t col_end = 0;         // columns below col_end;      0: Npad (the Gram launch of the condensed option narrows it)
+    int64_t src_c0 = -1;         // >= 0: global column of the first source column (tiles its active ranges leave at zero are skipped)
+    int ksplit = 1;              // split-K: grid.y splits of K columns each, split y accumulating into C + y * ks_cstride
+    int64_t ks_cstride = 0;
+    int waves = 0;               // waves per block; 0: BULK_WAVES
+    int sub0 = 0, nct_sub = 0;   // nct_sub > 0: only column tiles [sub0, sub0 + nct_sub) of local panel first_lp
+                                 // (128 wide; the sub-panels of a wide panel, factor_block)
+    int* used_bn = nullptr;      // out: the tile width of the instance that ran (64 / 128 / 256)
+    int prio = -1;               // >= 0: wave priority flag of the launch whatever `bulk` says
+};
 int launch_update128(Ctx* ctx, hipStream_t stream, const double* Lop, int64_t ldl, const double* Wop, int K,
-                     int64_t row_begin, int64_t first_lp, int64_t n_lp, bool bulk = true,
-                     int64_t ldw = 0, int64_t row_end = 0, int64_t col_end = 0, int64_t src_c0 = -1,
-                     int ksplit = 1, int64_t ks_cstride = 0, int waves = 0,        // waves: 0 = the handle's bulk_waves
-                     int head_ct = 0, unsigned* head_counter = nullptr, unsigned* head_count = nullptr, bool list_only = false,
-                     int sub0 = 0, int nct_sub = 0,    // nct_sub > 0: only column tiles [sub0, sub0 + nct_sub) of local panel first_lp
-                     int* used_bn = nullptr,           // out: the tile width of the instance that ran (128 / 256)
-                     int prio = -1);
-int timed_update(Ctx* ctx, int64_t p0, int64_t np, int64_t first_lp, int64_t n_lp, hipStream_t stream = nullptr,
-                 int head_ct = 0, unsigned* head_counter = nullptr, unsigned* head_count = nullptr, bool list_only = false,
-                 bool as_bulk = false);
+                     int64_t row_begin, int64_t first_lp, int64_t n_lp, const UpdLaunch& o = {});
+struct UpdTimed {
+    hipStream_t stream = nullptr;   // nullptr: the handle's
+    bool as_bulk = false;           // a bulk launch (instance, trailing figures) although it runs on another stream
+};
+int timed_update(Ctx* ctx, int64_t p0, int64_t np, int64_t first_lp, int64_t n_lp, const UpdTimed& o = {});
 int factor_panel(Ctx* ctx, int64_t p, hipStream_t stream, bool apply_pending = false);
 int fwd_panel(Ctx* ctx, int64_t p, double* v, hipStream_t stream = nullptr, int nrhs = 1, int64_t vstride = 0);
 int diag_panel(Ctx* ctx, int64_t p, double* v, hipStream_t stream = nullptr, int nrhs = 1, int64_t vstride = 0);
@@ -94,5 +105,50 @@ int launch_sumsq2(Ctx* ctx, hipStream_t st, double* out, const double* a, const 
 int launch_inpanel_update(Ctx* ctx, hipStream_t st, dim3 grid, double* Cm, int64_t ldc, int64_t ccol, const double* Lop, int64_t ldl,
                           const double* Wop, int64_t ldw, int64_t cglob, int K, int64_t row_begin, int64_t row_end,
                           int64_t a0, int64_t a1, int64_t b0, int64_t b1, int prio);
+
+
+// Iterative refinement of a solve: the host-side state machine of solve_finish, solve_many and solve_dist.
+// refine >= 0: that many steps of   r = b - Hc x ;  x += Hc^{-1} r   (Hc applied from the blocks, not from the factor).
+// refine <  0: adaptive -- measure |r|/|b| before every step and stop at refine_target, after refine_max steps or
+//              when a step gains less than 4x; a step that made it worse (or NaN) is taken back.  This is what turns the
+//              factor of a statically pivoted (perturbed) matrix into the solution of the UNperturbed system; the host
+//              reads the outcome with solve_info (the info_* fields).
+// The caller's kernels, buffers and streams (each callback returns a PYIPM code):  residual() enqueues r = b - Hc x;
+// berr(&e) gives |r|/|b| as a host double (several columns: the worst, NaN if any is);  save() / restore() copy x to / from
+// the spare iterate;  correct() enqueues x += Hc^{-1} r.
+inline int refine_steps(const Ctx* ctx, int refine) {      // a condensed solve gets at least cond_min_refine steps against the FULL blocks
+    return (ctx->cond_active && refine >= 0 && refine < ctx->cond_min_refine) ? ctx->cond_min_refine : refine;
+}
+template <class Residual, class Berr, class Save, class Restore, class Correct>
+int refine_loop(Ctx* ctx, int refine, Residual residual, Berr berr_of, Save save, Restore restore, Correct correct) {
+    refine = refine_steps(ctx, refine);
+    ctx->info_steps = 0; ctx->info_converged = 0; ctx->info_berr0 = -1.0; ctx->info_berr = -1.0;
+    const bool adaptive = refine < 0;
+    const int maxit = adaptive ? ctx->refine_max : refine;
+    double prev = -1.0;
+    for (int it = 0; it <= maxit; ++it) {
+        if (!adaptive && it == maxit) break;
+        int rc = residual(); if (rc) return rc;
+        if (adaptive) {
+            double berr = 0.0;
+            rc = berr_of(&berr); if (rc) return rc;
+            if (it == 0) ctx->info_berr0 = berr;
+            ctx->info_berr = berr;
+            if (prev >= 0.0 && !(berr <= prev)) {                             // the last step made it worse (or NaN): take it back
+                rc = restore(); if (rc) return rc;
+                ctx->info_berr = prev; ctx->info_steps = it - 1;
+                break;
+            }
+            if (!(berr <= 1.0e300)) break;                                    // NaN / Inf: nothing to refine
+            if (berr <= ctx->refine_target) { ctx->info_converged = 1; break; }
+            if (it == maxit || (prev >= 0.0 && berr > 0.25 * prev)) break;    // out of budget / stagnating
+            prev = berr;
+            rc = save(); if (rc) return rc;                                   // the iterate this error belongs to
+        }
+        rc = correct(); if (rc) return rc;
+        ctx->info_steps = it + 1;
+    }
+    return 0;
+}
 
 } }  // namespace pyipm::drv

@@ -158,7 +158,7 @@ int lb_factor_G(LbCtx* lb, double zeta, double reg_e, pyipm_factor_stats* st, bo
     Ctx* gc = lb->gcx;
     const Geo& g = gc->g;
     gc->stream = lb->stream;
-    const int ks = gc->xcd_swizzle ? lb->ksplit : 1;
+    const int ks = lb->ksplit;
     const int64_t cnt = g.Npad * g.Npad;
     int rc;
     if (timed) LB_HIP(hipEventRecord(lb->ev[1], lb->stream));
@@ -171,7 +171,8 @@ int lb_factor_G(LbCtx* lb, double zeta, double reg_e, pyipm_factor_stats* st, bo
             LB_HIP(hipMemsetAsync(lb->Cs, 0, (size_t)ks * (size_t)cnt * sizeof(double), lb->stream));
             gc->A = lb->Cs;
             rc = launch_update128(gc, lb->stream, lb->JT, lb->p_pad, lb->JT, (int)(lb->n_pad / ks), 0, 0,
-                                  (g.Npad + g.nb - 1) / g.nb, true, lb->p_pad, g.Npad, g.Npad, -1, ks, cnt);
+                                  (g.Npad + g.nb - 1) / g.nb,
+                                  {.ldw = lb->p_pad, .ksplit = ks, .ks_cstride = cnt});
             gc->A = keep;
             if (rc) { lb->err = gc->err; return rc; }
             hipLaunchKernelGGL(k_lb_ksum, grid1(cnt), dim3(256), 0, lb->stream, lb->Gc, lb->Cs, cnt, ks);
@@ -180,7 +181,8 @@ int lb_factor_G(LbCtx* lb, double zeta, double reg_e, pyipm_factor_stats* st, bo
             LB_HIP(hipMemsetAsync(lb->Gc, 0, (size_t)cnt * sizeof(double), lb->stream));
             gc->A = lb->Gc;
             rc = launch_update128(gc, lb->stream, lb->JT, lb->p_pad, lb->JT, (int)lb->n_pad, 0, 0,
-                                  (g.Npad + g.nb - 1) / g.nb, true, lb->p_pad, g.Npad, g.Npad);
+                                  (g.Npad + g.nb - 1) / g.nb,
+                                  {.ldw = lb->p_pad});
             gc->A = keep;
             if (rc) { lb->err = gc->err; return rc; }
         }

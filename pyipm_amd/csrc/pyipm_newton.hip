@@ -211,13 +211,13 @@ double active_area(int64_t row_begin, int64_t Npad, int64_t j0, int64_t j1, int6
 // far: 35 lists, 98 ms of host time, the GPU idle behind the host for 25 ms of the first step of every solve); a consumer on
 // another stream waits for the copy's event until it has been seen complete.  Device and host memory come from arenas.
 int tile_list(Ctx* ctx, const UpdGeo& u, int64_t nsup, const unsigned** dev, unsigned* count, int bn = 128,
-              unsigned* head_count = nullptr, hipStream_t consumer = nullptr) {
+              hipStream_t consumer = nullptr) {
     if (ctx->debug_fault == 1 || ctx->debug_fault == 2) {   // test hook (tests/test_gpu_host_abi.py): the containers below can throw
         const int k = ctx->debug_fault; ctx->debug_fault = 0;
         if (k == 1) throw std::bad_alloc();
         throw std::runtime_error("injected fault");
     }
-    std::vector<int64_t> key = {u.row_begin, u.Npad, u.first_lp, u.nrt, u.nct, u.a0, u.a1, u.b0, u.b1, u.nb, u.rt_min0, u.rt_step, bn, u.head_ct, u.sub0};
+    std::vector<int64_t> key = {u.row_begin, u.Npad, u.first_lp, u.nrt, u.nct, u.a0, u.a1, u.b0, u.b1, u.nb, u.rt_min0, u.rt_step, bn, u.sub0};
     auto it = ctx->tile_lists.find(key);
     if (it != ctx->tile_lists.end()) {
         Ctx::TileList& t = it->second;
@@ -225,7 +225,7 @@ int tile_list(Ctx* ctx, const UpdGeo& u, int64_t nsup, const unsigned** dev, uns
             if (hipEventQuery(t.ready) == hipSuccess) t.seen_done = true;
             else if (consumer != t.on) PYIPM_HIP(hipStreamWaitEvent(consumer, t.ready, 0));
         }
-        *dev = t.dev; *count = t.count; if (head_count) *head_count = t.head_count; return 0;
+        *dev = t.dev; *count = t.count; return 0;
     }
     if (ctx->tile_lists.size() >= 1024) {              // geometries that keep changing (condensed option: |A| varies): start over
         PYIPM_HIP(hipDeviceSynchronize());
@@ -264,24 +264,16 @@ int tile_list(Ctx* ctx, const UpdGeo& u, int64_t nsup, const unsigned** dev, uns
         if (!(ri && ci)) continue;
         seq[xcd].push_back((unsigned)rt | ((unsigned)ct << 16));
     }
-    unsigned nhead = 0;
-    if (u.head_ct > 0)                                  // fused head: the next group's columns first, on every XCD's sequence
-        for (auto& v : seq) {
-            std::stable_partition(v.begin(), v.end(), [&](unsigned c) { return (int)(c >> 16) < u.head_ct; });
-            for (unsigned c : v) nhead += (int)(c >> 16) < u.head_ct;
-        }
     size_t total = 0;
     for (auto& v : seq) total += v.size();
     const size_t target = (total + 7) / 8;
     std::vector<unsigned> spare;
     for (auto& v : seq) while (v.size() > target) { spare.push_back(v.back()); v.pop_back(); }
     for (auto& v : seq) while (v.size() < target && !spare.empty()) { v.push_back(spare.back()); spare.pop_back(); }
-    if (u.head_ct > 0)                                  // (levelling appends moved tails: keep the head tiles in front)
-        for (auto& v : seq) std::stable_partition(v.begin(), v.end(), [&](unsigned c) { return (int)(c >> 16) < u.head_ct; });
     std::vector<unsigned> list(8 * target, 0xffffffffu);
     for (int x = 0; x < 8; ++x) for (size_t j = 0; j < seq[x].size(); ++j) list[8 * j + x] = seq[x][j];
     Ctx::TileList tl;
-    tl.count = (unsigned)list.size(); tl.head_count = nhead;
+    tl.count = (unsigned)list.size();
     if (tl.count) {
         // a slot in the arenas (device + pinned host, 1 Mi entries each; a list longer than that gets an arena of its own)
         const size_t need = (list.size() + 63) / 64 * 64;
@@ -306,64 +298,57 @@ int tile_list(Ctx* ctx, const UpdGeo& u, int64_t nsup, const unsigned** dev, uns
         tl.on = consumer;
     }
     ctx->tile_lists[key] = tl;
-    *dev = tl.dev; *count = tl.count; if (head_count) *head_count = nhead;
+    *dev = tl.dev; *count = tl.count;
     return 0;
 }
 
-// Rank-K update of `n_lp` locally owned panels starting at local panel `first_lp`.
-// ldw / row_end / col_end default to the KKT storage's (the Gram launch of the condensed option narrows them).
+// Rank-K update of `n_lp` locally owned panels starting at local panel `first_lp` (UpdLaunch, driver.hpp: what a call may set).
 int launch_update128(Ctx* ctx, hipStream_t stream, const double* Lop, int64_t ldl, const double* Wop, int K,
-                     int64_t row_begin, int64_t first_lp, int64_t n_lp, bool bulk,
-                     int64_t ldw, int64_t row_end, int64_t col_end, int64_t src_c0,
-                     int ksplit, int64_t ks_cstride, int waves,        // waves: 0 = the handle's bulk_waves
-                     int head_ct, unsigned* head_counter, unsigned* head_count, bool list_only,
-                     int sub0, int nct_sub,    // nct_sub > 0: only column tiles [sub0, sub0 + nct_sub) of local panel first_lp
-                     int* used_bn,           // out: the tile width of the instance that ran (128 / 256)
-                     int prio) {                  // >= 0: wave priority flag of the launch whatever `bulk` says
-    const Geo& g = ctx->g;                             // (128 wide; the sub-panels of a wide panel, factor_block)
-    if (ldw <= 0) ldw = g.Npad;
-    if (row_end <= 0) row_end = g.Npad;
-    if (col_end <= 0) col_end = g.Npad;
+                     int64_t row_begin, int64_t first_lp, int64_t n_lp, const UpdLaunch& o) {
+    const Geo& g = ctx->g;
+    const int64_t ldw = o.ldw > 0 ? o.ldw : g.Npad;
+    const int64_t row_end = o.row_end > 0 ? o.row_end : g.Npad;
+    const int64_t col_end = o.col_end > 0 ? o.col_end : g.Npad;
+    const bool bulk = o.bulk;
+    const int waves = o.waves, ksplit = o.ksplit, nct_sub = o.nct_sub;
     const int64_t m = row_end - row_begin;
     if (m <= 0 || n_lp <= 0) return 0;
     UpdGeo u;
-    u.row_begin = row_begin; u.Npad = col_end; u.first_lp = first_lp; u.sub0 = sub0;
+    u.row_begin = row_begin; u.Npad = col_end; u.first_lp = first_lp; u.sub0 = o.sub0;
     u.nb = g.nb; u.world = g.world; u.rank = g.rank;
     u.nrt = (int)(m / BM); u.nct = nct_sub > 0 ? nct_sub : (int)(n_lp * (g.nb / 128));
     u.dbg = ctx->dbg_buf;
-    u.prio = prio >= 0 ? prio : (bulk ? 0 : ctx->side_prio);
+    u.prio = o.prio >= 0 ? o.prio : (bulk ? 0 : SIDE_PRIO);
     u.rt_min0 = 0; u.rt_step = 0; u.tiles = nullptr; u.ks_cstride = 0; u.persist = 0;
-    u.head_ct = head_ct; u.head_counter = head_counter;
-    if (src_c0 >= 0) active_ranges(ctx, src_c0, src_c0 + K, &u.a0, &u.a1, &u.b0, &u.b1);
+    u.head_ct = 0; u.head_counter = nullptr;          // (the fused head of round 3: no launch uses it)
+    if (o.src_c0 >= 0) active_ranges(ctx, o.src_c0, o.src_c0 + K, &u.a0, &u.a1, &u.b0, &u.b1);
     else { u.a0 = 0; u.a1 = g.Npad; u.b0 = 0; u.b1 = 0; }
-    const int use_waves = waves ? waves : ctx->bulk_waves;
+    const int use_waves = waves ? waves : BULK_WAVES;
     // (col_end % 256: Npad is a multiple of 128 only -- a 256-wide tile at the last 128 columns would read and rewrite 128
     // columns past the storage, i.e. the first W slot, and W rows past Npad; such shapes keep 128 x 128 tiles)
-    if (ctx->xcd_swizzle && bulk && ctx->bulk_bn == 256 && use_waves == 8 && waves == 0 && ksplit == 1 && g.nb % 256 == 0 &&
-        col_end % 256 == 0 && K >= ctx->bulk_bn_min_k && head_ct % 2 == 0 && nct_sub == 0 && (ctx->reserve_cus <= 0 || m > (ctx->bulk_bn_rows > ctx->persist_rows ? ctx->bulk_bn_rows : ctx->persist_rows))) {
+    if (bulk && ctx->bulk_bn == 256 && use_waves == 8 && waves == 0 && ksplit == 1 && g.nb % 256 == 0 &&
+        col_end % 256 == 0 && K >= BULK_BN_MIN_K && nct_sub == 0 && (ctx->reserve_cus <= 0 || m > (BULK_BN_ROWS > ctx->persist_rows ? BULK_BN_ROWS : ctx->persist_rows))) {
         // 128 x 256 tiles (the K = 1024 bulk launches of the single-rank schedule, the K = nb launches of the per-panel one)
         u.nct = (int)(n_lp * (g.nb / 256));
-        u.head_ct = head_ct / 2;                        // (fused head: the callers count 128-column tiles)
         upd_fill_affine<256>(u);
         const int64_t nsup = upd_super_count<256>(u);
         if (nsup <= 0) return 0;
         unsigned ntiles = 0;
-        int rc = tile_list(ctx, u, nsup, &u.tiles, &ntiles, 256, head_count, stream); if (rc) return rc;
-        if (used_bn) *used_bn = 256;
-        if (list_only || ntiles == 0) return 0;
+        int rc = tile_list(ctx, u, nsup, &u.tiles, &ntiles, 256, stream); if (rc) return rc;
+        if (o.used_bn) *o.used_bn = 256;
+        if (ntiles == 0) return 0;
         hipLaunchKernelGGL((k_update<256, true, 8>), dim3(ntiles), dim3(512), 0, stream, ctx->A, g.Npad, Lop, ldl, Wop, ldw, K, u);
         PYIPM_KCHECK();
-        if (used_bn) *used_bn = 256;
         return 0;
     }
-    if (ctx->xcd_swizzle && bulk && upd_swizzle_ok<128>(u)) {
+    if (bulk && upd_swizzle_ok<128>(u)) {
         upd_fill_affine<128>(u);
         const int64_t nsup = upd_super_count<128>(u);
         if (nsup <= 0) return 0;
         unsigned ntiles = 0;
-        int rc = tile_list(ctx, u, nsup, &u.tiles, &ntiles, 128, head_count, stream); if (rc) return rc;
-        if (list_only || ntiles == 0) return 0;
-        if (ctx->bulk_bn == 256 && use_waves == 8 && waves == 0 && ksplit == 1 && head_ct == 0 && nct_sub == 0 &&
+        int rc = tile_list(ctx, u, nsup, &u.tiles, &ntiles, 128, stream); if (rc) return rc;
+        if (ntiles == 0) return 0;
+        if (ctx->bulk_bn == 256 && use_waves == 8 && waves == 0 && ksplit == 1 && nct_sub == 0 &&
             ntiles <= (unsigned)(ctx->num_cus * 5 / 8) && upd_swizzle_ok<64>(u)) {
             // A launch that leaves most of the GPU idle (the last groups of a factorisation, the panel-by-panel updates of a small
             // system's first group): 128 x 64 tiles, twice as many blocks of half the length, no scratch.  (Config 2's K = 2048
@@ -375,16 +360,16 @@ int launch_update128(Ctx* ctx, hipStream_t stream, const double* Lop, int64_t ld
             upd_fill_affine<64>(v);
             const int64_t nsup64 = upd_super_count<64>(v);
             unsigned nt64 = 0;
-            if (nsup64 > 0) { rc = tile_list(ctx, v, nsup64, &v.tiles, &nt64, 64, nullptr, stream); if (rc) return rc; }
+            if (nsup64 > 0) { rc = tile_list(ctx, v, nsup64, &v.tiles, &nt64, 64, stream); if (rc) return rc; }
             if (nt64 > 0) {
                 hipLaunchKernelGGL((k_update<64, true, 8>), dim3(nt64), dim3(512), 0, stream, ctx->A, g.Npad, Lop, ldl, Wop, ldw, K, v);
                 PYIPM_KCHECK();
-                if (used_bn) *used_bn = 64;
+                if (o.used_bn) *o.used_bn = 64;
                 return 0;
             }
         }
         dim3 grid(ntiles, (unsigned)ksplit);             // K is the length of ONE split
-        if (ksplit > 1) u.ks_cstride = ks_cstride;
+        if (ksplit > 1) u.ks_cstride = o.ks_cstride;
         if (use_waves == 8 && waves == 0 && ksplit == 1 && ctx->reserve_cus > 0 &&
             m <= ctx->persist_rows) {
             // chain-bound phase: leave `reserve_cus` CUs without update blocks (two 8-wave blocks fill one)
@@ -396,7 +381,8 @@ int launch_update128(Ctx* ctx, hipStream_t stream, const double* Lop, int64_t ld
         else
             hipLaunchKernelGGL((k_update<128, true>), grid, dim3(256), 0, stream, ctx->A, g.Npad, Lop, ldl, Wop, ldw, K, u);
     } else {
-        if (ksplit > 1) { ctx->err = "split-K launches need the tile-list order (xcd_swizzle)"; return PYIPM_E_BADARG; }
+        // a panel-chain launch, or a panel width the tile-list decode does not cover: plain grid order
+        if (ksplit > 1) { ctx->err = "split-K launches need the tile-list order"; return PYIPM_E_BADARG; }
         dim3 grid((unsigned)u.nrt, (unsigned)u.nct);
         hipLaunchKernelGGL((k_update<128, false>), grid, dim3(256), 0, stream, ctx->A, g.Npad, Lop, ldl, Wop, ldw, K, u);
     }
@@ -408,7 +394,7 @@ int launch_update128(Ctx* ctx, hipStream_t stream, const double* Lop, int64_t ld
 // no message and no update launch (k_s_panel / k_s_schur_sigma).
 bool panel_in_s(const Ctx* ctx, int64_t p) {
     const Geo& g = ctx->g;
-    if (!ctx->s_fast || !ctx->skip_zeros || g.mi == 0 || !ctx->grp_of.empty() || ctx->cond_active) return false;
+    if (!ctx->skip_zeros || g.mi == 0 || !ctx->grp_of.empty() || ctx->cond_active) return false;
     const int64_t c0 = g.panel_c0(p);
     return c0 >= g.n && c0 + g.panel_w(p) <= g.n + g.mi;
 }
@@ -464,32 +450,27 @@ int factor_panel(Ctx* ctx, int64_t p, hipStream_t stream, bool apply_pending) {
     if (apply_pending && poff != 0) {
         const int64_t p0 = p - poff;
         const int K = (int)((p - p0) * g.nb);
-        if (g.Npad - c0 <= ctx->pending32_rows) {
+        if (g.Npad - c0 <= PENDING32_ROWS) {
             int64_t pa0, pa1, pb0, pb1;
             active_ranges(ctx, g.panel_c0(p0), g.panel_c0(p0) + K, &pa0, &pa1, &pb0, &pb1);
             hipLaunchKernelGGL(k_inpanel_update, dim3((unsigned)((g.Npad - c0) / 32), (unsigned)(nbw / TB)), dim3(256), 0, stream,
                                ctx->A, g.Npad, lc0, ctx->A + g.local_c0(p0) * g.Npad, g.Npad, wbuf(ctx, p0), g.Npad, c0, K, c0,
-                               g.Npad, pa0, pa1, pb0, pb1, ctx->side_prio);
+                               g.Npad, pa0, pa1, pb0, pb1, SIDE_PRIO);
             PYIPM_KCHECK();
         } else {
             int rc = launch_update128(ctx, stream, ctx->A + g.local_c0(p0) * g.Npad, g.Npad, wbuf(ctx, p0),
-                                      K, c0, lp, 1, /*bulk=*/false, 0, 0, 0, g.panel_c0(p0));
+                                      K, c0, lp, 1, {.bulk = false, .src_c0 = g.panel_c0(p0)});
             if (rc) return rc;
         }
     }
     // Panels inside the x block: the slack rows of the panel are exact zeros (active_ranges), whole 128-row tiles of
-    // them are skipped by the in-panel updates and the scalings too (single rank only: a receiver rebuilds L from W).
-    int64_t ha0 = 0, ha1 = g.Npad, hb0 = 0, hb1 = 0, hole0 = 0, hole1 = 0;
+    // them are skipped by the scalings (single rank only: a receiver rebuilds L from W).
+    int64_t hole0 = 0, hole1 = 0;
     // Only when the whole GROUP lies in the x block: a group's bulk update reads every W row the structure of its
     // source columns allows, so a mixed group needs all of them written.
     const bool grp_in_x = (size_t)p < ctx->grp_of.size() && !ctx->grp_x.empty() && ctx->grp_x[(size_t)ctx->grp_of[p]];
-    if (ctx->skip_zeros && g.world == 1 && g.mi > 0 && grp_in_x) {
-        active_ranges(ctx, c0, c0 + nbw, &ha0, &ha1, &hb0, &hb1);
-        slack_hole(g, &hole0, &hole1);
-    } else {
-        panel_hole(ctx, p, &hole0, &hole1);             // per-panel mode (any number of ranks)
-        if (hole1 > hole0) active_ranges(ctx, c0, c0 + nbw, &ha0, &ha1, &hb0, &hb1);
-    }
+    if (ctx->skip_zeros && g.world == 1 && g.mi > 0 && grp_in_x) slack_hole(g, &hole0, &hole1);
+    else panel_hole(ctx, p, &hole0, &hole1);            // per-panel mode (any number of ranks)
     if (ctx->tile_step && ctx->per_panel_mode && ctx->wide_sub >= 128 && ctx->wide_sub % 128 == 0 &&
         nbw > ctx->wide_sub && nt <= 32 && c0 + nbw < g.Npad)
         return factor_wide_panel(ctx, p, stream);
@@ -507,19 +488,12 @@ int factor_panel(Ctx* ctx, int64_t p, hipStream_t stream, bool apply_pending) {
         }
         return 0;
     }
-    const bool fused = ctx->fuse_su != 0;                   // a tile's scaling launch also updates the next column block
+    // panels of more than 16 tiles: one inversion and one scaling launch per tile; the scaling launch also updates the next
+    // tile's column block with the tiles before it (NextUpd): two dependent launches per tile instead of three
     for (int t = 0; t < nt; ++t) {
         const int64_t j0 = c0 + (int64_t)t * TB, lcol = lc0 + (int64_t)t * TB;
         const int64_t below = g.Npad - (j0 + TB);
-        if (t > 0 && !fused) {
-            // left-looking in-panel update of this tile's column block with the t tiles before it (32-row blocks)
-            const int64_t row_begin = (j0 / 32) * 32;
-            hipLaunchKernelGGL(k_inpanel_update, dim3((unsigned)((g.Npad - row_begin) / 32)), dim3(256), 0, stream,
-                               ctx->A, g.Npad, lcol, ctx->A + lc0 * g.Npad, g.Npad, W, g.Npad, j0, t * TB, row_begin, g.Npad,
-                               ha0, ha1, hb0, hb1, ctx->side_prio);
-            PYIPM_KCHECK();
-        }
-        const bool next = fused && t + 1 < nt && below > 0;   // the scaling launch below carries the update of tile t + 1
+        const bool next = t + 1 < nt && below > 0;   // the scaling launch below carries the update of tile t + 1
         hipLaunchKernelGGL(k_tile_invert, dim3(1), dim3(256), 0, stream, ctx->A, g.Npad, j0, lcol,
                            ctx->Dinv + (j0 / TB) * (int64_t)(TB * TB), ctx->Tsv + (j0 / TB) * (int64_t)(TB * TB),
                            ctx->Tflag + j0 / TB, ctx->refine_cond, ctx->dstats, g.N, ctx->pivtol_rel, ctx->anorm,
@@ -546,7 +520,7 @@ int ensure_rest_stream(Ctx* ctx) {
     if (!ctx->rest) {
         int lo = 0, hi = 0;
         PYIPM_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        PYIPM_HIP(hipStreamCreateWithPriority(&ctx->rest, hipStreamNonBlocking, ctx->rest_prio ? hi : lo));
+        PYIPM_HIP(hipStreamCreateWithPriority(&ctx->rest, hipStreamNonBlocking, hi));
     }
     return 0;
 }
@@ -622,10 +596,10 @@ int launch_tile_steps(Ctx* ctx, hipStream_t chain, int64_t gc0, int64_t glc0, in
         // (all launches: exposed panel 7.1 -> 10.9 ms at N = 32768; the per-panel schedule, whose ranks run their bulk updates
         // beside every chain: owners' chain path 31.0 -> 32.1 ms in the replay -- it keeps the 256-thread kernel)
         const int64_t m_left = g.Npad - gc0;
-        if (ctx->tile_waves == 8 && (ctx->per_panel_mode ? ctx->tile8_dist != 0 : (gc0 == 0 || m_left <= ctx->tile8_rows))) {
+        if (ctx->tile_waves == 8 && !ctx->per_panel_mode && (gc0 == 0 || m_left <= ctx->tile8_rows)) {
             const int units = (nT - j - 1) * ny;
-            const int free_cus = (gc0 == 0 || ctx->reserve_cus <= 0 || ctx->per_panel_mode) ? ctx->num_cus : ctx->tile_free_cus;
-            const int upb = ctx->tile_upb > 0 ? ctx->tile_upb : (units + 1 <= free_cus ? 1 : 2);
+            const int free_cus = (gc0 == 0 || ctx->reserve_cus <= 0) ? ctx->num_cus : TILE_FREE_CUS;
+            const int upb = units + 1 <= free_cus ? 1 : 2;          // (row tile, y) units per 512-thread block
             const unsigned nblk = 1u + (unsigned)((units + upb - 1) / upb);
             hipLaunchKernelGGL(k_tile_step8, dim3(nblk), dim3(512), 0, chain, ctx->A, g.Npad, gc0, glc0, j, nT, ny, upb,
                                Wg, g.Npad, Dv, Ts, ctx->Tflag + gc0 / TB, ctx->refine_cond, ctx->block_refine, ctx->dstats, g.N,
@@ -666,11 +640,11 @@ int factor_block(Ctx* ctx, const BlockDesc& bd, hipStream_t chain, const std::fu
     auto upd = [&](hipStream_t st, const double* Lop, const double* Wop, int K, int64_t row_begin, int64_t k1, int64_t cnt,
                    int64_t src_c0) -> int {
         if (!bd.wide)
-            return launch_update128(ctx, st, Lop, g.Npad, Wop, K, row_begin, bd.sp[(size_t)k1].id, cnt, /*bulk=*/false, 0, 0, 0, src_c0);
+            return launch_update128(ctx, st, Lop, g.Npad, Wop, K, row_begin, bd.sp[(size_t)k1].id, cnt, {.bulk = false, .src_c0 = src_c0});
         const int s0 = (int)((bd.sp[(size_t)k1].c0 - g.panel_c0(bd.lp * g.world + g.rank)) / 128);
         const int nc = (int)((int64_t)(toff[(size_t)(k1 + cnt)] - toff[(size_t)k1]) * TB / 128);
-        return launch_update128(ctx, st, Lop, g.Npad, Wop, K, row_begin, bd.lp, 1, /*bulk=*/false, 0, 0, 0, src_c0,
-                                1, 0, 0, 0, nullptr, nullptr, false, s0, nc);
+        return launch_update128(ctx, st, Lop, g.Npad, Wop, K, row_begin, bd.lp, 1,
+                                {.bulk = false, .src_c0 = src_c0, .sub0 = s0, .nct_sub = nc});
     };
     // sub-panel q's columns are final inside the diagonal block once the first tile of sub-panel q + 1 has applied its last
     // stage: the tile steps run in pieces that END with that step, an event after each
@@ -715,7 +689,7 @@ int factor_block(Ctx* ctx, const BlockDesc& bd, hipStream_t chain, const std::fu
         // are applied LEFT-looking -- all earlier sub-panels at once (K up to 768), right before the sub-panel's own
         // stages -- instead of one by one: half the read-modify-write passes over those rows and longer K per launch.
         // In the tail the one-by-one form keeps only the last sub-panel's stages behind the chain.  Same bits either way.
-        const bool left = ctx->pending_left_rows >= 0 && g.Npad - gend > ctx->pending_left_rows;
+        const bool left = g.Npad - gend > PENDING_LEFT_ROWS;
         if (g.Npad > gend && left && k > 0) {
             const int K = toff[(size_t)k] * TB;
             int rc = upd(rs, ctx->A + glc0 * g.Npad, Wg, K, gend, k, 1, gc0);
@@ -731,12 +705,12 @@ int factor_block(Ctx* ctx, const BlockDesc& bd, hipStream_t chain, const std::fu
                 const int K = nt * TB;
                 const SubPanel& nx = bd.sp[(size_t)k + 1];
                 const int64_t tc0 = nx.c0, ncols = (int64_t)(nT - toff[(size_t)k + 1]) * TB;
-                if (g.Npad - tc0 <= ctx->pending32_rows) {
+                if (g.Npad - tc0 <= PENDING32_ROWS) {
                     int64_t pa0, pa1, pb0, pb1;
                     active_ranges(ctx, c0, c0 + K, &pa0, &pa1, &pb0, &pb1);
                     hipLaunchKernelGGL(k_inpanel_update, dim3((unsigned)((g.Npad - gend) / 32), (unsigned)(ncols / TB)), dim3(256), 0,
                                        rs, ctx->A, g.Npad, nx.lc0, ctx->A + lc0 * g.Npad, g.Npad, q.W, g.Npad,
-                                       tc0, K, gend, g.Npad, pa0, pa1, pb0, pb1, ctx->side_prio);
+                                       tc0, K, gend, g.Npad, pa0, pa1, pb0, pb1, SIDE_PRIO);
                     PYIPM_KCHECK();
                 } else {
                     int rc = upd(rs, ctx->A + lc0 * g.Npad, q.W, K, gend, k + 1, n0 - 1 - k, c0);
@@ -854,14 +828,14 @@ int panel_rows(Ctx* ctx, int64_t p, int64_t r0, int64_t r1, hipStream_t stream) 
     // of it takes the same kernels)
     const int snt = ctx->wide_sub / TB;
     const int64_t gend = c0 + nbw, lp = p / g.world;
-    const bool left = ctx->pending_left_rows >= 0 && g.Npad - gend > ctx->pending_left_rows;
+    const bool left = g.Npad - gend > PENDING_LEFT_ROWS;
     for (int t = 0; t < nt; t += snt) {
         const int w = nt - t < snt ? nt - t : snt;
         const int64_t sc0 = c0 + (int64_t)t * TB, slc0 = lc0 + (int64_t)t * TB;
         double* sW = W + (int64_t)t * TB * g.Npad;
         if (left && t > 0) {
-            int rc = launch_update128(ctx, stream, ctx->A + lc0 * g.Npad, g.Npad, W, t * TB, r0, lp, 1, /*bulk=*/false, 0, r1, 0, c0,
-                                      1, 0, 0, 0, nullptr, nullptr, false, (t * TB) / 128, (w * TB) / 128);
+            int rc = launch_update128(ctx, stream, ctx->A + lc0 * g.Npad, g.Npad, W, t * TB, r0, lp, 1,
+                                      {.bulk = false, .row_end = r1, .src_c0 = c0, .sub0 = (t * TB) / 128, .nct_sub = (w * TB) / 128});
             if (rc) return rc;
         }
         hipLaunchKernelGGL(k_panel_rest, dim3((unsigned)((r1 - r0) / TB)), dim3(256), 0, stream, ctx->A, g.Npad, sc0, slc0, w, r0,
@@ -871,16 +845,16 @@ int panel_rows(Ctx* ctx, int64_t p, int64_t r0, int64_t r1, hipStream_t stream) 
         if (!left && t + w < nt) {
             const int K = w * TB;
             const int64_t tc0 = sc0 + K, ncols = (int64_t)(nt - t - w) * TB;
-            if (g.Npad - tc0 <= ctx->pending32_rows) {
+            if (g.Npad - tc0 <= PENDING32_ROWS) {
                 int64_t pa0, pa1, pb0, pb1;
                 active_ranges(ctx, sc0, sc0 + K, &pa0, &pa1, &pb0, &pb1);
                 hipLaunchKernelGGL(k_inpanel_update, dim3((unsigned)((r1 - r0) / 32), (unsigned)(ncols / TB)), dim3(256), 0, stream,
                                    ctx->A, g.Npad, slc0 + K, ctx->A + slc0 * g.Npad, g.Npad, sW, g.Npad, tc0, K, r0, g.Npad,
-                                   pa0, pa1, pb0, pb1, ctx->side_prio);
+                                   pa0, pa1, pb0, pb1, SIDE_PRIO);
                 PYIPM_KCHECK();
             } else {
-                int rc = launch_update128(ctx, stream, ctx->A + slc0 * g.Npad, g.Npad, sW, K, r0, lp, 1, /*bulk=*/false, 0, r1, 0, sc0,
-                                          1, 0, 0, 0, nullptr, nullptr, false, ((t + w) * TB) / 128, (int)(ncols / 128));
+                int rc = launch_update128(ctx, stream, ctx->A + slc0 * g.Npad, g.Npad, sW, K, r0, lp, 1,
+                                          {.bulk = false, .row_end = r1, .src_c0 = sc0, .sub0 = ((t + w) * TB) / 128, .nct_sub = (int)(ncols / 128)});
                 if (rc) return rc;
             }
         }
@@ -981,11 +955,9 @@ int unpack_panel_from(Ctx* ctx, int64_t p, const double* buf, int64_t row_from, 
 
 // One bulk k_update<128> launch: panels [p0, p0+np) (contiguous, same rank) applied with K = their total
 // width to local panels [first_lp, first_lp+n_lp); timed with HIP events on the handle's stream.
-int timed_update(Ctx* ctx, int64_t p0, int64_t np, int64_t first_lp, int64_t n_lp, hipStream_t stream,
-                 int head_ct, unsigned* head_counter, unsigned* head_count, bool list_only,
-                 bool as_bulk) {             // as_bulk: a bulk launch although it runs on another stream
+int timed_update(Ctx* ctx, int64_t p0, int64_t np, int64_t first_lp, int64_t n_lp, const UpdTimed& o) {
     const Geo& g = ctx->g;
-    if (!stream) stream = ctx->stream;
+    hipStream_t stream = o.stream ? o.stream : ctx->stream;
     if (n_lp <= 0) return 0;
     int K = 0;
     for (int64_t q = p0; q < p0 + np; ++q) K += (int)g.panel_w(q);
@@ -1016,10 +988,7 @@ int timed_update(Ctx* ctx, int64_t p0, int64_t np, int64_t first_lp, int64_t n_l
     // A launch on another stream than the handle's is a lookahead head riding the chain's stream: it overlaps the bulk launch
     // on the main stream, so its duration says nothing about the kernel's rate -- it is not part of the "trailing" figures
     // (time, flops, launches), and it uses the 4-wave instance of the kernel so that a kernel trace keeps the two apart.
-    const bool chain_side = stream != ctx->stream && !ctx->per_panel_mode && !as_bulk;
-    if (list_only)                                      // fused head: only build / look up the tile list (how many head tiles?)
-        return launch_update128(ctx, stream, Lop, g.Npad, wbuf(ctx, p0), K, row_begin, first_lp, n_lp, true, 0, 0, 0,
-                                g.panel_c0(p0), 1, 0, 0, head_ct, head_counter, head_count, true);
+    const bool chain_side = stream != ctx->stream && !ctx->per_panel_mode && !o.as_bulk;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     int used_bn = 128;
     if (ctx->profile && !chain_side) {
@@ -1031,18 +1000,17 @@ int timed_update(Ctx* ctx, int64_t p0, int64_t np, int64_t first_lp, int64_t n_l
         e0 = ctx->ev_trailing[ctx->n_trailing].first; e1 = ctx->ev_trailing[ctx->n_trailing].second;
         PYIPM_HIP(hipEventRecord(e0, stream));
     }
-    if (ctx->per_panel_mode && n_lp == 1 && g.Npad - row_begin <= ctx->head32_rows_dist) {
+    if (ctx->per_panel_mode && n_lp == 1 && g.Npad - row_begin <= HEAD32_ROWS_DIST) {
         // one panel of columns (the head of the per-panel schedule): 32 x 64 blocks instead of a handful of 128 x 128 tiles
         int64_t pa0, pa1, pb0, pb1;
         active_ranges(ctx, g.panel_c0(p0), g.panel_c0(p0) + K, &pa0, &pa1, &pb0, &pb1);
         hipLaunchKernelGGL(k_inpanel_update, dim3((unsigned)((g.Npad - row_begin) / 32), (unsigned)(g.panel_w(q0) / TB)), dim3(256), 0,
                            stream, ctx->A, g.Npad, first_lp * (int64_t)g.nb, Lop, g.Npad, wbuf(ctx, p0), g.Npad, row_begin, K,
-                           row_begin, g.Npad, pa0, pa1, pb0, pb1, ctx->side_prio);
+                           row_begin, g.Npad, pa0, pa1, pb0, pb1, SIDE_PRIO);
         PYIPM_KCHECK();
     } else {
-        int rc = launch_update128(ctx, stream, Lop, g.Npad, wbuf(ctx, p0), K, row_begin, first_lp, n_lp, true, 0, 0, 0,
-                                  g.panel_c0(p0), 1, 0, chain_side ? ctx->head_waves : 0, head_ct, head_counter, head_count, false, 0, 0,
-                                  &used_bn);
+        int rc = launch_update128(ctx, stream, Lop, g.Npad, wbuf(ctx, p0), K, row_begin, first_lp, n_lp,
+                                  {.src_c0 = g.panel_c0(p0), .waves = chain_side ? HEAD_WAVES : 0, .used_bn = &used_bn});
         if (rc) return rc;
     }
     if (chain_side) return 0;
@@ -1218,7 +1186,7 @@ int bwd_panel(Ctx* ctx, int64_t p, double* v, int nrhs, int64_t vstride, double*
                            c0 + nbw, g.Npad, v, part, vstride, pstride, a0, a1, b0, b1);
         PYIPM_KCHECK();
     }
-    if (ctx->bwd_diag4 && nbw <= 4 * TB)
+    if (nbw <= 4 * TB)                                  // on 1024 threads through shared memory; wider panels: thread k walks down column k
         hipLaunchKernelGGL(k_bwd_diag4, dim3(1, nrhs), dim3(1024), 0, ctx->stream, ctx->A, g.Npad, lc0, c0, nbw,
                            g.nb, part, nchunk, v, vstride, pstride);
     else
@@ -1438,7 +1406,7 @@ int solve_many(Ctx* ctx, int64_t k, const double* rhs, int64_t ld_rhs, double* d
                int memkind) {
     const Geo& g = ctx->g;
     const hipStream_t st = ctx->stream;
-    if (ctx->cond_active && refine >= 0 && refine < ctx->cond_min_refine) refine = ctx->cond_min_refine;
+    refine = refine_steps(ctx, refine);                 // (the buffers below depend on it)
     const bool adaptive = refine < 0;
     const int64_t kpad = (k + MS_KB - 1) / MS_KB * MS_KB, Np = g.Npad, Nc = ctx->cond_active ? ctx->gc.Npad : 0;
     const size_t col = (size_t)Np * (size_t)kpad;
@@ -1470,18 +1438,17 @@ int solve_many(Ctx* ctx, int64_t k, const double* rhs, int64_t ld_rhs, double* d
         PYIPM_HIP(hipMemsetAsync(R, 0, col * sizeof(double), st));             // (its pad columns stay zero)
     }
     int rc = solve_many_inplace(ctx, X, k, kpad, part, Xc); if (rc) return rc;
-    // refinement as in solve_finish, column by column for the product, all columns at once for the solve; the adaptive
-    // loop follows the WORST column's backward error
-    ctx->info_steps = 0; ctx->info_converged = 0; ctx->info_berr0 = -1.0; ctx->info_berr = -1.0;
-    const int maxit = adaptive ? ctx->refine_max : refine;
+    // refinement: column by column for the product, all columns at once for the solve; the adaptive loop follows the WORST
+    // column's backward error
     std::vector<double> ss(adaptive ? 2 * (size_t)k : 0);
-    double prev = -1.0;
-    for (int it = 0; it <= maxit; ++it) {
-        if (!adaptive && it == maxit) break;
-        for (int64_t j = 0; j < k; ++j) { rc = kkt_matvec_dev(ctx, X + j * Np, R + j * Np); if (rc) return rc; }
-        hipLaunchKernelGGL(k_axpby, grid1((int64_t)col), dim3(256), 0, st, R, B, R, 1.0, -1.0, (int64_t)col);
-        PYIPM_KCHECK();
-        if (adaptive) {
+    rc = refine_loop(ctx, refine,
+        [&]() -> int {                                          // R = B - Hc X
+            for (int64_t j = 0; j < k; ++j) { int r2 = kkt_matvec_dev(ctx, X + j * Np, R + j * Np); if (r2) return r2; }
+            hipLaunchKernelGGL(k_axpby, grid1((int64_t)col), dim3(256), 0, st, R, B, R, 1.0, -1.0, (int64_t)col);
+            PYIPM_KCHECK();
+            return 0;
+        },
+        [&](double* worst) -> int {
             hipLaunchKernelGGL(k_ms_sumsq2, dim3((unsigned)k), dim3(1024), 0, st, ss_dev, R, B, Np, g.N);
             PYIPM_KCHECK();
             PYIPM_HIP(hipMemcpyAsync(ss.data(), ss_dev, 2 * (size_t)k * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1491,24 +1458,18 @@ int solve_many(Ctx* ctx, int64_t k, const double* rhs, int64_t ld_rhs, double* d
                 const double b = ss[2 * j + 1] > 0.0 ? sqrt(ss[2 * j] / ss[2 * j + 1]) : sqrt(ss[2 * j]);
                 if (!(b <= berr) && berr == berr) berr = b;                        // (a NaN column makes the worst NaN)
             }
-            if (it == 0) ctx->info_berr0 = berr;
-            ctx->info_berr = berr;
-            if (prev >= 0.0 && !(berr <= prev)) {                                 // the last step made it worse (or NaN): take it back
-                PYIPM_HIP(hipMemcpyAsync(X, Xp, col * sizeof(double), hipMemcpyDeviceToDevice, st));
-                ctx->info_berr = prev; ctx->info_steps = it - 1;
-                break;
-            }
-            if (!(berr <= 1.0e300)) break;                                        // NaN / Inf: nothing to refine
-            if (berr <= ctx->refine_target) { ctx->info_converged = 1; break; }
-            if (it == maxit || (prev >= 0.0 && berr > 0.25 * prev)) break;        // out of budget / stagnating
-            prev = berr;
-            PYIPM_HIP(hipMemcpyAsync(Xp, X, col * sizeof(double), hipMemcpyDeviceToDevice, st));
-        }
-        rc = solve_many_inplace(ctx, R, k, kpad, part, Xc); if (rc) return rc;
-        hipLaunchKernelGGL(k_axpby, grid1((int64_t)col), dim3(256), 0, st, X, X, R, 1.0, 1.0, (int64_t)col);
-        PYIPM_KCHECK();
-        ctx->info_steps = it + 1;
-    }
+            *worst = berr;
+            return 0;
+        },
+        [&]() -> int { PYIPM_HIP(hipMemcpyAsync(Xp, X, col * sizeof(double), hipMemcpyDeviceToDevice, st)); return 0; },
+        [&]() -> int { PYIPM_HIP(hipMemcpyAsync(X, Xp, col * sizeof(double), hipMemcpyDeviceToDevice, st)); return 0; },
+        [&]() -> int {                                          // X += Hc^{-1} R
+            int r2 = solve_many_inplace(ctx, R, k, kpad, part, Xc); if (r2) return r2;
+            hipLaunchKernelGGL(k_axpby, grid1((int64_t)col), dim3(256), 0, st, X, X, R, 1.0, 1.0, (int64_t)col);
+            PYIPM_KCHECK();
+            return 0;
+        });
+    if (rc) return rc;
     const int64_t from = g.n + g.mi;
     if (flip && g.N > from) {
         hipLaunchKernelGGL(k_ms_flip, grid1((g.N - from) * k), dim3(256), 0, st, X, Np, from, g.N, k);
@@ -1519,10 +1480,6 @@ int solve_many(Ctx* ctx, int64_t k, const double* rhs, int64_t ld_rhs, double* d
     if (memkind == PYIPM_MEM_HOST) PYIPM_HIP(hipStreamSynchronize(st));
     return 0;
 }
-
-// y = Hc v from the staged blocks (Npad vectors on the device).  With several ranks every rank adds the terms of the
-// KKT columns it owns (row j of triu(d2L) | Je | Ji is column j of the lower triangle), rank 0 the element-wise s /
-// multiplier part; the caller sums y over the ranks (dist_impl.hpp).
 
 // y[0:n) = sym(triu(d2L)) v + delta v for the rows / columns this rank works on: one pass over the upper triangle
 // (k_symv_tiles + k_symv_finish; ctx->partial holds the partials)
@@ -1544,6 +1501,10 @@ int symv_dev(Ctx* ctx, const double* v, double* y, double delta, const RowMap& r
     PYIPM_KCHECK();
     return 0;
 }
+
+// y = Hc v from the staged blocks (Npad vectors on the device).  With several ranks every rank adds the terms of the
+// KKT columns it owns (row j of triu(d2L) | Je | Ji is column j of the lower triangle), rank 0 the element-wise s /
+// multiplier part; the caller sums y over the ranks (dist_impl.hpp).
 int kkt_matvec_dev(Ctx* ctx, const double* v, double* y) {
     const Geo& g = ctx->g;
     const int64_t n = g.n, me = g.me, mi = g.mi;
@@ -1614,7 +1575,7 @@ int residual_dev(Ctx* ctx) {
 //   A (ld = gc.Npad) <- tril [[H + delta I, Jx], [Jx', D]]   by K1 on the condensed geometry, Jx = [Je | Ji_A],
 //                        D = diag(-delta_c I, -1/Sigma_A);
 //   += Ji_I Sigma_I Ji_I'   as ONE rank-mi launch of the MFMA update kernel (C += JT * WT').
-void asm_grid(const Ctx* ctx, const Geo& g, dim3* grid, int* tri);
+void asm_grid(const Geo& g, dim3* grid, int* tri);
 int assemble_condensed(Ctx* ctx, double delta, double delta_c) {
     const Geo& g = ctx->g;
     const int64_t nx = (g.n + BM - 1) / BM * BM;                 // rows / columns of the x-x block the Gram launch touches
@@ -1660,7 +1621,7 @@ int assemble_condensed(Ctx* ctx, double delta, double delta_c) {
     }
     {
         dim3 grid; int tri = 0;
-        asm_grid(ctx, gc, &grid, &tri);
+        asm_grid(gc, &grid, &tri);
         PYIPM_HIP(hipMemsetAsync(ctx->anorm, 0, sizeof(unsigned long long), ctx->stream));
         hipLaunchKernelGGL(k_assemble, grid, dim3(256), 0, ctx->stream, ctx->A, gc.Npad, gc, ctx->d2L, ctx->ld_d2L,
                            Jx, ldx, (const double*)nullptr, (int64_t)0, ctx->s, ctx->lda, ctx->eps, delta, delta_c, ctx->anorm, 0, 0, 0, (int64_t)0, tri);
@@ -1684,7 +1645,7 @@ int assemble_condensed(Ctx* ctx, double delta, double delta_c) {
         // 0 .. ceil(#panels / world) - 1; a local panel past the block is cut off by col_end)
         const int64_t npx = (nx + gc.nb - 1) / gc.nb;
         int rc = launch_update128(ctx, ctx->stream, ctx->JT, ldt, ctx->WT, (int)mi_pad, 0, 0, (npx + gc.world - 1) / gc.world,
-                                  true, ldt, nx, nx);
+                                  {.ldw = ldt, .row_end = nx, .col_end = nx});
         if (rc) return rc;
     }
     if (ctx->profile) PYIPM_HIP(hipEventRecord(ctx->ev[7], ctx->stream));
@@ -1694,10 +1655,10 @@ int assemble_condensed(Ctx* ctx, double delta, double delta_c) {
 // Grid of a whole-matrix k_assemble launch.  Single rank, Npad a multiple of 512: a 1-D grid over the 512 x 16 patches on or
 // below the diagonal only (round 4: the 2-D grid started as many workgroups above the diagonal that returned at once --
 // 65000 of them at N = 32768 cost 0.5 of K1's 1.5 ms; with them gone K1 moves its algorithmic bytes at 6.5 TB/s).
-void asm_grid(const Ctx* ctx, const Geo& g, dim3* grid, int* tri) {
+void asm_grid(const Geo& g, dim3* grid, int* tri) {
     *grid = dim3((unsigned)((g.Npad + 511) / 512), (unsigned)((g.ncols_local + 15) / 16));
     *tri = 0;
-    if (ctx->asm_tri && g.world == 1 && g.Npad % 512 == 0) {
+    if (g.world == 1 && g.Npad % 512 == 0) {
         const int64_t nbx = g.Npad / 512, ngrp = (g.ncols_local / 16 + 31) / 32;          // column patches in groups of 32
         int64_t tot = 0;
         for (int64_t G = 0; G < ngrp; ++G) tot += 32 * (nbx - G);
@@ -1709,7 +1670,7 @@ void asm_grid(const Ctx* ctx, const Geo& g, dim3* grid, int* tri) {
 int64_t first_group_panels(const Ctx* ctx) {
     const Geo& g = ctx->g;
     const int tg = (!ctx->tail_group_user && g.Npad <= 8192) ? 8 : ctx->tail_group;
-    int64_t G = (tg > 0 && g.Npad <= ctx->tail_cols) ? tg : ctx->group;
+    int64_t G = (tg > 0 && g.Npad <= TAIL_COLS) ? tg : ctx->group;
     if (G > ctx->group) G = ctx->group;
     if (G > g.npanels) G = g.npanels;
     return G;
@@ -1738,7 +1699,7 @@ int assemble_dev(Ctx* ctx, double delta, double delta_c) {
     if (g.ncols_local > 0) {
         const int zip = (ctx->keep_zeros && !ctx->storage_exported && ctx->zeros_clean && g.world == 1 && g.mi > 0) ? 1 : 0;
         dim3 grid; int tri = 0;
-        asm_grid(ctx, g, &grid, &tri);
+        asm_grid(g, &grid, &tri);
         hipLaunchKernelGGL(k_assemble, grid, dim3(256), 0, ctx->stream, ctx->A, g.Npad, g, ctx->d2L, ctx->ld_d2L,
                            ctx->Je, ctx->ld_Je, ctx->Ji, ctx->ld_Ji, ctx->s, ctx->lda, ctx->eps, delta, delta_c, ctx->anorm, 0, ctx->sharded,
                            zip, (int64_t)0, tri);
@@ -1773,7 +1734,7 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
     }
     PYIPM_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
     // Group schedule: `group` panels per bulk update while the bulk update outlasts the panel chain; once at most
-    // tail_cols columns remain the chain is the critical path and shorter groups (less in-group update work on
+    // TAIL_COLS columns remain the chain is the critical path and shorter groups (less in-group update work on
     // the chain, more in the cheap bulk launches) end the factorisation sooner.
     const int64_t np = g.npanels;
     ctx->grp_of.assign((size_t)np, 0); ctx->grp_off.assign((size_t)np, 0); ctx->grp_first.clear();
@@ -1785,13 +1746,13 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
             //  boundary costs more than the in-group updates of the longer group: config 2 2.25 against 2.29 ms; N = 32768: 104.9
             //  against 102.4 ms, config 3 185.4 against 183.2: 4 stays there)
             const int tg = (!ctx->tail_group_user && g.Npad <= 8192) ? 8 : ctx->tail_group;
-            int64_t G = (tg > 0 && remaining <= ctx->tail_cols) ? tg : ctx->group;
+            int64_t G = (tg > 0 && remaining <= TAIL_COLS) ? tg : ctx->group;
             if (G > ctx->group) G = ctx->group;
             if (p + G > np) G = np - p;
-            // (round 5) the panels inside the slack block as ONE group: their kernels run up front (s_early) and what is left of
+            // (round 5) the panels inside the slack block as ONE group: their kernels run up front (enqueue_slack_first) and what is left of
             // a slack group in the loop below is a head, a k_s_schur launch and four stream hops -- 56 us per group of four
             // panels between the x block's last bulk update and the multiplier block's first chain (N = 32768: six groups)
-            if (ctx->s_early && ctx->s_fast && ctx->skip_zeros && g.mi > 0 && g.world == 1 && ctx->lookahead && p > 0 &&
+            if (ctx->skip_zeros && g.mi > 0 && g.world == 1 && ctx->lookahead && p > 0 &&
                 g.panel_c0(p) >= g.n && g.panel_c0(p + G - 1) + g.panel_w(p + G - 1) <= g.n + g.mi) {
                 while (p + G < np && g.panel_c0(p + G) + g.panel_w(p + G) <= g.n + g.mi) ++G;
             }
@@ -1806,7 +1767,7 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
             const int64_t pb = ctx->grp_first[gi + 1];
             ctx->grp_x[gi] = (g.panel_c0(pb - 1) + g.panel_w(pb - 1) <= g.n) ? 1 : 0;
         }
-        if (ctx->s_fast && ctx->skip_zeros && g.mi > 0 && g.world == 1)
+        if (ctx->skip_zeros && g.mi > 0 && g.world == 1)       // groups inside the slack block: closed-form elimination (k_s_panel)
             for (size_t gi = 0; gi + 1 < ctx->grp_first.size(); ++gi) {
                 const int64_t pa = ctx->grp_first[gi], pb = ctx->grp_first[gi + 1];
                 const int64_t ca = g.panel_c0(pa), cb = g.panel_c0(pb - 1) + g.panel_w(pb - 1);
@@ -1835,7 +1796,7 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
         PYIPM_HIP(hipEventRecord(ctx->ev_head, ctx->stream));          // v0 = rhs copy was enqueued on the main stream
         PYIPM_HIP(hipStreamWaitEvent(ctx->fwd, ctx->ev_head, 0));
     }
-    std::vector<char> s_done_early((size_t)np, 0);     // closed-form panels of the slack block already enqueued (s_early, below)
+    std::vector<char> s_done_early((size_t)np, 0);     // closed-form panels of the slack block already enqueued (enqueue_slack_first, below)
     auto after_panel = [&](int64_t q, hipStream_t used) -> int {
         if (!fuse_forward) return 0;
         if (!s_done_early[(size_t)q]) PYIPM_HIP(hipEventRecord(ctx->ev_done[q], used));      // (else: recorded behind its kernel)
@@ -1860,13 +1821,13 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
     // (n, me, mi = 3072, 512, 1024: 2.99 -> 3.08 ms): not applied there.  Fewer, persistent blocks per piece (64 ... 192
     // of them) only made the last piece longer.
     const bool early0 = ctx->lookahead >= 2 && ngroups > 2 && chain_group(0) && !ctx->grp_fast.empty() && !ctx->grp_fast[0] &&
-                        ctx->grp_fast[1] && ctx->s_early && ctx->head_on_side;
+                        ctx->grp_fast[1];
     if (early0 && !ctx->ev_early) PYIPM_HIP(hipEventCreateWithFlags(&ctx->ev_early, hipEventDisableTiming));
     auto early_piece = [&](int64_t q, hipStream_t used) -> int {
         const int64_t p1 = ctx->grp_first[1];
         PYIPM_HIP(hipEventRecord(ctx->ev_early, used));
         PYIPM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_early, 0));
-        return timed_update(ctx, q, 1, p1, np - p1, ctx->side, 0, nullptr, nullptr, false, /*as_bulk=*/true);
+        return timed_update(ctx, q, 1, p1, np - p1, {.stream = ctx->side, .as_bulk = true});
     };
     // all panels of one group on stream S
     auto run_group = [&](int64_t grp, hipStream_t S) -> int {
@@ -1882,14 +1843,14 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
         }
         return 0;
     };
-    // s_early (round 5): the closed-form panels of the slack block depend on nothing but the assembly -- no x-block update
+    // (round 5) The closed-form panels of the slack block depend on nothing but the assembly -- no x-block update
     // reaches their columns -- and used to sit, one 7 us launch after the other, between the x block's last chain and the
     // multiplier block's first (config 2: 0.15 of 2.7 ms, plus the last x group's bulk update queued behind them on the same
     // stream).  They are enqueued up front on the rows stream; what READS them (k_s_schur on the update stream, the forward
     // sweep) keeps its place and waits for one event.  Statistics are atomic sums / minima / maxima: the same numbers.
-    bool s_early = false;
-    auto enqueue_s_early = [&](hipStream_t after) -> int {
-        if (!(ctx->s_early && ctx->lookahead && g.world == 1 && ngroups > 1) || ctx->grp_fast.empty()) return 0;
+    bool slack_first = false;                          // ... done for this factorisation
+    auto enqueue_slack_first = [&](hipStream_t after) -> int {
+        if (!(ctx->lookahead && g.world == 1 && ngroups > 1) || ctx->grp_fast.empty()) return 0;
         bool any = false;
         for (int64_t gi = 1; gi < ngroups; ++gi) any = any || ctx->grp_fast[(size_t)gi];
         if (!any || (ctx->grp_fast[0])) return 0;
@@ -1906,11 +1867,11 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
             }
         }
         PYIPM_HIP(hipEventRecord(ctx->ev_sfast, ctx->rest));              // every closed-form panel is done
-        s_early = true;
+        slack_first = true;
         return 0;
     };
     rc = factor_begin(ctx); if (rc) return rc;
-    rc = enqueue_s_early(ctx->stream); if (rc) return rc;
+    rc = enqueue_slack_first(ctx->stream); if (rc) return rc;
     mark("chain+rows begin", 0, ctx->stream);
     rc = run_group(0, ctx->stream); if (rc) return rc;
     mark("chain+rows end", 0, ctx->stream);
@@ -1921,68 +1882,54 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
         if (ctx->lookahead) {
             // head: next group's columns (the next chain waits for it).  Sources: the panels of this group whose
             // contribution an early head has not applied yet (see below).
-            const int64_t hc0 = g.panel_c0(p1);
             const bool fast_src = !ctx->grp_fast.empty() && ctx->grp_fast[(size_t)grp];
             auto head_from = [&](int64_t q0, int64_t nq, int64_t tp, int64_t tn, hipStream_t hs, bool split = false) -> int {
                 const int64_t tc0 = g.panel_c0(tp);
-                if (split && !fast_src && g.Npad - tc0 <= ctx->head32_rows) {   // (where the chain is the bound)
-                    // The chain of the target group needs the head only inside that group's diagonal block (rows [tc0, tend));
-                    // the rows below it are first read by the group's rows stream.  Two launches: the block on the chain's
-                    // stream, the rest on ctx->rest behind it -- the same entries, the same operations.
+                if (!fast_src && g.Npad - tc0 <= HEAD32_ROWS) {            // (where the chain is the bound: 32 x 64 blocks)
                     int K = 0; int64_t cols = 0;
                     for (int64_t q = q0; q < q0 + nq; ++q) K += (int)g.panel_w(q);
                     for (int64_t q = tp; q < tp + tn; ++q) cols += g.panel_w(q);
                     const int64_t tend = tc0 + cols;
                     int64_t pa0, pa1, pb0, pb1;
                     active_ranges(ctx, g.panel_c0(q0), g.panel_c0(q0) + K, &pa0, &pa1, &pb0, &pb1);
-                    if (tend < g.Npad) {
+                    // split: the chain of the target group needs the head only inside that group's diagonal block (rows [tc0, tend));
+                    // the rows below it are first read by the group's rows stream.  Two launches: the block on the chain's
+                    // stream, the rest on ctx->rest behind it -- the same entries, the same operations.
+                    const bool below = split && tend < g.Npad;
+                    if (below) {
                         int r2 = ensure_rest_stream(ctx); if (r2) return r2;
                         if (!ctx->ev_split) PYIPM_HIP(hipEventCreateWithFlags(&ctx->ev_split, hipEventDisableTiming));
                         PYIPM_HIP(hipEventRecord(ctx->ev_split, hs));          // the source group is complete, the main stream's
                         PYIPM_HIP(hipStreamWaitEvent(ctx->rest, ctx->ev_split, 0));   // earlier updates of these columns are ordered
                     }
-                    hipLaunchKernelGGL(k_inpanel_update, dim3((unsigned)(cols / 32), (unsigned)(cols / TB)), dim3(256), 0,
+                    // W of a panel inside its group's buffer: wbuf(q0) addresses it (column offset of q0 in the group)
+                    const int64_t rows = split ? cols : g.Npad - tc0;
+                    hipLaunchKernelGGL(k_inpanel_update, dim3((unsigned)(rows / 32), (unsigned)(cols / TB)), dim3(256), 0,
                                        hs, ctx->A, g.Npad, g.local_c0(tp), ctx->A + g.local_c0(q0) * g.Npad, g.Npad,
-                                       wbuf(ctx, q0), g.Npad, tc0, K, tc0, g.Npad, pa0, pa1, pb0, pb1, ctx->side_prio);
+                                       wbuf(ctx, q0), g.Npad, tc0, K, tc0, g.Npad, pa0, pa1, pb0, pb1, SIDE_PRIO);
                     PYIPM_KCHECK();
-                    if (tend < g.Npad) {
-                        if (g.Npad - tend <= ctx->head32_rows) {
-                            hipLaunchKernelGGL(k_inpanel_update, dim3((unsigned)((g.Npad - tend) / 32), (unsigned)(cols / TB)), dim3(256), 0,
-                                               ctx->rest, ctx->A, g.Npad, g.local_c0(tp), ctx->A + g.local_c0(q0) * g.Npad, g.Npad,
-                                               wbuf(ctx, q0), g.Npad, tc0, K, tend, g.Npad, pa0, pa1, pb0, pb1, ctx->side_prio);
-                            PYIPM_KCHECK();
-                        } else {
-                            int r2 = launch_update128(ctx, ctx->rest, ctx->A + g.local_c0(q0) * g.Npad, g.Npad, wbuf(ctx, q0), K, tend, tp, tn,
-                                                      /*bulk=*/true, 0, 0, 0, g.panel_c0(q0), 1, 0, ctx->head_waves);
-                            if (r2) return r2;
-                        }
+                    if (below && g.Npad - tend <= HEAD32_ROWS) {
+                        hipLaunchKernelGGL(k_inpanel_update, dim3((unsigned)((g.Npad - tend) / 32), (unsigned)(cols / TB)), dim3(256), 0,
+                                           ctx->rest, ctx->A, g.Npad, g.local_c0(tp), ctx->A + g.local_c0(q0) * g.Npad, g.Npad,
+                                           wbuf(ctx, q0), g.Npad, tc0, K, tend, g.Npad, pa0, pa1, pb0, pb1, SIDE_PRIO);
+                        PYIPM_KCHECK();
+                    } else if (below) {
+                        return launch_update128(ctx, ctx->rest, ctx->A + g.local_c0(q0) * g.Npad, g.Npad, wbuf(ctx, q0), K, tend, tp, tn,
+                                                {.src_c0 = g.panel_c0(q0), .waves = HEAD_WAVES});
                     }
                     return 0;
                 }
-                if (!fast_src && g.Npad - tc0 <= ctx->head32_rows) {
-                    int K = 0; int64_t cols = 0;
-                    for (int64_t q = q0; q < q0 + nq; ++q) K += (int)g.panel_w(q);
-                    for (int64_t q = tp; q < tp + tn; ++q) cols += g.panel_w(q);
-                    int64_t pa0, pa1, pb0, pb1;
-                    active_ranges(ctx, g.panel_c0(q0), g.panel_c0(q0) + K, &pa0, &pa1, &pb0, &pb1);
-                    // W of a panel inside its group's buffer: wbuf(q0) addresses it (column offset of q0 in the group)
-                    hipLaunchKernelGGL(k_inpanel_update, dim3((unsigned)((g.Npad - tc0) / 32), (unsigned)(cols / TB)), dim3(256), 0,
-                                       hs, ctx->A, g.Npad, g.local_c0(tp), ctx->A + g.local_c0(q0) * g.Npad, g.Npad,
-                                       wbuf(ctx, q0), g.Npad, tc0, K, tc0, g.Npad, pa0, pa1, pb0, pb1, ctx->side_prio);
-                    PYIPM_KCHECK();
-                    return 0;
-                }
-                return timed_update(ctx, q0, nq, tp, tn, hs);
+                return timed_update(ctx, q0, nq, tp, tn, {.stream = hs});
             };
-            // The head follows the chain of this group on ITS stream when that is the side stream (every group but the first):
-            // chain -> head -> next chain then never cross streams.  It touches the columns the bulk update of the group before
-            // (and the early heads) touched on the main stream: ordered by one event, normally long complete.
-            // A next group inside the slack block is a handful of microsecond launches (closed form): it runs on the main stream,
-            // head included -- sending it through the side stream cost two stream crossings per group, 50-240 us each time for
-            // 30 us of work (config 2: 0.6 of 3.6 ms).
+            // Streams.  The next group runs on cs: the side stream, except a group inside the slack block -- a handful of
+            // microsecond launches (closed form) that stay on the main stream, head included (sending them through the side
+            // stream cost two stream crossings per group, 50-240 us each time for 30 us of work; config 2: 0.6 of 3.6 ms).
+            // The head runs on hs: the stream of the chain it follows, i.e. the side stream for every group but the first, so
+            // that chain -> head -> next chain never cross streams.  There it waits for ev_main (below): the bulk update of
+            // the group before (and the early heads) touched its columns on the main stream -- normally long complete.
             const bool nxt_fast = !ctx->grp_fast.empty() && ctx->grp_fast[(size_t)(grp + 1)];
-            hipStream_t cs = (nxt_fast && ctx->fast_on_main) ? ctx->stream : ctx->side;      // where the next group runs
-            hipStream_t hs = ctx->stream;
+            hipStream_t cs = nxt_fast ? ctx->stream : ctx->side;             // where the next group runs
+            hipStream_t hs = ctx->stream;                                    // where the head runs (group 0's; the others: below)
             // (the FIRST head stays on the main stream also when group 0 ran on the chain's stream: nothing runs beside it either
             //  way, and as a main-stream launch it takes the bulk instance and is part of the trailing figures, as in rounds 1-3)
             // (round 5) Lookahead ACROSS the slack block.  With its panels run up front the slack group between the last x group
@@ -1992,16 +1939,16 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
             // is treated as the lookahead target: a head (split: its diagonal block on the chain's stream, the rows below on the
             // rows stream) applies this group's contribution to its columns, the bulk update starts beyond them.  The same
             // products in the same order per entry (x groups in order, then the slack block's diagonal update).
-            const bool across = s_early && nxt_fast && !fast_src && grp > 0 && grp + 2 < ngroups &&
-                                !ctx->grp_fast[(size_t)(grp + 2)] && chain_group(grp + 2) && ctx->head_on_side;
+            const bool across = slack_first && nxt_fast && !fast_src && grp > 0 && grp + 2 < ngroups &&
+                                !ctx->grp_fast[(size_t)(grp + 2)] && chain_group(grp + 2);
             const int64_t pT = across ? ctx->grp_first[(size_t)(grp + 2)] : 0, nT = across ? gsize(grp + 2) : 0;
-            if (grp > 0 && ctx->head_on_side && (cs == ctx->side || across)) {
+            if (grp > 0 && (cs == ctx->side || across)) {
                 // (recorded at the end of the iteration before.  Behind an `across` iteration the source is the slack group: its
                 //  head is the diagonal update of the target's columns, ordered behind the x group's head on this stream, and the
                 //  x group's bulk update -- what the event would wait for -- no longer touches those columns)
                 if (!across_prev) PYIPM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_main, 0));
                 hs = ctx->side;
-                if (s_early && fast_src) PYIPM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_sfast, 0));   // (k_s_schur reads the slack columns)
+                if (slack_first && fast_src) PYIPM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_sfast, 0));   // (k_s_schur reads the slack columns)
             }
             const bool pieces = early0 && grp == 0;        // group 0's contribution is on the side stream already, panel by panel
             if (pieces) {
@@ -2010,26 +1957,21 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
                 if (ctx->rest) PYIPM_HIP(hipStreamWaitEvent(ctx->rest, ctx->ev_early, 0));
             }
             if (!pieces) {
-                const int64_t q = p0;
                 const bool split = chain_group(grp + 1) && cs != ctx->stream;
                 mark("head begin", grp, hs);
                 // (a head INTO the slack block is structurally empty: no x column reaches an s column, and a slack column's only
                 //  update is a diagonal entry of the multiplier block -- no launch, 10-15 us of the chain's path each)
-                const bool empty_head = ctx->s_early && nxt_fast;
                 if (across) { rc = head_from(p0, n0, pT, nT, hs, true); if (rc) return rc; }
-                else if (q < p0 + n0 && !empty_head) { rc = head_from(q, p0 + n0 - q, p1, n1, hs, split); if (rc) return rc; }
+                else if (!nxt_fast) { rc = head_from(p0, n0, p1, n1, hs, split); if (rc) return rc; }
                 mark("head end (its first launch's stream)", grp, hs);
             }
-            (void)hc0;
             if (hs == ctx->stream && cs == ctx->side) {
                 PYIPM_HIP(hipEventRecord(ctx->ev_head, ctx->stream));
                 PYIPM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_head, 0));
             }
             mark("chain+rows begin", grp + 1, cs);
-            if (s_early && nxt_fast) {                                   // its kernels ran up front: whoever follows on cs (and the
-                PYIPM_HIP(hipStreamWaitEvent(cs, ctx->ev_sfast, 0));      // update stream, for k_s_schur) is ordered behind them
-                if (cs != ctx->stream) PYIPM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_sfast, 0));
-            }
+            if (slack_first && nxt_fast)                                 // its kernels ran up front: whoever follows on cs (= the main
+                PYIPM_HIP(hipStreamWaitEvent(cs, ctx->ev_sfast, 0));      // stream: k_s_schur too) is ordered behind them
             rc = run_group(grp + 1, cs); if (rc) return rc;
             mark("chain+rows end", grp + 1, cs);
             PYIPM_HIP(hipEventRecord(ctx->ev_panel, cs));
@@ -2097,10 +2039,7 @@ int factor_dispatch(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward) {
     return rc;
 }
 
-void dist_free(Ctx* ctx);        // dist_impl.hpp
-
 // a failed create releases whatever the handle already owns (events, a library-owned workspace) the way destroy does
-int dist_set_option(Ctx* ctx, const char* name, double value, bool* handled);      // dist_impl.hpp
 int create_fail(Ctx* ctx, int code) {
     pyipm_newton_destroy(reinterpret_cast<pyipm_newton_ctx*>(ctx));
     return code;
@@ -2136,25 +2075,6 @@ size_t pyipm_newton_workspace_bytes(int64_t n, int64_t me, int64_t mi, int nb, i
     Geo g = make_geo(n, me, mi, nb, world, rank);
     return carve_workspace(nullptr, g, nullptr);
 } PYIPM_CATCH_SIZE
-
-static int create_impl(pyipm_newton_ctx** out, int64_t n, int64_t me, int64_t mi, int nb, int device,
-                       int world, int rank, void* workspace, size_t workspace_bytes, void* stream, bool provider_only);
-
-int pyipm_newton_create(pyipm_newton_ctx** out, int64_t n, int64_t me, int64_t mi, int nb, int device,
-                        int world, int rank, void* workspace, size_t workspace_bytes, void* stream) try {
-    return create_impl(out, n, me, mi, nb, device, world, rank, workspace, workspace_bytes, stream, false);
-} PYIPM_CATCH_NOH
-
-size_t pyipm_newton_workspace_bytes_provider(int64_t n, int64_t me, int64_t mi) try {
-    if (n <= 0 || me < 0 || mi < 0) return 0;
-    Geo g = make_geo(n, me, mi, 256, 1, 0);
-    return carve_workspace(nullptr, g, nullptr, true);
-} PYIPM_CATCH_SIZE
-
-int pyipm_newton_create_provider(pyipm_newton_ctx** out, int64_t n, int64_t me, int64_t mi, int device,
-                                 void* workspace, size_t workspace_bytes, void* stream) try {
-    return create_impl(out, n, me, mi, 256, device, 1, 0, workspace, workspace_bytes, stream, true);
-} PYIPM_CATCH_NOH
 
 static int create_impl(pyipm_newton_ctx** out, int64_t n, int64_t me, int64_t mi, int nb, int device,
                        int world, int rank, void* workspace, size_t workspace_bytes, void* stream, bool provider_only) {
@@ -2194,6 +2114,22 @@ static int create_impl(pyipm_newton_ctx** out, int64_t n, int64_t me, int64_t mi
     *out = reinterpret_cast<pyipm_newton_ctx*>(ctx);
     return PYIPM_OK;
 }
+
+int pyipm_newton_create(pyipm_newton_ctx** out, int64_t n, int64_t me, int64_t mi, int nb, int device,
+                        int world, int rank, void* workspace, size_t workspace_bytes, void* stream) try {
+    return create_impl(out, n, me, mi, nb, device, world, rank, workspace, workspace_bytes, stream, false);
+} PYIPM_CATCH_NOH
+
+size_t pyipm_newton_workspace_bytes_provider(int64_t n, int64_t me, int64_t mi) try {
+    if (n <= 0 || me < 0 || mi < 0) return 0;
+    Geo g = make_geo(n, me, mi, 256, 1, 0);
+    return carve_workspace(nullptr, g, nullptr, true);
+} PYIPM_CATCH_SIZE
+
+int pyipm_newton_create_provider(pyipm_newton_ctx** out, int64_t n, int64_t me, int64_t mi, int device,
+                                 void* workspace, size_t workspace_bytes, void* stream) try {
+    return create_impl(out, n, me, mi, 256, device, 1, 0, workspace, workspace_bytes, stream, true);
+} PYIPM_CATCH_NOH
 
 size_t pyipm_newton_workspace_bytes_batched(int64_t n, int64_t me, int64_t mi, int batch) try {
     if (n <= 0 || me < 0 || mi < 0 || batch < 1) return 0;
@@ -2519,9 +2455,9 @@ int pyipm_newton_factor(pyipm_newton_ctx* h, pyipm_factor_stats* stats) try {
     return rc;
 } PYIPM_CATCH_H(h)
 
-// load the right-hand side into v1 (kept for refinement) and v0 (solved in place)
 }  // extern "C"
 namespace pyipm { namespace drv {
+// load the right-hand side into v1 (kept for refinement) and v0 (solved in place)
 int solve_prepare(Ctx* ctx, const double* rhs, int memkind, bool for_fused_forward) {
     const Geo& g = ctx->g;
     if (rhs) {
@@ -2541,45 +2477,32 @@ extern "C" {
 static int solve_finish(Ctx* ctx, double* dz, int flip, int refine, int memkind, bool forward_done) {
     const Geo& g = ctx->g;
     int rc = solve_inplace(ctx, ctx->v0, forward_done); if (rc) return rc;
-    if (ctx->cond_active && refine >= 0 && refine < ctx->cond_min_refine) refine = ctx->cond_min_refine;
-    ctx->info_steps = 0; ctx->info_converged = 0; ctx->info_berr0 = -1.0; ctx->info_berr = -1.0;
-    // refine >= 0: that many steps of   r = b - Hc x ;  x += Hc^{-1} r   (Hc applied from the blocks, not from the factor).
-    // refine <  0: adaptive -- measure |r|/|b| before every step and stop at refine_target, after refine_max steps or
-    //              when a step gains less than 4x.  This is what turns the factor of a statically pivoted (perturbed)
-    //              matrix into the solution of the UNperturbed system; the host reads the outcome with solve_info.
-    const bool adaptive = refine < 0;
-    const int maxit = adaptive ? ctx->refine_max : refine;
-    double prev = -1.0;
-    for (int it = 0; it <= maxit; ++it) {
-        if (!adaptive && it == maxit) break;
-        rc = kkt_matvec_dev(ctx, ctx->v0, ctx->v2); if (rc) return rc;
-        hipLaunchKernelGGL(k_axpby, grid1(g.Npad), dim3(256), 0, ctx->stream, ctx->v2, ctx->v1, ctx->v2, 1.0, -1.0, g.Npad);
-        PYIPM_KCHECK();
-        if (adaptive) {
+    const size_t vbytes = (size_t)g.Npad * sizeof(double);
+    rc = refine_loop(ctx, refine,
+        [&]() -> int {                                          // v2 = b - Hc v0
+            int r2 = kkt_matvec_dev(ctx, ctx->v0, ctx->v2); if (r2) return r2;
+            hipLaunchKernelGGL(k_axpby, grid1(g.Npad), dim3(256), 0, ctx->stream, ctx->v2, ctx->v1, ctx->v2, 1.0, -1.0, g.Npad);
+            PYIPM_KCHECK();
+            return 0;
+        },
+        [&](double* berr) -> int {
             double ss[2];
             hipLaunchKernelGGL(k_sumsq2, dim3(1), dim3(1024), 0, ctx->stream, ctx->partial, ctx->v2, ctx->v1, g.N);
             PYIPM_KCHECK();
             PYIPM_HIP(hipMemcpyAsync(ss, ctx->partial, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
             PYIPM_HIP(hipStreamSynchronize(ctx->stream));
-            const double berr = ss[1] > 0.0 ? sqrt(ss[0] / ss[1]) : sqrt(ss[0]);
-            if (it == 0) ctx->info_berr0 = berr;
-            ctx->info_berr = berr;
-            if (prev >= 0.0 && !(berr <= prev)) {                             // the last step made it worse (or NaN): take it back
-                PYIPM_HIP(hipMemcpyAsync(ctx->v0, ctx->v3, g.Npad * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-                ctx->info_berr = prev; ctx->info_steps = it - 1;
-                break;
-            }
-            if (!(berr <= 1.0e300)) break;                                    // NaN / Inf: nothing to refine
-            if (berr <= ctx->refine_target) { ctx->info_converged = 1; break; }
-            if (it == maxit || (prev >= 0.0 && berr > 0.25 * prev)) break;    // out of budget / stagnating
-            prev = berr;
-            PYIPM_HIP(hipMemcpyAsync(ctx->v3, ctx->v0, g.Npad * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));   // the iterate this error belongs to
-        }
-        rc = solve_inplace(ctx, ctx->v2); if (rc) return rc;
-        hipLaunchKernelGGL(k_axpby, grid1(g.Npad), dim3(256), 0, ctx->stream, ctx->v0, ctx->v0, ctx->v2, 1.0, 1.0, g.Npad);
-        PYIPM_KCHECK();
-        ctx->info_steps = it + 1;
-    }
+            *berr = ss[1] > 0.0 ? sqrt(ss[0] / ss[1]) : sqrt(ss[0]);
+            return 0;
+        },
+        [&]() -> int { PYIPM_HIP(hipMemcpyAsync(ctx->v3, ctx->v0, vbytes, hipMemcpyDeviceToDevice, ctx->stream)); return 0; },
+        [&]() -> int { PYIPM_HIP(hipMemcpyAsync(ctx->v0, ctx->v3, vbytes, hipMemcpyDeviceToDevice, ctx->stream)); return 0; },
+        [&]() -> int {                                          // v0 += Hc^{-1} v2
+            int r2 = solve_inplace(ctx, ctx->v2); if (r2) return r2;
+            hipLaunchKernelGGL(k_axpby, grid1(g.Npad), dim3(256), 0, ctx->stream, ctx->v0, ctx->v0, ctx->v2, 1.0, 1.0, g.Npad);
+            PYIPM_KCHECK();
+            return 0;
+        });
+    if (rc) return rc;
     // flip + copy out (device staging through v2 so host copies stay contiguous)
     hipLaunchKernelGGL(k_copy_flip, grid1(g.N), dim3(256), 0, ctx->stream, ctx->v2, ctx->v0, g.N, g.n + g.mi,
                        (flip && (g.me + g.mi) > 0) ? 1 : 0);

@@ -12,9 +12,9 @@ and exactly zero rows, at shapes that reach every regime of the single-rank sche
     9216             (1024, 0, 4096)            early0, tail groups of 4
     11504 (11520)    (5003, 701, 2900), nb 512  every chain exposed (<= tile8_rows), groups of 4
     17001 (17024)    (9001, 0, 4000), nb 128    non-exposed chains as k_tile_step, reserved CUs (> persist_rows)
-    17000 (17024)    (12007, 4993, 0)           no slack block: no s_early / grp_fast
-    23545 (23552)    (12345, 2000, 4600)        128 x 256 bulk tiles (> bulk_bn_rows)
-    29928 (29952)    (14001, 3001, 6463)        groups of 8 panels before the tail (> tail_cols)
+    17000 (17024)    (12007, 4993, 0)           no slack block: no panels enqueued up front / grp_fast
+    23545 (23552)    (12345, 2000, 4600)        128 x 256 bulk tiles (> BULK_BN_ROWS)
+    29928 (29952)    (14001, 3001, 6463)        groups of 8 panels before the tail (> TAIL_COLS)
 
 Every reference is an O(N n) host product from the blocks; no LU or eigensolver at these sizes."""
 import numpy as np
@@ -78,7 +78,7 @@ def test_negative_curvature_inertia_and_forward_error(shape, nb):
     (n_pos, n_neg) = (|P| + mi, |Nn| + me + mi) -- every pivot kernel that ran adds to these counts, so a sign counted
     wrong in any of them shows --; solve(b) returns x_true to 1e-10; step(0, 0) satisfies the blocks to 1e-12.  Both
     substitution schedules (one-launch sweeps and per-panel launches).  Where the 128 x 256 bulk tiles must run
-    (Npad > bulk_bn_rows), they did, and nowhere else.
+    (Npad > BULK_BN_ROWS), they did, and nowhere else.
 
     The solves are those the backend makes for this factor: indefinite tiles pivot 2x2 inside their 64 x 64 tile and reach
     growth ~1e3 here, so HipNewtonBackend._at_risk sends them through adaptive refinement against the blocks (refine < 0).
