@@ -109,6 +109,25 @@ struct ChainGeo {
 };
 constexpr int CHAIN_DBG_WORDS = 256 + 64 * 4 * 32;
 
+// The group schedule of the single-rank driver as one value: which panels form a group (one bulk trailing update per group) and
+// what the KKT structure says about each group.  plan_groups (pyipm_newton.hip) builds it for one geometry.  The accessors hold
+// the fallback for a panel WITHOUT a schedule (per-panel phases, distributed driver): uniform groups of G panels, dense panels.
+struct GroupSched {
+    std::vector<int> of_, off_;           // per panel: group id and offset inside the group
+    std::vector<int64_t> first_;          // per group: first panel (+ one past the last group)
+    std::vector<char> fast_;              // per group: every panel of it lies inside the slack block: closed-form elimination (k_s_panel)
+    std::vector<char> in_x_;              // per group: lies inside the x block (its chain kernels may skip the slack rows)
+    bool active() const { return !of_.empty(); }
+    void clear() { of_.clear(); off_.clear(); first_.clear(); fast_.clear(); in_x_.clear(); }   // the only way into per-panel mode
+    bool has(int64_t p) const { return (size_t)p < of_.size(); }
+    int64_t group_of(int64_t p, int64_t G) const { return has(p) ? of_[(size_t)p] : p / G; }
+    int64_t offset_of(int64_t p, int64_t G) const { return has(p) ? off_[(size_t)p] : p % G; }
+    bool fast_panel(int64_t p) const { return has(p) && fast(of_[(size_t)p]); }     bool in_x_panel(int64_t p) const { return has(p) && in_x(of_[(size_t)p]); }
+    int64_t ngroups() const { return (int64_t)fast_.size(); }
+    int64_t first(int64_t grp) const { return first_[(size_t)grp]; }      int64_t size(int64_t grp) const { return first(grp + 1) - first(grp); }
+    bool fast(int64_t grp) const { return fast_[(size_t)grp] != 0; }      bool in_x(int64_t grp) const { return in_x_[(size_t)grp] != 0; }
+};
+
 struct Ctx {
     Geo g;
     int batch = 1;                        // problems of a batched small-system handle (kernels_batched.hpp)
@@ -126,8 +145,6 @@ struct Ctx {
     int lookahead = 2;                    // 0 none, 1 one group (two groups on a dedicated stream measured no faster: removed), 2 = 1 + the
                                           // first group's update panel by panel under its own chain where the slack block follows it (factor_all)
     hipEvent_t ev_early = nullptr;
-    std::vector<char> grp_fast;           // per group: every panel of it lies inside the slack block: closed-form elimination (k_s_panel; built by factor_all)
-    std::vector<char> grp_x;              // per group: lies inside the x block (its chain kernels may skip the slack rows)
     struct TileList { unsigned* dev = nullptr; unsigned count = 0;
                       hipEvent_t ready = nullptr; hipStream_t on = nullptr; bool seen_done = false; };   // the async upload: its event, its stream
     struct TlArena { unsigned* dev = nullptr; unsigned* host = nullptr; size_t cap = 0, used = 0; };    // device + pinned host memory of the lists
@@ -137,8 +154,7 @@ struct Ctx {
     int group = 1;                        // panels per bulk trailing update
     bool tail_group_user = false;         // set_option("tail_group") was called (else: 8 for systems of at most 8192 rows)
     int tail_group = 4;                   // group size once at most TAIL_COLS columns remain
-    std::vector<int> grp_of, grp_off;     // per panel: group id and offset inside the group (built by factor_all)
-    std::vector<int64_t> grp_first;       // per group: first panel (+ one past the last group)
+    GroupSched sched;                     // group schedule (plan_groups); not active: the per-panel phases or the distributed driver drive this factorisation
     double* Wnext = nullptr;              // 64 x 64: -S of the next diagonal tile's rows, handed from the tile kernel to the scaling launch
                                           // that carries the next tile's in-panel update (k_panel_scale + NextUpd, factor_panel)
     int group_chain = 1;                  // single rank: the panels of a group are chained tile to tile (factor_group), the rows
@@ -152,7 +168,6 @@ struct Ctx {
                                           // so every assembly is a full one until set_option("keep_zeros") is called again
     int tile_step = 1;                    // stepped panel schedule (kernels_panel.hpp): one launch per diagonal tile (the rows inside the
                                           // diagonal block), one for the rows below it; panels of at most 4 tiles; same bits
-    bool per_panel_mode = false;          // the per-panel phases (pyipm_newton_factor_begin ...) drive this factorisation
     int sweep_max_blocks = 0;             // test hook: cap on the workgroups of the one-launch sweeps (0 = as many as the GPU holds)
     int occ_fwd_sweep = 0, occ_bwd_sweep = 0;   // resident workgroups per CU of the one-launch sweeps (occupancy query, cached)
     int sweep_persist = 1;                // single rank, one right-hand side: the backward sweep as ONE device-driven launch (k_bwd_sweep)

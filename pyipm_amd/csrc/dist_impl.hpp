@@ -574,8 +574,7 @@ int factor_dist(Ctx* ctx, pyipm_factor_stats* stats, const double* fwd_b = nullp
 int factor_dist_geo(Ctx* ctx, pyipm_factor_stats* stats, const double* fwd_b) {
     const Geo& g = ctx->g;
     DistState* D; int rc = dist_state(ctx, &D); if (rc) return rc;
-    ctx->grp_of.clear(); ctx->grp_off.clear(); ctx->grp_fast.clear(); ctx->grp_x.clear();
-    ctx->per_panel_mode = true;
+    ctx->sched.clear();                                 // per-panel mode: uniform group map, dense panels
     ctx->zeros_clean = false;
     rc = factor_begin(ctx); if (rc) return rc;
     D->used = 0; D->spans.clear(); D->bytes_sent = 0; D->n_msgs = 0;

@@ -31,11 +31,8 @@ inline Ctx* C(pyipm_newton_ctx* h) { return reinterpret_cast<Ctx*>(h); }
 inline dim3 grid1(int64_t n, int b = 256) { return dim3((unsigned)((n + b - 1) / b)); }
 // -W columns of panel p: the buffer of its group (parity-alternating) + its offset inside the group
 inline double* wbuf(Ctx* ctx, int64_t p) {
-    // group id / offset: uniform groups unless factor_all built a variable schedule (short groups in the tail)
     const int64_t G = ctx->group;
-    const int64_t grp = (size_t)p < ctx->grp_of.size() ? ctx->grp_of[p] : p / G;
-    const int64_t off = (size_t)p < ctx->grp_off.size() ? ctx->grp_off[p] : p % G;
-    return ctx->Wbuf + ((grp % 3) * G + off) * ctx->g.Npad * (int64_t)ctx->g.nb;
+    return ctx->Wbuf + ((ctx->sched.group_of(p, G) % 3) * G + ctx->sched.offset_of(p, G)) * ctx->g.Npad * (int64_t)ctx->g.nb;
 }
 
 int single_only(Ctx* ctx);

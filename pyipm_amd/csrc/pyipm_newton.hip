@@ -394,7 +394,7 @@ int launch_update128(Ctx* ctx, hipStream_t stream, const double* Lop, int64_t ld
 // no message and no update launch (k_s_panel / k_s_schur_sigma).
 bool panel_in_s(const Ctx* ctx, int64_t p) {
     const Geo& g = ctx->g;
-    if (!ctx->skip_zeros || g.mi == 0 || !ctx->grp_of.empty() || ctx->cond_active) return false;
+    if (!ctx->skip_zeros || g.mi == 0 || ctx->sched.active() || ctx->cond_active) return false;
     const int64_t c0 = g.panel_c0(p);
     return c0 >= g.n && c0 + g.panel_w(p) <= g.n + g.mi;
 }
@@ -416,7 +416,7 @@ inline void slack_hole(const Geo& g, int64_t* h0, int64_t* h1) {
 void panel_hole(const Ctx* ctx, int64_t p, int64_t* h0, int64_t* h1) {
     const Geo& g = ctx->g;
     *h0 = 0; *h1 = 0;
-    if (!ctx->skip_zeros || g.mi == 0 || !ctx->grp_of.empty() || ctx->cond_active) return;
+    if (!ctx->skip_zeros || g.mi == 0 || ctx->sched.active() || ctx->cond_active) return;
     if (g.panel_c0(p) + g.panel_w(p) > g.n) return;
     int64_t a, b;
     slack_hole(g, &a, &b);
@@ -436,7 +436,7 @@ int factor_panel(Ctx* ctx, int64_t p, hipStream_t stream, bool apply_pending) {
     const int nbw = (int)g.panel_w(p);
     const int nt = nbw / TB;
     const int64_t lp = p / g.world;
-    if (((size_t)p < ctx->grp_of.size() && !ctx->grp_fast.empty() && ctx->grp_fast[(size_t)ctx->grp_of[p]]) || panel_in_s(ctx, p)) {
+    if (ctx->sched.fast_panel(p) || panel_in_s(ctx, p)) {
         // the whole group (or, per-panel mode, the panel) lies inside the slack block: closed form, no W, no updates
         hipLaunchKernelGGL(k_s_panel, dim3(1), dim3(256), 0, stream, ctx->A, g.Npad, c0, lc0, nt,
                            ctx->Dinv + (c0 / TB) * (int64_t)(TB * TB), ctx->Tsv + (c0 / TB) * (int64_t)(TB * TB),
@@ -446,7 +446,7 @@ int factor_panel(Ctx* ctx, int64_t p, hipStream_t stream, bool apply_pending) {
         return 0;
     }
     double* W = wbuf(ctx, p);
-    const int64_t poff = (size_t)p < ctx->grp_off.size() ? ctx->grp_off[p] : p % ctx->group;
+    const int64_t poff = ctx->sched.offset_of(p, ctx->group);
     if (apply_pending && poff != 0) {
         const int64_t p0 = p - poff;
         const int K = (int)((p - p0) * g.nb);
@@ -468,10 +468,9 @@ int factor_panel(Ctx* ctx, int64_t p, hipStream_t stream, bool apply_pending) {
     int64_t hole0 = 0, hole1 = 0;
     // Only when the whole GROUP lies in the x block: a group's bulk update reads every W row the structure of its
     // source columns allows, so a mixed group needs all of them written.
-    const bool grp_in_x = (size_t)p < ctx->grp_of.size() && !ctx->grp_x.empty() && ctx->grp_x[(size_t)ctx->grp_of[p]];
-    if (ctx->skip_zeros && g.world == 1 && g.mi > 0 && grp_in_x) slack_hole(g, &hole0, &hole1);
+    if (ctx->skip_zeros && g.world == 1 && g.mi > 0 && ctx->sched.in_x_panel(p)) slack_hole(g, &hole0, &hole1);
     else panel_hole(ctx, p, &hole0, &hole1);            // per-panel mode (any number of ranks)
-    if (ctx->tile_step && ctx->per_panel_mode && ctx->wide_sub >= 128 && ctx->wide_sub % 128 == 0 &&
+    if (ctx->tile_step && !ctx->sched.active() && ctx->wide_sub >= 128 && ctx->wide_sub % 128 == 0 &&
         nbw > ctx->wide_sub && nt <= 32 && c0 + nbw < g.Npad)
         return factor_wide_panel(ctx, p, stream);
     if (ctx->tile_step && nt <= 16) {
@@ -537,7 +536,7 @@ int ensure_rest_stream(Ctx* ctx) {
 // does the diagonal block at global column gc0 (nT tiles) take k_tile_chain (kernels_chain.hpp)?
 static bool chain_applies(const Ctx* ctx, int64_t gc0, int nT) {
     const Geo& g = ctx->g;
-    const bool exposed = ctx->per_panel_mode || gc0 == 0 || g.Npad - gc0 <= ctx->tile8_rows;   // (where the chain is what the step waits for)
+    const bool exposed = !ctx->sched.active() || gc0 == 0 || g.Npad - gc0 <= ctx->tile8_rows;   // (where the chain is what the step waits for)
     return ctx->tile_chain && nT >= 2 && nT <= 32 && (ctx->tile_chain >= 2 || exposed);
 }
 // nX > 0 (k_tile_chain only, ta = 0, tb = nT): nX row tiles right below the diagonal block take every stage in the same launch,
@@ -575,7 +574,7 @@ int launch_tile_steps(Ctx* ctx, hipStream_t chain, int64_t gc0, int64_t glc0, in
         const unsigned nblk = 1u + (unsigned)chain_units(ta, nT, cg.cpy, cg.nR);
         // dynamic shared memory nobody touches: with it a workgroup of the chain has its compute unit to itself (single-rank
         // schedule only: beside the bulk updates of the per-panel schedule it would wait for a whole CU to drain)
-        size_t pad = (ctx->chain_lds_kb > 0 && !ctx->per_panel_mode) ? (size_t)ctx->chain_lds_kb * 1024 : 0;
+        size_t pad = (ctx->chain_lds_kb > 0 && ctx->sched.active()) ? (size_t)ctx->chain_lds_kb * 1024 : 0;
         if (pad && !ctx->chain_lds_set) {
             if (hipFuncSetAttribute((const void*)k_tile_chain, hipFuncAttributeMaxDynamicSharedMemorySize, 110 * 1024) != hipSuccess) { (void)hipGetLastError(); ctx->chain_lds_kb = 0; pad = 0; }
             ctx->chain_lds_set = true;
@@ -596,7 +595,7 @@ int launch_tile_steps(Ctx* ctx, hipStream_t chain, int64_t gc0, int64_t glc0, in
         // (all launches: exposed panel 7.1 -> 10.9 ms at N = 32768; the per-panel schedule, whose ranks run their bulk updates
         // beside every chain: owners' chain path 31.0 -> 32.1 ms in the replay -- it keeps the 256-thread kernel)
         const int64_t m_left = g.Npad - gc0;
-        if (ctx->tile_waves == 8 && !ctx->per_panel_mode && (gc0 == 0 || m_left <= ctx->tile8_rows)) {
+        if (ctx->tile_waves == 8 && ctx->sched.active() && (gc0 == 0 || m_left <= ctx->tile8_rows)) {
             const int units = (nT - j - 1) * ny;
             const int free_cus = (gc0 == 0 || ctx->reserve_cus <= 0) ? ctx->num_cus : TILE_FREE_CUS;
             const int upb = units + 1 <= free_cus ? 1 : 2;          // (row tile, y) units per 512-thread block
@@ -740,11 +739,7 @@ int factor_group(Ctx* ctx, int64_t p0, int64_t n0, hipStream_t chain, const std:
         const int64_t q = p0 + k;
         bd.sp.push_back(SubPanel{g.panel_c0(q), g.local_c0(q), (int)(g.panel_w(q) / TB), wbuf(ctx, q), q});
     }
-    const size_t gi = (size_t)ctx->grp_of[(size_t)p0];
-    const bool grp_in_x = !ctx->grp_x.empty() && ctx->grp_x[gi];
-    if (ctx->skip_zeros && g.mi > 0 && grp_in_x) {
-        slack_hole(g, &bd.hole0, &bd.hole1);
-    }
+    if (ctx->skip_zeros && g.mi > 0 && ctx->sched.in_x_panel(p0)) slack_hole(g, &bd.hole0, &bd.hole1);
     return factor_block(ctx, bd, chain, on_done);
 }
 
@@ -961,7 +956,7 @@ int timed_update(Ctx* ctx, int64_t p0, int64_t np, int64_t first_lp, int64_t n_l
     if (n_lp <= 0) return 0;
     int K = 0;
     for (int64_t q = p0; q < p0 + np; ++q) K += (int)g.panel_w(q);
-    if ((size_t)p0 < ctx->grp_of.size() && !ctx->grp_fast.empty() && ctx->grp_fast[(size_t)ctx->grp_of[p0]]) {
+    if (ctx->sched.fast_panel(p0)) {
         // slack-block sources: each column updates one diagonal entry (k_s_schur), here for the target columns
         // of this launch -- on the update stream, where the dense launch would have run
         const int64_t tq0 = first_lp, tq1 = first_lp + n_lp;                       // single rank: local = global panels
@@ -988,7 +983,7 @@ int timed_update(Ctx* ctx, int64_t p0, int64_t np, int64_t first_lp, int64_t n_l
     // A launch on another stream than the handle's is a lookahead head riding the chain's stream: it overlaps the bulk launch
     // on the main stream, so its duration says nothing about the kernel's rate -- it is not part of the "trailing" figures
     // (time, flops, launches), and it uses the 4-wave instance of the kernel so that a kernel trace keeps the two apart.
-    const bool chain_side = stream != ctx->stream && !ctx->per_panel_mode && !o.as_bulk;
+    const bool chain_side = stream != ctx->stream && ctx->sched.active() && !o.as_bulk;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     int used_bn = 128;
     if (ctx->profile && !chain_side) {
@@ -1000,7 +995,7 @@ int timed_update(Ctx* ctx, int64_t p0, int64_t np, int64_t first_lp, int64_t n_l
         e0 = ctx->ev_trailing[ctx->n_trailing].first; e1 = ctx->ev_trailing[ctx->n_trailing].second;
         PYIPM_HIP(hipEventRecord(e0, stream));
     }
-    if (ctx->per_panel_mode && n_lp == 1 && g.Npad - row_begin <= HEAD32_ROWS_DIST) {
+    if (!ctx->sched.active() && n_lp == 1 && g.Npad - row_begin <= HEAD32_ROWS_DIST) {
         // one panel of columns (the head of the per-panel schedule): 32 x 64 blocks instead of a handful of 128 x 128 tiles
         int64_t pa0, pa1, pb0, pb1;
         active_ranges(ctx, g.panel_c0(p0), g.panel_c0(p0) + K, &pa0, &pa1, &pb0, &pb1);
@@ -1666,16 +1661,6 @@ void asm_grid(const Geo& g, dim3* grid, int* tri) {
     }
 }
 
-// panels of the first group of the single-rank schedule (the rule of factor_all)
-int64_t first_group_panels(const Ctx* ctx) {
-    const Geo& g = ctx->g;
-    const int tg = (!ctx->tail_group_user && g.Npad <= 8192) ? 8 : ctx->tail_group;
-    int64_t G = (tg > 0 && g.Npad <= TAIL_COLS) ? tg : ctx->group;
-    if (G > ctx->group) G = ctx->group;
-    if (G > g.npanels) G = g.npanels;
-    return G;
-}
-
 int assemble_dev(Ctx* ctx, double delta, double delta_c) {
     const Geo& g = ctx->g;
     if (ctx->provider_only) { ctx->err = "a provider-only handle has no KKT storage: block products and residuals only"; return PYIPM_E_BADARG; }
@@ -1712,17 +1697,224 @@ int assemble_dev(Ctx* ctx, double delta, double delta_c) {
     return 0;
 }
 
-// Single-rank factorisation.  Three-level hierarchy: 64-wide block pivots inside nb-wide panels inside
-// groups of `group` panels.  Panels of a group are factored left-looking against the group's earlier
-// panels; the trailing matrix is updated ONCE per group with K = group*nb, which divides the C-tile
-// read-modify-write traffic (the HBM bound of the rank-nb update) by `group`.  One-group lookahead: while
-// the bulk update of group g runs on the main stream, group g+1 (already updated by a head launch) is
-// factored on a second stream.
+// ---- single-rank factorisation: the plan (plan_groups, plan_step), then the enqueue (factor_all) ------------------------------
+// Three-level hierarchy: 64-wide block pivots inside nb-wide panels inside groups of `group` panels.  Panels of a
+// group are factored left-looking against the group's earlier panels; the trailing matrix is updated ONCE per group
+// with K = group*nb, which divides the C-tile read-modify-write traffic (the HBM bound of the rank-nb update) by `group`.
+// Group schedule: `group` panels per bulk update while the bulk update outlasts the panel chain; once at most
+// TAIL_COLS columns remain the chain is the critical path and shorter groups (less in-group update work on
+// the chain, more in the cheap bulk launches) end the factorisation sooner.  A pure function of its arguments.
+GroupSched plan_groups(const Geo& g, int group, int tail_group, bool tail_group_user, bool skip_zeros, int lookahead) {
+    GroupSched s;
+    const int64_t np = g.npanels;
+    const bool closed_form = skip_zeros && g.mi > 0;   // groups inside the slack block: closed-form elimination (k_s_panel)
+    s.of_.assign((size_t)np, 0); s.off_.assign((size_t)np, 0);
+    for (int64_t p = 0; p < np;) {
+        const int64_t remaining = g.Npad - g.panel_c0(p);
+        // (round 6: systems of at most 8192 rows take groups of 8 in the tail too -- with the chain of a group as ONE launch a group
+        //  boundary costs more than the in-group updates of the longer group: config 2 2.25 against 2.29 ms; N = 32768: 104.9
+        //  against 102.4 ms, config 3 185.4 against 183.2: 4 stays there)
+        const int tg = (!tail_group_user && g.Npad <= 8192) ? 8 : tail_group;
+        int64_t G = (tg > 0 && remaining <= TAIL_COLS) ? tg : group;
+        if (G > group) G = group;
+        if (p + G > np) G = np - p;
+        // (round 5) the panels inside the slack block as ONE group: their kernels run up front (enqueue_slack_first) and what is left of
+        // a slack group in the loop of factor_all is a head, a k_s_schur launch and four stream hops -- 56 us per group of four
+        // panels between the x block's last bulk update and the multiplier block's first chain (N = 32768: six groups)
+        if (closed_form && lookahead && p > 0 && g.panel_c0(p) >= g.n && g.panel_c0(p + G - 1) + g.panel_w(p + G - 1) <= g.n + g.mi)
+            while (p + G < np && g.panel_c0(p + G) + g.panel_w(p + G) <= g.n + g.mi) ++G;
+        const int64_t ca = g.panel_c0(p), cb = g.panel_c0(p + G - 1) + g.panel_w(p + G - 1);      // the group's columns [ca, cb)
+        for (int64_t q = 0; q < G; ++q) { s.of_[(size_t)(p + q)] = (int)s.first_.size(); s.off_[(size_t)(p + q)] = (int)q; }
+        s.first_.push_back(p);
+        s.in_x_.push_back(cb <= g.n ? 1 : 0);
+        s.fast_.push_back((closed_form && ca >= g.n && cb <= g.n + g.mi) ? 1 : 0);
+        p += G;
+    }
+    s.first_.push_back(np);
+    return s;
+}
+
+// diagnostics (PYIPM_GROUP_TRACE=1): where each group's chain, head and bulk update begin and end on the device, without a
+// tracer's per-call cost on the host (tools/group_trace.py)
+struct GroupTrace {
+    std::vector<std::pair<std::string, hipEvent_t>> marks;
+    static bool on() { static const bool v = getenv("PYIPM_GROUP_TRACE") != nullptr; return v; }
+    void mark(const char* what, int64_t grp, hipStream_t st) {
+        hipEvent_t e; if (!on() || hipEventCreate(&e) != hipSuccess) return;
+        hipEventRecord(e, st);
+        char buf[64]; snprintf(buf, sizeof(buf), "%s g%lld", what, (long long)grp);
+        marks.push_back({buf, e});
+    }
+    void report(hipEvent_t t0, hipEvent_t t1, float total_ms) {
+        if (!on()) return;
+        hipEventSynchronize(t1);
+        for (auto& m : marks) {
+            float t = 0.f;
+            if (hipEventSynchronize(m.second) == hipSuccess && hipEventElapsedTime(&t, t0, m.second) == hipSuccess)
+                fprintf(stderr, "[pyipm group trace] %9.1f us  %s\n", 1e3 * t, m.first.c_str());
+            hipEventDestroy(m.second);
+        }
+        fprintf(stderr, "[pyipm group trace] %9.1f us  factorisation end\n", 1e3 * total_ms);
+    }
+};
+
+// does group grp run as a tile chain (factor_group)?
+static bool chain_group(const Ctx* ctx, int64_t grp) {
+    return ctx->group_chain && !ctx->sched.fast(grp) && ctx->sched.size(grp) * (ctx->g.nb / TB) <= 32 && ctx->g.nb % 128 == 0;
+}
+
+struct FactorRun {                     // what holds for one whole factorisation: decided by factor_all before the first launch
+    bool fuse_forward;                 // y_p only needs panel p factored: the forward pass of the step's right-hand side trails on ctx->fwd
+    bool early0;                       // group 0 goes to the columns beyond it panel by panel (panel_done)
+    bool slack_first;                  // the closed-form panels of the slack block were enqueued up front (enqueue_slack_first) ...
+    bool done_early(const Ctx* ctx, int64_t q) const { return slack_first && ctx->sched.fast_panel(q); }   // ... panel q was
+};
+
+// Panel q of group grp is complete once `used` reaches this point.  The fused forward substitution takes it up.
+// Group 0 right-looking panel by panel (round 6, lookahead = 2): a system whose x block is ONE group followed by the slack
+// block (config 2).  Nothing runs beside the first group's chain, the slack group is no work, and the x group's bulk
+// update -- a launch of a hundred-odd tiles -- is what the multiplier block's chain waits for in full (272 us of 2.22 ms).
+// Here every panel of group 0 goes to the columns beyond the group as soon as it is complete: a K = nb launch on the side
+// stream (idle until the next chain) behind the panel's event, under the chain of the panels that follow; neither a head
+// nor a bulk update is left for group 0.  Every entry receives the same products in the same order.  Measured
+// (tools/r06_early.sh): config 2 2.225 -> 2.165 ms -- the chain itself slows from 880 to 970 us beside the pieces (its
+// round trips to memory share the fabric with their operands), the next chain starts 140 us earlier.  Where the next group
+// is an ordinary one the one-group lookahead already hides the bulk update under that group's chain and the pieces lose
+// (n, me, mi = 3072, 512, 1024: 2.99 -> 3.08 ms): not applied there.  Fewer, persistent blocks per piece (64 ... 192
+// of them) only made the last piece longer.
+static int panel_done(Ctx* ctx, const FactorRun& run, int64_t grp, int64_t q, hipStream_t used) {
+    if (run.fuse_forward) {
+        if (!run.done_early(ctx, q)) PYIPM_HIP(hipEventRecord(ctx->ev_done[q], used));      // (else: recorded behind its kernel)
+        PYIPM_HIP(hipStreamWaitEvent(ctx->fwd, ctx->ev_done[q], 0));
+        int r2 = fwd_panel(ctx, q, ctx->fwd_vec, ctx->fwd); if (r2) return r2;
+        r2 = diag_panel(ctx, q, ctx->fwd_vec, ctx->fwd); if (r2) return r2;
+    }
+    if (!(run.early0 && grp == 0)) return 0;
+    const int64_t p1 = ctx->sched.first(1);
+    PYIPM_HIP(hipEventRecord(ctx->ev_early, used));
+    PYIPM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_early, 0));
+    return timed_update(ctx, q, 1, p1, ctx->g.npanels - p1, {.stream = ctx->side, .as_bulk = true});
+}
+
+// all panels of one group on stream S
+static int run_group(Ctx* ctx, const FactorRun& run, int64_t grp, hipStream_t S) {
+    const int64_t pA = ctx->sched.first(grp), nA = ctx->sched.size(grp);
+    auto done = [&](int64_t q, hipStream_t used) { return panel_done(ctx, run, grp, q, used); };
+    if (chain_group(ctx, grp)) return factor_group(ctx, pA, nA, S, done);
+    for (int64_t q = pA; q < pA + nA; ++q) {
+        if (!run.done_early(ctx, q)) { int r2 = factor_panel(ctx, q, S, true); if (r2) return r2; }
+        int r2 = done(q, S); if (r2) return r2;
+    }
+    return 0;
+}
+
+// (round 5) The closed-form panels of the slack block depend on nothing but the assembly -- no x-block update
+// reaches their columns -- and used to sit, one 7 us launch after the other, between the x block's last chain and the
+// multiplier block's first (config 2: 0.15 of 2.7 ms, plus the last x group's bulk update queued behind them on the same
+// stream).  They are enqueued up front on the rows stream; what READS them (k_s_schur on the update stream, the forward
+// sweep) keeps its place and waits for one event.  Statistics are atomic sums / minima / maxima: the same numbers.
+static bool slack_first_applies(const Ctx* ctx) {
+    if (!ctx->lookahead || ctx->sched.fast(0)) return false;
+    for (int64_t gi = 1; gi < ctx->sched.ngroups(); ++gi) if (ctx->sched.fast(gi)) return true;
+    return false;
+}
+static int enqueue_slack_first(Ctx* ctx, const FactorRun& run, hipStream_t after) {
+    { int r0 = ensure_rest_stream(ctx); if (r0) return r0; }
+    PYIPM_HIP(hipEventRecord(ctx->ev_sfast, after));                  // the assembly and the reset of the statistics
+    PYIPM_HIP(hipStreamWaitEvent(ctx->rest, ctx->ev_sfast, 0));
+    for (int64_t q = 0; q < ctx->g.npanels; ++q) {
+        if (!ctx->sched.fast_panel(q)) continue;
+        int r2 = factor_panel(ctx, q, ctx->rest, true); if (r2) return r2;
+        if (run.fuse_forward) PYIPM_HIP(hipEventRecord(ctx->ev_done[q], ctx->rest));
+    }
+    PYIPM_HIP(hipEventRecord(ctx->ev_sfast, ctx->rest));              // every closed-form panel is done
+    return 0;
+}
+
+// Head on hs: panels [q0, q0 + nq) of a complete group applied to the columns of panels [tp, tp + tn) (the target's chain waits for it)
+static int head_from(Ctx* ctx, bool fast_src, int64_t q0, int64_t nq, int64_t tp, int64_t tn, hipStream_t hs, bool split) {
+    const Geo& g = ctx->g;
+    const int64_t tc0 = g.panel_c0(tp);
+    if (fast_src || g.Npad - tc0 > HEAD32_ROWS) return timed_update(ctx, q0, nq, tp, tn, {.stream = hs});   // (else, where the chain is the bound: 32 x 64 blocks)
+    int K = 0; int64_t cols = 0;
+    for (int64_t q = q0; q < q0 + nq; ++q) K += (int)g.panel_w(q);
+    for (int64_t q = tp; q < tp + tn; ++q) cols += g.panel_w(q);
+    const int64_t tend = tc0 + cols;
+    int64_t pa0, pa1, pb0, pb1;
+    active_ranges(ctx, g.panel_c0(q0), g.panel_c0(q0) + K, &pa0, &pa1, &pb0, &pb1);
+    // split: the chain of the target group needs the head only inside that group's diagonal block (rows [tc0, tend));
+    // the rows below it are first read by the group's rows stream.  Two launches: the block on the chain's
+    // stream, the rest on ctx->rest behind it -- the same entries, the same operations.
+    const bool below = split && tend < g.Npad;
+    if (below) {
+        int r2 = ensure_rest_stream(ctx); if (r2) return r2;
+        PYIPM_HIP(hipEventRecord(ctx->ev_split, hs));          // the source group is complete, the main stream's
+        PYIPM_HIP(hipStreamWaitEvent(ctx->rest, ctx->ev_split, 0));   // earlier updates of these columns are ordered
+    }
+    // W of a panel inside its group's buffer: wbuf(q0) addresses it (column offset of q0 in the group)
+    const int64_t rows = split ? cols : g.Npad - tc0;
+    hipLaunchKernelGGL(k_inpanel_update, dim3((unsigned)(rows / 32), (unsigned)(cols / TB)), dim3(256), 0,
+                       hs, ctx->A, g.Npad, g.local_c0(tp), ctx->A + g.local_c0(q0) * g.Npad, g.Npad,
+                       wbuf(ctx, q0), g.Npad, tc0, K, tc0, g.Npad, pa0, pa1, pb0, pb1, SIDE_PRIO);
+    PYIPM_KCHECK();
+    if (below && g.Npad - tend <= HEAD32_ROWS) {
+        hipLaunchKernelGGL(k_inpanel_update, dim3((unsigned)((g.Npad - tend) / 32), (unsigned)(cols / TB)), dim3(256), 0,
+                           ctx->rest, ctx->A, g.Npad, g.local_c0(tp), ctx->A + g.local_c0(q0) * g.Npad, g.Npad,
+                           wbuf(ctx, q0), g.Npad, tc0, K, tend, g.Npad, pa0, pa1, pb0, pb1, SIDE_PRIO);
+        PYIPM_KCHECK();
+    } else if (below) {
+        return launch_update128(ctx, ctx->rest, ctx->A + g.local_c0(q0) * g.Npad, g.Npad, wbuf(ctx, q0), K, tend, tp, tn,
+                                {.src_c0 = g.panel_c0(q0), .waves = HEAD_WAVES});
+    }
+    return 0;
+}
+
+// One iteration of the lookahead loop, decided (group grp is complete, group grp + 1 runs next)
+struct GroupStep {
+    bool fast_src, nxt_fast;      // group grp / group grp + 1 lies inside the slack block
+    bool across; int64_t pT, nT;  // the lookahead target and its panels: group grp + 1, or (across) group grp + 2 BEHIND the slack group
+    bool pieces, head, split;     // (early0) grp's contribution is applied already, panel by panel: no head, no bulk; a head is launched; in two launches
+    hipStream_t cs, hs;           // where group grp + 1 runs; where the head runs
+};
+static GroupStep plan_step(const Ctx* ctx, const FactorRun& run, int64_t grp) {
+    const GroupSched& sc = ctx->sched;
+    GroupStep st; st.fast_src = sc.fast(grp); st.nxt_fast = sc.fast(grp + 1);
+    // Streams.  The next group runs on cs: the side stream, except a group inside the slack block -- a handful of
+    // microsecond launches (closed form) that stay on the main stream, head included (sending them through the side
+    // stream cost two stream crossings per group, 50-240 us each time for 30 us of work; config 2: 0.6 of 3.6 ms).
+    st.cs = st.nxt_fast ? ctx->stream : ctx->side;
+    // (round 5) Lookahead ACROSS the slack block.  With its panels run up front the slack group between the last x group
+    // and the first multiplier group is no work at all -- but that multiplier group's columns used to get this group's
+    // contribution from its BULK update, and its chain started behind the whole launch and the slack group's hops
+    // (N = 32768: 1.6 + 0.3 ms with nothing else on the chain's path; config 2: 0.14 ms).  The group after the slack group
+    // is treated as the lookahead target: a head (split: its diagonal block on the chain's stream, the rows below on the
+    // rows stream) applies this group's contribution to its columns, the bulk update starts beyond them.  The same
+    // products in the same order per entry (x groups in order, then the slack block's diagonal update).
+    st.across = run.slack_first && st.nxt_fast && !st.fast_src && grp > 0 && grp + 2 < sc.ngroups() &&
+                !sc.fast(grp + 2) && chain_group(ctx, grp + 2);
+    st.pT = sc.first(grp + (st.across ? 2 : 1)); st.nT = sc.size(grp + (st.across ? 2 : 1));
+    // The head runs on hs: the stream of the chain it follows, i.e. the side stream for every group but the first, so
+    // that chain -> head -> next chain never cross streams.  There it waits for ev_main: the bulk update of
+    // the group before (and the early heads) touched its columns on the main stream -- normally long complete.
+    // (the FIRST head stays on the main stream also when group 0 ran on the chain's stream: nothing runs beside it either
+    //  way, and as a main-stream launch it takes the bulk instance and is part of the trailing figures, as in rounds 1-3)
+    st.hs = (grp > 0 && (st.cs == ctx->side || st.across)) ? ctx->side : ctx->stream;
+    st.pieces = run.early0 && grp == 0;
+    // (a head INTO the slack block is structurally empty: no x column reaches an s column, and a slack column's only
+    //  update is a diagonal entry of the multiplier block -- no launch, 10-15 us of the chain's path each)
+    st.head = !st.pieces && (st.across || !st.nxt_fast);
+    st.split = st.across || (chain_group(ctx, grp + 1) && st.cs != ctx->stream);
+    return st;
+}
+
+// The enqueue, in this order: the schedule (plan_groups, FactorRun); the closed-form panels of the slack block up front
+// (enqueue_slack_first); group 0 on the main stream; then per group grp, as plan_step decided: head (group grp -> the lookahead
+// target) on hs, group grp + 1 on cs, bulk update (group grp -> everything behind the target) on the main stream beside it --
+// one-group lookahead.  lookahead = 0: bulk update, then the next group, all on the main stream.
 int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
     const Geo& g = ctx->g;
     if (g.world != 1) { ctx->err = "factor(): single-rank entry point; use the per-panel phases when world > 1"; return PYIPM_E_BADARG; }
     if (!ctx->assembled) { ctx->err = "factor: assemble first"; return PYIPM_E_BADARG; }
-    ctx->per_panel_mode = false;
     const auto t_host0 = std::chrono::steady_clock::now();
     int rc = 0;
     if (!ctx->side) {
@@ -1730,65 +1922,16 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
         // CU slot a retiring bulk-update block frees instead of queueing behind the whole bulk grid
         int lo = 0, hi = 0;
         PYIPM_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
+        for (hipEvent_t* e : {&ctx->ev_main, &ctx->ev_early, &ctx->ev_split, &ctx->ev_sfast})      // the events of the schedule below
+            if (!*e) PYIPM_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
         PYIPM_HIP(hipStreamCreateWithPriority(&ctx->side, hipStreamNonBlocking, hi));
     }
     PYIPM_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
-    // Group schedule: `group` panels per bulk update while the bulk update outlasts the panel chain; once at most
-    // TAIL_COLS columns remain the chain is the critical path and shorter groups (less in-group update work on
-    // the chain, more in the cheap bulk launches) end the factorisation sooner.
-    const int64_t np = g.npanels;
-    ctx->grp_of.assign((size_t)np, 0); ctx->grp_off.assign((size_t)np, 0); ctx->grp_first.clear();
-    {
-        int64_t p = 0; int gid = 0;
-        while (p < np) {
-            const int64_t remaining = g.Npad - g.panel_c0(p);
-            // (round 6: systems of at most 8192 rows take groups of 8 in the tail too -- with the chain of a group as ONE launch a group
-            //  boundary costs more than the in-group updates of the longer group: config 2 2.25 against 2.29 ms; N = 32768: 104.9
-            //  against 102.4 ms, config 3 185.4 against 183.2: 4 stays there)
-            const int tg = (!ctx->tail_group_user && g.Npad <= 8192) ? 8 : ctx->tail_group;
-            int64_t G = (tg > 0 && remaining <= TAIL_COLS) ? tg : ctx->group;
-            if (G > ctx->group) G = ctx->group;
-            if (p + G > np) G = np - p;
-            // (round 5) the panels inside the slack block as ONE group: their kernels run up front (enqueue_slack_first) and what is left of
-            // a slack group in the loop below is a head, a k_s_schur launch and four stream hops -- 56 us per group of four
-            // panels between the x block's last bulk update and the multiplier block's first chain (N = 32768: six groups)
-            if (ctx->skip_zeros && g.mi > 0 && g.world == 1 && ctx->lookahead && p > 0 &&
-                g.panel_c0(p) >= g.n && g.panel_c0(p + G - 1) + g.panel_w(p + G - 1) <= g.n + g.mi) {
-                while (p + G < np && g.panel_c0(p + G) + g.panel_w(p + G) <= g.n + g.mi) ++G;
-            }
-            ctx->grp_first.push_back(p);
-            for (int64_t q = 0; q < G; ++q) { ctx->grp_of[(size_t)(p + q)] = gid; ctx->grp_off[(size_t)(p + q)] = (int)q; }
-            p += G; ++gid;
-        }
-        ctx->grp_first.push_back(np);
-        ctx->grp_fast.assign(ctx->grp_first.size() - 1, 0);
-        ctx->grp_x.assign(ctx->grp_first.size() - 1, 0);
-        for (size_t gi = 0; gi + 1 < ctx->grp_first.size(); ++gi) {
-            const int64_t pb = ctx->grp_first[gi + 1];
-            ctx->grp_x[gi] = (g.panel_c0(pb - 1) + g.panel_w(pb - 1) <= g.n) ? 1 : 0;
-        }
-        if (ctx->skip_zeros && g.mi > 0 && g.world == 1)       // groups inside the slack block: closed-form elimination (k_s_panel)
-            for (size_t gi = 0; gi + 1 < ctx->grp_first.size(); ++gi) {
-                const int64_t pa = ctx->grp_first[gi], pb = ctx->grp_first[gi + 1];
-                const int64_t ca = g.panel_c0(pa), cb = g.panel_c0(pb - 1) + g.panel_w(pb - 1);
-                ctx->grp_fast[gi] = (ca >= g.n && cb <= g.n + g.mi) ? 1 : 0;
-            }
-    }
-    const int64_t ngroups = (int64_t)ctx->grp_first.size() - 1;
-    auto gsize = [&](int64_t grp) { return ctx->grp_first[(size_t)grp + 1] - ctx->grp_first[(size_t)grp]; };
-    // diagnostics (PYIPM_GROUP_TRACE=1): where each group's chain, head and bulk update begin and end on the device, without a
-    // tracer's per-call cost on the host (tools/group_trace.py)
-    static const bool group_trace = getenv("PYIPM_GROUP_TRACE") != nullptr;
-    std::vector<std::pair<std::string, hipEvent_t>> marks;
-    auto mark = [&](const char* what, int64_t grp, hipStream_t st) {
-        if (!group_trace) return;
-        hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return;
-        hipEventRecord(e, st);
-        char buf[64]; snprintf(buf, sizeof(buf), "%s g%lld", what, (long long)grp);
-        marks.push_back({buf, e});
-    };
-    // Fused forward substitution: y_p only needs panel p factored, so the forward pass of the step's
-    // right-hand side (already in v0) trails the factorisation on its own stream.
+    ctx->sched = plan_groups(g, ctx->group, ctx->tail_group, ctx->tail_group_user, ctx->skip_zeros != 0, ctx->lookahead);
+    const GroupSched& sc = ctx->sched;
+    const int64_t np = g.npanels, ngroups = sc.ngroups();
+    const FactorRun run{fuse_forward, ctx->lookahead >= 2 && ngroups > 2 && chain_group(ctx, 0) && sc.fast(1), slack_first_applies(ctx)};
+    GroupTrace tr;
     ctx->forward_fused = false;
     if (fuse_forward) {
         if (!ctx->fwd) PYIPM_HIP(hipStreamCreateWithFlags(&ctx->fwd, hipStreamNonBlocking));
@@ -1796,202 +1939,57 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
         PYIPM_HIP(hipEventRecord(ctx->ev_head, ctx->stream));          // v0 = rhs copy was enqueued on the main stream
         PYIPM_HIP(hipStreamWaitEvent(ctx->fwd, ctx->ev_head, 0));
     }
-    std::vector<char> s_done_early((size_t)np, 0);     // closed-form panels of the slack block already enqueued (enqueue_slack_first, below)
-    auto after_panel = [&](int64_t q, hipStream_t used) -> int {
-        if (!fuse_forward) return 0;
-        if (!s_done_early[(size_t)q]) PYIPM_HIP(hipEventRecord(ctx->ev_done[q], used));      // (else: recorded behind its kernel)
-        PYIPM_HIP(hipStreamWaitEvent(ctx->fwd, ctx->ev_done[q], 0));
-        int r2 = fwd_panel(ctx, q, ctx->fwd_vec, ctx->fwd); if (r2) return r2;
-        return diag_panel(ctx, q, ctx->fwd_vec, ctx->fwd);
-    };
-    // does group grp run as a tile chain (factor_group)?
-    auto chain_group = [&](int64_t grp) -> bool {
-        const bool fast = !ctx->grp_fast.empty() && ctx->grp_fast[(size_t)grp];
-        return ctx->group_chain && !fast && gsize(grp) * (g.nb / TB) <= 32 && g.nb % 128 == 0;
-    };
-    // Group 0 right-looking panel by panel (round 6, lookahead = 2): a system whose x block is ONE group followed by the slack
-    // block (config 2).  Nothing runs beside the first group's chain, the slack group is no work, and the x group's bulk
-    // update -- a launch of a hundred-odd tiles -- is what the multiplier block's chain waits for in full (272 us of 2.22 ms).
-    // Here every panel of group 0 goes to the columns beyond the group as soon as it is complete: a K = nb launch on the side
-    // stream (idle until the next chain) behind the panel's event, under the chain of the panels that follow; neither a head
-    // nor a bulk update is left for group 0.  Every entry receives the same products in the same order.  Measured
-    // (tools/r06_early.sh): config 2 2.225 -> 2.165 ms -- the chain itself slows from 880 to 970 us beside the pieces (its
-    // round trips to memory share the fabric with their operands), the next chain starts 140 us earlier.  Where the next group
-    // is an ordinary one the one-group lookahead already hides the bulk update under that group's chain and the pieces lose
-    // (n, me, mi = 3072, 512, 1024: 2.99 -> 3.08 ms): not applied there.  Fewer, persistent blocks per piece (64 ... 192
-    // of them) only made the last piece longer.
-    const bool early0 = ctx->lookahead >= 2 && ngroups > 2 && chain_group(0) && !ctx->grp_fast.empty() && !ctx->grp_fast[0] &&
-                        ctx->grp_fast[1];
-    if (early0 && !ctx->ev_early) PYIPM_HIP(hipEventCreateWithFlags(&ctx->ev_early, hipEventDisableTiming));
-    auto early_piece = [&](int64_t q, hipStream_t used) -> int {
-        const int64_t p1 = ctx->grp_first[1];
-        PYIPM_HIP(hipEventRecord(ctx->ev_early, used));
-        PYIPM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_early, 0));
-        return timed_update(ctx, q, 1, p1, np - p1, {.stream = ctx->side, .as_bulk = true});
-    };
-    // all panels of one group on stream S
-    auto run_group = [&](int64_t grp, hipStream_t S) -> int {
-        const int64_t pA = ctx->grp_first[(size_t)grp], nA = gsize(grp);
-        auto done = [&](int64_t q, hipStream_t used) -> int {
-            int r2 = after_panel(q, used); if (r2) return r2;
-            return (early0 && grp == 0) ? early_piece(q, used) : 0;
-        };
-        if (chain_group(grp)) return factor_group(ctx, pA, nA, S, done);
-        for (int64_t q = pA; q < pA + nA; ++q) {
-            if (!s_done_early[(size_t)q]) { int r2 = factor_panel(ctx, q, S, true); if (r2) return r2; }
-            int r2 = done(q, S); if (r2) return r2;
-        }
-        return 0;
-    };
-    // (round 5) The closed-form panels of the slack block depend on nothing but the assembly -- no x-block update
-    // reaches their columns -- and used to sit, one 7 us launch after the other, between the x block's last chain and the
-    // multiplier block's first (config 2: 0.15 of 2.7 ms, plus the last x group's bulk update queued behind them on the same
-    // stream).  They are enqueued up front on the rows stream; what READS them (k_s_schur on the update stream, the forward
-    // sweep) keeps its place and waits for one event.  Statistics are atomic sums / minima / maxima: the same numbers.
-    bool slack_first = false;                          // ... done for this factorisation
-    auto enqueue_slack_first = [&](hipStream_t after) -> int {
-        if (!(ctx->lookahead && g.world == 1 && ngroups > 1) || ctx->grp_fast.empty()) return 0;
-        bool any = false;
-        for (int64_t gi = 1; gi < ngroups; ++gi) any = any || ctx->grp_fast[(size_t)gi];
-        if (!any || (ctx->grp_fast[0])) return 0;
-        { int r0 = ensure_rest_stream(ctx); if (r0) return r0; }
-        if (!ctx->ev_sfast) PYIPM_HIP(hipEventCreateWithFlags(&ctx->ev_sfast, hipEventDisableTiming));
-        PYIPM_HIP(hipEventRecord(ctx->ev_sfast, after));                  // the assembly and the reset of the statistics
-        PYIPM_HIP(hipStreamWaitEvent(ctx->rest, ctx->ev_sfast, 0));
-        for (int64_t gi = 1; gi < ngroups; ++gi) {
-            if (!ctx->grp_fast[(size_t)gi]) continue;
-            for (int64_t q = ctx->grp_first[(size_t)gi]; q < ctx->grp_first[(size_t)gi + 1]; ++q) {
-                int r2 = factor_panel(ctx, q, ctx->rest, true); if (r2) return r2;
-                if (fuse_forward) PYIPM_HIP(hipEventRecord(ctx->ev_done[q], ctx->rest));
-                s_done_early[(size_t)q] = 1;
-            }
-        }
-        PYIPM_HIP(hipEventRecord(ctx->ev_sfast, ctx->rest));              // every closed-form panel is done
-        slack_first = true;
-        return 0;
-    };
     rc = factor_begin(ctx); if (rc) return rc;
-    rc = enqueue_slack_first(ctx->stream); if (rc) return rc;
-    mark("chain+rows begin", 0, ctx->stream);
-    rc = run_group(0, ctx->stream); if (rc) return rc;
-    mark("chain+rows end", 0, ctx->stream);
+    if (run.slack_first) { rc = enqueue_slack_first(ctx, run, ctx->stream); if (rc) return rc; }
+    tr.mark("chain+rows begin", 0, ctx->stream);
+    rc = run_group(ctx, run, 0, ctx->stream); if (rc) return rc;
+    tr.mark("chain+rows end", 0, ctx->stream);
+    if (tr.on()) fprintf(stderr, "[pyipm group trace] %lld groups\n", (long long)ngroups);
     bool across_prev = false;
-    if (group_trace) fprintf(stderr, "[pyipm group trace] %lld groups\n", (long long)ngroups);
     for (int64_t grp = 0; grp + 1 < ngroups; ++grp) {
-        const int64_t p0 = ctx->grp_first[(size_t)grp], n0 = gsize(grp), p1 = p0 + n0, n1 = gsize(grp + 1);
-        if (ctx->lookahead) {
-            // head: next group's columns (the next chain waits for it).  Sources: the panels of this group whose
-            // contribution an early head has not applied yet (see below).
-            const bool fast_src = !ctx->grp_fast.empty() && ctx->grp_fast[(size_t)grp];
-            auto head_from = [&](int64_t q0, int64_t nq, int64_t tp, int64_t tn, hipStream_t hs, bool split = false) -> int {
-                const int64_t tc0 = g.panel_c0(tp);
-                if (!fast_src && g.Npad - tc0 <= HEAD32_ROWS) {            // (where the chain is the bound: 32 x 64 blocks)
-                    int K = 0; int64_t cols = 0;
-                    for (int64_t q = q0; q < q0 + nq; ++q) K += (int)g.panel_w(q);
-                    for (int64_t q = tp; q < tp + tn; ++q) cols += g.panel_w(q);
-                    const int64_t tend = tc0 + cols;
-                    int64_t pa0, pa1, pb0, pb1;
-                    active_ranges(ctx, g.panel_c0(q0), g.panel_c0(q0) + K, &pa0, &pa1, &pb0, &pb1);
-                    // split: the chain of the target group needs the head only inside that group's diagonal block (rows [tc0, tend));
-                    // the rows below it are first read by the group's rows stream.  Two launches: the block on the chain's
-                    // stream, the rest on ctx->rest behind it -- the same entries, the same operations.
-                    const bool below = split && tend < g.Npad;
-                    if (below) {
-                        int r2 = ensure_rest_stream(ctx); if (r2) return r2;
-                        if (!ctx->ev_split) PYIPM_HIP(hipEventCreateWithFlags(&ctx->ev_split, hipEventDisableTiming));
-                        PYIPM_HIP(hipEventRecord(ctx->ev_split, hs));          // the source group is complete, the main stream's
-                        PYIPM_HIP(hipStreamWaitEvent(ctx->rest, ctx->ev_split, 0));   // earlier updates of these columns are ordered
-                    }
-                    // W of a panel inside its group's buffer: wbuf(q0) addresses it (column offset of q0 in the group)
-                    const int64_t rows = split ? cols : g.Npad - tc0;
-                    hipLaunchKernelGGL(k_inpanel_update, dim3((unsigned)(rows / 32), (unsigned)(cols / TB)), dim3(256), 0,
-                                       hs, ctx->A, g.Npad, g.local_c0(tp), ctx->A + g.local_c0(q0) * g.Npad, g.Npad,
-                                       wbuf(ctx, q0), g.Npad, tc0, K, tc0, g.Npad, pa0, pa1, pb0, pb1, SIDE_PRIO);
-                    PYIPM_KCHECK();
-                    if (below && g.Npad - tend <= HEAD32_ROWS) {
-                        hipLaunchKernelGGL(k_inpanel_update, dim3((unsigned)((g.Npad - tend) / 32), (unsigned)(cols / TB)), dim3(256), 0,
-                                           ctx->rest, ctx->A, g.Npad, g.local_c0(tp), ctx->A + g.local_c0(q0) * g.Npad, g.Npad,
-                                           wbuf(ctx, q0), g.Npad, tc0, K, tend, g.Npad, pa0, pa1, pb0, pb1, SIDE_PRIO);
-                        PYIPM_KCHECK();
-                    } else if (below) {
-                        return launch_update128(ctx, ctx->rest, ctx->A + g.local_c0(q0) * g.Npad, g.Npad, wbuf(ctx, q0), K, tend, tp, tn,
-                                                {.src_c0 = g.panel_c0(q0), .waves = HEAD_WAVES});
-                    }
-                    return 0;
-                }
-                return timed_update(ctx, q0, nq, tp, tn, {.stream = hs});
-            };
-            // Streams.  The next group runs on cs: the side stream, except a group inside the slack block -- a handful of
-            // microsecond launches (closed form) that stay on the main stream, head included (sending them through the side
-            // stream cost two stream crossings per group, 50-240 us each time for 30 us of work; config 2: 0.6 of 3.6 ms).
-            // The head runs on hs: the stream of the chain it follows, i.e. the side stream for every group but the first, so
-            // that chain -> head -> next chain never cross streams.  There it waits for ev_main (below): the bulk update of
-            // the group before (and the early heads) touched its columns on the main stream -- normally long complete.
-            const bool nxt_fast = !ctx->grp_fast.empty() && ctx->grp_fast[(size_t)(grp + 1)];
-            hipStream_t cs = nxt_fast ? ctx->stream : ctx->side;             // where the next group runs
-            hipStream_t hs = ctx->stream;                                    // where the head runs (group 0's; the others: below)
-            // (the FIRST head stays on the main stream also when group 0 ran on the chain's stream: nothing runs beside it either
-            //  way, and as a main-stream launch it takes the bulk instance and is part of the trailing figures, as in rounds 1-3)
-            // (round 5) Lookahead ACROSS the slack block.  With its panels run up front the slack group between the last x group
-            // and the first multiplier group is no work at all -- but that multiplier group's columns used to get this group's
-            // contribution from its BULK update, and its chain started behind the whole launch and the slack group's hops
-            // (N = 32768: 1.6 + 0.3 ms with nothing else on the chain's path; config 2: 0.14 ms).  The group after the slack group
-            // is treated as the lookahead target: a head (split: its diagonal block on the chain's stream, the rows below on the
-            // rows stream) applies this group's contribution to its columns, the bulk update starts beyond them.  The same
-            // products in the same order per entry (x groups in order, then the slack block's diagonal update).
-            const bool across = slack_first && nxt_fast && !fast_src && grp > 0 && grp + 2 < ngroups &&
-                                !ctx->grp_fast[(size_t)(grp + 2)] && chain_group(grp + 2);
-            const int64_t pT = across ? ctx->grp_first[(size_t)(grp + 2)] : 0, nT = across ? gsize(grp + 2) : 0;
-            if (grp > 0 && (cs == ctx->side || across)) {
-                // (recorded at the end of the iteration before.  Behind an `across` iteration the source is the slack group: its
-                //  head is the diagonal update of the target's columns, ordered behind the x group's head on this stream, and the
-                //  x group's bulk update -- what the event would wait for -- no longer touches those columns)
-                if (!across_prev) PYIPM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_main, 0));
-                hs = ctx->side;
-                if (slack_first && fast_src) PYIPM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_sfast, 0));   // (k_s_schur reads the slack columns)
-            }
-            const bool pieces = early0 && grp == 0;        // group 0's contribution is on the side stream already, panel by panel
-            if (pieces) {
-                PYIPM_HIP(hipEventRecord(ctx->ev_early, ctx->side));          // the last piece
-                PYIPM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_early, 0)); // (later updates of those columns; cs, if it is the main stream)
-                if (ctx->rest) PYIPM_HIP(hipStreamWaitEvent(ctx->rest, ctx->ev_early, 0));
-            }
-            if (!pieces) {
-                const bool split = chain_group(grp + 1) && cs != ctx->stream;
-                mark("head begin", grp, hs);
-                // (a head INTO the slack block is structurally empty: no x column reaches an s column, and a slack column's only
-                //  update is a diagonal entry of the multiplier block -- no launch, 10-15 us of the chain's path each)
-                if (across) { rc = head_from(p0, n0, pT, nT, hs, true); if (rc) return rc; }
-                else if (!nxt_fast) { rc = head_from(p0, n0, p1, n1, hs, split); if (rc) return rc; }
-                mark("head end (its first launch's stream)", grp, hs);
-            }
-            if (hs == ctx->stream && cs == ctx->side) {
-                PYIPM_HIP(hipEventRecord(ctx->ev_head, ctx->stream));
-                PYIPM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_head, 0));
-            }
-            mark("chain+rows begin", grp + 1, cs);
-            if (slack_first && nxt_fast)                                 // its kernels ran up front: whoever follows on cs (= the main
-                PYIPM_HIP(hipStreamWaitEvent(cs, ctx->ev_sfast, 0));      // stream: k_s_schur too) is ordered behind them
-            rc = run_group(grp + 1, cs); if (rc) return rc;
-            mark("chain+rows end", grp + 1, cs);
-            PYIPM_HIP(hipEventRecord(ctx->ev_panel, cs));
-            mark("bulk begin", grp, ctx->stream);
-            across_prev = across;
-            if (pieces) { /* applied panel by panel */ }
-            else if (across) { rc = timed_update(ctx, p0, n0, pT + nT, np - (pT + nT)); if (rc) return rc; }   // (the target's columns: the head above)
-            else
-            { rc = timed_update(ctx, p0, n0, p1 + n1, np - (p1 + n1)); if (rc) return rc; }   // bulk (overlaps the side stream)
-            mark("bulk end", grp, ctx->stream);
-            // what the next head must not overtake on the main stream: this group's bulk update -- recorded
-            // BEFORE the main stream starts waiting for the side stream (the head would otherwise wait for its own stream,
-            // two stream crossings for nothing)
-            if (!ctx->ev_main) PYIPM_HIP(hipEventCreateWithFlags(&ctx->ev_main, hipEventDisableTiming));
-            PYIPM_HIP(hipEventRecord(ctx->ev_main, ctx->stream));
-            PYIPM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_panel, 0));
-        } else {
-            rc = timed_update(ctx, p0, n0, p1, np - p1); if (rc) return rc;
-            rc = run_group(grp + 1, ctx->stream); if (rc) return rc;
+        const int64_t p0 = sc.first(grp), n0 = sc.size(grp);            // the source: its contribution goes to everything behind it
+        if (!ctx->lookahead) {
+            rc = timed_update(ctx, p0, n0, p0 + n0, np - (p0 + n0)); if (rc) return rc;
+            rc = run_group(ctx, run, grp + 1, ctx->stream); if (rc) return rc;
+            continue;
         }
+        const GroupStep st = plan_step(ctx, run, grp);
+        if (st.hs == ctx->side) {
+            // (recorded at the end of the iteration before.  Behind an `across` iteration the source is the slack group: its
+            //  head is the diagonal update of the target's columns, ordered behind the x group's head on this stream, and the
+            //  x group's bulk update -- what the event would wait for -- no longer touches those columns)
+            if (!across_prev) PYIPM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_main, 0));
+            if (run.slack_first && st.fast_src) PYIPM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_sfast, 0));   // (k_s_schur reads the slack columns)
+        }
+        if (st.pieces) {
+            PYIPM_HIP(hipEventRecord(ctx->ev_early, ctx->side));          // the last piece
+            PYIPM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_early, 0)); // (later updates of those columns; cs, if it is the main stream)
+            if (ctx->rest) PYIPM_HIP(hipStreamWaitEvent(ctx->rest, ctx->ev_early, 0));
+        } else {
+            tr.mark("head begin", grp, st.hs);
+            if (st.head) { rc = head_from(ctx, st.fast_src, p0, n0, st.pT, st.nT, st.hs, st.split); if (rc) return rc; }
+            tr.mark("head end (its first launch's stream)", grp, st.hs);
+        }
+        if (st.hs == ctx->stream && st.cs == ctx->side) {
+            PYIPM_HIP(hipEventRecord(ctx->ev_head, ctx->stream));
+            PYIPM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_head, 0));
+        }
+        tr.mark("chain+rows begin", grp + 1, st.cs);
+        if (run.slack_first && st.nxt_fast)                              // its kernels ran up front: whoever follows on cs (= the main
+            PYIPM_HIP(hipStreamWaitEvent(st.cs, ctx->ev_sfast, 0));      // stream: k_s_schur too) is ordered behind them
+        rc = run_group(ctx, run, grp + 1, st.cs); if (rc) return rc;
+        tr.mark("chain+rows end", grp + 1, st.cs);
+        PYIPM_HIP(hipEventRecord(ctx->ev_panel, st.cs));
+        tr.mark("bulk begin", grp, ctx->stream);
+        // bulk (overlaps the side stream): everything behind the target, whose columns the head above took
+        if (!st.pieces) { rc = timed_update(ctx, p0, n0, st.pT + st.nT, np - (st.pT + st.nT)); if (rc) return rc; }
+        tr.mark("bulk end", grp, ctx->stream);
+        // what the next head must not overtake on the main stream: this group's bulk update -- recorded
+        // BEFORE the main stream starts waiting for the side stream (the head would otherwise wait for its own stream,
+        // two stream crossings for nothing)
+        PYIPM_HIP(hipEventRecord(ctx->ev_main, ctx->stream));
+        PYIPM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_panel, 0));
+        across_prev = st.across;
     }
     if (fuse_forward) {                     // join: the main stream continues after the forward pass
         PYIPM_HIP(hipEventRecord(ctx->ev_fwd, ctx->fwd));
@@ -2008,16 +2006,7 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
     rc = factor_end(ctx, stats);
     float ms = 0.f;
     PYIPM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    if (group_trace) {
-        hipEventSynchronize(ctx->ev[1]);
-        for (auto& m : marks) {
-            float t = 0.f;
-            if (hipEventSynchronize(m.second) == hipSuccess && hipEventElapsedTime(&t, ctx->ev[0], m.second) == hipSuccess)
-                fprintf(stderr, "[pyipm group trace] %9.1f us  %s\n", 1e3 * t, m.first.c_str());
-            hipEventDestroy(m.second);
-        }
-        fprintf(stderr, "[pyipm group trace] %9.1f us  factorisation end\n", 1e3 * ms);
-    }
+    tr.report(ctx->ev[0], ctx->ev[1], ms);
     ctx->t_factor = ms;
     ctx->t_panel = ctx->profile ? (ms - ctx->t_trailing_union) : 0.0;    // exposed panel time: no update launch running
     return rc;
@@ -2922,8 +2911,7 @@ int pyipm_newton_factor_begin(pyipm_newton_ctx* h) try {
     if (ctx->batched) return single_only(ctx);
     if (!ctx->assembled) { ctx->err = "factor_begin: assemble first"; return PYIPM_E_BADARG; }
     if (ctx->cond_active) { ctx->err = "per-panel phases do not apply to the condensed system; use factor()"; return PYIPM_E_BADARG; }
-    ctx->grp_of.clear(); ctx->grp_off.clear(); ctx->grp_fast.clear(); ctx->grp_x.clear();      // per-panel phases: uniform group map, dense panels
-    ctx->per_panel_mode = true;
+    ctx->sched.clear();                                 // per-panel phases: uniform group map, dense panels
     ctx->zeros_clean = false;                           // (the caller drives the panels: no promise about what gets written)
     return factor_begin(ctx);
 } PYIPM_CATCH_H(h)
