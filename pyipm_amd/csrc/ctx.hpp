@@ -9,8 +9,10 @@
 #include <new>
 #include <stdexcept>
 #include <map>
+#include <memory>
 #include <vector>
 #include "../../include/pyipm_newton.h"
+#include "owned.hpp"
 
 namespace pyipm {
 
@@ -128,26 +130,29 @@ struct GroupSched {
     bool fast(int64_t grp) const { return fast_[(size_t)grp] != 0; }      bool in_x(int64_t grp) const { return in_x_[(size_t)grp] != 0; }
 };
 
+struct DistState;                                       // dist_impl.hpp
+struct DistDelete { void operator()(DistState*) const; };   // (pyipm_dist.hip: the type is complete there)
+
 struct Ctx {
     Geo g;
     int batch = 1;                        // problems of a batched small-system handle (kernels_batched.hpp)
     bool batched = false;                 // batched handle: single-system entry points refuse it
     int64_t b_sH = 0, b_sJe = 0, b_sJi = 0;   // batch strides (doubles) of the caller's blocks
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t side = nullptr;           // panel lookahead stream (created on first factor)
-    hipEvent_t ev_head = nullptr, ev_panel = nullptr, ev_fwd = nullptr;
-    hipStream_t fwd = nullptr;            // fused forward-substitution stream
-    std::vector<hipEvent_t> ev_done;      // panel q factored
+    hipStream_t stream = nullptr;         // the caller's: not owned
+    Stream side;                          // panel lookahead stream (created on first factor)
+    Event ev_head, ev_panel, ev_fwd;      // (no event of the handle is a timing event but ev, ev_prov and ev_trailing)
+    Stream fwd;                           // fused forward-substitution stream
+    std::vector<Event> ev_done;           // panel q factored
     int fuse_forward = 1;
     bool forward_fused = false;
     bool forward_pending = false;         // factor() already forward-substituted the pending residual into v0
     int lookahead = 2;                    // 0 none, 1 one group (two groups on a dedicated stream measured no faster: removed), 2 = 1 + the
                                           // first group's update panel by panel under its own chain where the slack block follows it (factor_all)
-    hipEvent_t ev_early = nullptr;
+    Event ev_early;
     struct TileList { unsigned* dev = nullptr; unsigned count = 0;
-                      hipEvent_t ready = nullptr; hipStream_t on = nullptr; bool seen_done = false; };   // the async upload: its event, its stream
-    struct TlArena { unsigned* dev = nullptr; unsigned* host = nullptr; size_t cap = 0, used = 0; };    // device + pinned host memory of the lists
+                      Event ready; hipStream_t on = nullptr; bool seen_done = false; };   // the async upload: its event, its stream
+    struct TlArena { DevBuf<unsigned> dev; PinnedBuf<unsigned> host{hipHostMallocDefault}; size_t used = 0; };   // device + pinned host memory of the lists
     std::vector<TlArena> tl_arenas;
     std::map<std::vector<int64_t>, TileList> tile_lists;   // compact tile orders of the bulk launches (geometry repeats every step)
     int skip_zeros = 1;                   // trailing updates skip tiles that the KKT block structure makes exact zeros
@@ -159,9 +164,9 @@ struct Ctx {
                                           // that carries the next tile's in-panel update (k_panel_scale + NextUpd, factor_panel)
     int group_chain = 1;                  // single rank: the panels of a group are chained tile to tile (factor_group), the rows
                                           // below the group's diagonal block follow on their own stream; same bits
-    hipStream_t rest = nullptr;           // ... that stream (high priority, created on first use: ensure_rest_stream)
-    std::vector<hipEvent_t> ev_band;      // panel (by offset in its group): its tiles are inverted and applied inside the diagonal block
-    hipEvent_t ev_join = nullptr, ev_main = nullptr, ev_split = nullptr, ev_sfast = nullptr;
+    Stream rest;                          // ... that stream (high priority, created on first use: ensure_rest_stream)
+    std::vector<Event> ev_band;           // panel (by offset in its group): its tiles are inverted and applied inside the diagonal block
+    Event ev_join, ev_main, ev_split, ev_sfast;
     int keep_zeros = 1;                   // K1 does not store again the zeros nothing can fill in (k_assemble, zeros_in_place)
     bool zeros_clean = false;             // ... which requires that the last writer of those places was a full assembly
     bool storage_exported = false;        // kkt_storage() handed the pointer out: a holder may write into those zeros at any time,
@@ -171,11 +176,9 @@ struct Ctx {
     int sweep_max_blocks = 0;             // test hook: cap on the workgroups of the one-launch sweeps (0 = as many as the GPU holds)
     int occ_fwd_sweep = 0, occ_bwd_sweep = 0;   // resident workgroups per CU of the one-launch sweeps (occupancy query, cached)
     int sweep_persist = 1;                // single rank, one right-hand side: the backward sweep as ONE device-driven launch (k_bwd_sweep)
-    int64_t sweep_buf_n = 0;              // ... (allocated for this many rows)
-    double* sweep_buf = nullptr;          // ... the near sums as the column owners hand them to workgroup 0 (Npad doubles, NaN = not there yet)
-    double* ms_buf = nullptr;             // solve_many: its column blocks, partials and refinement vectors (lazily hipMalloc'd, grown on demand)
-    size_t ms_buf_bytes = 0;
-    unsigned* sweep_sync = nullptr;       // ... its flags and counters (3 npanels + 1 words, zeroed before every sweep)
+    DevBuf<double> sweep_buf;             // ... the near sums as the column owners hand them to workgroup 0 (Npad doubles, NaN = not there yet)
+    DevBuf<double> ms_buf;                // solve_many: its column blocks, partials and refinement vectors (allocated on first use, grown on demand)
+    DevBuf<unsigned> sweep_sync;          // ... its flags and counters (3 npanels + 1 words, zeroed before every sweep)
     bool sweep_used = false;              // ... a sweep ran since the error word was last read (solve_info / factor_end look at it)
     int dist_slices = 2;                  // distributed schedule: the two-message protocol (slices ahead of the panel message: the next owner's tile
                                           // chain starts on an nb x nb message); 0 = one message per panel (rounds 1-4); collective
@@ -201,16 +204,15 @@ struct Ctx {
     Geo gc;                               // geometry of the condensed system: (n, me + cond_na, 0), set by assemble
     double cond_sigma_max = 1.0e4;        // inequalities with Sigma above this stay explicit rows (-1/Sigma diagonal)
     int64_t cond_na = 0;                  // |A| of the current condensed system
-    int *cond_pos = nullptr, *cond_idx = nullptr, *cond_cnt = nullptr;   // device: position in A / members / count
-    double* Jx = nullptr; size_t jx_bytes = 0;     // [Je | Ji[:, A]] (lazily hipMalloc'd)
-    double *JT = nullptr, *WT = nullptr;  // Ji' and Sigma Ji' operands of the rank-mi update (lazily hipMalloc'd)
-    size_t jt_bytes = 0;
+    int *cond_pos = nullptr, *cond_idx = nullptr, *cond_cnt = nullptr;   // device: position in A / members / count: views, into the
+    DevBuf<int> cond_store;               // workspace of a batched handle, into this (allocated on first use) of a single-system one
+    DevBuf<double> Jx;                    // [Je | Ji[:, A]] (allocated on first use)
+    DevBuf<double> JT; double* WT = nullptr;   // Ji' and, behind it, Sigma Ji': operands of the rank-mi update (allocated on first use)
     double *vc = nullptr, *vt = nullptr;  // condensed vector / mi-sized temporary (carved)
     double* fwd_vec = nullptr;            // vector the fused forward substitution runs on
     double t_gram = 0;                    // ms of the Ji Sigma Ji' launch (profile)
     bool provider_only = false;           // pyipm_newton_create_provider: staged blocks + vectors, products and residuals; no factorisation
-    bool own_ws = false;
-    char* ws = nullptr; size_t ws_bytes = 0;
+    DevBuf<char> ws;                      // the workspace: the caller's (adopted) or the library's; capacity = the bytes the geometry needs
     // carved from workspace
     double *A = nullptr, *Wbuf = nullptr, *Lbuf = nullptr, *Dinv = nullptr;
     double *Tsv = nullptr;                // the diagonal tiles T_k themselves (refinement of the block solves)
@@ -224,23 +226,22 @@ struct Ctx {
     const double *d2L = nullptr, *Je = nullptr, *Ji = nullptr;
     int64_t ld_d2L = 0, ld_Je = 0, ld_Ji = 0;
     int sharded = 0;                      // the staged blocks hold only the rows of the x-columns this rank owns (local column order)
-    struct DistState* dist = nullptr;     // distributed driver (dist_impl.hpp): exchange, streams, message buffers
-    double *stg_d2L = nullptr, *stg_Je = nullptr, *stg_Ji = nullptr;   // lazily hipMalloc'd
-    size_t stg_d2L_sz = 0, stg_Je_sz = 0, stg_Ji_sz = 0;
+    std::unique_ptr<DistState, DistDelete> dist;   // distributed driver (dist_impl.hpp): exchange, streams, message buffers
+    DevBuf<double> stg_d2L, stg_Je, stg_Ji;        // staging of host blocks (allocated on first use)
     double mu = 0.2, eps = 2.220446049250313e-16;
     double delta = 0.0, delta_c = 0.0;
     bool have_blocks = false, have_vectors = false, have_rhs = false, assembled = false, factored = false;
     bool have_direction = false;          // v2 holds the last sign-flipped direction (for step_lengths)
     // merit-function pieces (kernels_merit.hpp): scratch, the products of the current direction with the blocks (Q dx | Je' dx | Ji' dx)
-    double* merit_buf = nullptr; double* ray_buf = nullptr; size_t ray_buf_n = 0;
+    DevBuf<double> merit_buf, ray_buf;
     const double* ray_for = nullptr; bool ray_valid = false, ray_quad_given = false;
     // last solve (pyipm_newton_solve_info): refinement steps taken, |b - Hc x|/|b| before the first and after the last
     // one (-1 = not measured: a fixed-count solve), 1 = the adaptive loop met its target
     int info_steps = 0, info_converged = 0;
     double info_berr0 = -1.0, info_berr = -1.0;
     int rcond_its[2] = {0, 0};            // power / inverse iterations the last pyipm_newton_rcond took (solve_info reports them)
-    double* rc_warm[2] = {nullptr, nullptr};   // warm start of the adaptive condition estimate: the vectors its power / inverse
-    int64_t rc_warm_n = 0;                // iterations ended with last time (the next estimate starts from them)
+    DevBuf<double> rc_warm_buf;           // warm start of the adaptive condition estimate: the vectors its power / inverse
+    double* rc_warm[2] = {nullptr, nullptr};   // iterations ended with last time (the next estimate starts from them): the halves of rc_warm_buf
     bool rc_warm_valid[2] = {false, false};
     double refine_target = 1.0e-14;       // adaptive refinement stops at this backward error ...
     int refine_max = 8;                   // ... or after this many steps, or when a step gains less than 4x
@@ -261,7 +262,7 @@ struct Ctx {
     bool chain_lds_set = false;
     int chain_cpy = 5;                    // ... column tiles per unit and stage a row tile is split for
     static constexpr int CHAIN_SLOTS = 8, CHAIN_WORDS = 160;
-    unsigned* chain_sync = nullptr;       // ... progress words (CHAIN_SLOTS regions used round robin, epoch-stamped) + the sticky error word
+    DevBuf<unsigned> chain_sync;          // ... progress words (CHAIN_SLOTS regions used round robin, epoch-stamped) + the sticky error word
     unsigned chain_epoch = 0;
     ChainGeo chain_last = {};             // ... the last chain launch (factor_block hands it to k_chain_wait)
     unsigned long long* chain_dbg = nullptr; int chain_dbg_launch = 0;   // diagnostics only (option debug_chain_ptr)
@@ -276,12 +277,12 @@ struct Ctx {
     double t_assemble = 0, t_panel = 0, t_trailing = 0, t_solve = 0, t_factor = 0;
     double t_trailing_union = 0; int64_t n_trailing_real = 0;   // time with some update launch running (launches may overlap); launches that did work
     double trailing_flops = 0, trailing_area = 0; int64_t n_trailing = 0;   // area: matrix entries updated, summed over launches
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_trailing;   // reused event pool
+    std::vector<std::pair<Event, Event>> ev_trailing;   // reused pool of timing-event pairs
     struct TrailTag { int bn; double flops, area, cbytes; };   // (area: the launch's algorithmic bytes -- C tiles once in, once out, operand panels once)
     std::vector<TrailTag> trailing_tag;   // per bulk launch of the last factorisation: which k_update instance ran, its flops / bytes
     double inst_ms[2] = {0, 0}, inst_flops[2] = {0, 0}, inst_area[2] = {0, 0}, inst_cbytes[2] = {0, 0}; int64_t inst_n[2] = {0, 0};   // [0]: 128 x 128 tiles, [1]: 128 x 256
-    hipEvent_t ev[8] = {};
-    hipEvent_t ev_prov[4] = {}; bool prov_valid[2] = {false, false}; double prov_bytes[2] = {0.0, 0.0};   // provider products
+    Event ev[8];                          // timing events
+    Event ev_prov[4]; bool prov_valid[2] = {false, false}; double prov_bytes[2] = {0.0, 0.0};   // provider products
     bool ev_assemble_valid = false, ev_solve_valid = false;
     double setup_lists_ms = 0.0; int setup_lists_n = 0;     // host time spent building tile lists (one-time per geometry; PYIPM_SETUP_TRACE)
     int debug_fault = 0;                  // test hook: 1 / 2 = the next tile-list build throws std::bad_alloc / std::runtime_error;

@@ -84,27 +84,27 @@ struct DistState {
                                                        // consumed and sent where it was produced.  (A stream of its own was measured: one more
                                                        // stream in the process and every kernel of a rank got slower -- unpack 4.2 -> 16 ms, bulk
                                                        // update 16 -> 22 ms per step at N = 32768 on 8 ranks: streams share hardware queues.)
-    hipStream_t side = nullptr, cs = nullptr;          // owner's factor + pack stream (high priority); collectives
-    hipStream_t fws = nullptr;                         // the forward substitution that trails the factorisation (step_dist)
-    hipEvent_t ev_fw = nullptr;
+    Stream side, cs;                                   // owner's factor + pack stream (high priority); collectives
+    Stream fws;                                        // the forward substitution that trails the factorisation (step_dist)
+    Event ev_fw;                                       // (every event here but the profile pool has timing disabled)
     bool fwd_done = false;                             // vloc holds the forward pass of the staged right-hand side
-    hipEvent_t ev_fact[2] = {}, ev_msg[2] = {}, ev_free[2] = {}, ev_head = nullptr, ev_join = nullptr;
-    hipEvent_t ev_hop[2] = {};                         // a collective asked for on another stream is run on `cs` between these
-    double* msg[2] = {nullptr, nullptr}; size_t msg_bytes = 0;
+    Event ev_fact[2], ev_msg[2], ev_free[2], ev_head, ev_join;
+    Event ev_hop[2];                                   // a collective asked for on another stream is run on `cs` between these
+    DevBuf<double> msg[2];                             // panel messages by parity (the largest of the geometry + W doubles of slack: sag_bcast)
     // two-message protocol: slice buffers [panel parity][slice 1 | 2] (a rank sends or receives a given slice, never both), the
     // L rows rebuilt from a received slice, and their events: packed (owner's stream -> cs), received (cs -> owner-to-be's
     // stream), free (the send has left / the slice is unpacked: the buffer may be written again)
-    double* sbuf[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}; double* EL[2] = {nullptr, nullptr}; size_t slice_bytes = 0;
-    hipEvent_t ev_spack[2][2] = {}, ev_srecv[2][2] = {}, ev_sfree[2][2] = {}, ev_pre = nullptr, ev_hr = nullptr, ev_hr2 = nullptr;
-    double* seg = nullptr;                             // nb doubles: the panel segment of the forward sum
-    double* vloc = nullptr;                            // Npad: this rank's share of the vector during the sweeps
-    double* small = nullptr;                           // 16 doubles: statistics reduction
+    DevBuf<double> sbuf[2][2], EL[2];
+    Event ev_spack[2][2], ev_srecv[2][2], ev_sfree[2][2], ev_pre, ev_hr, ev_hr2;
+    DevBuf<double> seg;                                // nb doubles: the panel segment of the forward sum
+    DevBuf<double> vloc;                               // Npad: this rank's share of the vector during the sweeps
+    DevBuf<double> small;                              // 16 doubles: statistics reduction
     int selfmsg = 0;                                   // world == 1: pack + broadcast anyway (measures the message path on one GPU)
     int sag = 0;                                       // panel messages travel as scatter + all-gather (set by comm_init after its self-test)
     int sag_ok = 0;                                    // ... what the last self-test decided (set_option("dist_sag", 1) goes back to it)
     size_t sag_min_bytes = (size_t)4 << 20;            // ... from this size on
     // profile (ms, last factor_dist / solve_dist): chain = owner's panel factorisations, pack, wait-for-message, unpack
-    std::vector<hipEvent_t> pool; size_t used = 0;
+    std::vector<Event> pool; size_t used = 0;          // timing events
     struct Span { int kind; hipEvent_t a, b; };
     std::vector<Span> spans;
     double t_chain = 0, t_pack = 0, t_bcast = 0, t_unpack = 0, t_factor = 0, t_solve = 0;
@@ -119,10 +119,10 @@ struct DistState {
     // peer never joined does not return an error -- its stream just stops; the host waits for the step with a bound
     // (set_option("dist_timeout_s")) and reports WHICH panel's message / update / chain did not complete (PYIPM_E_COMM) instead
     // of blocking for ever.
-    unsigned* xflag = nullptr; unsigned xtoken = 0;                   // extra rows of a panel's chain launch: the word their units wait for, the count it last got
-    hipEvent_t ev_x = nullptr;
-    unsigned* prog_host = nullptr; unsigned* prog_dev = nullptr;     // [0] panel messages, [1] bulk updates, [2] owned panels (count so far: index + 1)
-    hipEvent_t ev_all = nullptr;
+    DevBuf<unsigned> xflag; unsigned xtoken = 0;                      // extra rows of a panel's chain launch: the word their units wait for, the count it last got
+    Event ev_x;
+    PinnedBuf<unsigned> prog_host{hipHostMallocMapped}; unsigned* prog_dev = nullptr;    // [0] panel messages, [1] bulk updates, [2] owned panels (count so far: index + 1)
+    Event ev_all;
     bool broken = false;                               // a step timed out: the streams hold work that may never finish; only destroy is safe
 };
 
@@ -150,84 +150,57 @@ namespace {
 
 #define DIST_KCHECK() DIST_HIP(hipGetLastError())
 
+// The state, built on first use.  ev_all is made last: a creation that failed half way starts over at the next call, every
+// ensure / reserve skipping what exists.
 int dist_state(Ctx* ctx, DistState** out) {
-    if (!ctx->dist) ctx->dist = new DistState();
-    DistState* D = ctx->dist;
+    if (!ctx->dist) ctx->dist.reset(new DistState());
+    DistState* D = ctx->dist.get();
     const Geo& g = ctx->g;
-    if (!D->side) {
-        int lo = 0, hi = 0;
-        DIST_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        DIST_HIP(hipStreamCreateWithPriority(&D->side, hipStreamNonBlocking, hi));
-        DIST_HIP(hipStreamCreateWithPriority(&D->cs, hipStreamNonBlocking, hi));
+    if (!D->ev_all) {
+        DIST_HIP(D->side.ensure_highest(hipStreamNonBlocking));
+        DIST_HIP(D->cs.ensure_highest(hipStreamNonBlocking));
         for (int b = 0; b < 2; ++b) {
-            DIST_HIP(hipEventCreateWithFlags(&D->ev_fact[b], hipEventDisableTiming));
-            DIST_HIP(hipEventCreateWithFlags(&D->ev_msg[b], hipEventDisableTiming));
-            DIST_HIP(hipEventCreateWithFlags(&D->ev_free[b], hipEventDisableTiming));
+            DIST_HIP(D->ev_fact[b].ensure(hipEventDisableTiming));
+            DIST_HIP(D->ev_msg[b].ensure(hipEventDisableTiming));
+            DIST_HIP(D->ev_free[b].ensure(hipEventDisableTiming));
         }
-        DIST_HIP(hipEventCreateWithFlags(&D->ev_head, hipEventDisableTiming));
-        DIST_HIP(hipEventCreateWithFlags(&D->ev_join, hipEventDisableTiming));
-        DIST_HIP(hipEventCreateWithFlags(&D->ev_hop[0], hipEventDisableTiming));
-        DIST_HIP(hipEventCreateWithFlags(&D->ev_hop[1], hipEventDisableTiming));
-        DIST_HIP(hipMalloc((void**)&D->seg, (size_t)g.nb * sizeof(double)));
-        DIST_HIP(hipMalloc((void**)&D->vloc, (size_t)g.Npad * sizeof(double)));
-        DIST_HIP(hipMalloc((void**)&D->small, 16 * sizeof(double)));
-        DIST_HIP(hipHostMalloc((void**)&D->prog_host, 4 * sizeof(unsigned), hipHostMallocMapped));
-        DIST_HIP(hipHostGetDevicePointer((void**)&D->prog_dev, D->prog_host, 0));
+        for (Event* e : {&D->ev_head, &D->ev_join, &D->ev_hop[0], &D->ev_hop[1]}) DIST_HIP(e->ensure(hipEventDisableTiming));
+        DIST_HIP(D->seg.reserve((size_t)g.nb));
+        DIST_HIP(D->vloc.reserve((size_t)g.Npad));
+        DIST_HIP(D->small.reserve(16));
+        DIST_HIP(D->prog_host.reserve(4));
+        DIST_HIP(hipHostGetDevicePointer((void**)&D->prog_dev, D->prog_host.get(), 0));
         for (int k = 0; k < 4; ++k) D->prog_host[k] = 0u;
-        DIST_HIP(hipMalloc((void**)&D->xflag, 64));
+        DIST_HIP(D->xflag.reserve(16));
         DIST_HIP(hipMemset(D->xflag, 0, 64));
         DIST_HIP(hipDeviceSynchronize());              // (the fill is ordered on the NULL stream; the word is polled from non-blocking streams)
-        DIST_HIP(hipEventCreateWithFlags(&D->ev_x, hipEventDisableTiming));
-        DIST_HIP(hipEventCreateWithFlags(&D->ev_all, hipEventDisableTiming));
+        DIST_HIP(D->ev_x.ensure(hipEventDisableTiming));
+        DIST_HIP(D->ev_all.ensure(hipEventDisableTiming));
     }
     *out = D;
     return 0;
 }
 
 }  // namespace
-namespace pyipm { namespace drv {
-void dist_free(Ctx* ctx) {
-    DistState* D = ctx->dist;
+namespace pyipm {
+void DistDelete::operator()(DistState* D) const { delete D; }
+namespace drv {
+// teardown, in the order pyipm_newton_destroy calls them
+void dist_abort_broken(Ctx* ctx) {
+    DistState* D = ctx->dist.get();
+    if (!D || !D->broken || !g_rccl.CommAbort) return;                   // (stuck collectives: abort them, or the synchronisations never return)
+    if (D->comm2) { g_rccl.CommAbort(D->comm2); D->comm2 = nullptr; }
+    if (D->comm) { g_rccl.CommAbort(D->comm); D->comm = nullptr; }
+}
+void dist_sync(Ctx* ctx) {
+    if (DistState* D = ctx->dist.get()) { D->side.sync(); D->cs.sync(); D->fws.sync(); }
+}
+void dist_comm_destroy(Ctx* ctx) {
+    DistState* D = ctx->dist.get();
     if (!D) return;
-    if (D->broken && g_rccl.CommAbort) {                                 // (stuck collectives: abort them, or the synchronisations below never return)
-        if (D->comm2) { g_rccl.CommAbort(D->comm2); D->comm2 = nullptr; }
-        if (D->comm) { g_rccl.CommAbort(D->comm); D->comm = nullptr; }
-    }
-    if (D->prog_host) hipHostFree(D->prog_host);
-    if (D->xflag) hipFree(D->xflag);
-    if (D->ev_x) hipEventDestroy(D->ev_x);
-    if (D->ev_all) hipEventDestroy(D->ev_all);
-    if (D->side) { hipStreamSynchronize(D->side); hipStreamDestroy(D->side); }
-    if (D->cs) { hipStreamSynchronize(D->cs); hipStreamDestroy(D->cs); }
-    if (D->fws) { hipStreamSynchronize(D->fws); hipStreamDestroy(D->fws); }
-    if (D->ev_fw) hipEventDestroy(D->ev_fw);
-    for (int b = 0; b < 2; ++b) {
-        if (D->ev_fact[b]) hipEventDestroy(D->ev_fact[b]);
-        if (D->ev_msg[b]) hipEventDestroy(D->ev_msg[b]);
-        if (D->ev_free[b]) hipEventDestroy(D->ev_free[b]);
-        if (D->msg[b]) hipFree(D->msg[b]);
-    }
-    if (D->ev_head) hipEventDestroy(D->ev_head);
-    if (D->ev_join) hipEventDestroy(D->ev_join);
-    for (int b = 0; b < 2; ++b) for (int j = 0; j < 2; ++j) {
-        if (D->sbuf[b][j]) hipFree(D->sbuf[b][j]);
-        if (D->ev_spack[b][j]) hipEventDestroy(D->ev_spack[b][j]);
-        if (D->ev_srecv[b][j]) hipEventDestroy(D->ev_srecv[b][j]);
-        if (D->ev_sfree[b][j]) hipEventDestroy(D->ev_sfree[b][j]);
-    }
-    for (int j = 0; j < 2; ++j) if (D->EL[j]) hipFree(D->EL[j]);
-    if (D->ev_pre) hipEventDestroy(D->ev_pre);
-    if (D->ev_hr) hipEventDestroy(D->ev_hr);
-    if (D->ev_hr2) hipEventDestroy(D->ev_hr2);
-    for (int b = 0; b < 2; ++b) if (D->ev_hop[b]) hipEventDestroy(D->ev_hop[b]);
-    for (auto e : D->pool) hipEventDestroy(e);
-    if (D->seg) hipFree(D->seg);
-    if (D->vloc) hipFree(D->vloc);
-    if (D->small) hipFree(D->small);
     if (D->comm2 && g_rccl.CommDestroy) g_rccl.CommDestroy(D->comm2);
     if (D->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(D->comm);
-    delete D;
-    ctx->dist = nullptr;
+    D->comm2 = nullptr; D->comm = nullptr;
 }
 } }  // namespace pyipm::drv
 namespace {
@@ -249,7 +222,7 @@ int dist_set_option(Ctx* ctx, const char* name, double value, bool* handled) {
         *handled = true;
         ctx->dist_comm2 = (int)value != 0;
         if (ctx->dist) {
-            DistState* D = ctx->dist;
+            DistState* D = ctx->dist.get();
             if (ctx->dist_comm2 && D->comm && !D->comm2) { int rc = comm2_setup(ctx, D); if (rc) return rc; }   // (after comm_init: created here, by all ranks)
             D->use_comm2 = ctx->dist_comm2 && D->comm2 != nullptr;
         }
@@ -433,12 +406,12 @@ int exchange_selftest(Ctx* ctx, DistState* D) {
     const int W = ctx->g.world;
     if (W < 2) return PYIPM_OK;
     const char* env = getenv("PYIPM_DIST_SAG");
-    struct DevBuf { double* p = nullptr; ~DevBuf() { if (p) hipFree(p); } } scratch;
+    DevBuf<double> scratch;
     const size_t count = 100003, cap = ((count + (size_t)W - 1) / (size_t)W) * (size_t)W;
     int local_rc = 0; std::string local_err;
     auto lfail = [&](const char* what, hipError_t e) { if (!local_rc) { local_rc = PYIPM_E_HIP; local_err = std::string(what) + ": " + hipGetErrorString(e); } };
-    {   hipError_t e = hipMalloc((void**)&scratch.p, 2 * cap * sizeof(double)); if (e != hipSuccess) { scratch.p = nullptr; lfail("hipMalloc (self-test scratch)", e); } }
-    double *a = scratch.p, *b = scratch.p ? scratch.p + cap : nullptr, *flag = D->small;
+    {   hipError_t e = scratch.reserve(2 * cap); if (e != hipSuccess) lfail("hipMalloc (self-test scratch)", e); }
+    double *a = scratch.get(), *b = a ? a + cap : nullptr, *flag = D->small;
     auto agree = [&](double mine, int op, double* out) -> int {          // op: 0 sum, 1 max (a minimum is a maximum of negatives)
         hipError_t e = hipMemcpy(flag, &mine, sizeof(double), hipMemcpyHostToDevice); if (e != hipSuccess) lfail("hipMemcpy (self-test flag)", e);
         int rc = tr_allreduce(ctx, D, flag, 1, op, D->cs);                 // ... still issued: the peers are inside it
@@ -447,7 +420,7 @@ int exchange_selftest(Ctx* ctx, DistState* D) {
         e = hipMemcpy(out, flag, sizeof(double), hipMemcpyDeviceToHost); if (e != hipSuccess) lfail("hipMemcpy (self-test flag back)", e);
         return rc;
     };
-    const bool mine = !(env && env[0] == '0') && W >= 3 && tr_has_p2p(D) && scratch.p != nullptr;
+    const bool mine = !(env && env[0] == '0') && W >= 3 && tr_has_p2p(D) && a != nullptr;
     double neg_want = 0.0;
     int rc = agree(mine ? -1.0 : 0.0, 1, &neg_want);                       // max of (-want) = -(min of want)
     if (rc) return rc;
@@ -512,7 +485,7 @@ struct StreamScope {
 int span_begin(Ctx* ctx, DistState* D, int kind, hipStream_t st, size_t* idx) {
     *idx = (size_t)-1;
     if (!ctx->profile) return 0;
-    while (D->pool.size() < D->used + 2) { hipEvent_t e; DIST_HIP(hipEventCreate(&e)); D->pool.push_back(e); }
+    DIST_HIP(ensure_events(D->pool, D->used + 2, hipEventDefault));
     DistState::Span s{kind, D->pool[D->used], D->pool[D->used + 1]};
     D->used += 2;
     DIST_HIP(hipEventRecord(s.a, st));
@@ -592,13 +565,10 @@ int factor_dist_geo(Ctx* ctx, pyipm_factor_stats* stats, const double* fwd_b) {
     const bool wire = W > 1 || D->selfmsg;
     size_t need = 0;
     if (wire) for (int64_t p = 0; p < np; ++p) { const size_t b = dist_msg_bytes(ctx, p); if (b > need) need = b; }
-    if (need > D->msg_bytes) {
-        for (int b = 0; b < 2; ++b) { if (D->msg[b]) DIST_HIP(hipFree(D->msg[b])); D->msg[b] = nullptr; }
+    if (need > 0)
         for (int b = 0; b < 2; ++b)
-            if (hipMalloc((void**)&D->msg[b], need + (size_t)W * sizeof(double)) != hipSuccess) {     // (slack: W equal pieces, sag_bcast)
+            if (D->msg[b].reserve(need / sizeof(double) + (size_t)W) != hipSuccess) {                 // (slack: W equal pieces, sag_bcast)
                 ctx->err = "factor_dist: no memory for the panel messages"; return PYIPM_E_NOMEM; }
-        D->msg_bytes = need;
-    }
     auto below = [&](int64_t p) { return g.Npad - (g.panel_c0(p) + g.panel_w(p)); };
     auto own = [&](int64_t p) { return p >= 0 && p < np && g.owner(p) == g.rank; };
     auto msg_of = [&](int64_t p) -> size_t { return (wire && p < np && below(p) > 0) ? dist_msg_bytes(ctx, p) : 0; };
@@ -619,23 +589,15 @@ int factor_dist_geo(Ctx* ctx, pyipm_factor_stats* stats, const double* fwd_b) {
     if (slices_on) {
         size_t smax = 0;
         for (int64_t p = 0; p < np; ++p) for (int j = 1; j <= 2; ++j) { const size_t e = slice_numel(g, p, j); if (e > smax) smax = e; }
-        if (smax * sizeof(double) > D->slice_bytes) {
-            for (int b = 0; b < 2; ++b) for (int j = 0; j < 2; ++j) { if (D->sbuf[b][j]) DIST_HIP(hipFree(D->sbuf[b][j])); D->sbuf[b][j] = nullptr; }
-            for (int j = 0; j < 2; ++j) { if (D->EL[j]) DIST_HIP(hipFree(D->EL[j])); D->EL[j] = nullptr; }
-            for (int b = 0; b < 2; ++b) for (int j = 0; j < 2; ++j)
-                if (hipMalloc((void**)&D->sbuf[b][j], smax * sizeof(double)) != hipSuccess) { ctx->err = "factor_dist: no memory for the slice messages"; return PYIPM_E_NOMEM; }
-            for (int j = 0; j < 2; ++j)
-                if (hipMalloc((void**)&D->EL[j], (size_t)g.nb * g.nb * sizeof(double)) != hipSuccess) { ctx->err = "factor_dist: no memory for the slice messages"; return PYIPM_E_NOMEM; }
-            D->slice_bytes = smax * sizeof(double);
+        if (smax > 0) {
+            bool got = true;
+            for (int b = 0; b < 2; ++b) for (int j = 0; j < 2; ++j) got = got && D->sbuf[b][j].reserve(smax) == hipSuccess;
+            for (int j = 0; j < 2; ++j) got = got && D->EL[j].reserve((size_t)g.nb * g.nb) == hipSuccess;
+            if (!got) { ctx->err = "factor_dist: no memory for the slice messages"; return PYIPM_E_NOMEM; }
         }
-        if (!D->ev_spack[0][0])
-            for (int b = 0; b < 2; ++b) for (int j = 0; j < 2; ++j) {
-                DIST_HIP(hipEventCreateWithFlags(&D->ev_spack[b][j], hipEventDisableTiming));
-                DIST_HIP(hipEventCreateWithFlags(&D->ev_srecv[b][j], hipEventDisableTiming));
-                DIST_HIP(hipEventCreateWithFlags(&D->ev_sfree[b][j], hipEventDisableTiming));
-            }
-        if (!D->ev_pre) { DIST_HIP(hipEventCreateWithFlags(&D->ev_pre, hipEventDisableTiming)); DIST_HIP(hipEventCreateWithFlags(&D->ev_hr, hipEventDisableTiming));
-                          DIST_HIP(hipEventCreateWithFlags(&D->ev_hr2, hipEventDisableTiming)); }
+        for (int b = 0; b < 2; ++b) for (int j = 0; j < 2; ++j)
+            for (Event* e : {&D->ev_spack[b][j], &D->ev_srecv[b][j], &D->ev_sfree[b][j]}) DIST_HIP(e->ensure(hipEventDisableTiming));
+        for (Event* e : {&D->ev_pre, &D->ev_hr, &D->ev_hr2}) DIST_HIP(e->ensure(hipEventDisableTiming));
     }
     bool sfree_rec[2][2] = {{false, false}, {false, false}};
     bool pre_rec = false;
@@ -643,9 +605,9 @@ int factor_dist_geo(Ctx* ctx, pyipm_factor_stats* stats, const double* fwd_b) {
     if (D->broken) { ctx->err = "an earlier distributed step timed out: this handle's streams may hold collectives that never complete -- destroy it"; return PYIPM_E_COMM; }
     for (int k = 0; k < 3; ++k) D->prog_host[k] = 0u;
     if (fwd_b) {
-        if (!D->fws) DIST_HIP(hipStreamCreateWithFlags(&D->fws, hipStreamNonBlocking));
-        if (!D->ev_fw) DIST_HIP(hipEventCreateWithFlags(&D->ev_fw, hipEventDisableTiming));
-        while ((int64_t)ctx->ev_done.size() < np) { hipEvent_t e; DIST_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); ctx->ev_done.push_back(e); }
+        DIST_HIP(D->fws.ensure(hipStreamNonBlocking));
+        DIST_HIP(D->ev_fw.ensure(hipEventDisableTiming));
+        DIST_HIP(ensure_events(ctx->ev_done, (size_t)np, hipEventDisableTiming));
         DIST_HIP(hipEventRecord(D->ev_fw, main));                       // the right-hand side was produced on the main stream
         DIST_HIP(hipStreamWaitEvent(D->fws, D->ev_fw, 0));
         { int r_ = launch_mask_owned(ctx, D->fws, D->vloc, fwd_b); if (r_) return r_; }
@@ -1215,7 +1177,7 @@ int pyipm_newton_comm_ranks(pyipm_newton_ctx* h) try {
 int pyipm_newton_comm_bcast_mode(pyipm_newton_ctx* h) try {
     if (check_ctx(h)) return PYIPM_E_BADARG;
     Ctx* ctx = C(h);
-    return (ctx->dist && ctx->dist->sag && tr_has_p2p(ctx->dist)) ? 1 : 0;
+    return (ctx->dist && ctx->dist->sag && tr_has_p2p(ctx->dist.get())) ? 1 : 0;
 } PYIPM_CATCH_H(h)
 
 int64_t pyipm_newton_owned_rows(pyipm_newton_ctx* h, int64_t* rows) try {
@@ -1234,9 +1196,9 @@ int pyipm_newton_stage_blocks_owned(pyipm_newton_ctx* h, const double* d2L_rows,
     PYIPM_HIP(hipSetDevice(ctx->device));
     const int64_t nl = make_rowmap(g, 1).nloc;
     int rc;
-    rc = stage_block(ctx, d2L_rows, nl, g.n, ld_d2L, memkind, &ctx->stg_d2L, &ctx->stg_d2L_sz, &ctx->d2L, &ctx->ld_d2L); if (rc) return rc;
-    rc = stage_block(ctx, Je_rows, g.me ? nl : 0, g.me, ld_Je, memkind, &ctx->stg_Je, &ctx->stg_Je_sz, &ctx->Je, &ctx->ld_Je); if (rc) return rc;
-    rc = stage_block(ctx, Ji_rows, g.mi ? nl : 0, g.mi, ld_Ji, memkind, &ctx->stg_Ji, &ctx->stg_Ji_sz, &ctx->Ji, &ctx->ld_Ji); if (rc) return rc;
+    rc = stage_block(ctx, d2L_rows, nl, g.n, ld_d2L, memkind, ctx->stg_d2L, &ctx->d2L, &ctx->ld_d2L); if (rc) return rc;
+    rc = stage_block(ctx, Je_rows, g.me ? nl : 0, g.me, ld_Je, memkind, ctx->stg_Je, &ctx->Je, &ctx->ld_Je); if (rc) return rc;
+    rc = stage_block(ctx, Ji_rows, g.mi ? nl : 0, g.mi, ld_Ji, memkind, ctx->stg_Ji, &ctx->Ji, &ctx->ld_Ji); if (rc) return rc;
     ctx->sharded = g.world > 1 ? 1 : 0;
     ctx->have_blocks = true;
     return PYIPM_OK;

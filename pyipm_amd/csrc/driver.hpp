@@ -39,7 +39,7 @@ int single_only(Ctx* ctx);
 int put_vec(Ctx* ctx, double* dst, const double* src, size_t count, int memkind);
 int copy_out(Ctx* ctx, double* dst, const double* src_dev, size_t count, int memkind);
 int stage_block(Ctx* ctx, const double* src, int64_t rows, int64_t cols, int64_t ld, int memkind,
-                double** stg, size_t* stg_sz, const double** out_ptr, int64_t* out_ld);
+                DevBuf<double>& stg, const double** out_ptr, int64_t* out_ld);
 void active_ranges(const Ctx* ctx, int64_t cA, int64_t cB, int64_t* a0, int64_t* a1, int64_t* b0, int64_t* b1);
 bool panel_in_s(const Ctx* ctx, int64_t p);
 void panel_hole(const Ctx* ctx, int64_t p, int64_t* h0, int64_t* h1);
@@ -91,7 +91,9 @@ int kkt_matvec_dev(Ctx* ctx, const double* v, double* y);
 int residual_dev(Ctx* ctx);
 int solve_prepare(Ctx* ctx, const double* rhs, int memkind, bool for_fused_forward = false);
 // pyipm_dist.hip
-void dist_free(Ctx* ctx);
+void dist_abort_broken(Ctx* ctx);      // teardown (pyipm_newton_destroy), in this order: the communicators of a handle whose step
+void dist_sync(Ctx* ctx);              // timed out aborted, or the synchronisations never return;  the driver's streams drained;
+void dist_comm_destroy(Ctx* ctx);      // the communicators destroyed.  The state itself goes with the handle (Ctx::dist).
 int dist_set_option(Ctx* ctx, const char* name, double value, bool* handled);
 // kernels of pyipm_newton.hip on behalf of the other units
 int launch_axpby(Ctx* ctx, hipStream_t st, double* out, const double* a, const double* b, double alpha, double beta, int64_t n);

@@ -7,13 +7,14 @@
 
 namespace {
 
+struct NewtonDestroy { void operator()(Ctx* c) const { pyipm_newton_destroy(reinterpret_cast<pyipm_newton_ctx*>(c)); } };
 struct LbCtx {
     int64_t n = 0, me = 0, mi = 0, p = 0, N = 0;
     int cap = 0, rrmax = 0, device = 0, nb = 256;
     hipStream_t stream = nullptr;
-    Ctx* gcx = nullptr;                 // internal handle: symmetric system of order p (geometry (p, 0, 0))
+    std::unique_ptr<Ctx, NewtonDestroy> gcx;   // internal handle: symmetric system of order p (geometry (p, 0, 0))
     int64_t p_pad = 0, n_pad = 0;
-    char* ws = nullptr; size_t ws_bytes = 0;
+    DevBuf<char> ws;
     double *JT = nullptr;               // p_pad x n_pad, column-major (see kernels_lbfgs.hpp)
     int ksplit = 1;                     // split-K factor of the Gram launch (fixed by the shape)
     double *Cs = nullptr;               // ksplit partial Gram matrices, p_pad^2 each (ksplit > 1)
@@ -31,7 +32,7 @@ struct LbCtx {
     pyipm_lbfgs_allreduce_fn allreduce = nullptr; void* allreduce_user = nullptr;   // row-sharded use
     bool have_J = false;
     long long n_gram = 0;               // Gram launches so far
-    hipEvent_t ev[9] = {};
+    Event ev[9];                        // timing events
     bool ev_valid = false;
     double gram_flops = 0;
     bool did[8] = {};
@@ -155,7 +156,7 @@ int lb_put2d(LbCtx* lb, double* dst, int64_t dst_ld, const double* src, int64_t 
 
 // zeta*G = J'J + diag(0, zeta/Sigma) (+ zeta*reg on the equality block) into the internal handle, then factor.
 int lb_factor_G(LbCtx* lb, double zeta, double reg_e, pyipm_factor_stats* st, bool timed) {
-    Ctx* gc = lb->gcx;
+    Ctx* gc = lb->gcx.get();
     const Geo& g = gc->g;
     gc->stream = lb->stream;
     const int ks = lb->ksplit;
@@ -232,7 +233,7 @@ int pyipm_lbfgs_create(pyipm_lbfgs_ctx** out, int64_t n, int64_t me, int64_t mi,
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return PYIPM_E_NODEVICE;
     if (hipSetDevice(device) != hipSuccess) return PYIPM_E_NODEVICE;
-    LbCtx* lb = new LbCtx();
+    std::unique_ptr<LbCtx> lb(new LbCtx());       // an early return releases what the handle owns by then (~LbCtx)
     lb->n = n; lb->me = me; lb->mi = mi; lb->p = me + mi; lb->N = n + 2 * mi + me;
     lb->cap = max_pairs; lb->rrmax = 2 * max_pairs + 1; lb->device = device; lb->nb = nb;
     lb->stream = (hipStream_t)stream;
@@ -240,23 +241,20 @@ int pyipm_lbfgs_create(pyipm_lbfgs_ctx** out, int64_t n, int64_t me, int64_t mi,
     if (lb->p > 0) {
         pyipm_newton_ctx* gh = nullptr;
         int rc = pyipm_newton_create(&gh, lb->p, 0, 0, nb, device, 1, 0, nullptr, 0, stream);
-        if (rc) { delete lb; return rc; }
-        lb->gcx = C(gh);
+        if (rc) return rc;
+        lb->gcx.reset(C(gh));
         lb->p_pad = lb->gcx->g.Npad;
     }
     lb->nsplit = lb_nsplit(n, lb->p_pad, lb->rrmax);
-    lb->ws_bytes = lb_carve(nullptr, n, me, mi, max_pairs, lb->p_pad, lb->n_pad, nullptr);
-    if (hipMalloc((void**)&lb->ws, lb->ws_bytes) != hipSuccess) {
-        if (lb->gcx) pyipm_newton_destroy(reinterpret_cast<pyipm_newton_ctx*>(lb->gcx));
-        delete lb; return PYIPM_E_NOMEM;
-    }
-    if (getenv("PYIPM_POISON_WORKSPACE")) hipMemset(lb->ws, 0xFF, lb->ws_bytes);   // test hook (tests/conftest.py): NaN wherever nothing is written first
-    lb_carve(lb, n, me, mi, max_pairs, lb->p_pad, lb->n_pad, lb->ws);
+    const size_t ws_bytes = lb_carve(nullptr, n, me, mi, max_pairs, lb->p_pad, lb->n_pad, nullptr);
+    if (lb->ws.reserve(ws_bytes) != hipSuccess) return PYIPM_E_NOMEM;
+    if (getenv("PYIPM_POISON_WORKSPACE")) hipMemset(lb->ws, 0xFF, ws_bytes);   // test hook (tests/conftest.py): NaN wherever nothing is written first
+    lb_carve(lb.get(), n, me, mi, max_pairs, lb->p_pad, lb->n_pad, lb->ws);
     bool ok = true;
     if (lb->p > 0) ok = hipMemsetAsync(lb->JT, 0, (size_t)lb->p_pad * (size_t)lb->n_pad * sizeof(double), lb->stream) == hipSuccess;
-    for (int i = 0; i < 9 && ok; ++i) ok = hipEventCreate(&lb->ev[i]) == hipSuccess;
-    if (!ok) { pyipm_lbfgs_destroy(reinterpret_cast<pyipm_lbfgs_ctx*>(lb)); return PYIPM_E_HIP; }
-    *out = reinterpret_cast<pyipm_lbfgs_ctx*>(lb);
+    for (int i = 0; i < 9 && ok; ++i) ok = lb->ev[i].ensure(hipEventDefault) == hipSuccess;
+    if (!ok) { hipStreamSynchronize(lb->stream); return PYIPM_E_HIP; }       // (the fill above may be in flight)
+    *out = reinterpret_cast<pyipm_lbfgs_ctx*>(lb.release());
     return PYIPM_OK;
 } PYIPM_CATCH_NOH
 
@@ -265,10 +263,7 @@ int pyipm_lbfgs_destroy(pyipm_lbfgs_ctx* h) try {
     LbCtx* lb = LB(h);
     hipSetDevice(lb->device);
     hipStreamSynchronize(lb->stream);
-    for (int i = 0; i < 9; ++i) if (lb->ev[i]) hipEventDestroy(lb->ev[i]);
-    if (lb->gcx) pyipm_newton_destroy(reinterpret_cast<pyipm_newton_ctx*>(lb->gcx));
-    if (lb->ws) hipFree(lb->ws);
-    delete lb;
+    delete lb;                            // (with it the Newton handle of the Gram system, its events, its workspace)
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
@@ -295,7 +290,7 @@ int pyipm_lbfgs_set_option(pyipm_lbfgs_ctx* h, const char* name, double value) t
     if (!h) return PYIPM_E_BADARG;
     LbCtx* lb = LB(h);
     if (!lb->gcx) return PYIPM_OK;
-    int rc = pyipm_newton_set_option(reinterpret_cast<pyipm_newton_ctx*>(lb->gcx), name, value);
+    int rc = pyipm_newton_set_option(reinterpret_cast<pyipm_newton_ctx*>(lb->gcx.get()), name, value);
     if (rc) lb->err = lb->gcx->err;
     return rc;
 } PYIPM_CATCH_H(h)
@@ -385,7 +380,7 @@ int pyipm_lbfgs_direction(pyipm_lbfgs_ctx* h, const double* g, const double* s, 
         LB_KCHECK();
     } else {
         const int64_t ldp = lb->p_pad;
-        Ctx* gc = lb->gcx;
+        Ctx* gc = lb->gcx.get();
         if (mi > 0) {
             hipLaunchKernelGGL(k_lb_sigma, grid1(mi), dim3(256), 0, st, lb->sig, lb->s, lb->lda + me, eps, mi);
             LB_KCHECK();

@@ -150,21 +150,15 @@ int put_vec(Ctx* ctx, double* dst, const double* src, size_t count, int memkind)
 }
 
 int stage_block(Ctx* ctx, const double* src, int64_t rows, int64_t cols, int64_t ld, int memkind,
-                double** stg, size_t* stg_sz, const double** out_ptr, int64_t* out_ld) {
+                DevBuf<double>& stg, const double** out_ptr, int64_t* out_ld) {
     if (rows == 0 || cols == 0) { *out_ptr = nullptr; *out_ld = cols; return 0; }
     if (!src || ld < cols) { ctx->err = "bad block pointer / leading dimension"; return PYIPM_E_BADARG; }
     if (memkind == PYIPM_MEM_DEVICE) { *out_ptr = src; *out_ld = ld; return 0; }
-    const size_t need = (size_t)rows * (size_t)cols * sizeof(double);
-    if (*stg_sz < need) {
-        if (*stg) PYIPM_HIP(hipFree(*stg));
-        *stg = nullptr; *stg_sz = 0;
-        PYIPM_HIP(hipMalloc((void**)stg, need));
-        *stg_sz = need;
-    }
-    PYIPM_HIP(hipMemcpy2DAsync(*stg, (size_t)cols * sizeof(double), src, (size_t)ld * sizeof(double),
+    PYIPM_HIP(stg.reserve((size_t)rows * (size_t)cols));
+    PYIPM_HIP(hipMemcpy2DAsync(stg.get(), (size_t)cols * sizeof(double), src, (size_t)ld * sizeof(double),
                                (size_t)cols * sizeof(double), (size_t)rows, hipMemcpyHostToDevice, ctx->stream));
     PYIPM_HIP(hipStreamSynchronize(ctx->stream));
-    *out_ptr = *stg; *out_ld = cols;
+    *out_ptr = stg.get(); *out_ld = cols;
     return 0;
 }
 
@@ -229,7 +223,6 @@ int tile_list(Ctx* ctx, const UpdGeo& u, int64_t nsup, const unsigned** dev, uns
     }
     if (ctx->tile_lists.size() >= 1024) {              // geometries that keep changing (condensed option: |A| varies): start over
         PYIPM_HIP(hipDeviceSynchronize());
-        for (auto& kv : ctx->tile_lists) if (kv.second.ready) hipEventDestroy(kv.second.ready);
         ctx->tile_lists.clear();
         for (auto& a : ctx->tl_arenas) { a.used = 0; }
     }
@@ -278,14 +271,13 @@ int tile_list(Ctx* ctx, const UpdGeo& u, int64_t nsup, const unsigned** dev, uns
         // a slot in the arenas (device + pinned host, 1 Mi entries each; a list longer than that gets an arena of its own)
         const size_t need = (list.size() + 63) / 64 * 64;
         Ctx::TlArena* ar = nullptr;
-        for (auto& a : ctx->tl_arenas) if (a.cap - a.used >= need) { ar = &a; break; }
+        for (auto& a : ctx->tl_arenas) if (a.dev.capacity() - a.used >= need) { ar = &a; break; }
         if (!ar) {
             Ctx::TlArena a;
-            a.cap = need > ((size_t)1 << 20) ? need : ((size_t)1 << 20);
-            PYIPM_HIP(hipMalloc((void**)&a.dev, a.cap * sizeof(unsigned)));
-            if (hipHostMalloc((void**)&a.host, a.cap * sizeof(unsigned), hipHostMallocDefault) != hipSuccess) {
-                hipFree(a.dev); ctx->err = "no pinned host memory for the tile lists"; return PYIPM_E_NOMEM; }
-            ctx->tl_arenas.push_back(a);
+            const size_t cap = need > ((size_t)1 << 20) ? need : ((size_t)1 << 20);
+            PYIPM_HIP(a.dev.reserve(cap));
+            if (a.host.reserve(cap) != hipSuccess) { ctx->err = "no pinned host memory for the tile lists"; return PYIPM_E_NOMEM; }
+            ctx->tl_arenas.push_back(std::move(a));
             ar = &ctx->tl_arenas.back();
         }
         tl.dev = ar->dev + ar->used;
@@ -293,12 +285,12 @@ int tile_list(Ctx* ctx, const UpdGeo& u, int64_t nsup, const unsigned** dev, uns
         ar->used += need;
         memcpy(hsrc, list.data(), list.size() * sizeof(unsigned));
         PYIPM_HIP(hipMemcpyAsync(tl.dev, hsrc, list.size() * sizeof(unsigned), hipMemcpyHostToDevice, consumer));
-        PYIPM_HIP(hipEventCreateWithFlags(&tl.ready, hipEventDisableTiming));
+        PYIPM_HIP(tl.ready.ensure(hipEventDisableTiming));
         PYIPM_HIP(hipEventRecord(tl.ready, consumer));
         tl.on = consumer;
     }
-    ctx->tile_lists[key] = tl;
     *dev = tl.dev; *count = tl.count;
+    ctx->tile_lists[key] = std::move(tl);
     return 0;
 }
 
@@ -516,11 +508,7 @@ int factor_panel(Ctx* ctx, int64_t p, hipStream_t stream, bool apply_pending) {
 }
 
 int ensure_rest_stream(Ctx* ctx) {
-    if (!ctx->rest) {
-        int lo = 0, hi = 0;
-        PYIPM_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        PYIPM_HIP(hipStreamCreateWithPriority(&ctx->rest, hipStreamNonBlocking, hi));
-    }
+    PYIPM_HIP(ctx->rest.ensure_highest(hipStreamNonBlocking));
     return 0;
 }
 
@@ -548,7 +536,7 @@ int launch_tile_steps(Ctx* ctx, hipStream_t chain, int64_t gc0, int64_t glc0, in
     if (tb - ta >= 2 && chain_applies(ctx, gc0, nT)) {
         // the steps [ta, tb) as ONE launch of persistent workgroups (kernels_chain.hpp): no launch boundary between two tiles
         if (!ctx->chain_sync) {
-            PYIPM_HIP(hipMalloc((void**)&ctx->chain_sync, (size_t)(Ctx::CHAIN_SLOTS * Ctx::CHAIN_WORDS + 1) * sizeof(unsigned)));
+            PYIPM_HIP(ctx->chain_sync.reserve((size_t)(Ctx::CHAIN_SLOTS * Ctx::CHAIN_WORDS + 1)));
             PYIPM_HIP(hipMemset(ctx->chain_sync, 0, (size_t)(Ctx::CHAIN_SLOTS * Ctx::CHAIN_WORDS + 1) * sizeof(unsigned)));
             // (the fill is ordered on the NULL stream; k_chain_wait polls these words from a non-blocking stream: it met the words of
             //  an earlier handle's life in this memory -- larger epochs: "done" -- and let the rows kernels run ahead of the chain, on
@@ -630,8 +618,8 @@ int factor_block(Ctx* ctx, const BlockDesc& bd, hipStream_t chain, const std::fu
     const int64_t gc0 = bd.sp[0].c0, glc0 = bd.sp[0].lc0, gend = gc0 + (int64_t)nT * TB;
     const int64_t TT = (int64_t)TB * TB;
     { int r0 = ensure_rest_stream(ctx); if (r0) return r0; }
-    if (!ctx->ev_join) PYIPM_HIP(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-    while ((int64_t)ctx->ev_band.size() < n0) { hipEvent_t e; PYIPM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); ctx->ev_band.push_back(e); }
+    PYIPM_HIP(ctx->ev_join.ensure(hipEventDisableTiming));
+    PYIPM_HIP(ensure_events(ctx->ev_band, (size_t)n0, hipEventDisableTiming));
     double* Wg = bd.sp[0].W;
     double* Dv = ctx->Dinv + (gc0 / TB) * TT;
     double* Ts = ctx->Tsv + (gc0 / TB) * TT;
@@ -988,9 +976,9 @@ int timed_update(Ctx* ctx, int64_t p0, int64_t np, int64_t first_lp, int64_t n_l
     int used_bn = 128;
     if (ctx->profile && !chain_side) {
         if ((size_t)ctx->n_trailing >= ctx->ev_trailing.size()) {
-            hipEvent_t a, b;
-            PYIPM_HIP(hipEventCreate(&a)); PYIPM_HIP(hipEventCreate(&b));
-            ctx->ev_trailing.push_back({a, b});
+            std::pair<Event, Event> pr;
+            PYIPM_HIP(pr.first.ensure(hipEventDefault)); PYIPM_HIP(pr.second.ensure(hipEventDefault));
+            ctx->ev_trailing.push_back(std::move(pr));
         }
         e0 = ctx->ev_trailing[ctx->n_trailing].first; e1 = ctx->ev_trailing[ctx->n_trailing].second;
         PYIPM_HIP(hipEventRecord(e0, stream));
@@ -1053,6 +1041,16 @@ int factor_begin(Ctx* ctx, hipStream_t st) {
     return 0;
 }
 
+// the statistics record as the C-ABI hands it out (growth travels as the bit pattern of a non-negative double)
+pyipm_factor_stats to_stats(const DevStats& z) {
+    pyipm_factor_stats s;
+    s.n_neg = z.n_neg; s.n_zero = z.n_zero; s.n_2x2 = z.n_2x2; s.n_pos = z.n_pos;
+    s.d_min = z.d_min; s.d_max = z.d_max;
+    memcpy(&s.growth, &z.growth_bits, sizeof(s.growth));
+    s.nonfinite = z.nonfinite;
+    return s;
+}
+
 int factor_end(Ctx* ctx, pyipm_factor_stats* stats) {
     DevStats z;
     PYIPM_HIP(hipMemcpyAsync(&z, ctx->dstats, sizeof(z), hipMemcpyDeviceToHost, ctx->stream));
@@ -1113,12 +1111,7 @@ int factor_end(Ctx* ctx, pyipm_factor_stats* stats) {
         ctx->n_trailing_real = nreal;
     }
     ctx->factored = true;
-    if (stats) {
-        stats->n_neg = z.n_neg; stats->n_zero = z.n_zero; stats->n_2x2 = z.n_2x2; stats->n_pos = z.n_pos;
-        stats->d_min = z.d_min; stats->d_max = z.d_max;
-        long long gb = (long long)z.growth_bits; double gr; memcpy(&gr, &gb, sizeof(gr));
-        stats->growth = gr; stats->nonfinite = z.nonfinite;
-    }
+    if (stats) *stats = to_stats(z);
     if (z.nonfinite) { ctx->zeros_clean = false; ctx->err = "NaN/Inf met during factorisation"; return PYIPM_E_NONFINITE; }
     return 0;
 }
@@ -1199,13 +1192,9 @@ int solve_plain(Ctx* ctx, double* v, bool forward_done, int nrhs, int64_t vstrid
     const bool one_launch = ctx->sweep_persist && nrhs == 1 && g.world == 1 && g.nb <= 4 * TB && g.nb % TB == 0 && g.npanels >= 2 &&
                             g.npanels <= 4096 && g.Npad % 8 == 0 && g.Npad / TB <= 8192;
     if (one_launch) {
-        if (ctx->sweep_buf_n < g.Npad) {
-            if (ctx->sweep_buf) { PYIPM_HIP(hipStreamSynchronize(ctx->stream)); PYIPM_HIP(hipFree(ctx->sweep_buf)); ctx->sweep_buf = nullptr; }
-            PYIPM_HIP(hipMalloc((void**)&ctx->sweep_buf, (size_t)g.Npad * sizeof(double)));
-            ctx->sweep_buf_n = g.Npad;
-        }
+        PYIPM_HIP(ctx->sweep_buf.reserve((size_t)g.Npad));
         if (!ctx->sweep_sync) {
-            PYIPM_HIP(hipMalloc((void**)&ctx->sweep_sync, (3 * 4096 + 1) * sizeof(unsigned)));
+            PYIPM_HIP(ctx->sweep_sync.reserve(3 * 4096 + 1));
             PYIPM_HIP(hipMemsetAsync(ctx->sweep_sync + 3 * 4096, 0, sizeof(unsigned), ctx->stream));      // the error word: sticky
         }
     }
@@ -1409,11 +1398,9 @@ int solve_many(Ctx* ctx, int64_t k, const double* rhs, int64_t ld_rhs, double* d
     size_t need = col + (size_t)Nc * (size_t)kpad + n_part;                    // X, Xc, partials
     if (refine != 0) need += 2 * col;                                           // B, R
     if (adaptive) need += col + 2 * (size_t)kpad;                               // the spare iterate, per-column sums
-    if (ctx->ms_buf_bytes < need * sizeof(double)) {
-        if (ctx->ms_buf) { PYIPM_HIP(hipStreamSynchronize(st)); PYIPM_HIP(hipFree(ctx->ms_buf)); ctx->ms_buf = nullptr; ctx->ms_buf_bytes = 0; }
-        PYIPM_HIP(hipMalloc((void**)&ctx->ms_buf, need * sizeof(double)));
-        ctx->ms_buf_bytes = need * sizeof(double);
-        if (getenv("PYIPM_POISON_WORKSPACE")) PYIPM_HIP(hipMemsetAsync(ctx->ms_buf, 0xFF, ctx->ms_buf_bytes, st));   // as the workspace
+    if (ctx->ms_buf.capacity() < need) {
+        PYIPM_HIP(ctx->ms_buf.reserve(need));
+        if (getenv("PYIPM_POISON_WORKSPACE")) PYIPM_HIP(hipMemsetAsync(ctx->ms_buf, 0xFF, need * sizeof(double), st));   // as the workspace
     }
     double* X = ctx->ms_buf;
     double* Xc = X + col;
@@ -1575,15 +1562,10 @@ int assemble_condensed(Ctx* ctx, double delta, double delta_c) {
     const Geo& g = ctx->g;
     const int64_t nx = (g.n + BM - 1) / BM * BM;                 // rows / columns of the x-x block the Gram launch touches
     const int64_t mi_pad = (g.mi + BKU - 1) / BKU * BKU, ldt = nx;
-    const size_t need = 2 * (size_t)ldt * (size_t)mi_pad * sizeof(double);
-    if (ctx->jt_bytes < need) {
-        if (ctx->JT) PYIPM_HIP(hipFree(ctx->JT));
-        ctx->JT = nullptr; ctx->jt_bytes = 0;
-        if (hipMalloc((void**)&ctx->JT, need) != hipSuccess) { ctx->err = "condensed: no memory for the Ji' operands"; return PYIPM_E_NOMEM; }
-        ctx->jt_bytes = need;
-    }
+    if (ctx->JT.reserve(2 * (size_t)ldt * (size_t)mi_pad) != hipSuccess) { ctx->err = "condensed: no memory for the Ji' operands"; return PYIPM_E_NOMEM; }
     if (!ctx->cond_pos) {
-        if (hipMalloc((void**)&ctx->cond_pos, (size_t)(2 * g.mi + 4) * sizeof(int)) != hipSuccess) { ctx->err = "condensed: no memory"; return PYIPM_E_NOMEM; }
+        if (ctx->cond_store.reserve((size_t)(2 * g.mi + 4)) != hipSuccess) { ctx->err = "condensed: no memory"; return PYIPM_E_NOMEM; }
+        ctx->cond_pos = ctx->cond_store;
         ctx->cond_idx = ctx->cond_pos + g.mi;
         ctx->cond_cnt = ctx->cond_idx + g.mi;
     }
@@ -1601,13 +1583,7 @@ int assemble_condensed(Ctx* ctx, double delta, double delta_c) {
     ctx->WT = ctx->JT + (size_t)ldt * (size_t)mi_pad;
     const double* Jx = ctx->Je; int64_t ldx = ctx->ld_Je;
     if (na > 0) {
-        const size_t jneed = (size_t)g.n * (size_t)(g.me + g.mi) * sizeof(double);
-        if (ctx->jx_bytes < jneed) {
-            if (ctx->Jx) PYIPM_HIP(hipFree(ctx->Jx));
-            ctx->Jx = nullptr; ctx->jx_bytes = 0;
-            if (hipMalloc((void**)&ctx->Jx, jneed) != hipSuccess) { ctx->err = "condensed: no memory for [Je | Ji_A]"; return PYIPM_E_NOMEM; }
-            ctx->jx_bytes = jneed;
-        }
+        if (ctx->Jx.reserve((size_t)g.n * (size_t)(g.me + g.mi)) != hipSuccess) { ctx->err = "condensed: no memory for [Je | Ji_A]"; return PYIPM_E_NOMEM; }
         dim3 grid((unsigned)g.n, (unsigned)((mx + 255) / 256));
         hipLaunchKernelGGL(k_cond_gather_J, grid, dim3(256), 0, ctx->stream, ctx->Jx, mx, ctx->Je, ctx->ld_Je, g.me,
                            ctx->Ji, ctx->ld_Ji, ctx->cond_idx, (int64_t)na);
@@ -1737,13 +1713,13 @@ GroupSched plan_groups(const Geo& g, int group, int tail_group, bool tail_group_
 // diagnostics (PYIPM_GROUP_TRACE=1): where each group's chain, head and bulk update begin and end on the device, without a
 // tracer's per-call cost on the host (tools/group_trace.py)
 struct GroupTrace {
-    std::vector<std::pair<std::string, hipEvent_t>> marks;
+    std::vector<std::pair<std::string, Event>> marks;
     static bool on() { static const bool v = getenv("PYIPM_GROUP_TRACE") != nullptr; return v; }
     void mark(const char* what, int64_t grp, hipStream_t st) {
-        hipEvent_t e; if (!on() || hipEventCreate(&e) != hipSuccess) return;
+        Event e; if (!on() || e.ensure(hipEventDefault) != hipSuccess) return;
         hipEventRecord(e, st);
         char buf[64]; snprintf(buf, sizeof(buf), "%s g%lld", what, (long long)grp);
-        marks.push_back({buf, e});
+        marks.emplace_back(buf, std::move(e));
     }
     void report(hipEvent_t t0, hipEvent_t t1, float total_ms) {
         if (!on()) return;
@@ -1752,7 +1728,6 @@ struct GroupTrace {
             float t = 0.f;
             if (hipEventSynchronize(m.second) == hipSuccess && hipEventElapsedTime(&t, t0, m.second) == hipSuccess)
                 fprintf(stderr, "[pyipm group trace] %9.1f us  %s\n", 1e3 * t, m.first.c_str());
-            hipEventDestroy(m.second);
         }
         fprintf(stderr, "[pyipm group trace] %9.1f us  factorisation end\n", 1e3 * total_ms);
     }
@@ -1920,11 +1895,9 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
     if (!ctx->side) {
         // panel kernels are latency-critical and tiny: highest dispatch priority, so they take the first
         // CU slot a retiring bulk-update block frees instead of queueing behind the whole bulk grid
-        int lo = 0, hi = 0;
-        PYIPM_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        for (hipEvent_t* e : {&ctx->ev_main, &ctx->ev_early, &ctx->ev_split, &ctx->ev_sfast})      // the events of the schedule below
-            if (!*e) PYIPM_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-        PYIPM_HIP(hipStreamCreateWithPriority(&ctx->side, hipStreamNonBlocking, hi));
+        for (Event* e : {&ctx->ev_main, &ctx->ev_early, &ctx->ev_split, &ctx->ev_sfast})      // the events of the schedule below
+            PYIPM_HIP(e->ensure(hipEventDisableTiming));
+        PYIPM_HIP(ctx->side.ensure_highest(hipStreamNonBlocking));
     }
     PYIPM_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
     ctx->sched = plan_groups(g, ctx->group, ctx->tail_group, ctx->tail_group_user, ctx->skip_zeros != 0, ctx->lookahead);
@@ -1934,8 +1907,8 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
     GroupTrace tr;
     ctx->forward_fused = false;
     if (fuse_forward) {
-        if (!ctx->fwd) PYIPM_HIP(hipStreamCreateWithFlags(&ctx->fwd, hipStreamNonBlocking));
-        while ((int64_t)ctx->ev_done.size() < np) { hipEvent_t e; PYIPM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); ctx->ev_done.push_back(e); }
+        PYIPM_HIP(ctx->fwd.ensure(hipStreamNonBlocking));
+        PYIPM_HIP(ensure_events(ctx->ev_done, (size_t)np, hipEventDisableTiming));
         PYIPM_HIP(hipEventRecord(ctx->ev_head, ctx->stream));          // v0 = rhs copy was enqueued on the main stream
         PYIPM_HIP(hipStreamWaitEvent(ctx->fwd, ctx->ev_head, 0));
     }
@@ -2028,12 +2001,6 @@ int factor_dispatch(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward) {
     return rc;
 }
 
-// a failed create releases whatever the handle already owns (events, a library-owned workspace) the way destroy does
-int create_fail(Ctx* ctx, int code) {
-    pyipm_newton_destroy(reinterpret_cast<pyipm_newton_ctx*>(ctx));
-    return code;
-}
-
 // kernels of this translation unit on behalf of the others (a kernel is launched from the unit that defines it)
 int launch_axpby(Ctx* ctx, hipStream_t st, double* out, const double* a, const double* b, double alpha, double beta, int64_t n) {
     hipLaunchKernelGGL(k_axpby, grid1(n), dim3(256), 0, st, out, a, b, alpha, beta, n); PYIPM_KCHECK(); return 0; }
@@ -2065,43 +2032,57 @@ size_t pyipm_newton_workspace_bytes(int64_t n, int64_t me, int64_t mi, int nb, i
     return carve_workspace(nullptr, g, nullptr);
 } PYIPM_CATCH_SIZE
 
-static int create_impl(pyipm_newton_ctx** out, int64_t n, int64_t me, int64_t mi, int nb, int device,
-                       int world, int rank, void* workspace, size_t workspace_bytes, void* stream, bool provider_only) {
+// The one way a handle comes to be.  args_ok: the entry point's checks of its own arguments;  set(ctx): the fields of this kind of
+// handle (its device is current);  carve(ctx, base): the workspace layout (both NULL: only its size);  anorm_words: what of
+// ctx->anorm starts at zero;  schedule_events: the provider and lookahead events of a single-system handle beside the eight
+// timing events every handle has.  An early return releases whatever the handle owns by then (~Ctx).
+static int create_handle(pyipm_newton_ctx** out, bool args_ok, int device, void* workspace, size_t workspace_bytes, void* stream,
+                         const std::function<void(Ctx*)>& set, const std::function<size_t(Ctx*, char*)>& carve, size_t anorm_words,
+                         bool schedule_events) {
     if (!out) return PYIPM_E_BADARG;
     *out = nullptr;
-    if (n <= 0 || me < 0 || mi < 0 || world < 1 || rank < 0 || rank >= world) return PYIPM_E_BADARG;
-    if (nb == 0) nb = 256;
-    if (nb % 128 != 0 || nb > 1024) return PYIPM_E_BADARG;
+    if (!args_ok) return PYIPM_E_BADARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return PYIPM_E_NODEVICE;
-    Ctx* ctx = new Ctx();
-    ctx->g = make_geo(n, me, mi, nb, world, rank);
-    ctx->gc = make_geo(n, me, 0, nb, 1, 0);          // re-derived by every condensed assemble
-    ctx->group = default_group(world, nb);
+    std::unique_ptr<Ctx> ctx(new Ctx());
     ctx->device = device;
     ctx->stream = (hipStream_t)stream;
-    if (hipSetDevice(device) != hipSuccess) return create_fail(ctx, PYIPM_E_NODEVICE);
-    { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) ctx->num_cus = ncu; }
-    ctx->provider_only = provider_only;
-    const size_t need = carve_workspace(nullptr, ctx->g, nullptr, provider_only);
+    if (hipSetDevice(device) != hipSuccess) return PYIPM_E_NODEVICE;
+    set(ctx.get());
+    const size_t need = carve(nullptr, nullptr);
     if (workspace) {
-        if (workspace_bytes < need) return create_fail(ctx, PYIPM_E_NOMEM);
-        ctx->ws = (char*)workspace; ctx->own_ws = false;
+        if (workspace_bytes < need) return PYIPM_E_NOMEM;
+        ctx->ws.adopt((char*)workspace, need);
     } else {
-        if (hipMalloc((void**)&ctx->ws, need) != hipSuccess) return create_fail(ctx, PYIPM_E_NOMEM);
+        if (ctx->ws.reserve(need) != hipSuccess) return PYIPM_E_NOMEM;
         if (getenv("PYIPM_POISON_WORKSPACE")) hipMemset(ctx->ws, 0xFF, need);      // test hook: NaN wherever nothing is written before it is read
-        ctx->own_ws = true;
     }
-    ctx->ws_bytes = need;
-    carve_workspace(ctx, ctx->g, ctx->ws, provider_only);
-    if (hipMemset(ctx->anorm, 0, 2 * sizeof(unsigned long long)) != hipSuccess) return create_fail(ctx, PYIPM_E_HIP);      // [0] max |entry|, [1] "assembly pending"
-    for (int i = 0; i < 8; ++i) if (hipEventCreate(&ctx->ev[i]) != hipSuccess) return create_fail(ctx, PYIPM_E_HIP);
-    for (int i = 0; i < 4; ++i) if (hipEventCreate(&ctx->ev_prov[i]) != hipSuccess) return create_fail(ctx, PYIPM_E_HIP);
-    if (hipEventCreateWithFlags(&ctx->ev_fwd, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_head, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_panel, hipEventDisableTiming) != hipSuccess) return create_fail(ctx, PYIPM_E_HIP);
-    *out = reinterpret_cast<pyipm_newton_ctx*>(ctx);
+    carve(ctx.get(), ctx->ws.get());
+    if (hipMemset(ctx->anorm, 0, anorm_words * sizeof(unsigned long long)) != hipSuccess) return PYIPM_E_HIP;
+    for (Event& e : ctx->ev) if (e.ensure(hipEventDefault) != hipSuccess) return PYIPM_E_HIP;
+    if (schedule_events) {
+        for (Event& e : ctx->ev_prov) if (e.ensure(hipEventDefault) != hipSuccess) return PYIPM_E_HIP;
+        for (Event* e : {&ctx->ev_fwd, &ctx->ev_head, &ctx->ev_panel}) if (e->ensure(hipEventDisableTiming) != hipSuccess) return PYIPM_E_HIP;
+    }
+    *out = reinterpret_cast<pyipm_newton_ctx*>(ctx.release());
     return PYIPM_OK;
+}
+
+static int create_impl(pyipm_newton_ctx** out, int64_t n, int64_t me, int64_t mi, int nb, int device,
+                       int world, int rank, void* workspace, size_t workspace_bytes, void* stream, bool provider_only) {
+    if (nb == 0) nb = 256;
+    const bool args_ok = n > 0 && me >= 0 && mi >= 0 && world >= 1 && rank >= 0 && rank < world && nb % 128 == 0 && nb <= 1024;
+    const Geo g = args_ok ? make_geo(n, me, mi, nb, world, rank) : Geo{};
+    return create_handle(out, args_ok, device, workspace, workspace_bytes, stream,
+        [&](Ctx* ctx) {
+            ctx->g = g;
+            ctx->gc = make_geo(n, me, 0, nb, 1, 0);          // re-derived by every condensed assemble
+            ctx->group = default_group(world, nb);
+            { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) ctx->num_cus = ncu; }
+            ctx->provider_only = provider_only;
+        },
+        [&](Ctx* ctx, char* base) { return carve_workspace(ctx, g, base, provider_only); },
+        2 /* [0] max |entry|, [1] "assembly pending" */, true);
 }
 
 int pyipm_newton_create(pyipm_newton_ctx** out, int64_t n, int64_t me, int64_t mi, int nb, int device,
@@ -2129,40 +2110,39 @@ size_t pyipm_newton_workspace_bytes_batched(int64_t n, int64_t me, int64_t mi, i
 
 int pyipm_newton_create_batched(pyipm_newton_ctx** out, int64_t n, int64_t me, int64_t mi, int batch, int device,
                                 void* workspace, size_t workspace_bytes, void* stream) try {
-    if (!out) return PYIPM_E_BADARG;
-    *out = nullptr;
-    if (n <= 0 || me < 0 || mi < 0 || batch < 1) return PYIPM_E_BADARG;
-    Geo g = make_geo(n, me, mi, 128, 1, 0);
-    if (g.Npad > 1024) return PYIPM_E_BADARG;          // one workgroup per problem: Npad threads in the substitutions
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return PYIPM_E_NODEVICE;
-    Ctx* ctx = new Ctx();
-    ctx->g = g; ctx->gc = g;
-    ctx->batch = batch;
-    ctx->group = 1;
-    ctx->device = device;
-    ctx->stream = (hipStream_t)stream;
-    if (hipSetDevice(device) != hipSuccess) return create_fail(ctx, PYIPM_E_NODEVICE);
-    const size_t need = carve_batched(nullptr, g, batch, nullptr);
-    if (workspace) {
-        if (workspace_bytes < need) return create_fail(ctx, PYIPM_E_NOMEM);
-        ctx->ws = (char*)workspace; ctx->own_ws = false;
-    } else {
-        if (hipMalloc((void**)&ctx->ws, need) != hipSuccess) return create_fail(ctx, PYIPM_E_NOMEM);
-        if (getenv("PYIPM_POISON_WORKSPACE")) hipMemset(ctx->ws, 0xFF, need);      // test hook: NaN wherever nothing is written before it is read
-        ctx->own_ws = true;
-    }
-    ctx->ws_bytes = need;
-    carve_batched(ctx, g, batch, ctx->ws);
-    ctx->batched = true;
-    ctx->tile_blocked = 1;               // the blocked inversion in both forms since round 6 (512 x N = 768, full form: 3.24 against 3.44 ms;
-                                          // condensed: 0.99 against 1.10; round 3 measured the opposite for the full form, before the per-problem
-                                          // Gram kernel and the eight-wave-free register budget of today's k_b_factor)
-    if (hipMemset(ctx->anorm, 0, (size_t)batch * 2 * sizeof(unsigned long long)) != hipSuccess) return create_fail(ctx, PYIPM_E_HIP);
-    for (int i = 0; i < 8; ++i) if (hipEventCreate(&ctx->ev[i]) != hipSuccess) return create_fail(ctx, PYIPM_E_HIP);
-    *out = reinterpret_cast<pyipm_newton_ctx*>(ctx);
-    return PYIPM_OK;
+    bool args_ok = n > 0 && me >= 0 && mi >= 0 && batch >= 1;
+    const Geo g = args_ok ? make_geo(n, me, mi, 128, 1, 0) : Geo{};
+    args_ok = args_ok && g.Npad <= 1024;               // one workgroup per problem: Npad threads in the substitutions
+    return create_handle(out, args_ok, device, workspace, workspace_bytes, stream,
+        [&](Ctx* ctx) {
+            ctx->g = g; ctx->gc = g;
+            ctx->batch = batch;
+            ctx->group = 1;
+            ctx->batched = true;
+            ctx->tile_blocked = 1;       // the blocked inversion in both forms since round 6 (512 x N = 768, full form: 3.24 against 3.44 ms;
+                                         // condensed: 0.99 against 1.10; round 3 measured the opposite for the full form, before the per-problem
+                                         // Gram kernel and the eight-wave-free register budget of today's k_b_factor)
+        },
+        [&](Ctx* ctx, char* base) { return carve_batched(ctx, g, batch, base); },
+        (size_t)batch * 2, false);
 } PYIPM_CATCH_NOH
+
+// the statistics records of the last step_batched (waits for it) and its time
+static int fetch_batched_stats(Ctx* ctx, pyipm_factor_stats* stats) {
+    const int B = ctx->batch;
+    std::vector<DevStats> z((size_t)B);
+    PYIPM_HIP(hipMemcpyAsync(z.data(), ctx->dstats, (size_t)B * sizeof(DevStats), hipMemcpyDeviceToHost, ctx->stream));
+    PYIPM_HIP(hipStreamSynchronize(ctx->stream));
+    int rc = PYIPM_OK;
+    for (int b = 0; b < B; ++b) {
+        stats[b] = to_stats(z[b]);
+        if (z[b].nonfinite) { ctx->err = "NaN/Inf met during factorisation"; rc = PYIPM_E_NONFINITE; }
+    }
+    float ms = 0.f;
+    PYIPM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+    ctx->t_factor = ms;
+    return rc;
+}
 
 int pyipm_newton_stage_blocks_batched(pyipm_newton_ctx* h, const double* d2L, int64_t ld_d2L, int64_t stride_d2L,
                                       const double* Je, int64_t ld_Je, int64_t stride_Je,
@@ -2232,25 +2212,9 @@ int pyipm_newton_step_batched(pyipm_newton_ctx* h, double delta, double delta_c,
     ctx->ev_assemble_valid = true;
     if (memkind == PYIPM_MEM_HOST)
         PYIPM_HIP(hipMemcpyAsync(dz, ctx->v2, (size_t)B * g.N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    int rc = PYIPM_OK;
-    if (stats) {
-        std::vector<DevStats> z((size_t)B);
-        PYIPM_HIP(hipMemcpyAsync(z.data(), ctx->dstats, (size_t)B * sizeof(DevStats), hipMemcpyDeviceToHost, ctx->stream));
-        PYIPM_HIP(hipStreamSynchronize(ctx->stream));
-        for (int b = 0; b < B; ++b) {
-            stats[b].n_neg = z[b].n_neg; stats[b].n_zero = z[b].n_zero; stats[b].n_2x2 = z[b].n_2x2; stats[b].n_pos = z[b].n_pos;
-            stats[b].d_min = z[b].d_min; stats[b].d_max = z[b].d_max;
-            long long gb = (long long)z[b].growth_bits; double gr; memcpy(&gr, &gb, sizeof(gr));
-            stats[b].growth = gr; stats[b].nonfinite = z[b].nonfinite;
-            if (z[b].nonfinite) { ctx->err = "NaN/Inf met during factorisation"; rc = PYIPM_E_NONFINITE; }
-        }
-        float ms = 0.f;
-        PYIPM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-        ctx->t_factor = ms;
-    } else if (memkind == PYIPM_MEM_HOST) {
-        PYIPM_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return rc;
+    if (stats) return fetch_batched_stats(ctx, stats);
+    if (memkind == PYIPM_MEM_HOST) PYIPM_HIP(hipStreamSynchronize(ctx->stream));
+    return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
 // The per-problem statistics of the last step_batched, fetched when the caller wants them: a step called with stats = NULL
@@ -2262,22 +2226,7 @@ int pyipm_newton_stats_batched(pyipm_newton_ctx* h, pyipm_factor_stats* stats) t
     PYIPM_HIP(hipSetDevice(ctx->device));
     if (!ctx->batched) { ctx->err = "stats_batched: not a batched handle"; return PYIPM_E_BADARG; }
     if (!ctx->have_rhs) { ctx->err = "stats_batched: step_batched first"; return PYIPM_E_BADARG; }
-    const int B = ctx->batch;
-    std::vector<DevStats> z((size_t)B);
-    PYIPM_HIP(hipMemcpyAsync(z.data(), ctx->dstats, (size_t)B * sizeof(DevStats), hipMemcpyDeviceToHost, ctx->stream));
-    PYIPM_HIP(hipStreamSynchronize(ctx->stream));
-    int rc = PYIPM_OK;
-    for (int b = 0; b < B; ++b) {
-        stats[b].n_neg = z[b].n_neg; stats[b].n_zero = z[b].n_zero; stats[b].n_2x2 = z[b].n_2x2; stats[b].n_pos = z[b].n_pos;
-        stats[b].d_min = z[b].d_min; stats[b].d_max = z[b].d_max;
-        long long gb = (long long)z[b].growth_bits; double gr; memcpy(&gr, &gb, sizeof(gr));
-        stats[b].growth = gr; stats[b].nonfinite = z[b].nonfinite;
-        if (z[b].nonfinite) { ctx->err = "NaN/Inf met during factorisation"; rc = PYIPM_E_NONFINITE; }
-    }
-    float ms = 0.f;
-    PYIPM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    ctx->t_factor = ms;
-    return rc;
+    return fetch_batched_stats(ctx, stats);
 } PYIPM_CATCH_H(h)
 
 // out[b] = |g - Hc raw_b| / |g| of every problem of the last step_batched, Hc applied from the blocks (k_b_berr)
@@ -2298,44 +2247,17 @@ int pyipm_newton_backward_error_batched(pyipm_newton_ctx* h, const double* dz, d
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
+// Teardown is an order, not a list: stuck collectives aborted, every stream of the handle drained, the communicators gone --
+// after that nothing on the device refers to what the handle owns, and ~Ctx may release its members in any order.
 int pyipm_newton_destroy(pyipm_newton_ctx* h) try {
     if (check_ctx(h)) return PYIPM_E_BADARG;
     Ctx* ctx = C(h);
     hipSetDevice(ctx->device);
+    dist_abort_broken(ctx);
     hipStreamSynchronize(ctx->stream);
-    for (int i = 0; i < 8; ++i) if (ctx->ev[i]) hipEventDestroy(ctx->ev[i]);
-    for (int i = 0; i < 4; ++i) if (ctx->ev_prov[i]) hipEventDestroy(ctx->ev_prov[i]);
-    for (auto& pr : ctx->ev_trailing) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
-    if (ctx->ev_head) hipEventDestroy(ctx->ev_head);
-    if (ctx->ev_panel) hipEventDestroy(ctx->ev_panel);
-    dist_free(ctx);
-    if (ctx->side) { hipStreamSynchronize(ctx->side); hipStreamDestroy(ctx->side); }
-    if (ctx->fwd) { hipStreamSynchronize(ctx->fwd); hipStreamDestroy(ctx->fwd); }
-    if (ctx->rest) { hipStreamSynchronize(ctx->rest); hipStreamDestroy(ctx->rest); }
-    if (ctx->ev_fwd) hipEventDestroy(ctx->ev_fwd);
-    if (ctx->ev_join) hipEventDestroy(ctx->ev_join);
-    if (ctx->ev_split) hipEventDestroy(ctx->ev_split);
-    if (ctx->ev_early) hipEventDestroy(ctx->ev_early);
-    if (ctx->ev_sfast) hipEventDestroy(ctx->ev_sfast);
-    if (ctx->ev_main) hipEventDestroy(ctx->ev_main);
-    for (auto e : ctx->ev_band) hipEventDestroy(e);
-    for (auto e : ctx->ev_done) hipEventDestroy(e);
-    if (ctx->stg_d2L) hipFree(ctx->stg_d2L);
-    if (ctx->stg_Je) hipFree(ctx->stg_Je);
-    if (ctx->stg_Ji) hipFree(ctx->stg_Ji);
-    for (auto& kv : ctx->tile_lists) if (kv.second.ready) hipEventDestroy(kv.second.ready);
-    for (auto& a : ctx->tl_arenas) { if (a.dev) hipFree(a.dev); if (a.host) hipHostFree(a.host); }
-    if (ctx->JT) hipFree(ctx->JT);
-    if (ctx->Jx) hipFree(ctx->Jx);
-    if (ctx->cond_pos && !ctx->batched) hipFree(ctx->cond_pos);      // (a batched handle's lives in its workspace)
-    if (ctx->sweep_sync) hipFree(ctx->sweep_sync);
-    if (ctx->chain_sync) hipFree(ctx->chain_sync);
-    if (ctx->sweep_buf) hipFree(ctx->sweep_buf);
-    if (ctx->ms_buf) hipFree(ctx->ms_buf);
-    if (ctx->merit_buf) hipFree(ctx->merit_buf);
-    if (ctx->rc_warm[0]) hipFree(ctx->rc_warm[0]);
-    if (ctx->ray_buf) hipFree(ctx->ray_buf);
-    if (ctx->own_ws && ctx->ws) hipFree(ctx->ws);
+    dist_sync(ctx);
+    ctx->side.sync(); ctx->fwd.sync(); ctx->rest.sync();
+    dist_comm_destroy(ctx);
     delete ctx;
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
@@ -2355,7 +2277,7 @@ int pyipm_newton_geometry(pyipm_newton_ctx* h, int64_t out[8]) try {
     if (check_ctx(h) || !out) return PYIPM_E_BADARG;
     const Geo& g = C(h)->g;
     out[0] = g.N; out[1] = g.Npad; out[2] = g.nb; out[3] = g.npanels; out[4] = g.ncols_local;
-    out[5] = g.world; out[6] = g.rank; out[7] = (int64_t)C(h)->ws_bytes;
+    out[5] = g.world; out[6] = g.rank; out[7] = (int64_t)C(h)->ws.capacity();
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
@@ -2367,9 +2289,9 @@ int pyipm_newton_stage_blocks(pyipm_newton_ctx* h, const double* d2L, int64_t ld
     PYIPM_HIP(hipSetDevice(ctx->device));
     int rc;
     if (!d2L && ctx->provider_only) { ctx->d2L = nullptr; ctx->ld_d2L = g.n; }     // (a factored Hessian model: only the Jacobian products)
-    else { rc = stage_block(ctx, d2L, g.n, g.n, ld_d2L, memkind, &ctx->stg_d2L, &ctx->stg_d2L_sz, &ctx->d2L, &ctx->ld_d2L); if (rc) return rc; }
-    rc = stage_block(ctx, Je, g.me ? g.n : 0, g.me, ld_Je, memkind, &ctx->stg_Je, &ctx->stg_Je_sz, &ctx->Je, &ctx->ld_Je); if (rc) return rc;
-    rc = stage_block(ctx, Ji, g.mi ? g.n : 0, g.mi, ld_Ji, memkind, &ctx->stg_Ji, &ctx->stg_Ji_sz, &ctx->Ji, &ctx->ld_Ji); if (rc) return rc;
+    else { rc = stage_block(ctx, d2L, g.n, g.n, ld_d2L, memkind, ctx->stg_d2L, &ctx->d2L, &ctx->ld_d2L); if (rc) return rc; }
+    rc = stage_block(ctx, Je, g.me ? g.n : 0, g.me, ld_Je, memkind, ctx->stg_Je, &ctx->Je, &ctx->ld_Je); if (rc) return rc;
+    rc = stage_block(ctx, Ji, g.mi ? g.n : 0, g.mi, ld_Ji, memkind, ctx->stg_Ji, &ctx->Ji, &ctx->ld_Ji); if (rc) return rc;
     ctx->have_blocks = true;
     ctx->ray_valid = false;
     ctx->rc_warm_valid[0] = ctx->rc_warm_valid[1] = false;      // (another matrix: the condition estimate starts cold)
@@ -2604,10 +2526,9 @@ int pyipm_newton_rcond(pyipm_newton_ctx* h, int it_inv, int it_pow, double out[4
     // component along the extreme eigenvector is valid; the stopping rules are unchanged; a hashed start is taken whenever the
     // stored vector is missing, of another size, or not finite.  stage_blocks forgets it.
     const bool warm_ok = (adaptive_inv || adaptive_pow) && !ctx->cond_active && getenv("PYIPM_RCOND_COLD") == nullptr;
-    if (warm_ok && ctx->rc_warm_n != g.Npad) {
-        if (ctx->rc_warm[0]) { PYIPM_HIP(hipStreamSynchronize(ctx->stream)); PYIPM_HIP(hipFree(ctx->rc_warm[0])); ctx->rc_warm[0] = nullptr; }
-        if (hipMalloc((void**)&ctx->rc_warm[0], 2 * (size_t)g.Npad * sizeof(double)) != hipSuccess) { ctx->rc_warm[0] = nullptr; ctx->rc_warm_n = 0; }
-        else { ctx->rc_warm[1] = ctx->rc_warm[0] + g.Npad; ctx->rc_warm_n = g.Npad; }
+    if (warm_ok && ctx->rc_warm_buf.capacity() < 2 * (size_t)g.Npad) {      // (no memory: no warm start, asked for again next time)
+        const bool got = ctx->rc_warm_buf.reserve(2 * (size_t)g.Npad) == hipSuccess;
+        ctx->rc_warm[0] = ctx->rc_warm_buf; ctx->rc_warm[1] = got ? ctx->rc_warm[0] + g.Npad : nullptr;
         ctx->rc_warm_valid[0] = ctx->rc_warm_valid[1] = false;
     }
     for (int phase = 0; phase < 2; ++phase) {
@@ -2801,7 +2722,7 @@ int pyipm_newton_step_lengths(pyipm_newton_ctx* h, double tau, const double* dz_
 static int merit_scratch(Ctx* ctx) {
     if (ctx->merit_buf) return 0;
     // [partials | info out (MERIT_NQ) | gq (2) | dots (8) | alphas (MERIT_MAXK) | ray out (MERIT_MAXK)]
-    PYIPM_HIP(hipMalloc((void**)&ctx->merit_buf, (size_t)(MERIT_NB * MERIT_NQ + MERIT_NQ + 2 + 8 + 2 * 1024) * sizeof(double)));
+    PYIPM_HIP(ctx->merit_buf.reserve((size_t)(MERIT_NB * MERIT_NQ + MERIT_NQ + 2 + 8 + 2 * 1024)));
     return 0;
 }
 static const double* merit_direction(Ctx* ctx, const double* dz, const char* who) {
@@ -2876,11 +2797,7 @@ int pyipm_newton_merit_ray(pyipm_newton_ctx* h, const double* dz, double nu, dou
     if (!quad && !ctx->d2L) { ctx->err = "merit_ray: no d2L block staged (pass quad = dx' Q dx)"; return PYIPM_E_BADARG; }
     int rc = merit_scratch(ctx); if (rc) return rc;
     const size_t need = (size_t)(g.n + g.me + g.mi + 8);
-    if (ctx->ray_buf_n < need) {
-        if (ctx->ray_buf) { PYIPM_HIP(hipStreamSynchronize(ctx->stream)); PYIPM_HIP(hipFree(ctx->ray_buf)); ctx->ray_buf = nullptr; ctx->ray_buf_n = 0; }
-        PYIPM_HIP(hipMalloc((void**)&ctx->ray_buf, need * sizeof(double)));
-        ctx->ray_buf_n = need; ctx->ray_for = nullptr;
-    }
+    if (ctx->ray_buf.capacity() < need) { ctx->ray_for = nullptr; PYIPM_HIP(ctx->ray_buf.reserve(need)); }
     double* qd = ctx->ray_buf; double* dce = qd + g.n; double* dci = dce + g.me;
     double* gq = ctx->merit_buf + MERIT_NB * MERIT_NQ + MERIT_NQ;
     double* dal = gq + 2 + 8; double* dout = dal + 1024;
@@ -3150,10 +3067,11 @@ int pyipm_mfma_f64_peak(int device, int iters, double* tflops) try {
     if (hipSetDevice(device) != hipSuccess) return PYIPM_E_NODEVICE;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) != hipSuccess) return PYIPM_E_HIP;
-    double* d = nullptr;
-    if (hipMalloc((void**)&d, 64) != hipSuccess) return PYIPM_E_NOMEM;
+    DevBuf<double> d;
+    if (d.reserve(8) != hipSuccess) return PYIPM_E_NOMEM;
     const int blocks = prop.multiProcessorCount * 2;        // 8 waves per CU = 2 per SIMD
-    hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
+    Event e0, e1;
+    if (e0.ensure(hipEventDefault) != hipSuccess || e1.ensure(hipEventDefault) != hipSuccess) return PYIPM_E_HIP;
     hipLaunchKernelGGL(k_mfma_peak, dim3(blocks), dim3(256), 0, 0, d, 16);   // warm-up
     hipEventRecord(e0, 0);
     hipLaunchKernelGGL(k_mfma_peak, dim3(blocks), dim3(256), 0, 0, d, iters);
@@ -3162,7 +3080,6 @@ int pyipm_mfma_f64_peak(int device, int iters, double* tflops) try {
     float ms = 0.f; hipEventElapsedTime(&ms, e0, e1);
     const double flops = (double)blocks * 4.0 /*waves*/ * (double)iters * 32.0 * 2.0 * 16 * 16 * 4;
     *tflops = flops / (ms * 1e-3) / 1e12;
-    hipEventDestroy(e0); hipEventDestroy(e1); hipFree(d);
     return hipGetLastError() == hipSuccess ? PYIPM_OK : PYIPM_E_HIP;
 } PYIPM_CATCH_NOH
 
