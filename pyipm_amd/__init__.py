@@ -4,7 +4,7 @@ The package is deliberately thin: ``csrc/`` (hand-written HIP kernels + the C-AB
 in ``include/pyipm_newton.h``), ``newton.py`` (ctypes binding, PyTorch-ROCm
 tensors as the device container), ``ipm.py`` (host ``IPM`` class mirroring
 ``/root/reference/pyipm.py:23,311-314,1567,1863``), ``qp.py`` (the same loop
-device-resident for QPs), ``lbfgs.py`` (binding of ``include/pyipm_lbfgs.h``: the
+device-resident for QPs; both run ``loop.py``'s ``BarrierLoop``), ``lbfgs.py`` (binding of ``include/pyipm_lbfgs.h``: the
 limited-memory direction of ``lbfgs=m``), ``dist.py`` / ``batched.py`` (multi-GPU and batched
 drivers), ``problems.py`` (example problems + synthetic QP generator).  Submodules are imported lazily so that the
 pure-NumPy parts work in a GPU-less container; anything that needs the HIP

@@ -9,11 +9,11 @@ simply split by rank.  Same algorithm and tile-inversion code as the single-syst
 from __future__ import annotations
 
 import ctypes
-import os
 from ctypes import c_void_p
 
 import numpy as np
 
+from ._device import alloc_workspace, ptr, to_device
 from .newton import ERRORS, MEM_DEVICE, FactorStats, NewtonError, load_library
 
 
@@ -81,9 +81,7 @@ class BatchedNewton(object):
         if need == 0:
             raise NewtonError("batched handles need n + 2 mi + me <= 1024 (got %d)" % self.N)
         with torch.cuda.device(self.device):
-            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-            if os.environ.get("PYIPM_POISON_WORKSPACE"):     # test hook (tests/conftest.py): every byte the library does not write
-                self.workspace.fill_(255)                    # itself reads back as NaN -- zero pages of a fresh process hide such reads
+            self.workspace = alloc_workspace(need, self.device)
             h = c_void_p()
             rc = self.lib.pyipm_newton_create_batched(ctypes.byref(h), self.n, self.me, self.mi, batch, self.device.index,
                                                       c_void_p(self.workspace.data_ptr()), need,
@@ -118,13 +116,7 @@ class BatchedNewton(object):
         n, me, mi = self.n, self.me, self.mi
 
         def dev(a, shape):
-            if a is None:
-                return None
-            if isinstance(a, torch.Tensor):
-                t = a.to(device=self.device, dtype=torch.float64)
-            else:
-                t = torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64))).to(self.device)
-            return t.reshape(shape).contiguous()
+            return to_device(a, self.device, shape)
 
         B = int(d2L.shape[0])
         if self.h is None or B != self.batch:
@@ -133,9 +125,6 @@ class BatchedNewton(object):
         vecs = (dev(df, (B, n)), dev(ce, (B, me)) if me else None, dev(ci, (B, mi)) if mi else None,
                 dev(s, (B, mi)) if mi else None, dev(lda, (B, me + mi)) if (me + mi) else None)
         self._keep = (blocks, vecs)            # the library retains the block pointers
-
-        def ptr(t):
-            return c_void_p(0) if t is None else c_void_p(t.data_ptr())
 
         self._ck(self.lib.pyipm_newton_set_stream(self.h, c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
         self._ck(self.lib.pyipm_newton_stage_blocks_batched(self.h, ptr(blocks[0]), n, n * n, ptr(blocks[1]), me, n * me,

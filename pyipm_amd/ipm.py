@@ -29,6 +29,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from .loop import BarrierLoop, lbfgs_pair_update
+
 
 def pinv_apply(J, g):
     """pinv(J) @ g -- the reference's first multiplier estimate (pyipm.py:726-730) -- without the SVD where J allows it: for a
@@ -348,8 +350,9 @@ class HipLbfgsBackend(object):
         return dz.cpu().numpy()
 
 
-class IPM(object):
-    """Line-search primal-dual interior-point solver; see module docstring."""
+class IPM(BarrierLoop):
+    """Line-search primal-dual interior-point solver; see module docstring.  The barrier loop itself is
+    ``pyipm_amd.loop.BarrierLoop``: this class is its NumPy / user-callable side."""
 
     def __init__(self, x0=None, x_dev=None, f=None, df=None, d2f=None, ce=None, dce=None, d2ce=None, ci=None,
                  dci=None, d2ci=None, lda0=None, lambda_dev=None, s0=None, mu=0.2, nu=10.0, rho=0.1, tau=0.995,
@@ -543,16 +546,13 @@ class IPM(object):
                 pass
         return -np.linalg.lstsq(A, c_new, rcond=None)[0]
 
-    def search(self, x0, s0, lda0, dz, alpha_smax, alpha_lmax):
+    def search(self, x0, s0, lda0, dz, alpha_smax, alpha_lmax, info=None):
         """Backtracking Armijo search on the merit function with an optional second-order
-        feasibility correction (pyipm.py:1438-1565)."""
+        feasibility correction (pyipm.py:1438-1565).  ``info`` is the loop's hand-over slot and carries nothing here."""
         n, me, mi = self.nvar, self.neq, self.nineq
-        dx = dz[:n]
-        ds = dz[n:n + mi] if mi else np.zeros(0)
-        if me or mi:
-            dl = dz[n + mi:]
-        else:
-            dl, alpha_lmax = 0.0, 0.0
+        dx, ds = dz[:n], dz[n:n + mi]
+        if not (me or mi):
+            alpha_lmax = 0.0
         phi0 = self.phi(x0, s0)
         dphi0 = self.dphi(x0, s0, dz[:n + mi])
         armijo = lambda a: phi0 + a * self.eta * dphi0    # noqa: E731
@@ -567,19 +567,8 @@ class IPM(object):
                 c_new = self._con(x0 + alpha_smax * dx, s0 + alpha_smax * ds if mi else s0)
                 if np.sum(np.abs(c_new)) > np.sum(np.abs(c_old)):
                     dz_p = self._restoration(x0, c_new)
-                    if mi:
-                        xs = x0 + alpha_smax * dx + dz_p[:n]
-                        ss = s0 + alpha_smax * ds + dz_p[n:]
-                        if self.phi(xs, ss) <= armijo(alpha_smax):
-                            alpha_corr = self.step(s0, alpha_smax * ds + dz_p[n:])
-                            if (self.phi(x0 + alpha_corr * (alpha_smax * dx + dz_p[:n]),
-                                         s0 + alpha_corr * (alpha_smax * ds + dz_p[n:])) <= armijo(alpha_smax)):
-                                corrected = True
-                    else:
-                        if self.phi(x0 + alpha_smax * dx + dz_p[:n], s0) <= armijo(alpha_smax):
-                            alpha_corr, corrected = 1.0, True
-                    if corrected and self.verbosity > 2:
-                        print('Second-order feasibility correction accepted')
+                    corrected, alpha_corr = self._second_order_correction(x0, s0, dx, ds, dz_p, alpha_smax,
+                                                                          armijo(alpha_smax))
             if not corrected:
                 alpha_smax *= self.tau
                 alpha_lmax *= self.tau
@@ -594,14 +583,7 @@ class IPM(object):
                         return x0, s0, lda0
                     alpha_smax *= self.tau
                     alpha_lmax *= self.tau
-        if corrected:
-            x = x0 + alpha_corr * (alpha_smax * dx + dz_p[:n])
-            s = s0 + alpha_corr * (alpha_smax * ds + dz_p[n:]) if mi else np.copy(s0)
-        else:
-            x = x0 + alpha_smax * dx
-            s = s0 + alpha_smax * ds if mi else np.copy(s0)
-        lda = lda0 + alpha_lmax * dl if (me or mi) else np.copy(lda0)
-        return x, s, lda
+        return self._step_to(x0, s0, lda0, dz, alpha_smax, alpha_lmax, alpha_corr, dz_p if corrected else None)
 
     # ------------------------------------------------------------------ the Newton step (hot path)
     def newton_direction(self, x, s, lda):
@@ -638,34 +620,15 @@ class IPM(object):
         n, con = self.nvar, bool(self.neq or self.nineq)
         dx = x_new - x_old
         dg = g_old[:n] - g_new[:n]
-        curv = float(np.dot(dg, dx))
-        zeta_new = curv / ((np.dot(dx, dx) if con else np.dot(dg, dg)) + self.eps)
-        root = np.sqrt(self.eps)
-        if curv > root and zeta_new > root:
-            zeta = zeta_new
-            k = S.shape[1]
-            if k > self.lbfgs:                           # the reference lets the storage reach lbfgs+1 pairs (:1300)
-                S, Y = np.roll(S, -1, axis=1), np.roll(Y, -1, axis=1)
-                SS, L, D = (np.roll(Mx, (-1, -1), axis=(0, 1)) for Mx in (SS, L, D))
-                SS[-1, :] = SS[:, -1] = 0.0
-                L[-1, :] = L[:, -1] = 0.0
-                D[-1, :] = D[:, -1] = 0.0
-            else:
-                S, Y = np.pad(S, ((0, 0), (0, 1))), np.pad(Y, ((0, 0), (0, 1)))
-                SS, L, D = (np.pad(Mx, ((0, 1), (0, 1))) for Mx in (SS, L, D))
-            S[:, -1], Y[:, -1] = dx, dg
-            inner = S.T @ dx if con else Y.T @ dg
-            SS[:, -1] = SS[-1, :] = inner
-            if con:
-                L[-1, :] = dx @ Y
-                L[-1, -1] = 0.0
-            else:
-                L[:, -1] = S.T @ dg
-            D[-1, -1] = curv
-            lbfgs_fail = 0
-        else:
-            lbfgs_fail += 1
-        if lbfgs_fail > self.lbfgs_fail_max and S.shape[1] > 0:
+        drop = S.shape[1] > self.lbfgs                   # the reference lets the storage reach lbfgs+1 pairs (:1300)
+        Sn = np.concatenate([S[:, 1:] if drop else S, dx[:, None]], axis=1)
+        Yn = np.concatenate([Y[:, 1:] if drop else Y, dg[:, None]], axis=1)
+        accepted, reset, zeta, SS, L, D, lbfgs_fail = lbfgs_pair_update(
+            zeta, SS, L, D, lbfgs_fail, drop, Sn.T @ dx if con else Yn.T @ dg, dx @ Yn if con else Sn.T @ dg,
+            float(np.dot(dg, dx)), np.dot(dx, dx) if con else np.dot(dg, dg), con, self.lbfgs_fail_max, self.eps)
+        if accepted:
+            S, Y = Sn, Yn
+        if reset:
             if self.verbosity > 2:
                 print('Max failures reached, resetting storage arrays.')
             return self.lbfgs_init()
@@ -682,10 +645,43 @@ class IPM(object):
         reg = self.reg_coef * self.eta * (self.mu_host_dev ** self.beta)              # :1113
         return self.backend.lbfgs_direction(Je, Ji, s, lda, g, zeta, S, Y, SS, L, D, reg, self.eps)
 
-    # ------------------------------------------------------------------ driver
-    def _kkt_small(self, kkt, tol):
-        return all(np.linalg.norm(k) <= tol for k in kkt)
+    def _lbfgs_direction(self, x, s, lda, g, zeta, S, Y, SS, L, D):
+        dz = self.lbfgs_dir(x, s, lda, g, zeta, S, Y, SS, L, D)
+        if self.neq or self.nineq:
+            dz[self.nvar + self.nineq:] = -dz[self.nvar + self.nineq:]                # :1723-1725
+        return dz
 
+    # ------------------------------------------------------------------ what the loop asks for (pyipm_amd.loop.BarrierLoop)
+    def _kkt_norms(self, kkt):
+        return (np.linalg.norm(k) for k in kkt)        # lazily: the smallness tests stop at the first block above tol
+
+    def _neg_grad(self, x, s, lda):
+        return -self.grad(x, s, lda)
+
+    def _set_barrier(self, mu):
+        self.mu_host = self.mu_host_dev = mu              # mu_host_dev: value of the reference's shared mu_dev
+
+    def _step_lengths(self, s, lda, dz):
+        n, me, mi = self.nvar, self.neq, self.nineq
+        dev = self.backend.step_lengths(self.tau) if hasattr(self.backend, "step_lengths") else None
+        if dev is not None:
+            return dev
+        return self.step(s, dz[n:n + mi]), self.step(lda[me:], dz[n + mi + me:])
+
+    def _merit_threshold(self, x, s, lda, dz):
+        n, mi = self.nvar, self.nineq
+        if not (self.neq or mi):
+            return None, None
+        bcg = np.asarray(self.df(x), dtype=np.float64).reshape(n)
+        if mi:
+            bcg = np.concatenate([bcg, -self.mu_host_dev / (s + self.eps)])
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return np.dot(bcg, dz[:n + mi]) / (1 - self.rho) / np.sum(np.abs(self._con(x, s))), None
+
+    def _complementarity(self, x, s, lda):
+        return float(np.dot(s, lda[self.neq:])), np.min(s * lda[self.neq:])
+
+    # ------------------------------------------------------------------ driver
     def solve(self, x0=None, s0=None, lda0=None, force_recompile=False):
         if x0 is not None:
             self.x0 = x0
@@ -709,12 +705,10 @@ class IPM(object):
         if mi:
             s = (np.maximum(np.asarray(self.ci(x), dtype=np.float64).reshape(mi), self.Ktol)
                  if self.s0 is None else np.asarray(self.s0, dtype=np.float64))
-            self.mu_host = self.mu
-            self.mu_host_dev = self.mu            # value of the reference's shared mu_dev
+            self._set_barrier(self.mu)
         else:
             s = np.zeros(0)
-            self.mu_host = self.Ktol
-            self.mu_host_dev = self.Ktol
+            self._set_barrier(self.Ktol)
         self.nu_host = self.nu
         if me or mi:
             if self.lda0 is None:
@@ -726,118 +720,9 @@ class IPM(object):
                 lda = np.asarray(self.lda0, dtype=np.float64).copy()
         else:
             lda = np.zeros(0)
-        self.delta = 0.0
-        kkt = self.KKT(x, s, lda)
-
-        if self.lbfgs:                                           # pyipm.py:1633-1637
-            zeta, S, Y, SS, L, D, lbfgs_fail = self.lbfgs_init()
-            x_old = np.copy(x)
-            g = -self.grad(x, s, lda)
-
-        if self.verbosity > 0:
-            print('Searching for a feasible local minimizer using L-BFGS to approximate the Hessian.' if self.lbfgs
-                  else 'Searching for a feasible local minimizer using the exact Hessian.')
-        iter_count = 0
-        f_past = float(self.f(x)) if self.Ftol is not None else None
-        Ftol_converged = False
-        self.signal = 0
-        outer = inner = 0
-
-        for outer in range(self.niter):
-            if self._kkt_small(kkt, self.Ktol):
-                self.signal = 1
-                break
-            if self.verbosity > 0 and mi:
-                print('OUTER ITERATION {}'.format(outer + 1))
-            for inner in range(self.miter):
-                if self._kkt_small(kkt, max(self.Ktol, self.mu_host)):
-                    if not me and not mi:
-                        self.signal = 1
-                    break
-                if self.verbosity > 0:
-                    msg = ['* INNER ITERATION {}'.format(inner + 1) if mi else 'ITERATION {}'.format(iter_count + 1)]
-                    if self.verbosity > 1:
-                        msg.append('f(x) = {}'.format(self.f(x)))
-                    if self.verbosity > 2:
-                        msg.append('|dL/dx| = {}'.format(np.linalg.norm(kkt[0])))
-                        msg.append('|dL/ds| = {}'.format(np.linalg.norm(kkt[1])))
-                        msg.append('|ce| = {}'.format(np.linalg.norm(kkt[2])))
-                        msg.append('|ci-s| = {}'.format(np.linalg.norm(kkt[3])))
-                    print(', '.join(msg))
-
-                if self.lbfgs:                                    # pyipm.py:1702-1713
-                    if inner > 0 or outer > 0:
-                        g_old = -self.grad(x_old, s, lda)
-                        g_new = -self.grad(x, s, lda)
-                        zeta, S, Y, SS, L, D, lbfgs_fail = self.lbfgs_update(x_old, x, g_old, g_new, zeta, S, Y, SS,
-                                                                             L, D, lbfgs_fail)
-                        x_old = np.copy(x)
-                        g = np.copy(g_new)
-                    dz = self.lbfgs_dir(x, s, lda, g, zeta, S, Y, SS, L, D)
-                    if me or mi:
-                        dz[n + mi:] = -dz[n + mi:]                # :1723-1725
-                else:
-                    dz = self.newton_direction(x, s, lda)        # <-- the accelerated hot path
-
-                if me or mi:                                      # merit parameter (pyipm.py:1727-1735)
-                    bcg = np.asarray(self.df(x), dtype=np.float64).reshape(n)
-                    if mi:
-                        bcg = np.concatenate([bcg, -self.mu_host_dev / (s + self.eps)])
-                    with np.errstate(divide='ignore', invalid='ignore'):
-                        nu_thres = np.dot(bcg, dz[:n + mi]) / (1 - self.rho) / np.sum(np.abs(self._con(x, s)))
-                    if self.nu_host < nu_thres:
-                        self.nu_host = float(nu_thres)
-                if mi:
-                    dev = self.backend.step_lengths(self.tau) if hasattr(self.backend, "step_lengths") else None
-                    if dev is not None:
-                        a_s, a_l = dev
-                    else:
-                        a_s = self.step(s, dz[n:n + mi])
-                        a_l = self.step(lda[me:], dz[n + mi + me:])
-                    x, s, lda = self.search(x, s, lda, dz, float(a_s), float(a_l))
-                else:
-                    x, s, lda = self.search(x, s, lda, dz, 1.0, 1.0)
-                iter_count += 1
-                kkt = self.KKT(x, s, lda)
-
-                if self.Ftol is not None and not mi and self.signal != -2:
-                    f_new = float(self.f(x))
-                    if abs(f_past - f_new) <= abs(self.Ftol):
-                        self.signal = 2
-                        Ftol_converged = True
-                        break
-                    f_past = f_new
-                if self.signal == -2:
-                    break
-                if inner >= self.miter - 1 and self.verbosity > 0 and mi:
-                    print('MAXIMUM INNER ITERATIONS EXCEEDED')
-
-            if self.Ftol is not None and mi and self.signal != -2:
-                f_new = float(self.f(x))
-                if abs(f_past - f_new) <= abs(self.Ftol):
-                    self.signal = 2
-                    Ftol_converged = True
-                else:
-                    f_past = f_new
-            if Ftol_converged or self.signal == -2:
-                break
-            if outer >= self.niter - 1:
-                self.signal = -1
-                if self.verbosity > 0:
-                    print('MAXIMUM OUTER ITERATIONS EXCEEDED' if mi else 'MAXIMUM ITERATIONS EXCEEDED')
-                break
-            if mi:                                                # barrier update (pyipm.py:1804-1814)
-                comp = float(np.dot(s, lda[me:]))
-                xi = mi * np.min(s * lda[me:]) / (comp + self.eps)
-                mu_new = 0.1 * min(0.05 * (1.0 - xi) / (xi + self.eps), 2.0) ** 3 * comp / mi
-                self.mu_host = max(float(mu_new), 0.0)
-                self.mu_host_dev = self.mu_host
-
-        self.x, self.s, self.lda, self.kkt = x, s, lda, kkt
-        self.fval = self.f(x)
-        self.iter_count = iter_count
+        Ftol_converged, outer, inner = self._barrier_loop(x, s, lda)
         if self.verbosity >= 0:
-            self._report(kkt, Ftol_converged, outer, inner, iter_count)
+            self._report(self.kkt, Ftol_converged, outer, inner, self.iter_count)
         return self.x, self.s, self.lda, self.fval, self.kkt
 
     def _report(self, kkt, Ftol_converged, outer, inner, iter_count):
@@ -845,7 +730,7 @@ class IPM(object):
         words = []
         if self.signal == -2:
             words.append('Terminated due to bad direction in backtracking line search')
-        elif self._kkt_small(kkt, self.Ktol):
+        elif self._small(kkt, self.Ktol):
             words.append('Converged to Ktol tolerance')
         elif self.Ftol is not None and Ftol_converged:
             words.append('Converged to Ftol tolerance')

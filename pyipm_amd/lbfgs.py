@@ -12,6 +12,7 @@ from ctypes import POINTER, c_char_p, c_double, c_int, c_int64, c_size_t, c_void
 
 import numpy as np
 
+from ._device import RawDeviceArray, ptr, to_device
 from .newton import ERRORS, MEM_DEVICE, MEM_HOST, NewtonError, load_library
 
 
@@ -41,12 +42,6 @@ _SIG = {
 ALLREDUCE_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_int64, c_void_p)
 
 
-class _RawDeviceArray(object):
-    """fp64 device memory owned by the library, exposed to torch without a copy."""
-
-    def __init__(self, ptr, count):
-        self.__cuda_array_interface__ = {"data": (int(ptr), False), "shape": (int(count),), "typestr": "<f8",
-                                         "version": 2, "strides": None}
 _bound = None
 
 
@@ -112,7 +107,7 @@ class LbfgsCore(object):
 
         def cb(user, ptr, count, stream):
             try:
-                t = torch.as_tensor(_RawDeviceArray(ptr, count), device=self.device)
+                t = torch.as_tensor(RawDeviceArray(ptr, count), device=self.device)
                 if staged:
                     hbuf = t.cpu()                                   # synchronises the stream
                     dist.all_reduce(hbuf, op=dist.ReduceOp.SUM, group=self.group)
@@ -139,16 +134,9 @@ class LbfgsCore(object):
             raise err
 
     def _dev(self, a, shape):
-        torch = self.torch
-        if isinstance(a, torch.Tensor):
-            t = a.to(device=self.device, dtype=torch.float64)
-        else:
-            t = torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64))).to(self.device)
-        return t.reshape(shape).contiguous()
+        return to_device(a, self.device, shape)
 
-    @staticmethod
-    def _ptr(t):
-        return c_void_p(0) if t is None else c_void_p(t.data_ptr())
+    _ptr = staticmethod(ptr)
 
     def set_option(self, name, value):
         self._ck(self.lib.pyipm_lbfgs_set_option(self.h, name.encode(), float(value)))

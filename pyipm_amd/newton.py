@@ -15,6 +15,8 @@ from ctypes import POINTER, c_char_p, c_double, c_int, c_int64, c_size_t, c_void
 
 import numpy as np
 
+from ._device import RawDeviceArray as _RawDeviceArray, alloc_workspace, ptr, to_device  # noqa: F401  (dist.py, tools/rank_replay.py)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PYIPM_NEWTON_LIB") or os.path.join(_HERE, "libpyipm_newton.so")
 
@@ -176,13 +178,6 @@ RECV_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_size_t, c_int, c_void_p)
 ALLGATHER_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p)
 
 
-class _RawDeviceArray(object):
-    """fp64 device memory at a raw address, as torch.as_tensor understands it."""
-
-    def __init__(self, ptr, count):
-        self.__cuda_array_interface__ = {"data": (int(ptr), False), "shape": (int(count),), "typestr": "<f8", "version": 2}
-
-
 class NewtonCore(object):
     """One handle = one KKT system shape (n, me, mi) on one GPU (one rank of ``world``).
 
@@ -216,9 +211,7 @@ class NewtonCore(object):
         if need == 0:
             raise NewtonError("invalid geometry n=%d me=%d mi=%d nb=%d world=%d rank=%d" % (n, me, mi, nb, world, rank))
         with torch.cuda.device(self.device):
-            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-            if os.environ.get("PYIPM_POISON_WORKSPACE"):     # test hook (tests/conftest.py): every byte the library does not write
-                self.workspace.fill_(255)                    # itself reads back as NaN -- zero pages of a fresh process hide such reads
+            self.workspace = alloc_workspace(need, self.device)
             h = c_void_p()
             if self.provider_only:
                 rc = self.lib.pyipm_newton_create_provider(ctypes.byref(h), self.n, self.me, self.mi, self.device.index,
@@ -244,22 +237,10 @@ class NewtonCore(object):
             err.code, err.stats = rc, stats
             raise err
 
-    def _dev(self, a, shape=None):
-        """Return a contiguous fp64 device tensor for ``a`` (numpy / torch / None)."""
-        torch = self.torch
-        if a is None:
-            return None
-        if isinstance(a, torch.Tensor):
-            t = a.to(device=self.device, dtype=torch.float64)
-        else:
-            t = torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64))).to(self.device)
-        if shape is not None:
-            t = t.reshape(shape)
-        return t.contiguous()
+    def _dev(self, a, shape=None, contiguous=True):
+        return to_device(a, self.device, shape, contiguous)
 
-    @staticmethod
-    def _ptr(t):
-        return c_void_p(0) if t is None else c_void_p(t.data_ptr())
+    _ptr = staticmethod(ptr)
 
     on_device = True
 
@@ -351,10 +332,7 @@ class NewtonCore(object):
         contiguous (k, N) buffer.  Column j is bitwise independent of the other columns; see pyipm_newton_solve_many."""
         self._use_current_stream()
         torch = self.torch
-        if isinstance(B, torch.Tensor):
-            B = B.to(device=self.device, dtype=torch.float64)
-        else:
-            B = torch.from_numpy(np.ascontiguousarray(np.asarray(B, dtype=np.float64))).to(self.device)
+        B = self._dev(B, contiguous=False)               # (laid out below: one copy at the most)
         if B.dim() == 1:
             B = B.reshape(-1, 1)
         if B.dim() != 2 or B.shape[0] != self.N:

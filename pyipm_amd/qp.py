@@ -30,12 +30,16 @@ form ``("diag+lowrank", d, F)`` = diag(d) + F F' (a dense n x n Q is exactly wha
 """
 from __future__ import annotations
 
+import time
+
 import numpy as np
 
+from ._device import to_device
+from .loop import BarrierLoop, lbfgs_pair_update
 from .newton import NewtonError
 
 
-class QPDeviceIPM(object):
+class QPDeviceIPM(BarrierLoop):
     def __init__(self, Q, c, A=None, b=None, G=None, h=None, Je=None, Ji=None, x0=None, s0=None, lda0=None,
                  mu=0.2, nu=10.0, rho=0.1, tau=0.995, eta=1.0E-4, beta=0.4, miter=20, niter=10, Xtol=None,
                  Ktol=1.0E-4, Ftol=None, verbosity=1, device=None, nb=256, refine=0, condensed=False,
@@ -48,12 +52,7 @@ class QPDeviceIPM(object):
         dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
         self.device = dev
 
-        def dv(a):
-            if a is None:
-                return None
-            if isinstance(a, torch.Tensor):
-                return a.to(device=dev, dtype=torch.float64)
-            return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64))).to(dev)
+        dv = lambda a: to_device(a, dev, contiguous=False)  # noqa: E731  (the blocks are made contiguous below, once)
 
         self.c = dv(c)
         n = self.nvar = int(self.c.numel())
@@ -116,7 +115,6 @@ class QPDeviceIPM(object):
         update launches, the buffers of the one-launch sweeps -- is built here by ONE Newton step on a harmless point (x = 0,
         s = lda_i = 1, lda_e = 0: the KKT matrix of the staged blocks with Sigma = I), so that the first iteration of
         ``solve()`` costs what the others do (it took 50 ms more at N = 32768).  ``warm=False`` skips it."""
-        import time
         torch, n, me, mi = self.torch, self.nvar, self.neq, self.nineq
         t0 = time.perf_counter()
         z = lambda k: torch.zeros(k, dtype=torch.float64, device=self.device)            # noqa: E731
@@ -327,9 +325,7 @@ class QPDeviceIPM(object):
         phi(x0, s0) in closed form, as a difference (see kernels_merit.hpp)."""
         torch = self.torch
         n, me, mi = self.nvar, self.neq, self.nineq
-        dx = dz[:n]
-        ds = dz[n:n + mi]
-        dl = dz[n + mi:]
+        dx, ds = dz[:n], dz[n:n + mi]
         if not (me or mi):
             alpha_lmax = 0.0
         self._stage_point(x0, s0, lda0)
@@ -373,19 +369,8 @@ class QPDeviceIPM(object):
                 self.phi(xt, st)
                 if self._last_con_l1 > c_old_l1:
                     dz_p = self._restoration(x0, self._con(xt, st))
-                    if mi:
-                        xs = x0 + alpha_smax * dx + dz_p[:n]
-                        ss = s0 + alpha_smax * ds + dz_p[n:]
-                        if self.phi(xs, ss) <= armijo(alpha_smax):
-                            alpha_corr = self.step(s0, alpha_smax * ds + dz_p[n:])
-                            if (self.phi(x0 + alpha_corr * (alpha_smax * dx + dz_p[:n]),
-                                         s0 + alpha_corr * (alpha_smax * ds + dz_p[n:])) <= armijo(alpha_smax)):
-                                corrected = True
-                    else:
-                        if self.phi(x0 + alpha_smax * dx + dz_p[:n], s0) <= armijo(alpha_smax):
-                            alpha_corr, corrected = 1.0, True
-                    if corrected and self.verbosity > 2:
-                        print('Second-order feasibility correction accepted')
+                    corrected, alpha_corr = self._second_order_correction(x0, s0, dx, ds, dz_p, alpha_smax,
+                                                                          armijo(alpha_smax))
             if not corrected:
                 ndx = q["dx_norm"]
                 nds = q["ds_norm"] if mi else 0.0
@@ -409,14 +394,7 @@ class QPDeviceIPM(object):
                         self.signal = -2
                         return x0, s0, lda0
                     k += 1
-        if corrected:
-            x = x0 + alpha_corr * (alpha_smax * dx + dz_p[:n])
-            s = s0 + alpha_corr * (alpha_smax * ds + dz_p[n:]) if mi else s0.clone()
-        else:
-            x = x0 + alpha_smax * dx
-            s = s0 + alpha_smax * ds if mi else s0.clone()
-        lda = lda0 + alpha_lmax * dl if (me or mi) else lda0.clone()
-        return x, s, lda
+        return self._step_to(x0, s0, lda0, dz, alpha_smax, alpha_lmax, alpha_corr, dz_p if corrected else None)
 
     # ------------------------------------------------------------------ the Newton step (hot path)
     def newton_direction(self, x, s, lda):
@@ -431,50 +409,44 @@ class QPDeviceIPM(object):
         return dz
 
     # ------------------------------------------------------------------ L-BFGS mode (storage on the device)
-    def _gvec(self, x, s, lda):
+    def _neg_grad(self, x, s, lda):
         """-grad as ONE device vector (pyipm.py:1637, 1705-1706): the library's residual of the staged point."""
         self._stage_point(x, s, lda)
         return self._g[:self.nvar + 2 * self.nineq + self.neq].clone()
 
-    def _lbfgs_init(self):
+    def lbfgs_init(self):
         t, n, dev = self.torch, self.nvar, self.device
         e = lambda r, c: t.zeros((r, c), dtype=t.float64, device=dev)       # noqa: E731
         z = np.zeros((0, 0))
         return float(self.lbfgs_zeta), e(n, 0), e(n, 0), z, z.copy(), z.copy(), 0
 
-    def _lbfgs_update(self, x_old, x_new, g_old, g_new, zeta, S, Y, SS, L, D, fail):
+    def lbfgs_update(self, x_old, x_new, g_old, g_new, zeta, S, Y, SS, L, D, fail):
         """pyipm.py:1282-1371 with S, Y on the device; only the O(m) inner products cross PCIe."""
         t, n = self.torch, self.nvar
         con = bool(self.neq or self.nineq)
         dx = x_new - x_old
         dg = g_old[:n] - g_new[:n]
-        k = S.shape[1]
-        drop = k > self.lbfgs
+        drop = S.shape[1] > self.lbfgs
         Sn = t.cat([S[:, 1:] if drop else S, dx[:, None]], dim=1)
         Yn = t.cat([Y[:, 1:] if drop else Y, dg[:, None]], dim=1)
         prods = t.cat([Sn.t() @ dx if con else Yn.t() @ dg, dx @ Yn if con else Sn.t() @ dg,
                        t.stack([t.dot(dg, dx), t.dot(dx, dx) if con else t.dot(dg, dg)])]).tolist()     # ONE sync
         kk = Sn.shape[1]
-        inner, cross, curv, den = np.array(prods[:kk]), np.array(prods[kk:2 * kk]), prods[-2], prods[-1]
-        zeta_new = curv / (den + self.eps)
-        root = np.sqrt(self.eps)
-        if curv > root and zeta_new > root:
-            if drop:
-                SS, L, D = SS[1:, 1:], L[1:, 1:], D[1:, 1:]
-            SS, L, D = (np.pad(Mx, ((0, 1), (0, 1))) for Mx in (SS, L, D))
-            SS[:, -1] = SS[-1, :] = inner
-            if con:
-                L[-1, :] = cross
-                L[-1, -1] = 0.0
-            else:
-                L[:, -1] = cross
-            D[-1, -1] = curv
-            zeta, S, Y, fail = zeta_new, Sn.contiguous(), Yn.contiguous(), 0
-        else:
-            fail += 1
-        if fail > self.lbfgs and S.shape[1] > 0:
-            return self._lbfgs_init()
+        accepted, reset, zeta, SS, L, D, fail = lbfgs_pair_update(
+            zeta, SS, L, D, fail, drop, np.array(prods[:kk]), np.array(prods[kk:2 * kk]), prods[-2], prods[-1], con,
+            self.lbfgs, self.eps)
+        if accepted:
+            S, Y = Sn.contiguous(), Yn.contiguous()
+        if reset:
+            return self.lbfgs_init()
         return zeta, S, Y, SS, L, D, fail
+
+    def _lbfgs_direction(self, x, s, lda, g, zeta, S, Y, SS, L, D):
+        me, mi = self.neq, self.nineq
+        reg = self.reg_coef * self.eta * (self.mu_host ** self.beta)
+        dz, self.last_stats = self.lb.direction(g, s if mi else None, lda if (me or mi) else None, zeta,
+                                                S, Y, SS, L, D, reg=reg, eps=self.eps, flip=True)
+        return dz
 
     @staticmethod
     def _pinv_svd(J, g):
@@ -553,14 +525,50 @@ class QPDeviceIPM(object):
             info["path"] = "svd"
         return QPDeviceIPM._pinv_svd(J, g)
 
-    def _small(self, kkt, tol):
-        return all(k <= tol for k in kkt)
+    # ------------------------------------------------------------------ what the loop asks for (pyipm_amd.loop.BarrierLoop)
+    def _kkt_norms(self, kkt):
+        return kkt                                          # KKT() reduces on the device: already norms
+
+    def _step_lengths(self, s, lda, dz):
+        if self.lbfgs:
+            n, me, mi = self.nvar, self.neq, self.nineq
+            return self.step(s, dz[n:n + mi]), self.step(lda[me:], dz[n + mi + me:])
+        return self.backend.step_lengths(self.tau)
+
+    def _merit_threshold(self, x, s, lda, dz):
+        """The bound from the library's reductions over the staged point; the same ``q`` serves search(info=q)."""
+        me, mi = self.neq, self.nineq
+        self._stage_point(x, s, lda)                      # (L-BFGS mode: g of the current point was staged last)
+        q = self.core.merit_info(dz=dz)                   # ||c||_1, df.dx, sum ds/(s+eps), sum log s, |dx|, |ds|: one D2H
+        if not (me or mi):
+            return None, q
+        con_l1 = (q["ce_l1"] if me else 0.0) + (q["cis_l1"] if mi else 0.0)
+        den = (1 - self.rho) * con_l1
+        num = q["df_dx"] - (self.mu_host * q["ds_over_s"] if mi else 0.0)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return np.float64(num) / np.float64(den), q
+
+    def _complementarity(self, x, s, lda):
+        q = self._point_info(x, s, lda)                   # s'lda_i and min s lda_i of the staged point (k_merit_info)
+        return q["comp_sum"], q["comp_min"]
+
+    def _direction_begins(self):
+        self._t0 = time.perf_counter()
+
+    def _direction_done(self):
+        self.torch.cuda.synchronize(self.device)
+        self._t1 = time.perf_counter()
+
+    def _iteration_done(self):
+        t2 = time.perf_counter()
+        self.timings["newton_s"] += self._t1 - self._t0
+        self.timings["newton_each_s"].append(self._t1 - self._t0)
+        self.timings["search_s"] += t2 - self._t1
 
     # ------------------------------------------------------------------ driver (pyipm.py:1567-1863)
     def solve(self):
-        import time
         torch = self.torch
-        n, me, mi = self.nvar, self.neq, self.nineq
+        me, mi = self.neq, self.nineq
         x = self.x0.clone()
         if mi:
             s = torch.clamp(self.ci(x), min=self.Ktol) if self.s0 is None else self.s0.clone()
@@ -589,113 +597,10 @@ class QPDeviceIPM(object):
                 lda = self.lda0.clone()
         else:
             lda = torch.zeros(0, dtype=torch.float64, device=self.device)
-        self.delta = 0.0
-        kkt = self.KKT(x, s, lda)
-        if self.lbfgs:
-            zeta, S, Y, SS, L, D, lb_fail = self._lbfgs_init()
-            x_old, g = x.clone(), self._gvec(x, s, lda)
-        if self.verbosity > 0:
-            print('Searching for a feasible local minimizer using L-BFGS to approximate the Hessian.' if self.lbfgs
-                  else 'Searching for a feasible local minimizer using the exact Hessian.')
-        iter_count = 0
-        f_past = self.f(x) if self.Ftol is not None else None
-        Ftol_converged = False
-        self.signal = 0
-        outer = inner = 0
-        for outer in range(self.niter):
-            if self._small(kkt, self.Ktol):
-                self.signal = 1
-                break
-            if self.verbosity > 0 and mi:
-                print('OUTER ITERATION {}'.format(outer + 1))
-            for inner in range(self.miter):
-                if self._small(kkt, max(self.Ktol, self.mu_host)):
-                    if not me and not mi:
-                        self.signal = 1
-                    break
-                if self.verbosity > 0:
-                    msg = ['* INNER ITERATION {}'.format(inner + 1) if mi else 'ITERATION {}'.format(iter_count + 1)]
-                    if self.verbosity > 1:
-                        msg.append('f(x) = {}'.format(self.f(x)))
-                    if self.verbosity > 2:
-                        msg += ['|dL/dx| = {}'.format(kkt[0]), '|dL/ds| = {}'.format(kkt[1]),
-                                '|ce| = {}'.format(kkt[2]), '|ci-s| = {}'.format(kkt[3])]
-                    print(', '.join(msg))
-                t0 = time.perf_counter()
-                if self.lbfgs:                                    # pyipm.py:1702-1713, 1723-1725
-                    if inner > 0 or outer > 0:
-                        g_old, g_new = self._gvec(x_old, s, lda), self._gvec(x, s, lda)
-                        zeta, S, Y, SS, L, D, lb_fail = self._lbfgs_update(x_old, x, g_old, g_new, zeta, S, Y, SS, L, D,
-                                                                           lb_fail)
-                        x_old, g = x.clone(), g_new
-                    reg = self.reg_coef * self.eta * (self.mu_host ** self.beta)
-                    dz, self.last_stats = self.lb.direction(g, s if mi else None, lda if (me or mi) else None, zeta,
-                                                            S, Y, SS, L, D, reg=reg, eps=self.eps, flip=True)
-                    if mi:
-                        a_s, a_l = self.step(s, dz[n:n + mi]), self.step(lda[me:], dz[n + mi + me:])
-                else:
-                    dz = self.newton_direction(x, s, lda)        # <-- the accelerated hot path
-                    if mi:
-                        a_s, a_l = self.backend.step_lengths(self.tau)
-                torch.cuda.synchronize(self.device)
-                t1 = time.perf_counter()
-                self._stage_point(x, s, lda)                      # (L-BFGS mode: g of the current point was staged last)
-                q = self.core.merit_info(dz=dz)                   # ||c||_1, df.dx, sum ds/(s+eps), sum log s, |dx|, |ds|: one D2H
-                if me or mi:                                      # merit parameter (pyipm.py:1727-1735)
-                    con_l1 = (q["ce_l1"] if me else 0.0) + (q["cis_l1"] if mi else 0.0)
-                    den = (1 - self.rho) * con_l1
-                    num = q["df_dx"] - (self.mu_host * q["ds_over_s"] if mi else 0.0)
-                    with np.errstate(divide='ignore', invalid='ignore'):
-                        nu_thres = np.float64(num) / np.float64(den)
-                    if self.nu_host < nu_thres:
-                        self.nu_host = float(nu_thres)
-                if mi:
-                    x, s, lda = self.search(x, s, lda, dz, float(a_s), float(a_l), info=q)
-                else:
-                    x, s, lda = self.search(x, s, lda, dz, 1.0, 1.0, info=q)
-                iter_count += 1
-                kkt = self.KKT(x, s, lda)
-                t2 = time.perf_counter()
-                self.timings["newton_s"] += t1 - t0
-                self.timings["newton_each_s"].append(t1 - t0)
-                self.timings["search_s"] += t2 - t1
-                if self.Ftol is not None and not mi and self.signal != -2:
-                    f_new = self.f(x)
-                    if abs(f_past - f_new) <= abs(self.Ftol):
-                        self.signal = 2
-                        Ftol_converged = True
-                        break
-                    f_past = f_new
-                if self.signal == -2:
-                    break
-                if inner >= self.miter - 1 and self.verbosity > 0 and mi:
-                    print('MAXIMUM INNER ITERATIONS EXCEEDED')
-            if self.Ftol is not None and mi and self.signal != -2:
-                f_new = self.f(x)
-                if abs(f_past - f_new) <= abs(self.Ftol):
-                    self.signal = 2
-                    Ftol_converged = True
-                else:
-                    f_past = f_new
-            if Ftol_converged or self.signal == -2:
-                break
-            if outer >= self.niter - 1:
-                self.signal = -1
-                if self.verbosity > 0:
-                    print('MAXIMUM OUTER ITERATIONS EXCEEDED' if mi else 'MAXIMUM ITERATIONS EXCEEDED')
-                break
-            if mi:                                                # barrier update (pyipm.py:1804-1814)
-                q = self._point_info(x, s, lda)                   # s'lda_i and min s lda_i of the staged point (k_merit_info)
-                comp, mn = q["comp_sum"], q["comp_min"]
-                xi = mi * mn / (comp + self.eps)
-                mu_new = 0.1 * min(0.05 * (1.0 - xi) / (xi + self.eps), 2.0) ** 3 * comp / mi
-                self.mu_host = max(float(mu_new), 0.0)
-        self.x, self.s, self.lda, self.kkt = x, s, lda, kkt
-        self.fval = self.f(x)
-        self.iter_count = iter_count
+        Ftol_converged = self._barrier_loop(x, s, lda)[0]
         if self.verbosity >= 0:
             words = ('Terminated due to bad direction in backtracking line search' if self.signal == -2 else
-                     'Converged to Ktol tolerance' if self._small(kkt, self.Ktol) else
+                     'Converged to Ktol tolerance' if self._small(self.kkt, self.Ktol) else
                      'Converged to Ftol tolerance' if Ftol_converged else 'Maximum iterations reached')
-            print('{} ({} total iterations).'.format(words, iter_count))
+            print('{} ({} total iterations).'.format(words, self.iter_count))
         return self.x, self.s, self.lda, self.fval, self.kkt
