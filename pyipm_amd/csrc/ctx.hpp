@@ -130,6 +130,91 @@ struct GroupSched {
     bool fast(int64_t grp) const { return fast_[(size_t)grp] != 0; }      bool in_x(int64_t grp) const { return in_x_[(size_t)grp] != 0; }
 };
 
+// What a handle currently holds, as one record: which staged data, matrix, factor and work vectors are valid.  Fields are read
+// anywhere and written only by the transitions below, one per event; each carries the one statement of why it invalidates
+// what it invalidates (DESIGN.md section 1 has the table, with the work vector every entry borrows).
+struct Held {
+    bool have_blocks = false, have_vectors = false;
+    bool have_rhs = false;                // rhs holds g = -grad of the staged vectors
+    bool assembled = false, factored = false;
+    bool cond_active = false;             // the current assembled / factored matrix is the condensed one
+    bool forward_fused = false;           // the last factor_all ran a forward substitution under itself
+    bool forward_pending = false;         // v1 = the staged right-hand side, v0 (vc: condensed) = its forward pass: solve(rhs = NULL) starts at the diagonal
+    bool fwd_done = false;                // the same for the distributed driver: its vloc holds the forward pass.  A field of its own: it
+                                          // outlives a step_dist whose factorisation came back nonfinite, and only what writes vloc clears it
+    bool have_direction = false;          // v2 holds the last sign-flipped direction (for step_lengths)
+    bool ray_valid = false;               // ray_buf holds the block products of the direction ray_for (merit_ray)
+    bool zeros_clean = false;             // the last writer of the places K1 need not store again (keep_zeros) was a full assembly
+    bool storage_exported = false;        // kkt_storage() handed the pointer out: a holder may write into those zeros at any time,
+                                          // so every assembly is a full one until set_option("keep_zeros") is called again
+    bool rc_warm_valid[2] = {false, false};   // rc_warm[k] holds the vector the last adaptive condition estimate ended with
+    bool ev_assemble_valid = false, ev_solve_valid = false;   // events 2-3 / 4-5 have been recorded (last_timings)
+
+    enum : unsigned { V0 = 1, V1 = 2, V2 = 4, VLOC = 8 };
+    // Somebody writes work vectors of the handle.  v0 / v1 carry a pending fused forward pass and its right-hand side, vloc the
+    // distributed one; v2 is the last direction, which step_lengths, merit_info and the kept products of merit_ray refer to.
+    // (v3, vc, vt, partial carry nothing between calls -- except vc with the condensed factor, which goes with v0.)
+    void borrowed(unsigned v) {
+        if (v & (V0 | V1)) forward_pending = false;
+        if (v & VLOC) fwd_done = false;
+        if (v & V2) { have_direction = false; ray_valid = false; }
+    }
+    // Another matrix: the kept products of merit_ray belong to the old blocks and the condition estimate starts cold.
+    // stage_blocks_owned has never said so (forget = false): on a single-rank handle merit_ray / rcond after it see the old ones.
+    void blocks_staged(bool forget = true) {
+        have_blocks = true;
+        if (forget) { ray_valid = false; rc_warm_cold(); }
+    }
+    // g = -grad belongs to the vectors staged before, and so does the merit function along the kept ray.
+    void vectors_staged() { have_vectors = true; have_rhs = false; ray_valid = false; }
+    // rhs is rewritten: a forward pass that ran on the old one is worthless.
+    void residual_formed() { have_rhs = true; forward_pending = false; }
+    // Assembly, in two halves around its launches.  The condensed system lives in the same storage with another layout, so the
+    // zeros are gone as soon as it starts.
+    void assemble_begun(bool condensed) { if (condensed) zeros_clean = false; else cond_active = false; }
+    // The zeros of a full single-rank assembly survive a factorisation of finite numbers (every update that reaches them adds an
+    // exact zero); whatever else may write into the storage clears the flag.  The storage holds a matrix, no factor.
+    void assemble_done(bool condensed, bool single_rank) {
+        if (condensed) cond_active = true; else zeros_clean = single_rank;
+        assembled = true; factored = false; forward_pending = false;
+    }
+    void assemble_timed() { ev_assemble_valid = true; }
+    // The owner of the storage wrote a matrix into it (the L-BFGS Gram system): full layout, no residual of this handle's.
+    void matrix_written() { assembled = true; factored = false; have_rhs = false; forward_pending = false; cond_active = false; }
+    void step_batched_begun(bool condensed) { cond_active = condensed; }
+    void step_batched_enqueued() { have_rhs = true; ev_assemble_valid = true; }   // rhs = g of every problem (backward_error_batched reads it)
+    // Factorisation.  Per-panel phases (the caller or the distributed driver drives the panels): no promise about what gets written.
+    void panel_phases_begun() { zeros_clean = false; }
+    void factor_begun() { forward_fused = false; }
+    void forward_fused_under_factor() { forward_fused = true; }
+    void forward_done_dist() { fwd_done = true; }
+    void factor_enqueued() { assembled = false; }                  // the storage now holds the factor
+    void factor_invalid() { zeros_clean = false; }                 // a chain poll timed out: anything may be in the storage
+    void factor_read_back(bool nonfinite) { factored = true; if (nonfinite) zeros_clean = false; }
+    void factor_timed_out() { factored = false; }                  // distributed step: the device never completed it
+    // The factorisation call returns rc.  Failed: the zeros are no longer clean.  keep_forward: a fused forward pass stays
+    // pending for solve(rhs = NULL) -- factor() keeps it, after a nonfinite factorisation too; step() consumes it at once.
+    void factor_returned(int rc, bool keep_forward) {
+        if (rc) zeros_clean = false;
+        forward_pending = (rc == 0 || rc == PYIPM_E_NONFINITE) && keep_forward && forward_fused;
+    }
+    // v2 = dz with the reference's sign convention (or not: flip = 0 with multipliers).  The kept products of merit_ray are the OLD
+    // direction's -- solve_dist has never said so (ray_survives): on a single-rank handle merit_ray(dz = NULL) after it reuses them.
+    void solved(bool direction, bool ray_survives) {
+        ev_solve_valid = true; have_direction = direction;
+        if (!ray_survives) ray_valid = false;
+    }
+    void ray_formed() { ray_valid = true; }
+    void ray_dropped() { ray_valid = false; }
+    void rc_warm_cold() { rc_warm_valid[0] = rc_warm_valid[1] = false; }      // another or a shifted matrix, or a new buffer
+    void rc_warm_kept(int phase, bool good) { rc_warm_valid[phase] = good; }
+    // A holder of the pointer may write through it, now or later.
+    void storage_handed_out() { zeros_clean = false; storage_exported = true; }
+    void keep_zeros_set() { zeros_clean = false; storage_exported = false; }
+    // An exception unwound out of the middle of a schedule: the half-done state is dropped.
+    void quiesced() { factored = false; forward_pending = false; forward_fused = false; zeros_clean = false; }
+};
+
 struct DistState;                                       // dist_impl.hpp
 struct DistDelete { void operator()(DistState*) const; };   // (pyipm_dist.hip: the type is complete there)
 
@@ -145,8 +230,6 @@ struct Ctx {
     Stream fwd;                           // fused forward-substitution stream
     std::vector<Event> ev_done;           // panel q factored
     int fuse_forward = 1;
-    bool forward_fused = false;
-    bool forward_pending = false;         // factor() already forward-substituted the pending residual into v0
     int lookahead = 2;                    // 0 none, 1 one group (two groups on a dedicated stream measured no faster: removed), 2 = 1 + the
                                           // first group's update panel by panel under its own chain where the slack block follows it (factor_all)
     Event ev_early;
@@ -168,9 +251,6 @@ struct Ctx {
     std::vector<Event> ev_band;           // panel (by offset in its group): its tiles are inverted and applied inside the diagonal block
     Event ev_join, ev_main, ev_split, ev_sfast;
     int keep_zeros = 1;                   // K1 does not store again the zeros nothing can fill in (k_assemble, zeros_in_place)
-    bool zeros_clean = false;             // ... which requires that the last writer of those places was a full assembly
-    bool storage_exported = false;        // kkt_storage() handed the pointer out: a holder may write into those zeros at any time,
-                                          // so every assembly is a full one until set_option("keep_zeros") is called again (ADVICE r2)
     int tile_step = 1;                    // stepped panel schedule (kernels_panel.hpp): one launch per diagonal tile (the rows inside the
                                           // diagonal block), one for the rows below it; panels of at most 4 tiles; same bits
     int sweep_max_blocks = 0;             // test hook: cap on the workgroups of the one-launch sweeps (0 = as many as the GPU holds)
@@ -200,7 +280,6 @@ struct Ctx {
     int condensed = 0;                    // requested by set_option("condensed", 1); single-rank, mi > 0
     int cond_min_refine = 0;              // refinement steps against the FULL blocks every condensed solve gets at least
                                           // (dli = Sigma ds - b_s amplifies the rounding of ds by Sigma <= cond_sigma_max)
-    bool cond_active = false;             // the current assembled / factored matrix is the condensed one
     Geo gc;                               // geometry of the condensed system: (n, me + cond_na, 0), set by assemble
     double cond_sigma_max = 1.0e4;        // inequalities with Sigma above this stay explicit rows (-1/Sigma diagonal)
     int64_t cond_na = 0;                  // |A| of the current condensed system
@@ -230,11 +309,10 @@ struct Ctx {
     DevBuf<double> stg_d2L, stg_Je, stg_Ji;        // staging of host blocks (allocated on first use)
     double mu = 0.2, eps = 2.220446049250313e-16;
     double delta = 0.0, delta_c = 0.0;
-    bool have_blocks = false, have_vectors = false, have_rhs = false, assembled = false, factored = false;
-    bool have_direction = false;          // v2 holds the last sign-flipped direction (for step_lengths)
+    Held held;                            // what of all this is valid right now
     // merit-function pieces (kernels_merit.hpp): scratch, the products of the current direction with the blocks (Q dx | Je' dx | Ji' dx)
     DevBuf<double> merit_buf, ray_buf;
-    const double* ray_for = nullptr; bool ray_valid = false, ray_quad_given = false;
+    const double* ray_for = nullptr; bool ray_quad_given = false;
     // last solve (pyipm_newton_solve_info): refinement steps taken, |b - Hc x|/|b| before the first and after the last
     // one (-1 = not measured: a fixed-count solve), 1 = the adaptive loop met its target
     int info_steps = 0, info_converged = 0;
@@ -242,7 +320,6 @@ struct Ctx {
     int rcond_its[2] = {0, 0};            // power / inverse iterations the last pyipm_newton_rcond took (solve_info reports them)
     DevBuf<double> rc_warm_buf;           // warm start of the adaptive condition estimate: the vectors its power / inverse
     double* rc_warm[2] = {nullptr, nullptr};   // iterations ended with last time (the next estimate starts from them): the halves of rc_warm_buf
-    bool rc_warm_valid[2] = {false, false};
     double refine_target = 1.0e-14;       // adaptive refinement stops at this backward error ...
     int refine_max = 8;                   // ... or after this many steps, or when a step gains less than 4x
     // options
@@ -283,7 +360,6 @@ struct Ctx {
     double inst_ms[2] = {0, 0}, inst_flops[2] = {0, 0}, inst_area[2] = {0, 0}, inst_cbytes[2] = {0, 0}; int64_t inst_n[2] = {0, 0};   // [0]: 128 x 128 tiles, [1]: 128 x 256
     Event ev[8];                          // timing events
     Event ev_prov[4]; bool prov_valid[2] = {false, false}; double prov_bytes[2] = {0.0, 0.0};   // provider products
-    bool ev_assemble_valid = false, ev_solve_valid = false;
     double setup_lists_ms = 0.0; int setup_lists_n = 0;     // host time spent building tile lists (one-time per geometry; PYIPM_SETUP_TRACE)
     int debug_fault = 0;                  // test hook: 1 / 2 = the next tile-list build throws std::bad_alloc / std::runtime_error;
                                           // 3 = the message of the middle panel of the next distributed factorisation stalls (dist_impl.hpp)

@@ -87,7 +87,6 @@ struct DistState {
     Stream side, cs;                                   // owner's factor + pack stream (high priority); collectives
     Stream fws;                                        // the forward substitution that trails the factorisation (step_dist)
     Event ev_fw;                                       // (every event here but the profile pool has timing disabled)
-    bool fwd_done = false;                             // vloc holds the forward pass of the staged right-hand side
     Event ev_fact[2], ev_msg[2], ev_free[2], ev_head, ev_join;
     Event ev_hop[2];                                   // a collective asked for on another stream is run on `cs` between these
     DevBuf<double> msg[2];                             // panel messages by parity (the largest of the geometry + W doubles of slack: sag_bcast)
@@ -467,7 +466,7 @@ int bounded_wait(Ctx* ctx, DistState* D, hipStream_t main, int64_t np) {
                      "a collective a peer never joined?", bound, ctx->g.rank, ctx->g.world, m, u, c, (long long)np);
             ctx->err = buf;
             D->broken = true;
-            ctx->factored = false;
+            ctx->held.factor_timed_out();
             return PYIPM_E_COMM;
         }
         if (el > 0.2) { struct timespec ts = {0, 200000}; nanosleep(&ts, nullptr); }       // (a healthy step is over long before)
@@ -526,7 +525,7 @@ int update_range(Ctx* ctx, int64_t p, int64_t first, int64_t count, hipStream_t 
 // every rank runs its share of the bulk update of p on the main stream meanwhile.
 // fwd_b != NULL (step_dist): the forward substitution of that right-hand side (replicated, Npad) trails the factorisation on
 // its own stream -- y_p needs nothing but panel p factored on its owner and the segment sum of the panels before it -- and
-// the solve that follows starts at the backward sweep (D->fwd_done).  The segment sums go through the collective stream
+// the solve that follows starts at the backward sweep (Held::fwd_done).  The segment sums go through the collective stream
 // like every other exchange, at the same place of the loop on every rank.
 int factor_dist_geo(Ctx* ctx, pyipm_factor_stats* stats, const double* fwd_b);
 
@@ -535,8 +534,8 @@ int factor_dist_geo(Ctx* ctx, pyipm_factor_stats* stats, const double* fwd_b);
 // single-rank path (one positive and one negative eigenvalue each).  The forward substitution does not trail this
 // factorisation (its right-hand side is the reduced one: solve_dist reduces, sweeps and expands).
 int factor_dist(Ctx* ctx, pyipm_factor_stats* stats, const double* fwd_b = nullptr) {
-    if (!ctx->assembled) { ctx->err = "factor_dist: assemble first"; return PYIPM_E_BADARG; }
-    if (!ctx->cond_active) return factor_dist_geo(ctx, stats, fwd_b);
+    if (!ctx->held.assembled) { ctx->err = "factor_dist: assemble first"; return PYIPM_E_BADARG; }
+    if (!ctx->held.cond_active) return factor_dist_geo(ctx, stats, fwd_b);
     pyipm_factor_stats local; if (!stats) stats = &local;
     int rc;
     { GeoSwap sw(ctx, ctx->gc); rc = factor_dist_geo(ctx, stats, nullptr); }
@@ -548,7 +547,7 @@ int factor_dist_geo(Ctx* ctx, pyipm_factor_stats* stats, const double* fwd_b) {
     const Geo& g = ctx->g;
     DistState* D; int rc = dist_state(ctx, &D); if (rc) return rc;
     ctx->sched.clear();                                 // per-panel mode: uniform group map, dense panels
-    ctx->zeros_clean = false;
+    ctx->held.panel_phases_begun();
     rc = factor_begin(ctx); if (rc) return rc;
     D->used = 0; D->spans.clear(); D->bytes_sent = 0; D->n_msgs = 0;
     for (int k = 0; k < 12; ++k) D->wire[k] = 0.0;
@@ -601,7 +600,7 @@ int factor_dist_geo(Ctx* ctx, pyipm_factor_stats* stats, const double* fwd_b) {
     }
     bool sfree_rec[2][2] = {{false, false}, {false, false}};
     bool pre_rec = false;
-    D->fwd_done = false;
+    ctx->held.borrowed(Held::VLOC);
     if (D->broken) { ctx->err = "an earlier distributed step timed out: this handle's streams may hold collectives that never complete -- destroy it"; return PYIPM_E_COMM; }
     for (int k = 0; k < 3; ++k) D->prog_host[k] = 0u;
     if (fwd_b) {
@@ -906,14 +905,14 @@ int factor_dist_geo(Ctx* ctx, pyipm_factor_stats* stats, const double* fwd_b) {
     for (int64_t p = fwd_next; p < np; ++p) { rc = fwd_step(p); if (rc) return rc; }
     if (fwd_b) {
         DIST_HIP(hipEventRecord(D->ev_fw, D->fws)); DIST_HIP(hipStreamWaitEvent(main, D->ev_fw, 0));
-        D->fwd_done = true;
+        ctx->held.forward_done_dist();
     }
     // join the helper streams (the last panel may have been factored on the side stream; messages in flight)
     DIST_HIP(hipEventRecord(D->ev_join, side)); DIST_HIP(hipStreamWaitEvent(main, D->ev_join, 0));
     DIST_HIP(hipEventRecord(D->ev_head, cs));   DIST_HIP(hipStreamWaitEvent(main, D->ev_head, 0));
     if (ctx->rest) { DIST_HIP(hipEventRecord(D->ev_join, ctx->rest)); DIST_HIP(hipStreamWaitEvent(main, D->ev_join, 0)); }
     DIST_HIP(hipEventRecord(ctx->ev[1], main));
-    ctx->assembled = false;
+    ctx->held.factor_enqueued();
     rc = bounded_wait(ctx, D, main, np); if (rc) return rc;
     pyipm_factor_stats loc;
     rc = factor_end(ctx, &loc);
@@ -982,15 +981,16 @@ int solve_dist_once(Ctx* ctx, DistState* D, const double* b, double* x, bool for
 }
 
 // y = Hc v over the ranks (v, y replicated Npad vectors)
-int matvec_dist(Ctx* ctx, DistState* D, const double* v, double* y) {
+int matvec_dist(Ctx* ctx, const double* v, double* y) {
     int rc = kkt_matvec_dev(ctx, v, y); if (rc) return rc;
-    return ex_allreduce(ctx, D, y, (size_t)ctx->g.Npad, 0, ctx->stream);
+    return ex_allreduce(ctx, ctx->dist.get(), y, (size_t)ctx->g.Npad, 0, ctx->stream);
 }
 
 // x := Hc^{-1} b for whichever system was factored: with the condensed factor reduce the right-hand side (every rank, from
 // the full blocks: replicated), run the distributed sweeps on the condensed geometry, expand.
-int solve_dist_any(Ctx* ctx, DistState* D, const double* b, double* x, bool forward_done) {
-    if (!ctx->cond_active) return solve_dist_once(ctx, D, b, x, forward_done);
+int solve_dist_any(Ctx* ctx, const double* b, double* x, bool forward_done) {
+    DistState* D = ctx->dist.get();
+    if (!ctx->held.cond_active) return solve_dist_once(ctx, D, b, x, forward_done);
     const Geo& g = ctx->g;
     int rc = cond_reduce(ctx, b, ctx->vc); if (rc) return rc;
     { GeoSwap sw(ctx, ctx->gc); rc = solve_dist_once(ctx, D, ctx->vc, ctx->vc, false); }
@@ -999,45 +999,19 @@ int solve_dist_any(Ctx* ctx, DistState* D, const double* b, double* x, bool forw
     return cond_expand(ctx, ctx->vc, x);             // (x holds the right-hand side on entry: its s / lambda_i parts are read)
 }
 
+// (solve_dist has never reset the kept products of merit_ray: Held::solved)
+const SolveOps kDistOps = {solve_dist_any, matvec_dist, true};
+
 int solve_dist(Ctx* ctx, const double* rhs, double* dz, int flip, int refine, int memkind) {
-    const Geo& g = ctx->g;
     DistState* D; int rc = dist_state(ctx, &D); if (rc) return rc;
-    if (!ctx->factored) { ctx->err = "solve_dist: factor first"; return PYIPM_E_BADARG; }
+    rc = need_factor(ctx, "solve_dist"); if (rc) return rc;
     if (!dz) { ctx->err = "solve_dist: null output"; return PYIPM_E_BADARG; }
-    hipStream_t st = ctx->stream;
-    DIST_HIP(hipEventRecord(ctx->ev[4], st));
-    ctx->forward_pending = false;
+    DIST_HIP(hipEventRecord(ctx->ev[4], ctx->stream));
+    ctx->held.borrowed(Held::V0 | Held::V1);
     rc = solve_prepare(ctx, rhs, memkind); if (rc) return rc;          // v1 = v0 = b (replicated; pad zero)
-    const bool fwd_done = D->fwd_done && rhs == nullptr;                // the staged right-hand side went forward under the factorisation
-    D->fwd_done = false;
-    rc = solve_dist_any(ctx, D, ctx->v1, ctx->v0, fwd_done); if (rc) return rc;
-    const size_t vbytes = (size_t)g.Npad * sizeof(double);
-    rc = refine_loop(ctx, refine,
-        [&]() -> int {                                          // v2 = b - Hc v0 (the ranks' shares summed inside the product)
-            int r_ = matvec_dist(ctx, D, ctx->v0, ctx->v2); if (r_) return r_;
-            return launch_axpby(ctx, st, ctx->v2, ctx->v1, ctx->v2, 1.0, -1.0, g.Npad);
-        },
-        [&](double* berr) -> int {
-            double ss[2];
-            { int r_ = launch_sumsq2(ctx, st, ctx->partial, ctx->v2, ctx->v1, g.N); if (r_) return r_; }
-            DIST_HIP(hipMemcpyAsync(ss, ctx->partial, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-            DIST_HIP(hipStreamSynchronize(st));
-            *berr = ss[1] > 0.0 ? sqrt(ss[0] / ss[1]) : sqrt(ss[0]);             // identical on every rank: replicated vectors
-            return 0;
-        },
-        [&]() -> int { DIST_HIP(hipMemcpyAsync(ctx->v3, ctx->v0, vbytes, hipMemcpyDeviceToDevice, st)); return 0; },
-        [&]() -> int { DIST_HIP(hipMemcpyAsync(ctx->v0, ctx->v3, vbytes, hipMemcpyDeviceToDevice, st)); return 0; },
-        [&]() -> int {                                          // v0 += Hc^{-1} v2 (vc is the condensed solve's own vector)
-            int r_ = solve_dist_any(ctx, D, ctx->v2, ctx->v2, false); if (r_) return r_;
-            return launch_axpby(ctx, st, ctx->v0, ctx->v0, ctx->v2, 1.0, 1.0, g.Npad);
-        });
-    if (rc) return rc;
-    { int r_ = launch_copy_flip(ctx, st, ctx->v2, ctx->v0, (flip && (g.me + g.mi) > 0) ? 1 : 0); if (r_) return r_; }
-    DIST_HIP(hipEventRecord(ctx->ev[5], st));
-    rc = copy_out(ctx, dz, ctx->v2, g.N, memkind); if (rc) return rc;
-    ctx->ev_solve_valid = true;
-    ctx->have_direction = (flip != 0) || (g.me + g.mi == 0);
-    return 0;
+    const bool forward_done = ctx->held.fwd_done && rhs == nullptr;     // the staged right-hand side went forward under the factorisation
+    ctx->held.borrowed(Held::VLOC);                                     // consumed (or overwritten) either way
+    return solve_finish(ctx, kDistOps, dz, flip, refine, memkind, forward_done);
 }
 
 // g = -grad, complete on every rank (the ranks' shares summed)
@@ -1098,10 +1072,7 @@ int pyipm_newton_rccl_library(const char* path) try {
 } PYIPM_CATCH_NOH
 
 int pyipm_newton_set_exchange(pyipm_newton_ctx* h, pyipm_bcast_fn bcast, pyipm_allreduce_fn allreduce, void* user) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("set_exchange", G_SINGLE | G_DEVICE)
     DistState* D; int rc = dist_state(ctx, &D); if (rc) return rc;
     D->bcast = bcast; D->allreduce = allreduce; D->user = user;
     return PYIPM_OK;
@@ -1109,10 +1080,7 @@ int pyipm_newton_set_exchange(pyipm_newton_ctx* h, pyipm_bcast_fn bcast, pyipm_a
 
 int pyipm_newton_set_exchange_p2p(pyipm_newton_ctx* h, pyipm_send_fn send, pyipm_recv_fn recv, pyipm_allgather_fn allgather,
                                   int serialize) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("set_exchange_p2p", G_SINGLE | G_DEVICE)
     DistState* D; int rc = dist_state(ctx, &D); if (rc) return rc;
     D->send = send; D->recv = recv; D->allgather = allgather; D->serialize = serialize != 0;
     D->sag = D->sag_ok = 0;                                          // (whatever an earlier self-test decided belonged to another transport)
@@ -1120,10 +1088,7 @@ int pyipm_newton_set_exchange_p2p(pyipm_newton_ctx* h, pyipm_send_fn send, pyipm
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_exchange_selftest(pyipm_newton_ctx* h) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("exchange_selftest", G_SINGLE | G_DEVICE)
     DistState* D; int rc = dist_state(ctx, &D); if (rc) return rc;
     if (ctx->g.world > 1 && !D->comm && !(D->bcast && D->allreduce)) { ctx->err = "exchange_selftest: no exchange installed"; return PYIPM_E_COMM; }
     // (the second communicator of the slice messages is comm_init's business -- option dist_comm2; this entry only tests what is installed)
@@ -1131,8 +1096,8 @@ int pyipm_newton_exchange_selftest(pyipm_newton_ctx* h) try {
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_dist_wire(pyipm_newton_ctx* h, double out[12]) try {
-    if (check_ctx(h) || !out) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
+    PYIPM_ENTER("dist_wire", 0)
+    if (!out) return PYIPM_E_BADARG;
     DistState* D; int rc = dist_state(ctx, &D); if (rc) return rc;
     for (int k = 0; k < 12; ++k) out[k] = D->wire[k];
     return PYIPM_OK;
@@ -1149,10 +1114,8 @@ int pyipm_newton_comm_unique_id(void* id128) try {
 } PYIPM_CATCH_NOH
 
 int pyipm_newton_comm_init(pyipm_newton_ctx* h, const void* id128) try {
-    if (check_ctx(h) || !id128) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("comm_init", G_SINGLE | G_DEVICE)
+    if (!id128) return PYIPM_E_BADARG;
     DistState* D; int rc = dist_state(ctx, &D); if (rc) return rc;
     if (rccl_load(&ctx->err)) return PYIPM_E_COMM;
     if (D->comm) { g_rccl.CommDestroy(D->comm); D->comm = nullptr; }
@@ -1164,8 +1127,7 @@ int pyipm_newton_comm_init(pyipm_newton_ctx* h, const void* id128) try {
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_comm_ranks(pyipm_newton_ctx* h) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
+    PYIPM_ENTER("comm_ranks", 0)
     if (!ctx->dist || !ctx->dist->comm) return 0;
     if (!g_rccl.CommCount) { ctx->err = "RCCL library lacks ncclCommCount"; return PYIPM_E_COMM; }
     int n = 0;
@@ -1175,14 +1137,13 @@ int pyipm_newton_comm_ranks(pyipm_newton_ctx* h) try {
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_comm_bcast_mode(pyipm_newton_ctx* h) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
+    PYIPM_ENTER("comm_bcast_mode", 0)
     return (ctx->dist && ctx->dist->sag && tr_has_p2p(ctx->dist.get())) ? 1 : 0;
 } PYIPM_CATCH_H(h)
 
 int64_t pyipm_newton_owned_rows(pyipm_newton_ctx* h, int64_t* rows) try {
-    if (check_ctx(h)) return -1;
-    const Geo& g = C(h)->g;
+    Ctx* ctx; if (enter(h, "owned_rows", 0, &ctx)) return -1;
+    const Geo& g = ctx->g;
     const RowMap rm = make_rowmap(g, 1);
     if (rows) for (int64_t r = 0; r < rm.nloc; ++r) rows[r] = rm.glob(r);
     return rm.nloc;
@@ -1190,78 +1151,56 @@ int64_t pyipm_newton_owned_rows(pyipm_newton_ctx* h, int64_t* rows) try {
 
 int pyipm_newton_stage_blocks_owned(pyipm_newton_ctx* h, const double* d2L_rows, int64_t ld_d2L, const double* Je_rows,
                                     int64_t ld_Je, const double* Ji_rows, int64_t ld_Ji, int memkind) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); const Geo& g = ctx->g;
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("stage_blocks_owned", G_SINGLE | G_DEVICE) const Geo& g = ctx->g;
     const int64_t nl = make_rowmap(g, 1).nloc;
     int rc;
     rc = stage_block(ctx, d2L_rows, nl, g.n, ld_d2L, memkind, ctx->stg_d2L, &ctx->d2L, &ctx->ld_d2L); if (rc) return rc;
     rc = stage_block(ctx, Je_rows, g.me ? nl : 0, g.me, ld_Je, memkind, ctx->stg_Je, &ctx->Je, &ctx->ld_Je); if (rc) return rc;
     rc = stage_block(ctx, Ji_rows, g.mi ? nl : 0, g.mi, ld_Ji, memkind, ctx->stg_Ji, &ctx->Ji, &ctx->ld_Ji); if (rc) return rc;
     ctx->sharded = g.world > 1 ? 1 : 0;
-    ctx->have_blocks = true;
+    ctx->held.blocks_staged(false);
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_residual_dist(pyipm_newton_ctx* h, double* g_out, int memkind) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("residual_dist", G_SINGLE | G_DEVICE)
     int rc = residual_dist(ctx); if (rc) return rc;
     return copy_out(ctx, g_out, ctx->rhs, ctx->g.N, memkind);
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_factor_dist(pyipm_newton_ctx* h, pyipm_factor_stats* stats) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("factor_dist", G_SINGLE | G_DEVICE)
     return factor_dist(ctx, stats);
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_solve_dist(pyipm_newton_ctx* h, const double* rhs, double* dz, int flip, int refine, int memkind) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("solve_dist", G_SINGLE | G_DEVICE)
     return solve_dist(ctx, rhs, dz, flip, refine, memkind);
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_kkt_matvec_dist(pyipm_newton_ctx* h, const double* v, double* y, int memkind) try {
-    if (check_ctx(h) || !v || !y) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); const Geo& g = ctx->g;
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
-    DistState* D; int rc = dist_state(ctx, &D); if (rc) return rc;
-    ctx->forward_pending = false;
-    { int r_ = launch_fill(ctx, ctx->stream, ctx->v1, 0.0, g.Npad); if (r_) return r_; }
-    rc = put_vec(ctx, ctx->v1, v, g.N, memkind); if (rc) return rc;
-    rc = matvec_dist(ctx, D, ctx->v1, ctx->vc); if (rc) return rc;
-    return copy_out(ctx, y, ctx->vc, g.N, memkind);
+    PYIPM_ENTER("kkt_matvec_dist", G_SINGLE | G_DEVICE)
+    if (!v || !y) return PYIPM_E_BADARG;
+    { DistState* D; int rc = dist_state(ctx, &D); if (rc) return rc; }
+    return kkt_matvec_io(ctx, kDistOps, v, y, memkind);
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_step_dist(pyipm_newton_ctx* h, double delta, double delta_c, int refine, double* dz,
                            pyipm_factor_stats* stats, int memkind) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("step_dist", G_SINGLE | G_DEVICE)
     if (!dz) { ctx->err = "step_dist: null output"; return PYIPM_E_BADARG; }
     int rc = residual_dist(ctx); if (rc) return rc;
-    rc = pyipm_newton_assemble(h, delta, delta_c); if (rc) return rc;
+    rc = assemble_timed(ctx, delta, delta_c); if (rc) return rc;
     rc = factor_dist(ctx, stats, ctx->fuse_forward ? ctx->rhs : nullptr); if (rc) return rc;
     return solve_dist(ctx, nullptr, dz, 1, refine, memkind);
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_dist_timings(pyipm_newton_ctx* h, double out[8]) try {
-    if (check_ctx(h) || !out) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("dist_timings", G_DEVICE)
+    if (!out) return PYIPM_E_BADARG;
     DistState* D; int rc = dist_state(ctx, &D); if (rc) return rc;
     PYIPM_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->ev_solve_valid) { float ms = 0.f; PYIPM_HIP(hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5])); D->t_solve = ms; }
+    if (ctx->held.ev_solve_valid) { float ms = 0.f; PYIPM_HIP(hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5])); D->t_solve = ms; }
     out[0] = D->t_factor; out[1] = D->t_chain; out[2] = D->t_pack; out[3] = D->t_bcast; out[4] = D->t_unpack;
     out[5] = D->t_solve; out[6] = (double)D->bytes_sent; out[7] = (double)D->n_msgs;
     return PYIPM_OK;

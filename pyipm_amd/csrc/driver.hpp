@@ -1,6 +1,6 @@
 // driver.hpp -- what the translation units of the library share (round 6: pyipm_newton.hip = the single-rank driver and the
 // C-ABI of include/pyipm_newton.h, pyipm_dist.hip = the distributed driver, pyipm_lbfgs.hip = include/pyipm_lbfgs.h).  Host
-// functions only: a kernel is launched from the unit that defines it (launch_* wrappers below).
+// functions only: a kernel is launched from the unit that defines it (the two launch_* wrappers below).
 #pragma once
 #include "ctx.hpp"
 #include <algorithm>
@@ -19,15 +19,39 @@ inline void quiesce_noexcept(Ctx* c) noexcept {
         if (c->rest) hipStreamSynchronize(c->rest);
         if (c->dist) hipDeviceSynchronize();            // the distributed driver's own streams
         if (c->stream) hipStreamSynchronize(c->stream); else hipDeviceSynchronize();
-        c->factored = false; c->forward_pending = false; c->forward_fused = false; c->zeros_clean = false;
+        c->held.quiesced();
     } catch (...) {}
 }
 #define PYIPM_SETERR_NEWTON(msg_) (quiesce_noexcept(reinterpret_cast<Ctx*>(h)), set_err_noexcept(reinterpret_cast<Ctx*>(h), (msg_)))
 #define PYIPM_CATCH_H(h_)  PYIPM_CATCH_CORE(PYIPM_SETERR_NEWTON, PYIPM_E_NOMEM, PYIPM_E_HIP)
 
 
-inline int check_ctx(pyipm_newton_ctx* h) { return h ? 0 : PYIPM_E_BADARG; }
-inline Ctx* C(pyipm_newton_ctx* h) { return reinterpret_cast<Ctx*>(h); }
+// The entry guard: every extern "C" entry that takes a handle starts with it.  `need` says what the entry requires of the handle;
+// the checks run in the order of the bits, the entry's own argument checks follow, and the texts of the refusals live here.
+enum : unsigned {
+    G_SINGLE = 1,        // refuses a batched handle
+    G_BATCHED = 2,       // requires one
+    G_FACTOR_ABLE = 4,   // not a provider-only handle
+    G_ONE_RANK = 8,      // world == 1
+    G_FACTORED = 16,     // a factor is in the storage
+    G_DEVICE = 32,       // makes the handle's device current (last: a refusal costs no HIP call)
+};
+inline int need_factor(Ctx* ctx, const char* name) {
+    if (ctx->held.factored) return 0;
+    ctx->err = std::string(name) + ": factor first"; return PYIPM_E_BADARG;
+}
+inline int enter(pyipm_newton_ctx* h, const char* name, unsigned need, Ctx** out) {
+    Ctx* ctx = *out = reinterpret_cast<Ctx*>(h);
+    if (!ctx) return PYIPM_E_BADARG;
+    if ((need & G_SINGLE) && ctx->batched) { ctx->err = "batched handle: only stage_*_batched / stage_vectors / step_batched apply"; return PYIPM_E_BADARG; }
+    if ((need & G_BATCHED) && !ctx->batched) { ctx->err = std::string(name) + ": not a batched handle"; return PYIPM_E_BADARG; }
+    if ((need & G_FACTOR_ABLE) && ctx->provider_only) { ctx->err = std::string(name) + ": a provider-only handle has no factor"; return PYIPM_E_BADARG; }
+    if ((need & G_ONE_RANK) && ctx->g.world != 1) { ctx->err = std::string(name) + "(): single-rank entry point"; return PYIPM_E_BADARG; }
+    if (need & G_FACTORED) { int rc = need_factor(ctx, name); if (rc) return rc; }
+    if (need & G_DEVICE) PYIPM_HIP(hipSetDevice(ctx->device));
+    return 0;
+}
+#define PYIPM_ENTER(name_, need_)  Ctx* ctx; { const int rc_ = enter(h, name_, need_, &ctx); if (rc_) return rc_; }
 inline dim3 grid1(int64_t n, int b = 256) { return dim3((unsigned)((n + b - 1) / b)); }
 // -W columns of panel p: the buffer of its group (parity-alternating) + its offset inside the group
 inline double* wbuf(Ctx* ctx, int64_t p) {
@@ -35,7 +59,6 @@ inline double* wbuf(Ctx* ctx, int64_t p) {
     return ctx->Wbuf + ((ctx->sched.group_of(p, G) % 3) * G + ctx->sched.offset_of(p, G)) * ctx->g.Npad * (int64_t)ctx->g.nb;
 }
 
-int single_only(Ctx* ctx);
 int put_vec(Ctx* ctx, double* dst, const double* src, size_t count, int memkind);
 int copy_out(Ctx* ctx, double* dst, const double* src_dev, size_t count, int memkind);
 int stage_block(Ctx* ctx, const double* src, int64_t rows, int64_t cols, int64_t ld, int memkind,
@@ -96,17 +119,23 @@ void dist_sync(Ctx* ctx);              // timed out aborted, or the synchronisat
 void dist_comm_destroy(Ctx* ctx);      // the communicators destroyed.  The state itself goes with the handle (Ctx::dist).
 int dist_set_option(Ctx* ctx, const char* name, double value, bool* handled);
 // kernels of pyipm_newton.hip on behalf of the other units
-int launch_axpby(Ctx* ctx, hipStream_t st, double* out, const double* a, const double* b, double alpha, double beta, int64_t n);
-int launch_fill(Ctx* ctx, hipStream_t st, double* out, double v, int64_t n);
 int launch_mask_owned(Ctx* ctx, hipStream_t st, double* v, const double* b);
-int launch_copy_flip(Ctx* ctx, hipStream_t st, double* out, const double* in, int flip);
-int launch_sumsq2(Ctx* ctx, hipStream_t st, double* out, const double* a, const double* b, int64_t n);
 int launch_inpanel_update(Ctx* ctx, hipStream_t st, dim3 grid, double* Cm, int64_t ldc, int64_t ccol, const double* Lop, int64_t ldl,
                           const double* Wop, int64_t ldw, int64_t cglob, int K, int64_t row_begin, int64_t row_end,
                           int64_t a0, int64_t a1, int64_t b0, int64_t b1, int prio);
 
+// The two operations a solve is written in; the single-rank and the distributed driver each bring theirs (pyipm_newton.hip).
+struct SolveOps {
+    int (*solve)(Ctx*, const double* b, double* x, bool forward_done);   // x := Hc^{-1} b.  x holds a copy of b on entry (b may BE x) -- or, with
+                                                                         // forward_done, the driver's own vector holds b's forward pass already
+    int (*matvec)(Ctx*, const double* v, double* y);                     // y := Hc v, from the blocks
+    bool ray_survives;                                                   // Held::solved
+};
+int assemble_timed(Ctx* ctx, double delta, double delta_c);
+int solve_finish(Ctx* ctx, const SolveOps& ops, double* dz, int flip, int refine, int memkind, bool forward_done);
+int kkt_matvec_io(Ctx* ctx, const SolveOps& ops, const double* v, double* y, int memkind);
 
-// Iterative refinement of a solve: the host-side state machine of solve_finish, solve_many and solve_dist.
+// Iterative refinement of a solve: the host-side state machine of solve_finish and solve_many.
 // refine >= 0: that many steps of   r = b - Hc x ;  x += Hc^{-1} r   (Hc applied from the blocks, not from the factor).
 // refine <  0: adaptive -- measure |r|/|b| before every step and stop at refine_target, after refine_max steps or
 //              when a step gains less than 4x; a step that made it worse (or NaN) is taken back.  This is what turns the
@@ -116,7 +145,7 @@ int launch_inpanel_update(Ctx* ctx, hipStream_t st, dim3 grid, double* Cm, int64
 // berr(&e) gives |r|/|b| as a host double (several columns: the worst, NaN if any is);  save() / restore() copy x to / from
 // the spare iterate;  correct() enqueues x += Hc^{-1} r.
 inline int refine_steps(const Ctx* ctx, int refine) {      // a condensed solve gets at least cond_min_refine steps against the FULL blocks
-    return (ctx->cond_active && refine >= 0 && refine < ctx->cond_min_refine) ? ctx->cond_min_refine : refine;
+    return (ctx->held.cond_active && refine >= 0 && refine < ctx->cond_min_refine) ? ctx->cond_min_refine : refine;
 }
 template <class Residual, class Berr, class Save, class Restore, class Correct>
 int refine_loop(Ctx* ctx, int refine, Residual residual, Berr berr_of, Save save, Restore restore, Correct correct) {

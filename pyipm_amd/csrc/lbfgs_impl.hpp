@@ -196,11 +196,10 @@ int lb_factor_G(LbCtx* lb, double zeta, double reg_e, pyipm_factor_stats* st, bo
     hipLaunchKernelGGL(k_lb_gram_diag, grid1(g.Npad), dim3(256), 0, lb->stream, gc->A, g.Npad, lb->p, lb->me, lb->sig,
                        zeta, reg_e);
     LB_KCHECK();
-    gc->assembled = true; gc->factored = false; gc->have_rhs = false; gc->forward_pending = false; gc->cond_active = false;
+    gc->held.matrix_written();
     rc = factor_dispatch(gc, st, false);
     if (rc && rc != PYIPM_E_NONFINITE) { lb->err = gc->err; return rc; }
-    gc->factored = true;
-    return rc;
+    return rc;                               // (0 or nonfinite: factor_end has read it back, Held::factored)
 }
 
 }  // namespace
@@ -242,7 +241,7 @@ int pyipm_lbfgs_create(pyipm_lbfgs_ctx** out, int64_t n, int64_t me, int64_t mi,
         pyipm_newton_ctx* gh = nullptr;
         int rc = pyipm_newton_create(&gh, lb->p, 0, 0, nb, device, 1, 0, nullptr, 0, stream);
         if (rc) return rc;
-        lb->gcx.reset(C(gh));
+        lb->gcx.reset(reinterpret_cast<Ctx*>(gh));
         lb->p_pad = lb->gcx->g.Npad;
     }
     lb->nsplit = lb_nsplit(n, lb->p_pad, lb->rrmax);

@@ -136,7 +136,6 @@ BatchCond batch_cond(Ctx* ctx) {
     return bc;
 }
 
-int single_only(Ctx* ctx) { ctx->err = "batched handle: only stage_*_batched / stage_vectors / step_batched apply"; return PYIPM_E_BADARG; }
 
 // copy `count` doubles from caller memory (host or device) into library device memory
 int put_vec(Ctx* ctx, double* dst, const double* src, size_t count, int memkind) {
@@ -386,7 +385,7 @@ int launch_update128(Ctx* ctx, hipStream_t stream, const double* Lop, int64_t ld
 // no message and no update launch (k_s_panel / k_s_schur_sigma).
 bool panel_in_s(const Ctx* ctx, int64_t p) {
     const Geo& g = ctx->g;
-    if (!ctx->skip_zeros || g.mi == 0 || ctx->sched.active() || ctx->cond_active) return false;
+    if (!ctx->skip_zeros || g.mi == 0 || ctx->sched.active() || ctx->held.cond_active) return false;
     const int64_t c0 = g.panel_c0(p);
     return c0 >= g.n && c0 + g.panel_w(p) <= g.n + g.mi;
 }
@@ -408,7 +407,7 @@ inline void slack_hole(const Geo& g, int64_t* h0, int64_t* h1) {
 void panel_hole(const Ctx* ctx, int64_t p, int64_t* h0, int64_t* h1) {
     const Geo& g = ctx->g;
     *h0 = 0; *h1 = 0;
-    if (!ctx->skip_zeros || g.mi == 0 || ctx->sched.active() || ctx->cond_active) return;
+    if (!ctx->skip_zeros || g.mi == 0 || ctx->sched.active() || ctx->held.cond_active) return;
     if (g.panel_c0(p) + g.panel_w(p) > g.n) return;
     int64_t a, b;
     slack_hole(g, &a, &b);
@@ -1065,7 +1064,7 @@ int factor_end(Ctx* ctx, pyipm_factor_stats* stats) {
     ctx->chain_used = false;
     if (chain_err) {
         PYIPM_HIP(hipMemsetAsync(chain_errw, 0, sizeof(unsigned), ctx->stream));
-        ctx->zeros_clean = false;
+        ctx->held.factor_invalid();
         ctx->err = "tile chain (k_tile_chain): a poll timed out -- a workgroup of the chain did not become resident; this factorisation is invalid "
                    "(set_option(\"tile_chain\", 0) runs one launch per tile)";
         return PYIPM_E_HIP;
@@ -1110,9 +1109,9 @@ int factor_end(Ctx* ctx, pyipm_factor_stats* stats) {
         ctx->t_trailing_union = uni;
         ctx->n_trailing_real = nreal;
     }
-    ctx->factored = true;
+    ctx->held.factor_read_back(z.nonfinite != 0);
     if (stats) *stats = to_stats(z);
-    if (z.nonfinite) { ctx->zeros_clean = false; ctx->err = "NaN/Inf met during factorisation"; return PYIPM_E_NONFINITE; }
+    if (z.nonfinite) { ctx->err = "NaN/Inf met during factorisation"; return PYIPM_E_NONFINITE; }
     return 0;
 }
 
@@ -1120,12 +1119,14 @@ int factor_end(Ctx* ctx, pyipm_factor_stats* stats) {
 // callers use the defaults.
 // A panel wider than wide_sub columns is swept in sub-panels of that width (the in-panel kernels are one workgroup with nt - 1
 // dependent steps: at nb = 1024 the sweeps took 5.9 ms instead of 2.1): the launches of the same matrix at nb = wide_sub.
+static int sub_width(const Ctx* ctx, int pw) {
+    return (ctx->wide_sub >= TB && ctx->wide_sub % TB == 0 && pw > ctx->wide_sub) ? ctx->wide_sub : pw;
+}
 int fwd_panel(Ctx* ctx, int64_t p, double* v, hipStream_t stream, int nrhs, int64_t vstride) {
     if (!stream) stream = ctx->stream;
     const Geo& g = ctx->g;
     const int64_t pc0 = g.panel_c0(p), plc0 = g.local_c0(p);
-    const int pw = (int)g.panel_w(p);
-    const int sw = (ctx->wide_sub >= TB && ctx->wide_sub % TB == 0 && pw > ctx->wide_sub) ? ctx->wide_sub : pw;
+    const int pw = (int)g.panel_w(p), sw = sub_width(ctx, pw);
     for (int off = 0; off < pw; off += sw) {
     const int64_t c0 = pc0 + off, lc0 = plc0 + off;
     const int nbw = pw - off < sw ? pw - off : sw;
@@ -1159,8 +1160,7 @@ int bwd_panel(Ctx* ctx, int64_t p, double* v, int nrhs, int64_t vstride, double*
     const Geo& g = ctx->g;
     if (!part) part = ctx->partial;
     const int64_t pc0 = g.panel_c0(p), plc0 = g.local_c0(p);
-    const int pw = (int)g.panel_w(p);
-    const int sw = (ctx->wide_sub >= TB && ctx->wide_sub % TB == 0 && pw > ctx->wide_sub) ? ctx->wide_sub : pw;
+    const int pw = (int)g.panel_w(p), sw = sub_width(ctx, pw);
     for (int off = ((pw - 1) / sw) * sw; off >= 0; off -= sw) {        // sub-panels of a wide panel, last first (see fwd_panel)
     const int64_t c0 = pc0 + off, lc0 = plc0 + off;
     const int nbw = pw - off < sw ? pw - off : sw;
@@ -1300,7 +1300,7 @@ int cond_expand(Ctx* ctx, const double* vc, double* v) {
 // factor: reduce, solve the (n+me) system, expand.  forward_done: the fused pass already ran (on v, or on
 // ctx->vc for the condensed factor, in which case v still holds the right-hand side).
 int solve_inplace(Ctx* ctx, double* v, bool forward_done) {
-    if (!ctx->cond_active) return solve_plain(ctx, v, forward_done);
+    if (!ctx->held.cond_active) return solve_plain(ctx, v, forward_done);
     int rc;
     if (!forward_done) { rc = cond_reduce(ctx, v, ctx->vc); if (rc) return rc; }
     { GeoSwap sw(ctx, ctx->gc); rc = solve_plain(ctx, ctx->vc, forward_done); }
@@ -1315,12 +1315,9 @@ int solve_inplace(Ctx* ctx, double* v, bool forward_done) {
 int solve_many_plain(Ctx* ctx, double* V, int64_t ldv, int64_t kpad, double* part) {
     const Geo& g = ctx->g;
     const hipStream_t st = ctx->stream;
-    auto sub_width = [&](int pw) {                        // wide_sub as in fwd_panel, and never above MS_SUBW (the in-panel kernels' limit)
-        const int sw = (ctx->wide_sub >= TB && ctx->wide_sub % TB == 0 && pw > ctx->wide_sub) ? ctx->wide_sub : pw;
-        return sw > MS_SUBW ? MS_SUBW : sw;
-    };
+    auto ms_width = [&](int pw) { return std::min(sub_width(ctx, pw), (int)MS_SUBW); };     // (the in-panel kernels' limit)
     for (int64_t p = 0; p < g.npanels; ++p) {
-        const int pw = (int)g.panel_w(p), sw = sub_width(pw);
+        const int pw = (int)g.panel_w(p), sw = ms_width(pw);
         for (int off = 0; off < pw; off += sw) {
             const int64_t c0 = g.panel_c0(p) + off, lc0 = g.local_c0(p) + off;
             const int nbw = pw - off < sw ? pw - off : sw;
@@ -1341,7 +1338,7 @@ int solve_many_plain(Ctx* ctx, double* V, int64_t ldv, int64_t kpad, double* par
                        ctx->Tflag, ctx->block_refine, V, ldv);
     PYIPM_KCHECK();
     for (int64_t p = g.npanels - 1; p >= 0; --p) {
-        const int pw = (int)g.panel_w(p), sw = sub_width(pw);
+        const int pw = (int)g.panel_w(p), sw = ms_width(pw);
         for (int off = ((pw - 1) / sw) * sw; off >= 0; off -= sw) {
             const int64_t c0 = g.panel_c0(p) + off, lc0 = g.local_c0(p) + off;
             const int nbw = pw - off < sw ? pw - off : sw;
@@ -1373,7 +1370,7 @@ int solve_many_plain(Ctx* ctx, double* V, int64_t ldv, int64_t kpad, double* par
 // are O(N) per column apart from the Ji products).
 int solve_many_inplace(Ctx* ctx, double* X, int64_t k, int64_t kpad, double* part, double* Xc) {
     const Geo& g = ctx->g;
-    if (!ctx->cond_active) return solve_many_plain(ctx, X, g.Npad, kpad, part);
+    if (!ctx->held.cond_active) return solve_many_plain(ctx, X, g.Npad, kpad, part);
     const int64_t ldc = ctx->gc.Npad;
     int rc;
     if (kpad > k) PYIPM_HIP(hipMemsetAsync(Xc + k * ldc, 0, (size_t)((kpad - k) * ldc) * sizeof(double), ctx->stream));
@@ -1392,7 +1389,7 @@ int solve_many(Ctx* ctx, int64_t k, const double* rhs, int64_t ld_rhs, double* d
     const hipStream_t st = ctx->stream;
     refine = refine_steps(ctx, refine);                 // (the buffers below depend on it)
     const bool adaptive = refine < 0;
-    const int64_t kpad = (k + MS_KB - 1) / MS_KB * MS_KB, Np = g.Npad, Nc = ctx->cond_active ? ctx->gc.Npad : 0;
+    const int64_t kpad = (k + MS_KB - 1) / MS_KB * MS_KB, Np = g.Npad, Nc = ctx->held.cond_active ? ctx->gc.Npad : 0;
     const size_t col = (size_t)Np * (size_t)kpad;
     const size_t n_part = (size_t)((Np + MS_RCH - 1) / MS_RCH + 1) * (size_t)kpad * (size_t)MS_SUBW;   // partials + their sums
     size_t need = col + (size_t)Nc * (size_t)kpad + n_part;                    // X, Xc, partials
@@ -1490,7 +1487,7 @@ int symv_dev(Ctx* ctx, const double* v, double* y, double delta, const RowMap& r
 int kkt_matvec_dev(Ctx* ctx, const double* v, double* y) {
     const Geo& g = ctx->g;
     const int64_t n = g.n, me = g.me, mi = g.mi;
-    if (!ctx->have_blocks || !ctx->have_vectors) { ctx->err = "matvec: stage blocks and vectors first"; return PYIPM_E_BADARG; }
+    if (!ctx->held.have_blocks || !ctx->held.have_vectors) { ctx->err = "matvec: stage blocks and vectors first"; return PYIPM_E_BADARG; }
     const RowMap rm = make_rowmap(g, ctx->sharded);
     const int64_t nl = rm.nloc;
     if (g.world > 1) { hipLaunchKernelGGL(k_fill, grid1(g.Npad), dim3(256), 0, ctx->stream, y, 0.0, g.Npad); PYIPM_KCHECK(); }
@@ -1535,7 +1532,7 @@ int kkt_matvec_dev(Ctx* ctx, const double* v, double* y) {
 // elsewhere; the distributed driver sums it over the ranks.
 int residual_dev(Ctx* ctx) {
     const Geo& g = ctx->g;
-    if (!ctx->have_blocks || !ctx->have_vectors) { ctx->err = "residual: stage blocks and vectors first"; return PYIPM_E_BADARG; }
+    if (!ctx->held.have_blocks || !ctx->held.have_vectors) { ctx->err = "residual: stage blocks and vectors first"; return PYIPM_E_BADARG; }
     const RowMap rm = make_rowmap(g, ctx->sharded);
     if (g.world > 1) { hipLaunchKernelGGL(k_fill, grid1(g.Npad), dim3(256), 0, ctx->stream, ctx->rhs, 0.0, g.Npad); PYIPM_KCHECK(); }
     if (rm.nloc > 0) {
@@ -1548,8 +1545,7 @@ int residual_dev(Ctx* ctx) {
                            ctx->s, ctx->lda, ctx->mu, ctx->eps);
         PYIPM_KCHECK();
     }
-    ctx->have_rhs = true;
-    ctx->forward_pending = false;
+    ctx->held.residual_formed();
     return 0;
 }
 
@@ -1640,25 +1636,24 @@ void asm_grid(const Geo& g, dim3* grid, int* tri) {
 int assemble_dev(Ctx* ctx, double delta, double delta_c) {
     const Geo& g = ctx->g;
     if (ctx->provider_only) { ctx->err = "a provider-only handle has no KKT storage: block products and residuals only"; return PYIPM_E_BADARG; }
-    if (!ctx->have_blocks || !ctx->have_vectors) { ctx->err = "assemble: stage blocks and vectors first"; return PYIPM_E_BADARG; }
-    if (delta != ctx->delta || delta_c != ctx->delta_c) ctx->rc_warm_valid[0] = ctx->rc_warm_valid[1] = false;   // (a shifted matrix: the condition estimate starts cold)
+    if (!ctx->held.have_blocks || !ctx->held.have_vectors) { ctx->err = "assemble: stage blocks and vectors first"; return PYIPM_E_BADARG; }
+    if (delta != ctx->delta || delta_c != ctx->delta_c) ctx->held.rc_warm_cold();      // a shifted matrix
     ctx->delta = delta; ctx->delta_c = delta_c;
     if (ctx->condensed && g.mi > 0 && g.world > 1 && ctx->sharded) {
         ctx->err = "condensed option across ranks needs the full blocks on every rank (stage_blocks, not stage_blocks_owned): "
                    "a column of Ji Sigma Ji' takes every row of Ji";
         return PYIPM_E_BADARG;
     }
-    if (ctx->condensed && g.mi > 0) {
-        ctx->zeros_clean = false;                       // the condensed system lives in the same storage with another layout
+    const bool condensed = ctx->condensed && g.mi > 0;
+    ctx->held.assemble_begun(condensed);
+    if (condensed) {
         int rc = assemble_condensed(ctx, delta, delta_c); if (rc) return rc;
-        ctx->cond_active = true;
-        ctx->assembled = true; ctx->factored = false; ctx->forward_pending = false;
+        ctx->held.assemble_done(true, g.world == 1);
         return 0;
     }
-    ctx->cond_active = false;
     PYIPM_HIP(hipMemsetAsync(ctx->anorm, 0, sizeof(unsigned long long), ctx->stream));
     if (g.ncols_local > 0) {
-        const int zip = (ctx->keep_zeros && !ctx->storage_exported && ctx->zeros_clean && g.world == 1 && g.mi > 0) ? 1 : 0;
+        const int zip = (ctx->keep_zeros && !ctx->held.storage_exported && ctx->held.zeros_clean && g.world == 1 && g.mi > 0) ? 1 : 0;
         dim3 grid; int tri = 0;
         asm_grid(g, &grid, &tri);
         hipLaunchKernelGGL(k_assemble, grid, dim3(256), 0, ctx->stream, ctx->A, g.Npad, g, ctx->d2L, ctx->ld_d2L,
@@ -1666,10 +1661,7 @@ int assemble_dev(Ctx* ctx, double delta, double delta_c) {
                            zip, (int64_t)0, tri);
         PYIPM_KCHECK();
     }
-    // the zeros of this assembly survive a factorisation of finite numbers (every update that reaches them adds an exact zero);
-    // whatever else may write into the storage clears the flag (zeros_dirty)
-    ctx->zeros_clean = g.world == 1;
-    ctx->assembled = true; ctx->factored = false; ctx->forward_pending = false;
+    ctx->held.assemble_done(false, g.world == 1);
     return 0;
 }
 
@@ -1889,7 +1881,7 @@ static GroupStep plan_step(const Ctx* ctx, const FactorRun& run, int64_t grp) {
 int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
     const Geo& g = ctx->g;
     if (g.world != 1) { ctx->err = "factor(): single-rank entry point; use the per-panel phases when world > 1"; return PYIPM_E_BADARG; }
-    if (!ctx->assembled) { ctx->err = "factor: assemble first"; return PYIPM_E_BADARG; }
+    if (!ctx->held.assembled) { ctx->err = "factor: assemble first"; return PYIPM_E_BADARG; }
     const auto t_host0 = std::chrono::steady_clock::now();
     int rc = 0;
     if (!ctx->side) {
@@ -1905,7 +1897,7 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
     const int64_t np = g.npanels, ngroups = sc.ngroups();
     const FactorRun run{fuse_forward, ctx->lookahead >= 2 && ngroups > 2 && chain_group(ctx, 0) && sc.fast(1), slack_first_applies(ctx)};
     GroupTrace tr;
-    ctx->forward_fused = false;
+    ctx->held.factor_begun();
     if (fuse_forward) {
         PYIPM_HIP(ctx->fwd.ensure(hipStreamNonBlocking));
         PYIPM_HIP(ensure_events(ctx->ev_done, (size_t)np, hipEventDisableTiming));
@@ -1967,10 +1959,10 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
     if (fuse_forward) {                     // join: the main stream continues after the forward pass
         PYIPM_HIP(hipEventRecord(ctx->ev_fwd, ctx->fwd));
         PYIPM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_fwd, 0));
-        ctx->forward_fused = true;
+        ctx->held.forward_fused_under_factor();
     }
     PYIPM_HIP(hipEventRecord(ctx->ev[1], ctx->stream));
-    ctx->assembled = false;                 // storage now holds the factor
+    ctx->held.factor_enqueued();
     if (getenv("PYIPM_SETUP_TRACE")) {
         const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
         fprintf(stderr, "[pyipm] factor_all: host enqueue %.2f ms (tile lists built so far: %d in %.2f ms)\n", host_ms,
@@ -1989,7 +1981,7 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
 // every eliminated (s_k, lambda_i_k) pair [[Sigma_k, -1], [-1, 0]] has determinant -1, i.e. one positive
 // and one negative eigenvalue whatever the sign of Sigma_k.
 int factor_dispatch(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward) {
-    if (!ctx->cond_active) { ctx->fwd_vec = ctx->v0; return factor_all(ctx, stats, fuse_forward); }
+    if (!ctx->held.cond_active) { ctx->fwd_vec = ctx->v0; return factor_all(ctx, stats, fuse_forward); }
     pyipm_factor_stats local; if (!stats) stats = &local;
     int rc;
     ctx->fwd_vec = ctx->vc;
@@ -2002,21 +1994,100 @@ int factor_dispatch(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward) {
 }
 
 // kernels of this translation unit on behalf of the others (a kernel is launched from the unit that defines it)
-int launch_axpby(Ctx* ctx, hipStream_t st, double* out, const double* a, const double* b, double alpha, double beta, int64_t n) {
-    hipLaunchKernelGGL(k_axpby, grid1(n), dim3(256), 0, st, out, a, b, alpha, beta, n); PYIPM_KCHECK(); return 0; }
-int launch_fill(Ctx* ctx, hipStream_t st, double* out, double v, int64_t n) {
-    hipLaunchKernelGGL(k_fill, grid1(n), dim3(256), 0, st, out, v, n); PYIPM_KCHECK(); return 0; }
-int launch_copy_flip(Ctx* ctx, hipStream_t st, double* out, const double* in, int flip) {
-    hipLaunchKernelGGL(k_copy_flip, grid1(ctx->g.N), dim3(256), 0, st, out, in, ctx->g.N, ctx->g.n + ctx->g.mi, flip); PYIPM_KCHECK(); return 0; }
 int launch_mask_owned(Ctx* ctx, hipStream_t st, double* v, const double* b) {
     hipLaunchKernelGGL(k_mask_owned, grid1(ctx->g.Npad), dim3(256), 0, st, v, b, ctx->g); PYIPM_KCHECK(); return 0; }
-int launch_sumsq2(Ctx* ctx, hipStream_t st, double* out, const double* a, const double* b, int64_t n) {
-    hipLaunchKernelGGL(k_sumsq2, dim3(1), dim3(1024), 0, st, out, a, b, n); PYIPM_KCHECK(); return 0; }
 int launch_inpanel_update(Ctx* ctx, hipStream_t st, dim3 grid, double* Cm, int64_t ldc, int64_t ccol, const double* Lop, int64_t ldl,
                           const double* Wop, int64_t ldw, int64_t cglob, int K, int64_t row_begin, int64_t row_end,
                           int64_t a0, int64_t a1, int64_t b0, int64_t b1, int prio) {
     hipLaunchKernelGGL(k_inpanel_update, grid, dim3(256), 0, st, Cm, ldc, ccol, Lop, ldl, Wop, ldw, cglob, K, row_begin, row_end, a0, a1, b0, b1, prio);
     PYIPM_KCHECK(); return 0; }
+
+int copy_out(Ctx* ctx, double* dst, const double* src_dev, size_t count, int memkind) {
+    if (!dst || count == 0) return 0;
+    PYIPM_HIP(hipMemcpyAsync(dst, src_dev, count * sizeof(double),
+                             memkind == PYIPM_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
+    if (memkind == PYIPM_MEM_HOST) PYIPM_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// load the right-hand side into v1 (kept for refinement) and v0 (solved in place)
+int solve_prepare(Ctx* ctx, const double* rhs, int memkind, bool for_fused_forward) {
+    const Geo& g = ctx->g;
+    if (rhs) {
+        hipLaunchKernelGGL(k_fill, grid1(g.Npad), dim3(256), 0, ctx->stream, ctx->v1, 0.0, g.Npad); PYIPM_KCHECK();
+        int rc = put_vec(ctx, ctx->v1, rhs, g.N, memkind); if (rc) return rc;
+    } else {
+        if (!ctx->held.have_rhs) { ctx->err = "solve: no right-hand side (call residual or pass rhs)"; return PYIPM_E_BADARG; }
+        PYIPM_HIP(hipMemcpyAsync(ctx->v1, ctx->rhs, g.Npad * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    PYIPM_HIP(hipMemcpyAsync(ctx->v0, ctx->v1, g.Npad * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    if (for_fused_forward && ctx->held.cond_active) return cond_reduce(ctx, ctx->v0, ctx->vc);   // the fused pass runs on vc
+    return 0;
+}
+
+// The tail of every solve: v1 = b and v0 = b (solve_prepare) -> x in v0, refined against the blocks (v2 the residual, v3 the spare
+// iterate), flipped into v2 and copied out.  Events 4 (the caller) and 5 bracket it.
+int solve_finish(Ctx* ctx, const SolveOps& ops, double* dz, int flip, int refine, int memkind, bool forward_done) {
+    const Geo& g = ctx->g;
+    int rc = ops.solve(ctx, ctx->v1, ctx->v0, forward_done); if (rc) return rc;
+    const size_t vbytes = (size_t)g.Npad * sizeof(double);
+    rc = refine_loop(ctx, refine,
+        [&]() -> int {                                          // v2 = b - Hc v0
+            int r2 = ops.matvec(ctx, ctx->v0, ctx->v2); if (r2) return r2;
+            hipLaunchKernelGGL(k_axpby, grid1(g.Npad), dim3(256), 0, ctx->stream, ctx->v2, ctx->v1, ctx->v2, 1.0, -1.0, g.Npad);
+            PYIPM_KCHECK();
+            return 0;
+        },
+        [&](double* berr) -> int {
+            double ss[2];
+            hipLaunchKernelGGL(k_sumsq2, dim3(1), dim3(1024), 0, ctx->stream, ctx->partial, ctx->v2, ctx->v1, g.N);
+            PYIPM_KCHECK();
+            PYIPM_HIP(hipMemcpyAsync(ss, ctx->partial, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            PYIPM_HIP(hipStreamSynchronize(ctx->stream));
+            *berr = ss[1] > 0.0 ? sqrt(ss[0] / ss[1]) : sqrt(ss[0]);
+            return 0;
+        },
+        [&]() -> int { PYIPM_HIP(hipMemcpyAsync(ctx->v3, ctx->v0, vbytes, hipMemcpyDeviceToDevice, ctx->stream)); return 0; },
+        [&]() -> int { PYIPM_HIP(hipMemcpyAsync(ctx->v0, ctx->v3, vbytes, hipMemcpyDeviceToDevice, ctx->stream)); return 0; },
+        [&]() -> int {                                          // v0 += Hc^{-1} v2
+            int r2 = ops.solve(ctx, ctx->v2, ctx->v2, false); if (r2) return r2;
+            hipLaunchKernelGGL(k_axpby, grid1(g.Npad), dim3(256), 0, ctx->stream, ctx->v0, ctx->v0, ctx->v2, 1.0, 1.0, g.Npad);
+            PYIPM_KCHECK();
+            return 0;
+        });
+    if (rc) return rc;
+    // flip + copy out (device staging through v2 so host copies stay contiguous)
+    hipLaunchKernelGGL(k_copy_flip, grid1(g.N), dim3(256), 0, ctx->stream, ctx->v2, ctx->v0, g.N, g.n + g.mi,
+                       (flip && (g.me + g.mi) > 0) ? 1 : 0);
+    PYIPM_KCHECK();
+    PYIPM_HIP(hipEventRecord(ctx->ev[5], ctx->stream));
+    rc = copy_out(ctx, dz, ctx->v2, g.N, memkind); if (rc) return rc;
+    ctx->held.solved((flip != 0) || (g.me + g.mi == 0), ops.ray_survives);
+    return PYIPM_OK;
+}
+
+static int solve_local(Ctx* ctx, const double*, double* x, bool forward_done) { return solve_inplace(ctx, x, forward_done); }
+static const SolveOps kLocalOps = {solve_local, kkt_matvec_dev, false};
+
+// events 2 and 3 around the assembly (last_timings)
+int assemble_timed(Ctx* ctx, double delta, double delta_c) {
+    PYIPM_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
+    int rc = assemble_dev(ctx, delta, delta_c); if (rc) return rc;
+    PYIPM_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
+    ctx->held.assemble_timed();
+    return PYIPM_OK;
+}
+
+// y = Hc v for the caller.  The product goes through vc (free outside a condensed solve), so v2 -- the direction of the last
+// solve, which step_lengths() reads -- survives a backward-error check; v1 takes the operand.
+int kkt_matvec_io(Ctx* ctx, const SolveOps& ops, const double* v, double* y, int memkind) {
+    const Geo& g = ctx->g;
+    ctx->held.borrowed(Held::V1);
+    hipLaunchKernelGGL(k_fill, grid1(g.Npad), dim3(256), 0, ctx->stream, ctx->v1, 0.0, g.Npad); PYIPM_KCHECK();
+    int rc = put_vec(ctx, ctx->v1, v, g.N, memkind); if (rc) return rc;
+    rc = ops.matvec(ctx, ctx->v1, ctx->vc); if (rc) return rc;
+    return copy_out(ctx, y, ctx->vc, g.N, memkind);
+}
 
 } }  // namespace pyipm::drv
 
@@ -2147,32 +2218,27 @@ static int fetch_batched_stats(Ctx* ctx, pyipm_factor_stats* stats) {
 int pyipm_newton_stage_blocks_batched(pyipm_newton_ctx* h, const double* d2L, int64_t ld_d2L, int64_t stride_d2L,
                                       const double* Je, int64_t ld_Je, int64_t stride_Je,
                                       const double* Ji, int64_t ld_Ji, int64_t stride_Ji) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); const Geo& g = ctx->g;
-    if (!ctx->batched) { ctx->err = "stage_blocks_batched: not a batched handle"; return PYIPM_E_BADARG; }
+    PYIPM_ENTER("stage_blocks_batched", G_BATCHED) const Geo& g = ctx->g;
     if (!d2L || ld_d2L < g.n || (g.me && (!Je || ld_Je < g.me)) || (g.mi && (!Ji || ld_Ji < g.mi))) {
         ctx->err = "stage_blocks_batched: bad block pointer / leading dimension (device pointers only)"; return PYIPM_E_BADARG; }
     ctx->d2L = d2L; ctx->ld_d2L = ld_d2L; ctx->b_sH = stride_d2L;
     ctx->Je = g.me ? Je : nullptr; ctx->ld_Je = ld_Je; ctx->b_sJe = stride_Je;
     ctx->Ji = g.mi ? Ji : nullptr; ctx->ld_Ji = ld_Ji; ctx->b_sJi = stride_Ji;
-    ctx->have_blocks = true;
+    ctx->held.blocks_staged();              // (nothing on a batched handle ever forms the products it forgets)
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_step_batched(pyipm_newton_ctx* h, double delta, double delta_c, double* dz,
                               pyipm_factor_stats* stats, int memkind) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); const Geo& g = ctx->g;
-    PYIPM_HIP(hipSetDevice(ctx->device));
-    if (!ctx->batched) { ctx->err = "step_batched: not a batched handle"; return PYIPM_E_BADARG; }
-    if (!ctx->have_blocks || !ctx->have_vectors) { ctx->err = "step_batched: stage blocks and vectors first"; return PYIPM_E_BADARG; }
+    PYIPM_ENTER("step_batched", G_BATCHED | G_DEVICE) const Geo& g = ctx->g;
+    if (!ctx->held.have_blocks || !ctx->held.have_vectors) { ctx->err = "step_batched: stage blocks and vectors first"; return PYIPM_E_BADARG; }
     if (!dz) { ctx->err = "step_batched: null output"; return PYIPM_E_BADARG; }
     const int B = ctx->batch;
     BatchPtrs bp = batch_ptrs(ctx);
     BatchCond bc = batch_cond(ctx);
     const int cond = (ctx->condensed && g.mi > 0) ? 1 : 0;
     ctx->delta = delta; ctx->delta_c = delta_c;
-    ctx->cond_active = cond != 0;
+    ctx->held.step_batched_begun(cond != 0);
     PYIPM_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
     PYIPM_HIP(hipMemsetAsync(ctx->anorm, 0, (size_t)B * 2 * sizeof(unsigned long long), ctx->stream));
     if (cond) {
@@ -2208,8 +2274,7 @@ int pyipm_newton_step_batched(pyipm_newton_ctx* h, double delta, double delta_c,
                        ctx->block_refine, (g.me + g.mi) > 0 ? 1 : 0, out_dev, bc, cond, ctx->eps);
     PYIPM_KCHECK();
     PYIPM_HIP(hipEventRecord(ctx->ev[1], ctx->stream));
-    ctx->have_rhs = true;                 // g = -grad of every problem is in rhs (backward_error_batched reads it)
-    ctx->ev_assemble_valid = true;
+    ctx->held.step_batched_enqueued();
     if (memkind == PYIPM_MEM_HOST)
         PYIPM_HIP(hipMemcpyAsync(dz, ctx->v2, (size_t)B * g.N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (stats) return fetch_batched_stats(ctx, stats);
@@ -2221,21 +2286,17 @@ int pyipm_newton_step_batched(pyipm_newton_ctx* h, double delta, double delta_c,
 // returns as soon as its five launches are enqueued (round 6: the copy of 512 statistics records and the synchronisation in
 // front of it were 0.3 of the 1.4 ms a batch step took on the host's clock).
 int pyipm_newton_stats_batched(pyipm_newton_ctx* h, pyipm_factor_stats* stats) try {
-    if (check_ctx(h) || !stats) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
-    PYIPM_HIP(hipSetDevice(ctx->device));
-    if (!ctx->batched) { ctx->err = "stats_batched: not a batched handle"; return PYIPM_E_BADARG; }
-    if (!ctx->have_rhs) { ctx->err = "stats_batched: step_batched first"; return PYIPM_E_BADARG; }
+    PYIPM_ENTER("stats_batched", G_BATCHED | G_DEVICE)
+    if (!stats) return PYIPM_E_BADARG;
+    if (!ctx->held.have_rhs) { ctx->err = "stats_batched: step_batched first"; return PYIPM_E_BADARG; }
     return fetch_batched_stats(ctx, stats);
 } PYIPM_CATCH_H(h)
 
 // out[b] = |g - Hc raw_b| / |g| of every problem of the last step_batched, Hc applied from the blocks (k_b_berr)
 int pyipm_newton_backward_error_batched(pyipm_newton_ctx* h, const double* dz, double* out, int memkind) try {
-    if (check_ctx(h) || !dz || !out) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); const Geo& g = ctx->g;
-    PYIPM_HIP(hipSetDevice(ctx->device));
-    if (!ctx->batched) { ctx->err = "backward_error_batched: not a batched handle"; return PYIPM_E_BADARG; }
-    if (!ctx->have_blocks || !ctx->have_vectors || !ctx->have_rhs) { ctx->err = "backward_error_batched: step_batched first"; return PYIPM_E_BADARG; }
+    PYIPM_ENTER("backward_error_batched", G_BATCHED | G_DEVICE) const Geo& g = ctx->g;
+    if (!dz || !out) return PYIPM_E_BADARG;
+    if (!ctx->held.have_blocks || !ctx->held.have_vectors || !ctx->held.have_rhs) { ctx->err = "backward_error_batched: step_batched first"; return PYIPM_E_BADARG; }
     BatchPtrs bp = batch_ptrs(ctx);
     double* dev = (memkind == PYIPM_MEM_DEVICE) ? out : ctx->vt;
     hipLaunchKernelGGL(k_b_berr, dim3(ctx->batch), dim3(256), 0, ctx->stream, bp, g, dz, ctx->eps, ctx->delta, ctx->delta_c, dev);
@@ -2250,8 +2311,7 @@ int pyipm_newton_backward_error_batched(pyipm_newton_ctx* h, const double* dz, d
 // Teardown is an order, not a list: stuck collectives aborted, every stream of the handle drained, the communicators gone --
 // after that nothing on the device refers to what the handle owns, and ~Ctx may release its members in any order.
 int pyipm_newton_destroy(pyipm_newton_ctx* h) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
+    PYIPM_ENTER("destroy", 0)
     hipSetDevice(ctx->device);
     dist_abort_broken(ctx);
     hipStreamSynchronize(ctx->stream);
@@ -2263,46 +2323,39 @@ int pyipm_newton_destroy(pyipm_newton_ctx* h) try {
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_set_stream(pyipm_newton_ctx* h, void* stream) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    C(h)->stream = (hipStream_t)stream;
+    PYIPM_ENTER("set_stream", 0)
+    ctx->stream = (hipStream_t)stream;
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
 const char* pyipm_newton_last_error(pyipm_newton_ctx* h) {
-    if (!h) return "null handle";
-    return C(h)->err.c_str();
+    Ctx* ctx;
+    return enter(h, "last_error", 0, &ctx) ? "null handle" : ctx->err.c_str();
 }
 
 int pyipm_newton_geometry(pyipm_newton_ctx* h, int64_t out[8]) try {
-    if (check_ctx(h) || !out) return PYIPM_E_BADARG;
-    const Geo& g = C(h)->g;
+    PYIPM_ENTER("geometry", 0) const Geo& g = ctx->g;
+    if (!out) return PYIPM_E_BADARG;
     out[0] = g.N; out[1] = g.Npad; out[2] = g.nb; out[3] = g.npanels; out[4] = g.ncols_local;
-    out[5] = g.world; out[6] = g.rank; out[7] = (int64_t)C(h)->ws.capacity();
+    out[5] = g.world; out[6] = g.rank; out[7] = (int64_t)ctx->ws.capacity();
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_stage_blocks(pyipm_newton_ctx* h, const double* d2L, int64_t ld_d2L, const double* Je,
                               int64_t ld_Je, const double* Ji, int64_t ld_Ji, int memkind) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); const Geo& g = ctx->g;
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("stage_blocks", G_SINGLE | G_DEVICE) const Geo& g = ctx->g;
     int rc;
     if (!d2L && ctx->provider_only) { ctx->d2L = nullptr; ctx->ld_d2L = g.n; }     // (a factored Hessian model: only the Jacobian products)
     else { rc = stage_block(ctx, d2L, g.n, g.n, ld_d2L, memkind, ctx->stg_d2L, &ctx->d2L, &ctx->ld_d2L); if (rc) return rc; }
     rc = stage_block(ctx, Je, g.me ? g.n : 0, g.me, ld_Je, memkind, ctx->stg_Je, &ctx->Je, &ctx->ld_Je); if (rc) return rc;
     rc = stage_block(ctx, Ji, g.mi ? g.n : 0, g.mi, ld_Ji, memkind, ctx->stg_Ji, &ctx->Ji, &ctx->ld_Ji); if (rc) return rc;
-    ctx->have_blocks = true;
-    ctx->ray_valid = false;
-    ctx->rc_warm_valid[0] = ctx->rc_warm_valid[1] = false;      // (another matrix: the condition estimate starts cold)
+    ctx->held.blocks_staged();
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_stage_vectors(pyipm_newton_ctx* h, const double* df, const double* ce, const double* ci,
                                const double* s, const double* lda, double mu, double eps, int memkind) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); const Geo& g = ctx->g;
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("stage_vectors", G_DEVICE) const Geo& g = ctx->g;
     int rc;
     const size_t B = (size_t)ctx->batch;          // batched handles: every vector is [batch][len], contiguous
     rc = put_vec(ctx, ctx->df, df, B * g.n, memkind); if (rc) return rc;
@@ -2311,167 +2364,61 @@ int pyipm_newton_stage_vectors(pyipm_newton_ctx* h, const double* df, const doub
     rc = put_vec(ctx, ctx->s, s, B * g.mi, memkind); if (rc) return rc;
     rc = put_vec(ctx, ctx->lda, lda, B * (g.me + g.mi), memkind); if (rc) return rc;
     ctx->mu = mu; ctx->eps = eps;
-    ctx->have_vectors = true;
-    ctx->have_rhs = false;                        // (g = -grad belongs to the vectors staged before)
-    ctx->ray_valid = false;
+    ctx->held.vectors_staged();
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
-}  // extern "C"
-namespace pyipm { namespace drv {
-int copy_out(Ctx* ctx, double* dst, const double* src_dev, size_t count, int memkind) {
-    if (!dst || count == 0) return 0;
-    PYIPM_HIP(hipMemcpyAsync(dst, src_dev, count * sizeof(double),
-                             memkind == PYIPM_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
-    if (memkind == PYIPM_MEM_HOST) PYIPM_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-} }
-extern "C" {
-
 int pyipm_newton_residual(pyipm_newton_ctx* h, double* g_out, int memkind) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("residual", G_SINGLE | G_DEVICE)
     int rc = residual_dev(ctx); if (rc) return rc;
     return copy_out(ctx, g_out, ctx->rhs, ctx->g.N, memkind);
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_assemble(pyipm_newton_ctx* h, double delta, double delta_c) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
-    PYIPM_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
-    int rc = assemble_dev(ctx, delta, delta_c); if (rc) return rc;
-    PYIPM_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
-    ctx->ev_assemble_valid = true;
-    return PYIPM_OK;
+    PYIPM_ENTER("assemble", G_SINGLE | G_DEVICE)
+    return assemble_timed(ctx, delta, delta_c);
 } PYIPM_CATCH_H(h)
 
-
 int pyipm_newton_factor(pyipm_newton_ctx* h, pyipm_factor_stats* stats) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("factor", G_SINGLE | G_DEVICE)
     // a residual is pending (pyipm.py:1717 precedes :1718): let its forward substitution trail the
     // factorisation; solve(rhs = NULL) then only runs the block-diagonal and backward parts
-    const bool fuse = ctx->fuse_forward && ctx->have_rhs && ctx->g.world == 1 && ctx->assembled;
+    const bool fuse = ctx->fuse_forward && ctx->held.have_rhs && ctx->g.world == 1 && ctx->held.assembled;
     if (fuse) { int rc = solve_prepare(ctx, nullptr, PYIPM_MEM_DEVICE, true); if (rc) return rc; }
     int rc = factor_dispatch(ctx, stats, fuse);
-    if (rc) ctx->zeros_clean = false;
-    ctx->forward_pending = (rc == 0 || rc == PYIPM_E_NONFINITE) ? (fuse && ctx->forward_fused) : false;
+    ctx->held.factor_returned(rc, fuse);
     return rc;
 } PYIPM_CATCH_H(h)
 
-}  // extern "C"
-namespace pyipm { namespace drv {
-// load the right-hand side into v1 (kept for refinement) and v0 (solved in place)
-int solve_prepare(Ctx* ctx, const double* rhs, int memkind, bool for_fused_forward) {
-    const Geo& g = ctx->g;
-    if (rhs) {
-        hipLaunchKernelGGL(k_fill, grid1(g.Npad), dim3(256), 0, ctx->stream, ctx->v1, 0.0, g.Npad); PYIPM_KCHECK();
-        int rc = put_vec(ctx, ctx->v1, rhs, g.N, memkind); if (rc) return rc;
-    } else {
-        if (!ctx->have_rhs) { ctx->err = "solve: no right-hand side (call residual or pass rhs)"; return PYIPM_E_BADARG; }
-        PYIPM_HIP(hipMemcpyAsync(ctx->v1, ctx->rhs, g.Npad * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    PYIPM_HIP(hipMemcpyAsync(ctx->v0, ctx->v1, g.Npad * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    if (for_fused_forward && ctx->cond_active) return cond_reduce(ctx, ctx->v0, ctx->vc);   // the fused pass runs on vc
-    return 0;
-}
-} }
-extern "C" {
-
-static int solve_finish(Ctx* ctx, double* dz, int flip, int refine, int memkind, bool forward_done) {
-    const Geo& g = ctx->g;
-    int rc = solve_inplace(ctx, ctx->v0, forward_done); if (rc) return rc;
-    const size_t vbytes = (size_t)g.Npad * sizeof(double);
-    rc = refine_loop(ctx, refine,
-        [&]() -> int {                                          // v2 = b - Hc v0
-            int r2 = kkt_matvec_dev(ctx, ctx->v0, ctx->v2); if (r2) return r2;
-            hipLaunchKernelGGL(k_axpby, grid1(g.Npad), dim3(256), 0, ctx->stream, ctx->v2, ctx->v1, ctx->v2, 1.0, -1.0, g.Npad);
-            PYIPM_KCHECK();
-            return 0;
-        },
-        [&](double* berr) -> int {
-            double ss[2];
-            hipLaunchKernelGGL(k_sumsq2, dim3(1), dim3(1024), 0, ctx->stream, ctx->partial, ctx->v2, ctx->v1, g.N);
-            PYIPM_KCHECK();
-            PYIPM_HIP(hipMemcpyAsync(ss, ctx->partial, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-            PYIPM_HIP(hipStreamSynchronize(ctx->stream));
-            *berr = ss[1] > 0.0 ? sqrt(ss[0] / ss[1]) : sqrt(ss[0]);
-            return 0;
-        },
-        [&]() -> int { PYIPM_HIP(hipMemcpyAsync(ctx->v3, ctx->v0, vbytes, hipMemcpyDeviceToDevice, ctx->stream)); return 0; },
-        [&]() -> int { PYIPM_HIP(hipMemcpyAsync(ctx->v0, ctx->v3, vbytes, hipMemcpyDeviceToDevice, ctx->stream)); return 0; },
-        [&]() -> int {                                          // v0 += Hc^{-1} v2
-            int r2 = solve_inplace(ctx, ctx->v2); if (r2) return r2;
-            hipLaunchKernelGGL(k_axpby, grid1(g.Npad), dim3(256), 0, ctx->stream, ctx->v0, ctx->v0, ctx->v2, 1.0, 1.0, g.Npad);
-            PYIPM_KCHECK();
-            return 0;
-        });
-    if (rc) return rc;
-    // flip + copy out (device staging through v2 so host copies stay contiguous)
-    hipLaunchKernelGGL(k_copy_flip, grid1(g.N), dim3(256), 0, ctx->stream, ctx->v2, ctx->v0, g.N, g.n + g.mi,
-                       (flip && (g.me + g.mi) > 0) ? 1 : 0);
-    PYIPM_KCHECK();
-    PYIPM_HIP(hipEventRecord(ctx->ev[5], ctx->stream));
-    rc = copy_out(ctx, dz, ctx->v2, g.N, memkind); if (rc) return rc;
-    ctx->ev_solve_valid = true;
-    ctx->have_direction = (flip != 0) || (g.me + g.mi == 0);     // v2 = dz with the reference's sign convention
-    ctx->ray_valid = false;                                      // (merit_ray: the products of the OLD direction)
-    return PYIPM_OK;
-}
-
 int pyipm_newton_solve(pyipm_newton_ctx* h, const double* rhs, double* dz, int flip, int refine, int memkind) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); const Geo& g = ctx->g;
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
-    if (g.world != 1) { ctx->err = "solve(): single-rank entry point"; return PYIPM_E_BADARG; }
-    if (!ctx->factored) { ctx->err = "solve: factor first"; return PYIPM_E_BADARG; }
+    PYIPM_ENTER("solve", G_SINGLE | G_ONE_RANK | G_FACTORED | G_DEVICE) const Geo& g = ctx->g;
     if (!dz) { ctx->err = "solve: null output"; return PYIPM_E_BADARG; }
     PYIPM_HIP(hipEventRecord(ctx->ev[4], ctx->stream));
-    const bool pending = ctx->forward_pending && rhs == nullptr;      // v0 already holds the forward-substituted residual
-    ctx->forward_pending = false;                                     // consumed (or overwritten) either way
+    const bool pending = ctx->held.forward_pending && rhs == nullptr;      // v0 already holds the forward-substituted residual
+    ctx->held.borrowed(Held::V0 | Held::V1);                               // consumed (or overwritten) either way
     if (!pending) { int rc = solve_prepare(ctx, rhs, memkind); if (rc) return rc; }
-    return solve_finish(ctx, dz, flip, refine, memkind, pending);
+    return solve_finish(ctx, kLocalOps, dz, flip, refine, memkind, pending);
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_kkt_matvec(pyipm_newton_ctx* h, const double* v, double* y, int memkind) try {
-    if (check_ctx(h) || !v || !y) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); const Geo& g = ctx->g;
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
-    ctx->forward_pending = false;                     // v1 (the saved right-hand side) is about to be reused
-    // the product goes through vc (free outside a condensed solve), so v2 -- the direction of the last
-    // solve, which step_lengths() reads -- survives a backward-error check
-    hipLaunchKernelGGL(k_fill, grid1(g.Npad), dim3(256), 0, ctx->stream, ctx->v1, 0.0, g.Npad); PYIPM_KCHECK();
-    int rc = put_vec(ctx, ctx->v1, v, g.N, memkind); if (rc) return rc;
-    rc = kkt_matvec_dev(ctx, ctx->v1, ctx->vc); if (rc) return rc;
-    return copy_out(ctx, y, ctx->vc, g.N, memkind);
+    PYIPM_ENTER("kkt_matvec", G_SINGLE | G_DEVICE)
+    if (!v || !y) return PYIPM_E_BADARG;
+    return kkt_matvec_io(ctx, kLocalOps, v, y, memkind);
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_solve_info(pyipm_newton_ctx* h, double out[4]) try {
-    if (check_ctx(h) || !out) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
+    PYIPM_ENTER("solve_info", 0)
+    if (!out) return PYIPM_E_BADARG;
     out[0] = (double)ctx->info_steps; out[1] = ctx->info_berr0; out[2] = ctx->info_berr; out[3] = (double)ctx->info_converged;
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_solve_many(pyipm_newton_ctx* h, int64_t k, const double* rhs, int64_t ld_rhs, double* dz, int64_t ld_dz,
                             int flip, int refine, int memkind) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); const Geo& g = ctx->g;
-    if (ctx->batched) return single_only(ctx);
-    if (ctx->provider_only) { ctx->err = "solve_many: a provider-only handle has no factor"; return PYIPM_E_BADARG; }
-    if (g.world != 1) { ctx->err = "solve_many(): single-rank entry point"; return PYIPM_E_BADARG; }
+    PYIPM_ENTER("solve_many", G_SINGLE | G_FACTOR_ABLE | G_ONE_RANK) const Geo& g = ctx->g;
     if (k < 0) { ctx->err = "solve_many: k < 0"; return PYIPM_E_BADARG; }
-    if (k == 0) return PYIPM_OK;
-    if (!ctx->factored) { ctx->err = "solve_many: factor first"; return PYIPM_E_BADARG; }
+    if (k == 0) return PYIPM_OK;                             // (an empty sweep needs no factor)
+    { int rc = need_factor(ctx, "solve_many"); if (rc) return rc; }
     if (!rhs || !dz) { ctx->err = "solve_many: null right-hand side or output"; return PYIPM_E_BADARG; }
     if (ld_rhs < g.N || ld_dz < g.N) { ctx->err = "solve_many: leading dimension below N"; return PYIPM_E_BADARG; }
     if (memkind != PYIPM_MEM_DEVICE && memkind != PYIPM_MEM_HOST) { ctx->err = "solve_many: bad memkind"; return PYIPM_E_BADARG; }
@@ -2484,12 +2431,8 @@ int pyipm_newton_solve_many(pyipm_newton_ctx* h, int64_t k, const double* rhs, i
 // the factor (each step one substitution sweep).  Few iterations suffice for a threshold test at eps: a singular
 // direction dominates inv(Hc) by many orders of magnitude.
 int pyipm_newton_rcond(pyipm_newton_ctx* h, int it_inv, int it_pow, double out[4]) try {
-    if (check_ctx(h) || !out) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); const Geo& g = ctx->g;
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
-    if (g.world != 1) { ctx->err = "rcond(): single-rank entry point"; return PYIPM_E_BADARG; }
-    if (!ctx->factored) { ctx->err = "rcond: factor first"; return PYIPM_E_BADARG; }
+    PYIPM_ENTER("rcond", G_SINGLE | G_ONE_RANK | G_FACTORED | G_DEVICE) const Geo& g = ctx->g;
+    if (!out) return PYIPM_E_BADARG;
     // it_inv / it_pow >= 1: that many iterations of each; 0 = the defaults of rounds 2-3 (3 and 6).  < 0 = ADAPTIVE (round 4): an estimate for a
     // THRESHOLD test does not need the converged value.  Power iteration stops when two successive estimates agree to 10 %
     // (at most 6); inverse iteration stops when converged likewise (at most 3) -- or as soon as even a pessimistic correction
@@ -2504,10 +2447,11 @@ int pyipm_newton_rcond(pyipm_newton_ctx* h, int it_inv, int it_pow, double out[4
     // work vectors: v3 (the adaptive refinement's spare iterate) and vc (free outside a condensed solve), so that v0 / v1 -- a
     // right-hand side already forward-substituted under the factorisation -- and v2, the last direction, survive: the solve
     // that follows starts at the backward sweep (1.3 ms at N = 32768, at every suspect iterate).  With the condensed system
-    // the substitution itself goes through vc: v0 / v1 as before, the pending forward pass is redone.
-    double* wa = ctx->cond_active ? ctx->v0 : ctx->v3;
-    double* wb = ctx->cond_active ? ctx->v1 : ctx->vc;
-    if (ctx->cond_active) { ctx->forward_pending = false; ctx->have_direction = false; ctx->ray_valid = false; }
+    // the substitution itself goes through vc: v0 / v1 as before, the pending forward pass is redone (and the direction in v2,
+    // which nothing here writes, has always been dropped with them).
+    double* wa = ctx->held.cond_active ? ctx->v0 : ctx->v3;
+    double* wb = ctx->held.cond_active ? ctx->v1 : ctx->vc;
+    if (ctx->held.cond_active) ctx->held.borrowed(Held::V0 | Held::V1 | Held::V2);
     double ss[2], lmax = 0.0, linv = 0.0;
     int used_pow = 0, used_inv = 0;
     const bool trace = getenv("PYIPM_RCOND_TRACE") != nullptr;
@@ -2525,15 +2469,15 @@ int pyipm_newton_rcond(pyipm_newton_ctx* h, int it_inv, int it_pow, double out[4
     // sweeps instead of three, two products instead of up to six (-5 ms per late iterate at N = 32768).  Any start vector with a
     // component along the extreme eigenvector is valid; the stopping rules are unchanged; a hashed start is taken whenever the
     // stored vector is missing, of another size, or not finite.  stage_blocks forgets it.
-    const bool warm_ok = (adaptive_inv || adaptive_pow) && !ctx->cond_active && getenv("PYIPM_RCOND_COLD") == nullptr;
+    const bool warm_ok = (adaptive_inv || adaptive_pow) && !ctx->held.cond_active && getenv("PYIPM_RCOND_COLD") == nullptr;
     if (warm_ok && ctx->rc_warm_buf.capacity() < 2 * (size_t)g.Npad) {      // (no memory: no warm start, asked for again next time)
         const bool got = ctx->rc_warm_buf.reserve(2 * (size_t)g.Npad) == hipSuccess;
         ctx->rc_warm[0] = ctx->rc_warm_buf; ctx->rc_warm[1] = got ? ctx->rc_warm[0] + g.Npad : nullptr;
-        ctx->rc_warm_valid[0] = ctx->rc_warm_valid[1] = false;
+        ctx->held.rc_warm_cold();
     }
     for (int phase = 0; phase < 2; ++phase) {
         const bool adaptive_phase = phase == 0 ? adaptive_pow : adaptive_inv;
-        const bool warm = warm_ok && adaptive_phase && ctx->rc_warm[0] && ctx->rc_warm_valid[phase];
+        const bool warm = warm_ok && adaptive_phase && ctx->rc_warm[0] && ctx->held.rc_warm_valid[phase];
         // The start vector is hashed; a warm start ADDS the stored iterate to it, both normalised: the stored vector
         // has been through inverse (power) iterations on every earlier call, so along a direction that has only just become
         // (nearly) singular -- or a Sigma entry that has only just become dominant -- it holds rounding noise, and the stopping
@@ -2580,7 +2524,7 @@ int pyipm_newton_rcond(pyipm_newton_ctx* h, int it_inv, int it_pow, double out[4
             // keep the iterate (unnormalised: the next call normalises it) -- if it is finite
             const bool good = nrm > 0.0 && nrm <= 1.0e300;
             if (good) PYIPM_HIP(hipMemcpyAsync(ctx->rc_warm[phase], wb, g.Npad * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-            ctx->rc_warm_valid[phase] = good;
+            ctx->held.rc_warm_kept(phase, good);
         }
     }
     ctx->rcond_its[0] = used_pow; ctx->rcond_its[1] = used_inv;
@@ -2593,8 +2537,9 @@ int pyipm_newton_rcond(pyipm_newton_ctx* h, int it_inv, int it_pow, double out[4
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_anorm(pyipm_newton_ctx* h, double** dev_ptr) try {
-    if (check_ctx(h) || !dev_ptr) return PYIPM_E_BADARG;
-    *dev_ptr = reinterpret_cast<double*>(C(h)->anorm);        // bits of a non-negative double ARE that double
+    PYIPM_ENTER("anorm", 0)
+    if (!dev_ptr) return PYIPM_E_BADARG;
+    *dev_ptr = reinterpret_cast<double*>(ctx->anorm);        // bits of a non-negative double ARE that double
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
@@ -2604,17 +2549,15 @@ int pyipm_newton_anorm(pyipm_newton_ctx* h, double** dev_ptr) try {
 // so these are passes over the staged d2L (its UPPER triangle, as everywhere), Je and Ji.
 static int block_products_dev(Ctx* ctx, const double* v, double* Qv, double* JeTv, double* JiTv);
 int pyipm_newton_block_products(pyipm_newton_ctx* h, const double* v, double* Qv, double* JeTv, double* JiTv) try {
-    if (check_ctx(h) || !v) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("block_products", G_SINGLE | G_DEVICE)
+    if (!v) return PYIPM_E_BADARG;
     return block_products_dev(ctx, v, Qv, JeTv, JiTv);
 } PYIPM_CATCH_H(h)
 
 static int block_products_dev(Ctx* ctx, const double* v, double* Qv, double* JeTv, double* JiTv) {
     const Geo& g = ctx->g;
     if (g.world != 1 || ctx->sharded) { ctx->err = "block_products: single-rank handles with fully staged blocks"; return PYIPM_E_BADARG; }
-    if (!ctx->have_blocks) { ctx->err = "block_products: stage blocks first"; return PYIPM_E_BADARG; }
+    if (!ctx->held.have_blocks) { ctx->err = "block_products: stage blocks first"; return PYIPM_E_BADARG; }
     if (Qv && !ctx->d2L) { ctx->err = "block_products: no d2L block staged on this provider-only handle (pass Qv = NULL)"; return PYIPM_E_BADARG; }
     const RowMap rm = make_rowmap(g, 0);
     const int64_t n = g.n, me = g.me, mi = g.mi;
@@ -2649,12 +2592,10 @@ static int block_products_dev(Ctx* ctx, const double* v, double* Qv, double* JeT
 
 // out (n) = Je le + Ji li  (either may be NULL): the Jacobian terms of dL/dx (pyipm.py:655-668)
 int pyipm_newton_block_products_t(pyipm_newton_ctx* h, const double* le, const double* li, double* out) try {
-    if (check_ctx(h) || !out) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); const Geo& g = ctx->g;
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("block_products_t", G_SINGLE | G_DEVICE) const Geo& g = ctx->g;
+    if (!out) return PYIPM_E_BADARG;
     if (g.world != 1 || ctx->sharded) { ctx->err = "block_products_t: single-rank handles with fully staged blocks"; return PYIPM_E_BADARG; }
-    if (!ctx->have_blocks) { ctx->err = "block_products_t: stage blocks first"; return PYIPM_E_BADARG; }
+    if (!ctx->held.have_blocks) { ctx->err = "block_products_t: stage blocks first"; return PYIPM_E_BADARG; }
     const int64_t me = le ? g.me : 0, mi = li ? g.mi : 0;
     if (ctx->profile) PYIPM_HIP(hipEventRecord(ctx->ev_prov[2], ctx->stream));
     hipLaunchKernelGGL(k_rowdot2, grid1(g.n, 4), dim3(256), 0, ctx->stream, out, (const double*)nullptr, g.n,
@@ -2668,9 +2609,8 @@ int pyipm_newton_block_products_t(pyipm_newton_ctx* h, const double* le, const d
 // out[0] = ms of the last block_products call ("profile" = 1), out[1] = the bytes of the blocks it passed over,
 // out[2], out[3] = the same for block_products_t
 int pyipm_newton_provider_stats(pyipm_newton_ctx* h, double out[4]) try {
-    if (check_ctx(h) || !out) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("provider_stats", G_DEVICE)
+    if (!out) return PYIPM_E_BADARG;
     PYIPM_HIP(hipStreamSynchronize(ctx->stream));
     for (int k = 0; k < 2; ++k) {
         float ms = 0.f;
@@ -2682,30 +2622,26 @@ int pyipm_newton_provider_stats(pyipm_newton_ctx* h, double out[4]) try {
 
 int pyipm_newton_step(pyipm_newton_ctx* h, double delta, double delta_c, int refine, double* dz,
                       pyipm_factor_stats* stats, int memkind) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("step", G_SINGLE | G_DEVICE)
     if (!dz) { ctx->err = "step: null output"; return PYIPM_E_BADARG; }
     int rc = residual_dev(ctx); if (rc) return rc;
-    rc = pyipm_newton_assemble(h, delta, delta_c); if (rc) return rc;
+    rc = assemble_timed(ctx, delta, delta_c); if (rc) return rc;
     const bool fuse = ctx->fuse_forward != 0;
     if (fuse) { rc = solve_prepare(ctx, nullptr, memkind, true); if (rc) return rc; }     // v0 = v1 = g before factoring
-    rc = factor_dispatch(ctx, stats, fuse); if (rc) { ctx->zeros_clean = false; return rc; }
-    ctx->forward_pending = false;
+    rc = factor_dispatch(ctx, stats, fuse);
+    ctx->held.factor_returned(rc, false);                    // (the solve below consumes the fused pass at once)
+    if (rc) return rc;
     PYIPM_HIP(hipEventRecord(ctx->ev[4], ctx->stream));
     if (!fuse) { rc = solve_prepare(ctx, nullptr, memkind); if (rc) return rc; }
-    return solve_finish(ctx, dz, 1, refine, memkind, fuse && ctx->forward_fused);
+    return solve_finish(ctx, kLocalOps, dz, 1, refine, memkind, fuse && ctx->held.forward_fused);
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_step_lengths(pyipm_newton_ctx* h, double tau, const double* dz_in, double* alpha_s, double* alpha_l) try {
-    if (check_ctx(h) || !alpha_s || !alpha_l) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); const Geo& g = ctx->g;
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("step_lengths", G_SINGLE | G_DEVICE) const Geo& g = ctx->g;
+    if (!alpha_s || !alpha_l) return PYIPM_E_BADARG;
     *alpha_s = 1.0; *alpha_l = 1.0;
     if (g.mi == 0) return PYIPM_OK;
-    if (!ctx->have_vectors || (!dz_in && !ctx->have_direction)) { ctx->err = "step_lengths: stage vectors and solve first (or pass dz)"; return PYIPM_E_BADARG; }
+    if (!ctx->held.have_vectors || (!dz_in && !ctx->held.have_direction)) { ctx->err = "step_lengths: stage vectors and solve first (or pass dz)"; return PYIPM_E_BADARG; }
     // v2 holds the last direction in the reference's order with the multiplier block already sign-flipped
     const double* dz = dz_in ? dz_in : ctx->v2;
     hipLaunchKernelGGL(k_step_lengths, dim3(1), dim3(256), 0, ctx->stream, ctx->partial, ctx->s, ctx->lda + g.me,
@@ -2727,7 +2663,7 @@ static int merit_scratch(Ctx* ctx) {
 }
 static const double* merit_direction(Ctx* ctx, const double* dz, const char* who) {
     if (dz) return dz;
-    if (!ctx->have_direction) { ctx->err = std::string(who) + ": no direction (solve with flip first, or pass dz)"; return nullptr; }
+    if (!ctx->held.have_direction) { ctx->err = std::string(who) + ": no direction (solve with flip first, or pass dz)"; return nullptr; }
     return ctx->v2;
 }
 
@@ -2737,15 +2673,13 @@ static const double* merit_direction(Ctx* ctx, const double* dz, const char* who
 //   [5..8] the KKT report |dL/dx|, |s (lda_i - mu/(s+eps))|, |ce|, |ci - s| (2-norms; from g = -grad: NaN before residual())
 //   [9] sum s lda_i  [10] min s lda_i  [11] |dx|_2  [12] |ds|_2
 int pyipm_newton_merit_info(pyipm_newton_ctx* h, const double* dz, double* out) try {
-    if (check_ctx(h) || !out) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); const Geo& g = ctx->g;
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("merit_info", G_SINGLE | G_DEVICE) const Geo& g = ctx->g;
+    if (!out) return PYIPM_E_BADARG;
     if (g.world != 1) { ctx->err = "merit_info: single-rank handles"; return PYIPM_E_BADARG; }
-    if (!ctx->have_vectors) { ctx->err = "merit_info: stage vectors first"; return PYIPM_E_BADARG; }
+    if (!ctx->held.have_vectors) { ctx->err = "merit_info: stage vectors first"; return PYIPM_E_BADARG; }
     int rc = merit_scratch(ctx); if (rc) return rc;
-    const double* d = dz ? dz : (ctx->have_direction ? ctx->v2 : nullptr);
-    const double* gres = ctx->have_rhs ? ctx->rhs : nullptr;
+    const double* d = dz ? dz : (ctx->held.have_direction ? ctx->v2 : nullptr);
+    const double* gres = ctx->held.have_rhs ? ctx->rhs : nullptr;
     double* part = ctx->merit_buf; double* res = part + MERIT_NB * MERIT_NQ;
     hipLaunchKernelGGL(k_merit_info, dim3(MERIT_NB), dim3(256), 0, ctx->stream, part, g, ctx->df, ctx->ce, ctx->ci, ctx->s,
                        ctx->lda, d, gres, ctx->eps);
@@ -2768,9 +2702,8 @@ int pyipm_newton_merit_info(pyipm_newton_ctx* h, const double* dz, double* out) 
 // out[p] = a_p . b_p, count <= 8 pairs of device vectors (host array of device pointers); fixed summation order.
 int pyipm_newton_dots(pyipm_newton_ctx* h, int count, const double* const* a, const double* const* b, const int64_t* len,
                       double* out) try {
-    if (check_ctx(h) || !a || !b || !len || !out || count < 1 || count > 8) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("dots", G_DEVICE)
+    if (!a || !b || !len || !out || count < 1 || count > 8) return PYIPM_E_BADARG;
     int rc = merit_scratch(ctx); if (rc) return rc;
     DotPairs dp; memset(&dp, 0, sizeof(dp));
     for (int p = 0; p < count; ++p) { dp.a[p] = a[p]; dp.b[p] = b[p]; dp.len[p] = len[p]; if ((!a[p] || !b[p]) && len[p] > 0) return PYIPM_E_BADARG; }
@@ -2787,12 +2720,10 @@ int pyipm_newton_dots(pyipm_newton_ctx* h, int count, const double* const* a, co
 // next solve / stage_vectors.  quad: NULL = dx' d2L dx from the staged block, else *quad (a caller whose Q is not staged).
 int pyipm_newton_merit_ray(pyipm_newton_ctx* h, const double* dz, double nu, double mu, const double* quad,
                            const double* alphas, int K, double* out) try {
-    if (check_ctx(h) || !alphas || !out || K < 1 || K > 1024) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); const Geo& g = ctx->g;
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("merit_ray", G_SINGLE | G_DEVICE) const Geo& g = ctx->g;
+    if (!alphas || !out || K < 1 || K > 1024) return PYIPM_E_BADARG;
     if (g.world != 1 || ctx->sharded) { ctx->err = "merit_ray: single-rank handles with fully staged blocks"; return PYIPM_E_BADARG; }
-    if (!ctx->have_vectors || !ctx->have_blocks) { ctx->err = "merit_ray: stage blocks and vectors first"; return PYIPM_E_BADARG; }
+    if (!ctx->held.have_vectors || !ctx->held.have_blocks) { ctx->err = "merit_ray: stage blocks and vectors first"; return PYIPM_E_BADARG; }
     const double* d = merit_direction(ctx, dz, "merit_ray"); if (!d) return PYIPM_E_BADARG;
     if (!quad && !ctx->d2L) { ctx->err = "merit_ray: no d2L block staged (pass quad = dx' Q dx)"; return PYIPM_E_BADARG; }
     int rc = merit_scratch(ctx); if (rc) return rc;
@@ -2801,17 +2732,17 @@ int pyipm_newton_merit_ray(pyipm_newton_ctx* h, const double* dz, double nu, dou
     double* qd = ctx->ray_buf; double* dce = qd + g.n; double* dci = dce + g.me;
     double* gq = ctx->merit_buf + MERIT_NB * MERIT_NQ + MERIT_NQ;
     double* dal = gq + 2 + 8; double* dout = dal + 1024;
-    if (ctx->ray_for != d || !ctx->ray_valid) {
+    if (ctx->ray_for != d || !ctx->held.ray_valid) {
         rc = block_products_dev(ctx, d, quad ? nullptr : qd, g.me ? dce : nullptr, g.mi ? dci : nullptr); if (rc) return rc;
         DotPairs dp; memset(&dp, 0, sizeof(dp));
         dp.a[0] = ctx->df; dp.b[0] = d; dp.len[0] = g.n;
         dp.a[1] = d; dp.b[1] = qd; dp.len[1] = quad ? 0 : g.n;
         hipLaunchKernelGGL(k_dots, dim3(2), dim3(1024), 0, ctx->stream, gq, dp);
         PYIPM_KCHECK();
-        ctx->ray_for = d; ctx->ray_valid = true; ctx->ray_quad_given = quad != nullptr;
+        ctx->ray_for = d; ctx->held.ray_formed(); ctx->ray_quad_given = quad != nullptr;
     }
     if (quad) PYIPM_HIP(hipMemcpyAsync(gq + 1, quad, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    else if (ctx->ray_quad_given) { ctx->ray_valid = false; ctx->err = "merit_ray: quad given for this direction before, missing now"; return PYIPM_E_BADARG; }
+    else if (ctx->ray_quad_given) { ctx->held.ray_dropped(); ctx->err = "merit_ray: quad given for this direction before, missing now"; return PYIPM_E_BADARG; }
     PYIPM_HIP(hipMemcpyAsync(dal, alphas, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_merit_ray, dim3((unsigned)K), dim3(256), 0, ctx->stream, dout, dal, g, gq, ctx->ce, dce, ctx->ci, dci,
                        ctx->s, d + g.n, nu, mu);
@@ -2823,40 +2754,30 @@ int pyipm_newton_merit_ray(pyipm_newton_ctx* h, const double* dz, double nu, dou
 
 // ---- per-panel phases -----------------------------------------------------------------------------
 int pyipm_newton_factor_begin(pyipm_newton_ctx* h) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); PYIPM_HIP(hipSetDevice(ctx->device));
-    if (ctx->batched) return single_only(ctx);
-    if (!ctx->assembled) { ctx->err = "factor_begin: assemble first"; return PYIPM_E_BADARG; }
-    if (ctx->cond_active) { ctx->err = "per-panel phases do not apply to the condensed system; use factor()"; return PYIPM_E_BADARG; }
+    PYIPM_ENTER("factor_begin", G_SINGLE | G_DEVICE)
+    if (!ctx->held.assembled) { ctx->err = "factor_begin: assemble first"; return PYIPM_E_BADARG; }
+    if (ctx->held.cond_active) { ctx->err = "per-panel phases do not apply to the condensed system; use factor()"; return PYIPM_E_BADARG; }
     ctx->sched.clear();                                 // per-panel phases: uniform group map, dense panels
-    ctx->zeros_clean = false;                           // (the caller drives the panels: no promise about what gets written)
+    ctx->held.panel_phases_begun();
     return factor_begin(ctx);
 } PYIPM_CATCH_H(h)
 int pyipm_newton_factor_end(pyipm_newton_ctx* h, pyipm_factor_stats* stats) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); PYIPM_HIP(hipSetDevice(ctx->device));
-    if (ctx->batched) return single_only(ctx);
-    ctx->assembled = false;
+    PYIPM_ENTER("factor_end", G_SINGLE | G_DEVICE)
+    ctx->held.factor_enqueued();
     return factor_end(ctx, stats);
 } PYIPM_CATCH_H(h)
 int pyipm_newton_factor_panel(pyipm_newton_ctx* h, int64_t p) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); PYIPM_HIP(hipSetDevice(ctx->device));
-    if (ctx->batched) return single_only(ctx);
+    PYIPM_ENTER("factor_panel", G_SINGLE | G_DEVICE)
     return factor_panel(ctx, p, ctx->stream, false);
 } PYIPM_CATCH_H(h)
 int pyipm_newton_trailing_update(pyipm_newton_ctx* h, int64_t p) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); PYIPM_HIP(hipSetDevice(ctx->device));
-    if (ctx->batched) return single_only(ctx);
+    PYIPM_ENTER("trailing_update", G_SINGLE | G_DEVICE)
     if (p < 0 || p >= ctx->g.npanels) return PYIPM_E_BADARG;
     return trailing_update(ctx, p);
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_trailing_update_range(pyipm_newton_ctx* h, int64_t p, int64_t first, int64_t count) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); PYIPM_HIP(hipSetDevice(ctx->device));
-    if (ctx->batched) return single_only(ctx);
+    PYIPM_ENTER("trailing_update_range", G_SINGLE | G_DEVICE)
     const Geo& g = ctx->g;
     if (p < 0 || p >= g.npanels || first <= p || count < 0) return PYIPM_E_BADARG;
     if (g.panel_c0(p) + g.panel_w(p) >= g.Npad) return PYIPM_OK;
@@ -2872,21 +2793,19 @@ int pyipm_newton_trailing_update_range(pyipm_newton_ctx* h, int64_t p, int64_t f
 
 // message = [ W rows below the panel (m x nbw, column-major, ld = m) | nbw/64 tile inverses | nbw/64 tiles | nbw/64 flags ]
 size_t pyipm_newton_panel_msg_bytes(pyipm_newton_ctx* h, int64_t p) try {
-    if (check_ctx(h)) return 0;
-    const Geo& g = C(h)->g;
+    Ctx* ctx; if (enter(h, "panel_msg_bytes", 0, &ctx)) return 0;
+    const Geo& g = ctx->g;
     if (p < 0 || p >= g.npanels) return 0;
-    if (panel_in_s(C(h), p)) return 0;                    // slack-block panel: every rank derives what it needs locally
+    if (panel_in_s(ctx, p)) return 0;                    // slack-block panel: every rank derives what it needs locally
     int64_t h0, h1;
-    panel_hole(C(h), p, &h0, &h1);
+    panel_hole(ctx, p, &h0, &h1);
     const int64_t nbw = g.panel_w(p), m = g.Npad - (g.panel_c0(p) + nbw) - (h1 - h0);    // slack rows of an x panel stay home
     return (size_t)(m * nbw + 2 * (nbw / TB) * TB * TB + nbw / TB) * sizeof(double);
 } PYIPM_CATCH_SIZE
 
 int pyipm_newton_panel_pack(pyipm_newton_ctx* h, int64_t p, double* buf) try {
-    if (check_ctx(h) || !buf) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); const Geo& g = ctx->g;
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("panel_pack", G_SINGLE | G_DEVICE) const Geo& g = ctx->g;
+    if (!buf) return PYIPM_E_BADARG;
     if (p < 0 || p >= g.npanels || g.owner(p) != g.rank) { ctx->err = "panel_pack: not the owner"; return PYIPM_E_BADARG; }
     int64_t h0, h1;
     panel_hole(ctx, p, &h0, &h1);
@@ -2910,56 +2829,48 @@ int pyipm_newton_panel_pack(pyipm_newton_ctx* h, int64_t p, double* buf) try {
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_panel_unpack(pyipm_newton_ctx* h, int64_t p, const double* buf) try {
-    if (check_ctx(h) || !buf) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); const Geo& g = ctx->g;
-    if (ctx->batched) return single_only(ctx);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("panel_unpack", G_SINGLE | G_DEVICE) const Geo& g = ctx->g;
+    if (!buf) return PYIPM_E_BADARG;
     if (p < 0 || p >= g.npanels || g.owner(p) == g.rank) { ctx->err = "panel_unpack: owner does not unpack"; return PYIPM_E_BADARG; }
     { int rc = unpack_panel_from(ctx, p, buf, 0, /*with_tiles=*/true, ctx->stream); if (rc) return rc; }
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_fwd_panel(pyipm_newton_ctx* h, int64_t p, double* v) try {
-    if (check_ctx(h) || !v) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); PYIPM_HIP(hipSetDevice(ctx->device));
-    if (ctx->batched) return single_only(ctx);
+    PYIPM_ENTER("fwd_panel", G_SINGLE | G_DEVICE)
+    if (!v) return PYIPM_E_BADARG;
     if (p < 0 || p >= ctx->g.npanels || ctx->g.owner(p) != ctx->g.rank) return PYIPM_E_BADARG;
     return fwd_panel(ctx, p, v);
 } PYIPM_CATCH_H(h)
 int pyipm_newton_diag_panel(pyipm_newton_ctx* h, int64_t p, double* v) try {
-    if (check_ctx(h) || !v) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); PYIPM_HIP(hipSetDevice(ctx->device));
-    if (ctx->batched) return single_only(ctx);
+    PYIPM_ENTER("diag_panel", G_SINGLE | G_DEVICE)
+    if (!v) return PYIPM_E_BADARG;
     if (p < 0 || p >= ctx->g.npanels) return PYIPM_E_BADARG;
     return diag_panel(ctx, p, v);
 } PYIPM_CATCH_H(h)
 int pyipm_newton_bwd_panel(pyipm_newton_ctx* h, int64_t p, double* v) try {
-    if (check_ctx(h) || !v) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h); PYIPM_HIP(hipSetDevice(ctx->device));
-    if (ctx->batched) return single_only(ctx);
+    PYIPM_ENTER("bwd_panel", G_SINGLE | G_DEVICE)
+    if (!v) return PYIPM_E_BADARG;
     if (p < 0 || p >= ctx->g.npanels || ctx->g.owner(p) != ctx->g.rank) return PYIPM_E_BADARG;
     return bwd_panel(ctx, p, v);
 } PYIPM_CATCH_H(h)
 
 // ---- introspection --------------------------------------------------------------------------------
 int pyipm_newton_kkt_storage(pyipm_newton_ctx* h, double** ptr, int64_t* ld, int64_t* ncols) try {
-    if (check_ctx(h)) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
-    if (ptr) { *ptr = ctx->A; ctx->zeros_clean = false; ctx->storage_exported = true; }   // the caller may write through it, now or
-                                                                // later: every assembly is a full one until "keep_zeros" is set again
-    if (ld) *ld = ctx->cond_active ? ctx->gc.Npad : ctx->g.Npad;
-    if (ncols) *ncols = ctx->cond_active ? ctx->gc.ncols_local : ctx->g.ncols_local;
+    PYIPM_ENTER("kkt_storage", 0)
+    if (ptr) { *ptr = ctx->A; ctx->held.storage_handed_out(); }
+    if (ld) *ld = ctx->held.cond_active ? ctx->gc.Npad : ctx->g.Npad;
+    if (ncols) *ncols = ctx->held.cond_active ? ctx->gc.ncols_local : ctx->g.ncols_local;
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_last_timings(pyipm_newton_ctx* h, double out[8]) try {
-    if (check_ctx(h) || !out) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
-    PYIPM_HIP(hipSetDevice(ctx->device));
+    PYIPM_ENTER("last_timings", G_DEVICE)
+    if (!out) return PYIPM_E_BADARG;
     PYIPM_HIP(hipStreamSynchronize(ctx->stream));          // timers are resolved lazily, never inside a step
     if (ctx->batched) {                                    // step_batched: [0] residual + assembly, [6] factorisation, [3] substitutions, [1] whole step
         for (int k = 0; k < 8; ++k) out[k] = 0.0;
-        if (ctx->ev_assemble_valid) {
+        if (ctx->held.ev_assemble_valid) {
             float a = 0.f, f = 0.f, sv = 0.f, all = 0.f;
             PYIPM_HIP(hipEventElapsedTime(&a, ctx->ev[0], ctx->ev[2])); PYIPM_HIP(hipEventElapsedTime(&f, ctx->ev[2], ctx->ev[3]));
             PYIPM_HIP(hipEventElapsedTime(&sv, ctx->ev[3], ctx->ev[1])); PYIPM_HIP(hipEventElapsedTime(&all, ctx->ev[0], ctx->ev[1]));
@@ -2967,17 +2878,17 @@ int pyipm_newton_last_timings(pyipm_newton_ctx* h, double out[8]) try {
         }
         return PYIPM_OK;
     }
-    if (ctx->ev_assemble_valid) { float ms = 0.f; PYIPM_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3])); ctx->t_assemble = ms; }
-    if (ctx->ev_solve_valid) { float ms = 0.f; PYIPM_HIP(hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5])); ctx->t_solve = ms; }
+    if (ctx->held.ev_assemble_valid) { float ms = 0.f; PYIPM_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3])); ctx->t_assemble = ms; }
+    if (ctx->held.ev_solve_valid) { float ms = 0.f; PYIPM_HIP(hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5])); ctx->t_solve = ms; }
     out[0] = ctx->t_assemble; out[1] = ctx->t_panel; out[2] = ctx->t_trailing; out[3] = ctx->t_solve;
     out[4] = (double)(ctx->n_trailing_real > 0 ? ctx->n_trailing_real : ctx->n_trailing); out[5] = ctx->trailing_flops; out[6] = ctx->t_factor;
-    out[7] = ctx->cond_active ? ctx->t_gram : ctx->trailing_area;   // full system: entries updated by the trailing launches
+    out[7] = ctx->held.cond_active ? ctx->t_gram : ctx->trailing_area;   // full system: entries updated by the trailing launches
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_trailing_instances(pyipm_newton_ctx* h, double out[8]) try {
-    if (check_ctx(h) || !out) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
+    PYIPM_ENTER("trailing_instances", 0)
+    if (!out) return PYIPM_E_BADARG;
     for (int k = 0; k < 2; ++k) {
         out[4 * k + 0] = (double)ctx->inst_n[k]; out[4 * k + 1] = ctx->inst_ms[k];
         out[4 * k + 2] = ctx->inst_flops[k]; out[4 * k + 3] = ctx->inst_area[k];
@@ -2989,15 +2900,15 @@ int pyipm_newton_trailing_instances(pyipm_newton_ctx* h, double out[8]) try {
 // out[k] = C tiles only (16 B per updated entry: read once, written once), out[2 + k] = C tiles + the two operand panels read once
 // (what trailing_instances reports); k = 0: 128 x 128 tiles, k = 1: 128 x 256.  Sums over the launches of the last factorisation.
 int pyipm_newton_trailing_bytes(pyipm_newton_ctx* h, double out[4]) try {
-    if (check_ctx(h) || !out) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
+    PYIPM_ENTER("trailing_bytes", 0)
+    if (!out) return PYIPM_E_BADARG;
     for (int k = 0; k < 2; ++k) { out[k] = ctx->inst_cbytes[k]; out[2 + k] = ctx->inst_area[k]; }
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_set_option(pyipm_newton_ctx* h, const char* name, double value) try {
-    if (check_ctx(h) || !name) return PYIPM_E_BADARG;
-    Ctx* ctx = C(h);
+    PYIPM_ENTER("set_option", 0)
+    if (!name) return PYIPM_E_BADARG;
     if (!strcmp(name, "expert")) { ctx->expert = (int)value != 0; return PYIPM_OK; }
     {   // expert switches (include/pyipm_newton.h): measurement knobs, test hooks, parked experiments
         static const char* const kExpert[] = {
@@ -3049,7 +2960,7 @@ int pyipm_newton_set_option(pyipm_newton_ctx* h, const char* name, double value)
     { bool handled = false; int rc = dist_set_option(ctx, name, value, &handled); if (handled) return rc; }
     if (!strcmp(name, "tile_step")) { ctx->tile_step = (int)value != 0; return PYIPM_OK; }
     if (!strcmp(name, "group_chain")) { ctx->group_chain = (int)value != 0; return PYIPM_OK; }
-    if (!strcmp(name, "keep_zeros")) { ctx->keep_zeros = (int)value != 0; ctx->zeros_clean = false; ctx->storage_exported = false; return PYIPM_OK; }
+    if (!strcmp(name, "keep_zeros")) { ctx->keep_zeros = (int)value != 0; ctx->held.keep_zeros_set(); return PYIPM_OK; }
     if (!strcmp(name, "wide_sub")) { ctx->wide_sub = (int)value; return PYIPM_OK; }
     if (!strcmp(name, "sweep_persist")) { ctx->sweep_persist = (int)value; return PYIPM_OK; }
     if (!strcmp(name, "sweep_max_blocks")) { ctx->sweep_max_blocks = (int)value; return PYIPM_OK; }

@@ -12,7 +12,7 @@ and exactly zero rows, at shapes that reach every regime of the single-rank sche
     9216             (1024, 0, 4096)            early0, tail groups of 4
     11504 (11520)    (5003, 701, 2900), nb 512  every chain exposed (<= tile8_rows), groups of 4
     17001 (17024)    (9001, 0, 4000), nb 128    non-exposed chains as k_tile_step, reserved CUs (> persist_rows)
-    17000 (17024)    (12007, 4993, 0)           no slack block: no panels enqueued up front / grp_fast
+    17000 (17024)    (12007, 4993, 0)           no slack block: no panels enqueued up front / no fast group (GroupSched::fast)
     23545 (23552)    (12345, 2000, 4600)        128 x 256 bulk tiles (> BULK_BN_ROWS)
     29928 (29952)    (14001, 3001, 6463)        groups of 8 panels before the tail (> TAIL_COLS)
 
