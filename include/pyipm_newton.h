@@ -386,6 +386,28 @@ int pyipm_newton_stats_batched(pyipm_newton_ctx* ctx, pyipm_factor_stats* stats)
  * kkt_matvec check of a single system.  out: batch doubles, host or device per memkind. */
 int pyipm_newton_backward_error_batched(pyipm_newton_ctx* ctx, const double* dz, double* out, int memkind);
 
+/* A batched step with every problem's OWN barrier parameter and shifts: after the first barrier update (pyipm.py:1804-1814)
+ * and the first reghess (pyipm.py:1373-1406, which persists one delta per system) no two problems of a multi-start batch share
+ * them.  mu, delta, delta_c: batch doubles; active: batch flags or NULL = every problem; host or device per memkind, copied on
+ * the handle's stream.  The handle keeps, per problem, the values of the last step the problem took part in (step_batched
+ * fills them with its scalars and stage_vectors' mu, every problem active; backward_error_batched reads each problem's own).
+ * A problem with active[b] == 0 sits the step out: every kernel of the step returns at once for it, its row of dz is NOT
+ * written, its statistics record, its mu / delta / delta_c and the scale of its static pivots stay those of its last step --
+ * a retry of the one problem of 512 whose inertia came out wrong leaves the directions of the other 511 alone.
+ * Both forms (full, condensed).  Returns once the launches are enqueued, like step_batched(stats = NULL) (host output: once
+ * the rows of the active problems have arrived); statistics through pyipm_newton_stats_batched.
+ * PYIPM_E_BADARG: not a batched handle, blocks / vectors not staged, NULL mu / delta / delta_c / dz. */
+int pyipm_newton_step_batched_each(pyipm_newton_ctx* ctx, const double* mu, const double* delta, const double* delta_c,
+                                   const int32_t* active, double* dz, int memkind);
+
+/* The fraction-to-the-boundary rule (pyipm.py:1408-1436, the two IPM.step calls at 1737-1742) for every problem of a batch in
+ * one launch, one wave per problem: alpha[b] = (alpha_s, alpha_l), the closed form of pyipm_newton_step_lengths with its
+ * arithmetic entry by entry -- bit for bit what a single-system handle returns for that problem; (1, 1) when mi == 0.
+ * dz: DEVICE [batch][N], multiplier block sign-flipped as the steps return it; NULL = the directions of the last step, which
+ * the handle keeps only where that step's output was host memory (PYIPM_E_BADARG otherwise: pass the tensor the step wrote).
+ * alpha: [batch][2], host or device per memkind (host: synchronises).  Needs stage_vectors. */
+int pyipm_newton_step_lengths_batched(pyipm_newton_ctx* ctx, double tau, const double* dz, double* alpha, int memkind);
+
 /* ---- introspection for tests / bench ------------------------------------------------------ */
 
 /* Device pointer + leading dimension of the local KKT storage (column-major lower).  The caller may write through the
@@ -501,8 +523,9 @@ int pyipm_newton_set_option(pyipm_newton_ctx* ctx, const char* name, double valu
 /* Version of this interface: bumped whenever an entry point changes its argument list (round 5 added `dz` to
  * pyipm_newton_step_lengths in place: a caller built against the older header would have passed a host pointer where the
  * device direction goes).  A binding checks pyipm_newton_abi_version() == PYIPM_NEWTON_ABI_VERSION of the header it was
- * written against before any other call (pyipm_amd/newton.py does). */
-#define PYIPM_NEWTON_ABI_VERSION 6
+ * written against before any other call (pyipm_amd/newton.py does).  7: step_batched_each, step_lengths_batched; the
+ * workspace of a batched handle grew by the per-problem parameters. */
+#define PYIPM_NEWTON_ABI_VERSION 7
 int pyipm_newton_abi_version(void);
 
 /* fp64 MFMA peak micro-benchmark: register-resident v_mfma_f64_16x16x4_f64 only.

@@ -113,25 +113,9 @@ class BatchedNewton(object):
         d2L (B,n,n), Je (B,n,me), Ji (B,n,mi), df (B,n), ce (B,me), ci (B,mi), s (B,mi), lda (B,me+mi).
         Returns (dz (B,N) device tensor, list of per-problem factor statistics)."""
         torch = self.torch
-        n, me, mi = self.n, self.me, self.mi
-
-        def dev(a, shape):
-            return to_device(a, self.device, shape)
-
-        B = int(d2L.shape[0])
-        if self.h is None or B != self.batch:
-            self._create(B)
-        blocks = (dev(d2L, (B, n, n)), dev(Je, (B, n, me)) if me else None, dev(Ji, (B, n, mi)) if mi else None)
-        vecs = (dev(df, (B, n)), dev(ce, (B, me)) if me else None, dev(ci, (B, mi)) if mi else None,
-                dev(s, (B, mi)) if mi else None, dev(lda, (B, me + mi)) if (me + mi) else None)
-        self._keep = (blocks, vecs)            # the library retains the block pointers
-
-        self._ck(self.lib.pyipm_newton_set_stream(self.h, c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
-        self._ck(self.lib.pyipm_newton_stage_blocks_batched(self.h, ptr(blocks[0]), n, n * n, ptr(blocks[1]), me, n * me,
-                                                            ptr(blocks[2]), mi, n * mi))
-        self._ck(self.lib.pyipm_newton_stage_vectors(self.h, ptr(vecs[0]), ptr(vecs[1]), ptr(vecs[2]), ptr(vecs[3]),
-                                                     ptr(vecs[4]), float(mu), float(eps), MEM_DEVICE))
-        out = torch.empty((B, self.N), dtype=torch.float64, device=self.device)
+        me, mi = self.me, self.mi
+        B = self.stage(d2L, Je, Ji, df, ce, ci, s, lda, mu=mu, eps=eps)
+        out = self._last_out = torch.empty((B, self.N), dtype=torch.float64, device=self.device)
         # the step is five launches and returns once they are enqueued; the B statistics records stay on the device until somebody
         # looks at them (LazyStats: round 6 -- copying and unpacking 512 records per step was a third of the step's wall time)
         self._ck(self.lib.pyipm_newton_step_batched(self.h, float(delta), float(delta_c), ptr(out), None, MEM_DEVICE))
@@ -155,6 +139,157 @@ class BatchedNewton(object):
                 finally:
                     self._ck(self.lib.pyipm_newton_set_option(self.h, b"condensed", 1.0))
         return out, stats
+
+    def stage(self, d2L, Je=None, Ji=None, df=None, ce=None, ci=None, s=None, lda=None, mu=0.2,
+              eps=float(np.finfo(np.float64).eps)):
+        """Stage the blocks and vectors of a batch (arguments as ``step_all``'s; the handle is created for the batch's size
+        when there is none of that size).  ``mu`` is the one ``step_all`` steps with; ``step_each`` brings its own.
+        Returns the batch size."""
+        torch = self.torch
+        n, me, mi = self.n, self.me, self.mi
+
+        def dev(a, shape):
+            return to_device(a, self.device, shape)
+
+        B = int(d2L.shape[0])
+        if self.h is None or B != self.batch:
+            self._create(B)
+        blocks = (dev(d2L, (B, n, n)), dev(Je, (B, n, me)) if me else None, dev(Ji, (B, n, mi)) if mi else None)
+        vecs = (dev(df, (B, n)), dev(ce, (B, me)) if me else None, dev(ci, (B, mi)) if mi else None,
+                dev(s, (B, mi)) if mi else None, dev(lda, (B, me + mi)) if (me + mi) else None)
+        self._keep = (blocks, vecs)            # the library retains the block pointers
+
+        self._ck(self.lib.pyipm_newton_set_stream(self.h, c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        self._ck(self.lib.pyipm_newton_stage_blocks_batched(self.h, ptr(blocks[0]), n, n * n, ptr(blocks[1]), me, n * me,
+                                                            ptr(blocks[2]), mi, n * mi))
+        self._ck(self.lib.pyipm_newton_stage_vectors(self.h, ptr(vecs[0]), ptr(vecs[1]), ptr(vecs[2]), ptr(vecs[3]),
+                                                     ptr(vecs[4]), float(mu), float(eps), MEM_DEVICE))
+        self._eps = float(eps)
+        self._last_out = None                  # (directions of other vectors)
+        return B
+
+    def _per_problem(self, x, dtype):
+        """A scalar or (B,) array / tensor as a contiguous device tensor of B entries."""
+        torch = self.torch
+        if isinstance(x, torch.Tensor):
+            return x.to(device=self.device, dtype=dtype).expand(self.batch).contiguous()
+        a = np.broadcast_to(np.asarray(x, dtype=np.float64 if dtype == torch.float64 else np.int32), (self.batch,)).copy()
+        return torch.from_numpy(a).to(self.device)
+
+    def step_each(self, mu, delta, delta_c, active=None, out=None):
+        """One step on the blocks / vectors staged last (``stage`` or ``step_all``) with each problem's own ``mu``, ``delta``,
+        ``delta_c`` (scalars or (B,)), for the problems ``active`` selects ((B,) flags; None = all): the thin call over
+        ``pyipm_newton_step_batched_each``.  A problem that sits out keeps its row of ``out``, its statistics record and its
+        parameters in the handle.  ``out``: the (B, N) device tensor to write into -- e.g. the one an earlier step returned;
+        None = a new one, whose rows of inactive problems are NaN.  Returns (dz, LazyStats); no guard, no fallback here."""
+        torch = self.torch
+        if self.h is None:
+            raise NewtonError("step_each: stage a batch first (stage / step_all)")
+        f64 = torch.float64
+        pm, pd, pc = (self._per_problem(x, f64) for x in (mu, delta, delta_c))
+        pa = None if active is None else self._per_problem(active, torch.int32)
+        if out is None:
+            out = torch.empty((self.batch, self.N), dtype=f64, device=self.device)
+            if pa is not None:
+                out.fill_(float("nan"))
+        elif tuple(out.shape) != (self.batch, self.N) or out.dtype != f64 or not out.is_contiguous() or out.device != self.device:
+            raise NewtonError("step_each: out must be a contiguous float64 (B, N) tensor on the handle's device")
+        self._ck(self.lib.pyipm_newton_set_stream(self.h, c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        self._ck(self.lib.pyipm_newton_step_batched_each(self.h, ptr(pm), ptr(pd), ptr(pc), ptr(pa), ptr(out), MEM_DEVICE))
+        self._step_id += 1
+        self._last_out = out
+        return out, LazyStats(self, self._step_id)
+
+    def step_lengths_all(self, tau, dz=None):
+        """Fraction-to-the-boundary step lengths of every problem (pyipm.py:1408-1436) for the staged s, lda and the directions
+        ``dz`` ((B, N) device tensor; None = what the last step returned): device tensor (B, 2) of (alpha_s, alpha_l)."""
+        torch = self.torch
+        if dz is None:
+            dz = self._last_out
+            if dz is None:
+                raise NewtonError("step_lengths_all: no direction (step first, or pass dz)")
+        dz = to_device(dz, self.device, (self.batch, self.N))
+        al = torch.empty((self.batch, 2), dtype=torch.float64, device=self.device)
+        self._ck(self.lib.pyipm_newton_set_stream(self.h, c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        self._ck(self.lib.pyipm_newton_step_lengths_batched(self.h, float(tau), ptr(dz), ptr(al), MEM_DEVICE))
+        return al
+
+    n_factor = 0                           # passes over the batch (direction_all)
+    n_inertia_retries = 0                  # problem x shifted pass whose inertia was still wrong (delta *= 10, pyipm.py:1399-1403)
+    _shift_info = None
+
+    def shift_info(self):
+        """What the last ``direction_all`` decided, per problem: ``failed`` (entered the shift loop), ``suspect`` (the
+        pivot-level ``rcond <= eps`` trigger fired on pass 1), ``delta_c`` (what its retry passes were given), ``delta`` (the
+        shift its last pass ran with; 0 where none), ``passes`` (retry passes it took part in)."""
+        return self._shift_info
+
+    def direction_all(self, d2L, Je, Ji, df, ce, ci, s, lda, mu, delta=0.0, eta=1e-4, beta=0.4, reg_coef=None, delta0=None,
+                      max_shift_tries=60):
+        """``reghess`` + solve (pyipm.py:1373-1406, 1717-1725) per problem of the batch, in the order ``HipNewtonBackend.direction``
+        uses; ``mu`` and ``delta`` (the delta each problem persists from its last call) are scalars or (B,).
+        Pass 1: no shifts, every problem.  A problem fails when its inertia is wrong (n_neg != me + mi), a NaN / Inf was met, or
+        it is suspect singular (static pivots, or d_min / d_max <= eps on its block pivots: the pivot-level trigger for the
+        reference's rcond <= eps -- there is no condition estimate on this path).  Failing problems get delta_c (suspect and
+        me > 0) and delta0 / max(delta / 2, delta0), and are stepped again ALONE (``active``) with delta *= 10 until their
+        inertia is right; the others keep the bits of pass 1.  With ``condensed`` pass 1 is condensed, a problem that misses
+        the guard fails too, and the retry passes run in the full form.
+        Returns (dz, delta (B,) float64, list of statistics): delta as the reference persists it, unchanged without a shift."""
+        torch = self.torch
+        me, mi, need = self.me, self.mi, self.me + self.mi
+        eps = float(np.finfo(np.float64).eps)
+        reg_coef = float(np.sqrt(eps)) if reg_coef is None else float(reg_coef)      # pyipm.py:353
+        delta0 = reg_coef if delta0 is None else float(delta0)                       # pyipm.py:372
+        B = self.stage(d2L, Je, Ji, df, ce, ci, s, lda, mu=float(np.asarray(mu, dtype=np.float64).reshape(-1)[0]), eps=eps)
+        mu_v = np.broadcast_to(np.asarray(mu, dtype=np.float64), (B,)).copy()
+        delta_v = np.broadcast_to(np.asarray(delta, dtype=np.float64), (B,)).copy()
+        dc_v, zero = np.zeros(B), np.zeros(B)
+        out, st = self.step_each(mu_v, zero, zero)
+        self.n_factor += 1
+        stats = list(st)
+
+        def wrong(x):
+            return x["n_neg"] != need or bool(x["nonfinite"])
+
+        def suspect(x):
+            return bool(x["nonfinite"]) or x["n_zero"] > 0 or (x["d_max"] > 0 and x["d_min"] / x["d_max"] <= eps)
+
+        sus = np.array([suspect(x) for x in stats])
+        failed = np.array([wrong(x) for x in stats]) | sus
+        cond = bool(self._opts_get("condensed")) and mi > 0
+        if cond and self.guard:
+            be = self.last_backward_errors = self.backward_errors(out)
+            failed |= ((be > self.condensed_tol) | ~torch.isfinite(be)).cpu().numpy()
+        passes = np.zeros(B, dtype=np.int64)
+        fail = np.flatnonzero(failed)
+        for b in fail:
+            dc_v[b] = reg_coef * eta * mu_v[b] ** beta if (sus[b] and me) else 0.0
+            delta_v[b] = delta0 if delta_v[b] == 0.0 else max(delta_v[b] / 2.0, delta0)
+        if fail.size and cond:
+            self.n_condensed_fallback += 1
+            self._ck(self.lib.pyipm_newton_set_option(self.h, b"condensed", 0.0))
+        try:
+            tries = 0
+            while fail.size:
+                act = np.zeros(B, dtype=np.int32)
+                act[fail] = 1
+                _, st = self.step_each(mu_v, np.where(act, delta_v, 0.0), np.where(act, dc_v, 0.0), act, out=out)
+                self.n_factor += 1
+                passes[fail] += 1
+                stats = list(st)
+                fail = np.array([b for b in fail if wrong(stats[b])], dtype=np.int64)
+                if fail.size:
+                    tries += 1
+                    self.n_inertia_retries += int(fail.size)
+                    if tries > max_shift_tries:
+                        raise RuntimeError("inertia not corrected after %d diagonal shifts: problems %s" % (tries, fail.tolist()))
+                    delta_v[fail] *= 10.0
+        finally:
+            if failed.any() and cond:
+                self._ck(self.lib.pyipm_newton_set_option(self.h, b"condensed", 1.0))
+        self._shift_info = {"failed": failed.copy(), "suspect": sus, "delta_c": dc_v, "delta": np.where(failed, delta_v, 0.0),
+                            "passes": passes}
+        return out, delta_v, stats
 
     def _fetch_stats(self, step_id):
         if step_id != self._step_id:

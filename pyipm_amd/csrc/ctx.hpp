@@ -182,7 +182,9 @@ struct Held {
     // The owner of the storage wrote a matrix into it (the L-BFGS Gram system): full layout, no residual of this handle's.
     void matrix_written() { assembled = true; factored = false; have_rhs = false; forward_pending = false; cond_active = false; }
     void step_batched_begun(bool condensed) { cond_active = condensed; }
-    void step_batched_enqueued() { have_rhs = true; ev_assemble_valid = true; }   // rhs = g of every problem (backward_error_batched reads it)
+    // rhs = g of every problem (backward_error_batched reads it).  v2 is the staging copy of a HOST output: the directions of the
+    // problems that took part (step_lengths_batched with dz = NULL reads it); a device output is the caller's tensor alone.
+    void step_batched_enqueued(bool host_out) { have_rhs = true; ev_assemble_valid = true; have_direction = host_out; }
     // Factorisation.  Per-panel phases (the caller or the distributed driver drives the panels): no promise about what gets written.
     void panel_phases_begun() { zeros_clean = false; }
     void factor_begun() { forward_fused = false; }
@@ -223,6 +225,11 @@ struct Ctx {
     int batch = 1;                        // problems of a batched small-system handle (kernels_batched.hpp)
     bool batched = false;                 // batched handle: single-system entry points refuse it
     int64_t b_sH = 0, b_sJe = 0, b_sJi = 0;   // batch strides (doubles) of the caller's blocks
+    // per-problem parameters of a batched handle, [batch] each, carved from the workspace (ws owns it): mu, delta, delta_c and
+    // the activity flag of the last step each problem took part in (k_b_begin writes them); b_in / b_in_act: where host arrays
+    // of step_batched_each land before that launch ([3][batch] doubles, [batch] flags); b_alpha: staging of host step lengths
+    double *b_mu = nullptr, *b_delta = nullptr, *b_delta_c = nullptr, *b_in = nullptr, *b_alpha = nullptr;
+    int *b_act = nullptr, *b_in_act = nullptr;
     int device = 0;
     hipStream_t stream = nullptr;         // the caller's: not owned
     Stream side;                          // panel lookahead stream (created on first factor)

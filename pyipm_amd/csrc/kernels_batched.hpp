@@ -23,7 +23,32 @@ struct BatchPtrs {
     const double *d2L, *Je, *Ji; int64_t sH, sJe, sJi, ldh, ldje, ldji;      // caller blocks, batch strides in doubles
     const double *df, *ce, *ci, *s, *lda;  // staged vectors [B][n], [B][me], [B][mi], [B][mi], [B][me+mi]
     unsigned long long* anorm;             // [2 B]: per problem, bits of max |assembled entry| (scale of a static pivot) and the "assembly pending" word (always 0 here)
+    double *pmu, *pdelta, *pdelta_c;       // [B]: barrier parameter and reghess' shifts (pyipm.py:1373-1406) of the last step each problem took part in
+    int* act;                              // [B]: 1 = the problem takes part in the current step; 0 = every kernel of the step returns at once for it
 };
+
+// What a step hands to k_b_begin: per-problem arrays (step_batched_each; active == NULL: every problem) or, where an array
+// pointer is NULL, one scalar for the whole batch (step_batched).
+struct BatchEach {
+    const double *mu, *delta, *delta_c; const int* active;
+    double mu0, delta0, delta_c0;
+};
+
+// First launch of every batched step (grid ceil(B / 256)): the activity flags, and for the problems that take part their
+// parameters and the reset of their anorm words.  A problem that sits out keeps all of it -- mu, shifts, the scale of its
+// static pivots: the values of the last step it took part in.
+__global__ __launch_bounds__(256) void k_b_begin(BatchPtrs bp, BatchEach in, int B)
+{
+    const int b = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (b >= B) return;
+    const int a = in.active ? (in.active[b] != 0 ? 1 : 0) : 1;
+    bp.act[b] = a;
+    if (!a) return;
+    bp.pmu[b] = in.mu ? in.mu[b] : in.mu0;
+    bp.pdelta[b] = in.delta ? in.delta[b] : in.delta0;
+    bp.pdelta_c[b] = in.delta_c ? in.delta_c[b] : in.delta_c0;
+    bp.anorm[2 * b] = 0ull; bp.anorm[2 * b + 1] = 0ull;
+}
 
 // The condensed form of a batched step (round 5; the big path's option, DESIGN section 7b, per problem): inequalities with
 // Sigma_k = lda_k / (s_k + eps) <= sigma_max are eliminated analytically (their Ji Sigma Ji' joins the x-x block), the rest
@@ -40,9 +65,11 @@ struct BatchCond {
 };
 
 // K1 for the batch: grid (Npad/512, Npad/16, B)
-__global__ __launch_bounds__(256) void k_b_assemble(BatchPtrs bp, Geo g, double eps, double delta, double delta_c)
+__global__ __launch_bounds__(256) void k_b_assemble(BatchPtrs bp, Geo g, double eps)
 {
     const int64_t b = blockIdx.z;
+    if (!bp.act[b]) return;
+    const double delta = bp.pdelta[b], delta_c = bp.pdelta_c[b];
     double* A = bp.A + b * bp.sA;
     const double* d2L = bp.d2L + b * bp.sH;
     const double* Je = bp.Je ? bp.Je + b * bp.sJe : nullptr;
@@ -74,9 +101,11 @@ __global__ __launch_bounds__(256) void k_b_assemble(BatchPtrs bp, Geo g, double 
 }
 
 // K2 for the batch: g = -grad (pyipm.py:655-668, 1717).  grid B, 256 threads (one wave per row of the x part).
-__global__ __launch_bounds__(256) void k_b_residual(BatchPtrs bp, Geo g, double mu, double eps)
+__global__ __launch_bounds__(256) void k_b_residual(BatchPtrs bp, Geo g, double eps)
 {
     const int64_t b = blockIdx.x;
+    if (!bp.act[b]) return;
+    const double mu = bp.pmu[b];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t n = g.n, me = g.me, mi = g.mi;
     double* out = bp.rhs + b * bp.sV;
@@ -101,11 +130,13 @@ __global__ __launch_bounds__(256) void k_b_residual(BatchPtrs bp, Geo g, double 
 // Condensed form, step 1 (grid B, 256 threads): the active set of problem b, its full right-hand side g = -grad (bp.rhs: the
 // expansion and the backward-error check read it) and the condensed one (bp.sol, solved in place):
 //   vc = [ g_x + Ji_I (Sigma_I g_i + g_s)_I ; g_e ; (g_i + g_s / Sigma)_A ; 0 ... ]
-__global__ __launch_bounds__(256) void k_bc_prep(BatchPtrs bp, Geo g, double mu, double eps, BatchCond bc)
+__global__ __launch_bounds__(256) void k_bc_prep(BatchPtrs bp, Geo g, double eps, BatchCond bc)
 {
     __shared__ int part[256];
     __shared__ double tsh[512];                         // (mi <= 511: n + 2 mi + me <= 1024)
     const int64_t b = blockIdx.x;
+    if (!bp.act[b]) return;                             // (block-uniform: no barrier is left waiting)
+    const double mu = bp.pmu[b];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t n = g.n, me = g.me, mi = g.mi;
     const double* lda = bp.lda + b * (me + mi);
@@ -231,11 +262,13 @@ __device__ __forceinline__ void bc_store_strip(const BatchPtrs& bp, const Geo& g
     anorm_publish(bp.anorm + 2 * b, amax);
 }
 
-__global__ __launch_bounds__(256) void k_bc_assemble(BatchPtrs bp, Geo g, double eps, double delta, double delta_c, BatchCond bc, int nt0)
+__global__ __launch_bounds__(256) void k_bc_assemble(BatchPtrs bp, Geo g, double eps, BatchCond bc, int nt0)
 {
     __shared__ double XA[TB][TB + 2];
     __shared__ double XB[TB][TB + 2];
     const int64_t b = blockIdx.y;
+    if (!bp.act[b]) return;
+    const double delta = bp.pdelta[b], delta_c = bp.pdelta_c[b];
     const int64_t n = g.n, me = g.me, mi = g.mi;
     const int na = bc.cnt[b];
     const int64_t nc = n + me + na;
@@ -404,11 +437,13 @@ __device__ __forceinline__ void bc_gram_problem(double (&V)[2][64 * NX][34], dou
 }
 
 template <int NX>
-__global__ __launch_bounds__(128 * NX) void k_bc_assemble_p(BatchPtrs bp, Geo g, double eps, double delta, double delta_c, BatchCond bc)
+__global__ __launch_bounds__(128 * NX) void k_bc_assemble_p(BatchPtrs bp, Geo g, double eps, BatchCond bc)
 {
     __shared__ double V[2][64 * NX][34];
     __shared__ double SG[2][32];
     const int64_t b = blockIdx.x;
+    if (!bp.act[b]) return;
+    const double delta = bp.pdelta[b], delta_c = bp.pdelta_c[b];
     const int na = bc.cnt[b];
     const int64_t nc = g.n + g.me + na;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -428,14 +463,15 @@ __global__ __launch_bounds__(128 * NX) void k_bc_assemble_p(BatchPtrs bp, Geo g,
 }
 
 // Backward error of a batch of directions against the KKT blocks (never the factor): out[b] = |g - Hc raw| / |g| with raw the
-// direction with the multiplier flip undone, Hc the full 4-block matrix with the shifts of the last step.  grid B, 256
+// direction with the multiplier flip undone, Hc the full 4-block matrix with each problem's own shifts (bp.pdelta / pdelta_c:
+// those of the last step it took part in).  grid B, 256
 // threads; g = -grad must be in bp.rhs (every batched step leaves it there).  The guard of the condensed form, and a check
 // any caller can afford: O(N^2) per problem.
-__global__ __launch_bounds__(256) void k_b_berr(BatchPtrs bp, Geo g, const double* __restrict__ dz, double eps, double delta,
-                                                double delta_c, double* __restrict__ out)
+__global__ __launch_bounds__(256) void k_b_berr(BatchPtrs bp, Geo g, const double* __restrict__ dz, double eps, double* __restrict__ out)
 {
     __shared__ double red[2][4];
     const int64_t b = blockIdx.x;
+    const double delta = bp.pdelta[b], delta_c = bp.pdelta_c[b];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t n = g.n, me = g.me, mi = g.mi;
     const double* d = dz + b * g.N;
@@ -529,6 +565,7 @@ __global__ __launch_bounds__(256) void k_b_factor(BatchPtrs bp, Geo g, double re
     __shared__ TileScratch sm;
     __shared__ double X[TB][TB + 2];
     const int64_t bi = blockIdx.x, ld = g.Npad;
+    if (!bp.act[bi]) return;                   // (sits this step out: its factor and its statistics record stay)
     const Geo gfull = g;
     int cond_na = 0;
     if (cond_cnt) {
@@ -707,6 +744,7 @@ __global__ void k_b_solve(BatchPtrs bp, Geo g, int nref, int flip, double* __res
     double* y = lds;
     double* w = lds + g.Npad;
     const int64_t bi = blockIdx.x, ld = g.Npad;
+    if (!bp.act[bi]) return;                   // (its row of dz is not written)
     const double* A = bp.A + bi * bp.sA;
     const int tid = threadIdx.x, lane = tid & 63, t = tid >> 6;
     const int na = cond ? bc.cnt[bi] : 0;
@@ -794,6 +832,36 @@ __global__ void k_b_solve(BatchPtrs bp, Geo g, int nref, int flip, double* __res
     }
     bp.sol[bi * bp.sV + tid] = x;
     if (tid < g.N) dz[bi * g.N + tid] = (flip && tid >= g.n + g.mi) ? -x : x;
+}
+
+// Fraction-to-the-boundary step lengths of every problem of a batch (pyipm.py:1408-1436 in closed form): ONE WAVE per problem,
+// four problems per 256-thread block, grid ceil(B / 4).  The lanes stride over the mi inequalities with the arithmetic of
+// k_step_lengths (kernels_assemble.hpp) entry by entry, the minimum crosses the wave by shuffles -- no shared memory, no
+// barrier, no atomics -- and a minimum does not depend on the order it is taken in: the bits of the single-system kernel.
+// out[2 b] = alpha_s, out[2 b + 1] = alpha_l; mi = 0 gives (1, 1).  dz: [B][N], multiplier block sign-flipped.
+__global__ __launch_bounds__(256) void k_b_step_lengths(double* __restrict__ out, const double* __restrict__ s, const double* __restrict__ lda,
+                                                        const double* __restrict__ dz, Geo g, int B, double tau)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;                                      // (wave-uniform)
+    const int64_t mi = g.mi;
+    const double* sb = s + b * mi;
+    const double* li = lda + b * (g.me + mi) + g.me;
+    const double* ds = dz + b * g.N + g.n;
+    const double* dl = ds + mi + g.me;
+    double as = 1.0, al = 1.0;
+    for (int64_t i = lane; i < mi; i += 64) {
+        const double a = ds[i], c = dl[i];
+        if (a < 0.0) as = fmin(as, -tau * sb[i] / a);
+        if (c < 0.0) al = fmin(al, -tau * li[i] / c);
+    }
+    #pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        as = fmin(as, __shfl_xor(as, off, 64));
+        al = fmin(al, __shfl_xor(al, off, 64));
+    }
+    if (lane == 0) { out[2 * b] = as; out[2 * b + 1] = al; }
 }
 
 }  // namespace pyipm

@@ -97,7 +97,17 @@ size_t carve_batched(Ctx* c, const Geo& g, int64_t B, char* base) {
     const size_t ocp = cv.take((size_t)B * (size_t)(2 * g.mi + 2) * sizeof(int) + (size_t)B * sizeof(int));
     const size_t obe = cv.take((size_t)B * sizeof(double));
     const size_t osg = cv.take((size_t)B * (size_t)(g.mi + 1) * sizeof(double));
+    // per-problem mu / delta / delta_c and activity flags, the landing place of host arrays for them, host step lengths
+    const size_t opar = cv.take((size_t)B * 3 * D);
+    const size_t oact = cv.take((size_t)B * sizeof(int));
+    const size_t oin = cv.take((size_t)B * 3 * D);
+    const size_t oia = cv.take((size_t)B * sizeof(int));
+    const size_t oal = cv.take((size_t)B * 2 * D);
     if (base) {
+        c->b_mu = (double*)(base + opar); c->b_delta = c->b_mu + B; c->b_delta_c = c->b_delta + B;
+        c->b_act = (int*)(base + oact);
+        c->b_in = (double*)(base + oin); c->b_in_act = (int*)(base + oia);
+        c->b_alpha = (double*)(base + oal);
         c->WT = (double*)(base + osg);                  // (batched handle: Sigma of the eliminated pairs, the Gram operand's scaling)
         c->cond_pos = (int*)(base + ocp); c->cond_idx = c->cond_pos + (size_t)B * (size_t)(g.mi + 1);
         c->cond_cnt = c->cond_idx + (size_t)B * (size_t)(g.mi + 1);
@@ -126,6 +136,7 @@ BatchPtrs batch_ptrs(Ctx* ctx) {
     bp.ldh = ctx->ld_d2L; bp.ldje = ctx->ld_Je; bp.ldji = ctx->ld_Ji;
     bp.df = ctx->df; bp.ce = ctx->ce; bp.ci = ctx->ci; bp.s = ctx->s; bp.lda = ctx->lda;
     bp.anorm = ctx->anorm;
+    bp.pmu = ctx->b_mu; bp.pdelta = ctx->b_delta; bp.pdelta_c = ctx->b_delta_c; bp.act = ctx->b_act;
     return bp;
 }
 
@@ -2228,40 +2239,40 @@ int pyipm_newton_stage_blocks_batched(pyipm_newton_ctx* h, const double* d2L, in
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
-int pyipm_newton_step_batched(pyipm_newton_ctx* h, double delta, double delta_c, double* dz,
-                              pyipm_factor_stats* stats, int memkind) try {
-    PYIPM_ENTER("step_batched", G_BATCHED | G_DEVICE) const Geo& g = ctx->g;
-    if (!ctx->held.have_blocks || !ctx->held.have_vectors) { ctx->err = "step_batched: stage blocks and vectors first"; return PYIPM_E_BADARG; }
-    if (!dz) { ctx->err = "step_batched: null output"; return PYIPM_E_BADARG; }
+// The launches of one batched step, for both entries: k_b_begin (who takes part, with which mu / delta / delta_c), residual or
+// condensed prep, assembly, factorisation, substitutions.  A problem whose flag is 0 costs a workgroup that returns at once
+// in each of them; its matrix, factor, statistics record, anorm words and row of dz stay as its last step left them.
+static int step_batched_enqueue(Ctx* ctx, const BatchEach& in, double* dz, int memkind) {
+    const Geo& g = ctx->g;
     const int B = ctx->batch;
     BatchPtrs bp = batch_ptrs(ctx);
     BatchCond bc = batch_cond(ctx);
     const int cond = (ctx->condensed && g.mi > 0) ? 1 : 0;
-    ctx->delta = delta; ctx->delta_c = delta_c;
     ctx->held.step_batched_begun(cond != 0);
     PYIPM_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
-    PYIPM_HIP(hipMemsetAsync(ctx->anorm, 0, (size_t)B * 2 * sizeof(unsigned long long), ctx->stream));
+    hipLaunchKernelGGL(k_b_begin, grid1(B), dim3(256), 0, ctx->stream, bp, in, B);
+    PYIPM_KCHECK();
     if (cond) {
         // condensed form: per problem n + me + |A| columns instead of n + 2 mi + me (config 5: 256 instead of 768) -- the
         // (s, lambda_i) pairs with Sigma <= condensed_sigma_max eliminated analytically (pyipm.py:824-842's block structure)
-        hipLaunchKernelGGL(k_bc_prep, dim3(B), dim3(256), 0, ctx->stream, bp, g, ctx->mu, ctx->eps, bc);
+        hipLaunchKernelGGL(k_bc_prep, dim3(B), dim3(256), 0, ctx->stream, bp, g, ctx->eps, bc);
         PYIPM_KCHECK();
         const int nt0 = (int)((g.n + g.me + TB - 1) / TB);
         const int nx = (g.n % TB == 0 && g.n >= TB && g.n <= 4 * TB && g.mi % 32 == 0 && ctx->bc_per_problem) ? (int)(g.n / TB) : 0;
         // one workgroup per problem while the Jacobian chunk of all n columns fits shared memory twice (n <= 256), else a tile each
-        if (nx == 4)      hipLaunchKernelGGL((k_bc_assemble_p<4>), dim3((unsigned)B), dim3(512), 0, ctx->stream, bp, g, ctx->eps, delta, delta_c, bc);
-        else if (nx == 3) hipLaunchKernelGGL((k_bc_assemble_p<3>), dim3((unsigned)B), dim3(384), 0, ctx->stream, bp, g, ctx->eps, delta, delta_c, bc);
-        else if (nx == 2) hipLaunchKernelGGL((k_bc_assemble_p<2>), dim3((unsigned)B), dim3(256), 0, ctx->stream, bp, g, ctx->eps, delta, delta_c, bc);
-        else if (nx == 1) hipLaunchKernelGGL((k_bc_assemble_p<1>), dim3((unsigned)B), dim3(128), 0, ctx->stream, bp, g, ctx->eps, delta, delta_c, bc);
+        if (nx == 4)      hipLaunchKernelGGL((k_bc_assemble_p<4>), dim3((unsigned)B), dim3(512), 0, ctx->stream, bp, g, ctx->eps, bc);
+        else if (nx == 3) hipLaunchKernelGGL((k_bc_assemble_p<3>), dim3((unsigned)B), dim3(384), 0, ctx->stream, bp, g, ctx->eps, bc);
+        else if (nx == 2) hipLaunchKernelGGL((k_bc_assemble_p<2>), dim3((unsigned)B), dim3(256), 0, ctx->stream, bp, g, ctx->eps, bc);
+        else if (nx == 1) hipLaunchKernelGGL((k_bc_assemble_p<1>), dim3((unsigned)B), dim3(128), 0, ctx->stream, bp, g, ctx->eps, bc);
         else
             hipLaunchKernelGGL(k_bc_assemble, dim3((unsigned)(nt0 * (nt0 + 1) / 2 + 1), (unsigned)B), dim3(256), 0, ctx->stream, bp, g,
-                               ctx->eps, delta, delta_c, bc, nt0);
+                               ctx->eps, bc, nt0);
         PYIPM_KCHECK();
     } else {
-        hipLaunchKernelGGL(k_b_residual, dim3(B), dim3(256), 0, ctx->stream, bp, g, ctx->mu, ctx->eps);
+        hipLaunchKernelGGL(k_b_residual, dim3(B), dim3(256), 0, ctx->stream, bp, g, ctx->eps);
         PYIPM_KCHECK();
         dim3 grid((unsigned)((g.Npad + 511) / 512), (unsigned)((g.Npad + 15) / 16), (unsigned)B);
-        hipLaunchKernelGGL(k_b_assemble, grid, dim3(256), 0, ctx->stream, bp, g, ctx->eps, delta, delta_c);
+        hipLaunchKernelGGL(k_b_assemble, grid, dim3(256), 0, ctx->stream, bp, g, ctx->eps);
         PYIPM_KCHECK();
     }
     PYIPM_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
@@ -2274,11 +2285,79 @@ int pyipm_newton_step_batched(pyipm_newton_ctx* h, double delta, double delta_c,
                        ctx->block_refine, (g.me + g.mi) > 0 ? 1 : 0, out_dev, bc, cond, ctx->eps);
     PYIPM_KCHECK();
     PYIPM_HIP(hipEventRecord(ctx->ev[1], ctx->stream));
-    ctx->held.step_batched_enqueued();
+    ctx->held.step_batched_enqueued(memkind == PYIPM_MEM_HOST);
+    return PYIPM_OK;
+}
+
+int pyipm_newton_step_batched(pyipm_newton_ctx* h, double delta, double delta_c, double* dz,
+                              pyipm_factor_stats* stats, int memkind) try {
+    PYIPM_ENTER("step_batched", G_BATCHED | G_DEVICE) const Geo& g = ctx->g;
+    if (!ctx->held.have_blocks || !ctx->held.have_vectors) { ctx->err = "step_batched: stage blocks and vectors first"; return PYIPM_E_BADARG; }
+    if (!dz) { ctx->err = "step_batched: null output"; return PYIPM_E_BADARG; }
+    const int B = ctx->batch;
+    ctx->delta = delta; ctx->delta_c = delta_c;
+    // one mu (stage_vectors') and one pair of shifts for every problem, all of them active
+    const BatchEach in = {nullptr, nullptr, nullptr, nullptr, ctx->mu, delta, delta_c};
+    { int rc = step_batched_enqueue(ctx, in, dz, memkind); if (rc) return rc; }
     if (memkind == PYIPM_MEM_HOST)
         PYIPM_HIP(hipMemcpyAsync(dz, ctx->v2, (size_t)B * g.N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (stats) return fetch_batched_stats(ctx, stats);
     if (memkind == PYIPM_MEM_HOST) PYIPM_HIP(hipStreamSynchronize(ctx->stream));
+    return PYIPM_OK;
+} PYIPM_CATCH_H(h)
+
+// A step with each problem's own mu, delta, delta_c (after the first barrier update, pyipm.py:1804-1814, and the first reghess,
+// pyipm.py:1373-1406, no two problems of a multi-start batch share them) for the problems `active` selects.
+int pyipm_newton_step_batched_each(pyipm_newton_ctx* h, const double* mu, const double* delta, const double* delta_c,
+                                   const int32_t* active, double* dz, int memkind) try {
+    PYIPM_ENTER("step_batched_each", G_BATCHED | G_DEVICE) const Geo& g = ctx->g;
+    if (!ctx->held.have_blocks || !ctx->held.have_vectors) { ctx->err = "step_batched_each: stage blocks and vectors first"; return PYIPM_E_BADARG; }
+    if (!mu || !delta || !delta_c) { ctx->err = "step_batched_each: null mu / delta / delta_c"; return PYIPM_E_BADARG; }
+    if (!dz) { ctx->err = "step_batched_each: null output"; return PYIPM_E_BADARG; }
+    if (memkind != PYIPM_MEM_DEVICE && memkind != PYIPM_MEM_HOST) { ctx->err = "step_batched_each: bad memkind"; return PYIPM_E_BADARG; }
+    const size_t B = (size_t)ctx->batch;
+    BatchEach in = {mu, delta, delta_c, (const int*)active, 0.0, 0.0, 0.0};
+    if (memkind == PYIPM_MEM_HOST) {
+        // host arrays land in the handle first; k_b_begin then moves the entries of the problems that take part
+        PYIPM_HIP(hipMemcpyAsync(ctx->b_in, mu, B * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        PYIPM_HIP(hipMemcpyAsync(ctx->b_in + B, delta, B * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        PYIPM_HIP(hipMemcpyAsync(ctx->b_in + 2 * B, delta_c, B * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        if (active) PYIPM_HIP(hipMemcpyAsync(ctx->b_in_act, active, B * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        in.mu = ctx->b_in; in.delta = ctx->b_in + B; in.delta_c = ctx->b_in + 2 * B; in.active = active ? ctx->b_in_act : nullptr;
+    }
+    { int rc = step_batched_enqueue(ctx, in, dz, memkind); if (rc) return rc; }
+    if (memkind == PYIPM_MEM_HOST) {
+        // only the rows of the problems that took part, run by run
+        const size_t row = (size_t)g.N;
+        for (size_t b0 = 0; b0 < B;) {
+            if (active && !active[b0]) { ++b0; continue; }
+            size_t b1 = b0 + 1;
+            while (b1 < B && (!active || active[b1])) ++b1;
+            PYIPM_HIP(hipMemcpyAsync(dz + b0 * row, ctx->v2 + b0 * row, (b1 - b0) * row * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            b0 = b1;
+        }
+        PYIPM_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return PYIPM_OK;
+} PYIPM_CATCH_H(h)
+
+// alpha[b] = (alpha_s, alpha_l) of every problem for the staged s, lda and the directions dz (k_b_step_lengths)
+int pyipm_newton_step_lengths_batched(pyipm_newton_ctx* h, double tau, const double* dz, double* alpha, int memkind) try {
+    PYIPM_ENTER("step_lengths_batched", G_BATCHED | G_DEVICE) const Geo& g = ctx->g;
+    if (!alpha) { ctx->err = "step_lengths_batched: null output"; return PYIPM_E_BADARG; }
+    if (memkind != PYIPM_MEM_DEVICE && memkind != PYIPM_MEM_HOST) { ctx->err = "step_lengths_batched: bad memkind"; return PYIPM_E_BADARG; }
+    if (!ctx->held.have_vectors) { ctx->err = "step_lengths_batched: stage vectors first"; return PYIPM_E_BADARG; }
+    if (!dz && !ctx->held.have_direction) {
+        ctx->err = "step_lengths_batched: the handle keeps the directions of a step with host output only -- pass dz"; return PYIPM_E_BADARG; }
+    const int B = ctx->batch;
+    double* dev = (memkind == PYIPM_MEM_DEVICE) ? alpha : ctx->b_alpha;
+    hipLaunchKernelGGL(k_b_step_lengths, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, ctx->stream, dev, ctx->s, ctx->lda,
+                       dz ? dz : ctx->v2, g, B, tau);
+    PYIPM_KCHECK();
+    if (memkind == PYIPM_MEM_HOST) {
+        PYIPM_HIP(hipMemcpyAsync(alpha, ctx->b_alpha, (size_t)B * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        PYIPM_HIP(hipStreamSynchronize(ctx->stream));
+    }
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
@@ -2292,14 +2371,14 @@ int pyipm_newton_stats_batched(pyipm_newton_ctx* h, pyipm_factor_stats* stats) t
     return fetch_batched_stats(ctx, stats);
 } PYIPM_CATCH_H(h)
 
-// out[b] = |g - Hc raw_b| / |g| of every problem of the last step_batched, Hc applied from the blocks (k_b_berr)
+// out[b] = |g - Hc raw_b| / |g| of every problem, Hc applied from the blocks with the problem's own shifts (k_b_berr)
 int pyipm_newton_backward_error_batched(pyipm_newton_ctx* h, const double* dz, double* out, int memkind) try {
     PYIPM_ENTER("backward_error_batched", G_BATCHED | G_DEVICE) const Geo& g = ctx->g;
     if (!dz || !out) return PYIPM_E_BADARG;
     if (!ctx->held.have_blocks || !ctx->held.have_vectors || !ctx->held.have_rhs) { ctx->err = "backward_error_batched: step_batched first"; return PYIPM_E_BADARG; }
     BatchPtrs bp = batch_ptrs(ctx);
     double* dev = (memkind == PYIPM_MEM_DEVICE) ? out : ctx->vt;
-    hipLaunchKernelGGL(k_b_berr, dim3(ctx->batch), dim3(256), 0, ctx->stream, bp, g, dz, ctx->eps, ctx->delta, ctx->delta_c, dev);
+    hipLaunchKernelGGL(k_b_berr, dim3(ctx->batch), dim3(256), 0, ctx->stream, bp, g, dz, ctx->eps, dev);
     PYIPM_KCHECK();
     if (memkind == PYIPM_MEM_HOST) {
         PYIPM_HIP(hipMemcpyAsync(out, ctx->vt, (size_t)ctx->batch * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
