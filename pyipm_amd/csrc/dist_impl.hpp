@@ -70,6 +70,20 @@ int rccl_load(std::string* err) {
 
 namespace pyipm {
 
+// Wire accounting of the last factor_dist (pyipm_newton_dist_wire), in the order of WIRE_KEYS (pyipm_amd/newton.py) + two
+enum WireSlot {
+    WIRE_BCAST_MSGS, WIRE_BCAST_BYTES,     // panel messages in the plain-broadcast form, their bytes
+    WIRE_SAG_MSGS, WIRE_SAG_BYTES,         // ... in the scatter + all-gather form, their bytes
+    WIRE_P2P_PIECES, WIRE_ALLGATHERS,      // point-to-point pieces this rank sent or received; all-gathers
+    WIRE_STREAM_HOPS,                      // hops through the collective stream
+    WIRE_SLICE_MSGS, WIRE_SLICE_BYTES,     // slice messages (two-message protocol) this rank sent or received, their bytes
+    WIRE_SLICES_AS_BCAST,                  // slice messages that travelled as a broadcast (no point-to-point transport)
+    WIRE_REST_MS,                          // ms of the owner's rows work behind the chain path (profile)
+    WIRE_CHAINS_EXTRA_ROWS,                // chains that took the second slice's rows along in their own launch
+    WIRE_SLOTS
+};
+static_assert(WIRE_SLOTS == 12, "pyipm_newton_dist_wire hands out 12 doubles");
+
 struct DistState {
     pyipm_bcast_fn bcast = nullptr; pyipm_allreduce_fn allreduce = nullptr; void* user = nullptr;
     // the optional point-to-point half of a caller-supplied exchange (pyipm_newton_set_exchange_p2p): with all three the
@@ -108,11 +122,7 @@ struct DistState {
     std::vector<Span> spans;
     double t_chain = 0, t_pack = 0, t_bcast = 0, t_unpack = 0, t_factor = 0, t_solve = 0;
     size_t bytes_sent = 0; int64_t n_msgs = 0;
-    // wire accounting of the last factor_dist (pyipm_newton_dist_wire): [0] panel messages in the plain-broadcast form, [1] their
-    // bytes, [2] messages in the scatter + all-gather form, [3] their bytes, [4] point-to-point pieces this rank sent or received,
-    // [5] all-gathers, [6] hops through the collective stream, [7] slice messages (two-message protocol) this rank sent or
-    // received, [8] their bytes, [9] slice messages that travelled as a broadcast (no point-to-point transport)
-    double wire[12] = {};
+    double wire[WIRE_SLOTS] = {};                      // wire accounting of the last factor_dist, by WireSlot
     // Progress of the last factor_dist as the DEVICE saw it (round 6): pinned host words a one-thread kernel writes behind each
     // panel message (collective stream), each bulk update (main stream) and each owned panel (owner's stream).  A collective a
     // peer never joined does not return an error -- its stream just stops; the host waits for the step with a bound
@@ -265,7 +275,7 @@ struct CsHop {
     Ctx* ctx; DistState* D; hipStream_t st; bool hop; int rc = 0;
     CsHop(Ctx* c, DistState* d, hipStream_t s) : ctx(c), D(d), st(s), hop(tr_serial(d) && s != d->cs) {
         if (hop) {
-            D->wire[6] += 1.0;
+            D->wire[WIRE_STREAM_HOPS] += 1.0;
             if (hipEventRecord(D->ev_hop[0], st) != hipSuccess || hipStreamWaitEvent(D->cs, D->ev_hop[0], 0) != hipSuccess) rc = PYIPM_E_HIP;
         }
     }
@@ -299,21 +309,21 @@ inline hipStream_t tr_slice_stream(const DistState* D) {
     return D->serialize ? D->cs : D->side;
 }
 int tr_send(Ctx* ctx, DistState* D, const double* buf, size_t count, int peer, hipStream_t st, bool slice = false) {
-    D->wire[4] += 1.0;
+    D->wire[WIRE_P2P_PIECES] += 1.0;
     if (D->comm) { ncclResult_t r = g_rccl.Send(buf, count, ncclDouble, peer, (slice && D->comm2 && D->use_comm2) ? D->comm2 : D->comm, st); return r == ncclSuccess ? 0 : tr_fail(ctx, "ncclSend", r); }
     if (!D->send) { ctx->err = "no point-to-point send installed (pyipm_newton_set_exchange_p2p)"; return PYIPM_E_COMM; }
     if (D->send(D->user, buf, count * sizeof(double), peer, (void*)st)) { ctx->err = "the send callback failed"; return PYIPM_E_COMM; }
     return 0;
 }
 int tr_recv(Ctx* ctx, DistState* D, double* buf, size_t count, int peer, hipStream_t st, bool slice = false) {
-    D->wire[4] += 1.0;
+    D->wire[WIRE_P2P_PIECES] += 1.0;
     if (D->comm) { ncclResult_t r = g_rccl.Recv(buf, count, ncclDouble, peer, (slice && D->comm2 && D->use_comm2) ? D->comm2 : D->comm, st); return r == ncclSuccess ? 0 : tr_fail(ctx, "ncclRecv", r); }
     if (!D->recv) { ctx->err = "no point-to-point receive installed (pyipm_newton_set_exchange_p2p)"; return PYIPM_E_COMM; }
     if (D->recv(D->user, buf, count * sizeof(double), peer, (void*)st)) { ctx->err = "the receive callback failed"; return PYIPM_E_COMM; }
     return 0;
 }
 int tr_allgather(Ctx* ctx, DistState* D, const double* sendbuf, double* recvbuf, size_t count_per_rank, hipStream_t st) {
-    D->wire[5] += 1.0;
+    D->wire[WIRE_ALLGATHERS] += 1.0;
     if (D->comm) { ncclResult_t r = g_rccl.AllGather(sendbuf, recvbuf, count_per_rank, ncclDouble, D->comm, st); return r == ncclSuccess ? 0 : tr_fail(ctx, "ncclAllGather", r); }
     if (!D->allgather) { ctx->err = "no all-gather installed (pyipm_newton_set_exchange_p2p)"; return PYIPM_E_COMM; }
     if (D->allgather(D->user, sendbuf, recvbuf, count_per_rank * sizeof(double), (void*)st)) { ctx->err = "the all-gather callback failed"; return PYIPM_E_COMM; }
@@ -370,13 +380,13 @@ int ex_bcast(Ctx* ctx, DistState* D, void* buf, size_t bytes, int root, hipStrea
     if (ctx->g.world == 1 && !D->comm && !D->bcast) return 0;                          // one rank, nothing installed: nothing to do
     const bool panel = buf == D->msg[0] || buf == D->msg[1];
     if (D->sag && tr_has_p2p(D) && bytes >= D->sag_min_bytes && panel) {
-        D->wire[2] += 1.0; D->wire[3] += (double)bytes;
+        D->wire[WIRE_SAG_MSGS] += 1.0; D->wire[WIRE_SAG_BYTES] += (double)bytes;
         CsHop h(ctx, D, st); if (h.rc) return h.done();
         int rc = sag_bcast(ctx, D, static_cast<double*>(buf), bytes / sizeof(double), root, h.stream());
         if (rc) return rc;
         return h.done();
     }
-    if (panel) { D->wire[0] += 1.0; D->wire[1] += (double)bytes; }
+    if (panel) { D->wire[WIRE_BCAST_MSGS] += 1.0; D->wire[WIRE_BCAST_BYTES] += (double)bytes; }
     CsHop h(ctx, D, st); if (h.rc) return h.done();
     int rc = tr_bcast(ctx, D, static_cast<double*>(buf), bytes / sizeof(double), root, h.stream());
     if (rc) return rc;
@@ -498,7 +508,7 @@ int span_end(Ctx* ctx, DistState* D, size_t idx, hipStream_t st) {
     return 0;
 }
 
-size_t dist_msg_bytes(Ctx* ctx, int64_t p) {
+size_t dist_msg_bytes(const Ctx* ctx, int64_t p) {
     const Geo& g = ctx->g;
     if (panel_in_s(ctx, p)) return 0;
     int64_t h0, h1;
@@ -520,14 +530,525 @@ int update_range(Ctx* ctx, int64_t p, int64_t first, int64_t count, hipStream_t 
     return timed_update(ctx, p, 1, q / g.world, n_lp, {.stream = st});
 }
 
-// The factorisation across the ranks: one-panel lookahead.  As soon as panel p has arrived, the owner of p+1 updates
-// only panel p+1 (head), factors and packs it on the side stream and starts its broadcast on the collective stream;
-// every rank runs its share of the bulk update of p on the main stream meanwhile.
+// ---- the factorisation across the ranks: the plan (plan_dist, plan_slot), then the enqueue (factor_dist_geo) -----------------
+// One-panel lookahead.  As soon as panel p has arrived, the owner of p+1 updates only panel p+1 (head), factors and packs it
+// on the side stream and starts its broadcast on the collective stream; every rank runs its share of the bulk update of p on
+// the main stream meanwhile.
+// The two-message protocol (round 5): slices ahead of the panel message.  sl(k): the rows of panel k that meet the diagonal
+// block of panel k + 1 (slice 1, with the tile inverses) and the rows of panel k + 2 (slice 2) travel from owner(k) to
+// owner(k + 1) point to point AHEAD of the panel message.  owner(k + 1) starts its tile chain on slice 1, runs the stages of its
+// rows of panel k + 2 on slice 2 and hands ITS slice 1 on -- the chain of owners no longer waits for a panel message (hundreds
+// of MB), its unpacking, or the rows work of the panel before: what it waits for is nb x nb.  The panel message itself is
+// unchanged and follows for everybody's bulk update.
+// Both plans are decided from the geometry, the options and the transport's capabilities alone -- no HIP call, no stream, nothing
+// mutated: every rank takes the same decision for every panel, which is what lets a blocking transport run the order below.
+struct DistPlan {                      // what holds for one whole factorisation: decided by plan_dist before the first launch
+    const Ctx* ctx;
+    int64_t np; int W;
+    bool wire;                         // panels travel: several ranks, or one that packs and "sends" anyway (dist_selfmsg)
+    bool slices_on, p2p;               // the two-message protocol; the transport has point-to-point operations
+    hipStream_t ps;                    // where the point-to-point slices travel
+    bool s2_late;                      // ... the owner's own stream: the receiver posts its receive of slice 2 BEHIND its tile chain
+                                       // (in front of it the stream would sit waiting for a message the chain does not need)
+    size_t msg_max, slice_max;         // bytes of the largest panel message, doubles of the largest slice: the buffers' sizes
+    bool fwd;                          // the forward substitution of the step's right-hand side trails the factorisation (step_dist)
+    int64_t below(int64_t p) const { return ctx->g.Npad - (ctx->g.panel_c0(p) + ctx->g.panel_w(p)); }
+    bool own(int64_t p) const { return p >= 0 && p < np && ctx->g.owner(p) == ctx->g.rank; }
+    size_t msg_of(int64_t p) const { return (wire && p < np && below(p) > 0) ? dist_msg_bytes(ctx, p) : 0; }
+    bool sl(int64_t k) const {         // panel k sends slices: panel k + 1 is factored in pieces on them
+        return slices_on && k >= 0 && k + 1 < np && msg_of(k) > 0 && ctx->g.owner(k + 1) != ctx->g.owner(k) && !panel_in_s(ctx, k) &&
+               panel_piecewise_ok(ctx, k + 1) && below(k + 1) >= 0;
+    }
+};
+DistPlan plan_dist(const Ctx* ctx, const DistState* D, bool fwd) {
+    const Geo& g = ctx->g;
+    DistPlan P{};
+    P.ctx = ctx; P.np = g.npanels; P.W = g.world; P.fwd = fwd;
+    P.wire = P.W > 1 || D->selfmsg;
+    P.slices_on = ctx->dist_slices && P.W > 1;
+    P.p2p = tr_has_p2p(D);
+    P.ps = tr_slice_stream(D);
+    P.s2_late = P.p2p && P.ps == (hipStream_t)D->side;
+    if (P.wire) for (int64_t p = 0; p < P.np; ++p) P.msg_max = std::max(P.msg_max, dist_msg_bytes(ctx, p));
+    if (P.slices_on) for (int64_t p = 0; p < P.np; ++p) for (int j = 1; j <= 2; ++j) P.slice_max = std::max(P.slice_max, slice_numel(g, p, j));
+    return P;
+}
+
+// One iteration of the slot loop, decided (panel k's message travels, panel k + 1 is factored on its owner)
+enum class Head { none, range, wide_split, whole };
+struct SlotPlan {
+    int64_t k, nxt; int b;             // the slot, k + 1, the parity of k (message and slice buffers, events)
+    int64_t c1n, c2n, c3n, c4n;        // first column of panels k + 1 ... k + 4 (Npad beyond the last)
+    bool own_k, own_nxt;
+    bool early, sl_nxt;                // panel k + 1 is factored in pieces, on slices of panel k; panel k + 1 sends slices itself
+    bool ext;                          // owner of k + 1: its rows of panel k + 2 ride in the chain's own launch (chains-with-extra-rows)
+    bool got_slices;                   // this rank received panel k's slices: its unpack of the panel message starts beyond their rows
+    Head head;                         // owner of a classic k + 1: through update_range / a wide panel's in two launches / whole
+    bool s1_after;                     // slice 1 of a classic k + 1 follows the panel message of k
+};
+SlotPlan plan_slot(const Ctx* ctx, const DistPlan& P, int64_t k) {
+    const Geo& g = ctx->g;
+    SlotPlan S{};
+    S.k = k; S.nxt = k + 1; S.b = (int)(k & 1);
+    auto c0_of = [&](int64_t p) { return p < P.np ? g.panel_c0(p) : g.Npad; };
+    S.c1n = c0_of(k + 1); S.c2n = c0_of(k + 2); S.c3n = c0_of(k + 3); S.c4n = c0_of(k + 4);
+    S.own_k = P.own(k); S.own_nxt = P.own(S.nxt);
+    S.early = P.sl(k); S.sl_nxt = P.sl(S.nxt);
+    // (round 6) The rows of panel k + 2 -- what the NEXT owner's chain waits for as its slice 1 -- ride in the chain's own
+    // launch: their units apply every stage as the chain publishes it, instead of a k_panel_rest launch behind the chain
+    // (34 us + two launch boundaries per panel on the owners' path).  Their head comes from slice 2 of panel k, which is
+    // still on its way when the chain starts: it is unpacked and applied on the rows stream, and a word set behind it
+    // releases those units (bounded poll, as every poll of that kernel).  Not with slices posted on the owner's own
+    // stream behind the chain (s2_late): the receive would sit behind the kernel that waits for it.
+    S.ext = S.early && S.own_nxt && S.c3n > S.c2n && !P.s2_late && ctx->dist_slices >= 2 && chain_extra_ok(ctx, S.nxt, S.c3n - S.c2n);
+    S.got_slices = S.early && S.own_nxt;
+    S.head = Head::none;
+    if (S.own_nxt && !S.early) {
+        // (factor_panel sends a wide panel to factor_wide_panel without the slack-block and % 32 conjuncts; the head's first launch
+        //  covers the diagonal block in 32-row blocks, and a slack-block source or target takes update_range anyway)
+        const int64_t nbwn = g.panel_w(S.nxt);
+        const bool wide_next = ctx->tile_step && panel_is_wide(ctx, S.nxt) && nbwn / TB <= 32 && S.c1n + nbwn < g.Npad &&
+                               !panel_in_s(ctx, S.nxt) && !panel_in_s(ctx, k) && nbwn % 32 == 0;
+        S.head = (panel_in_s(ctx, k) || panel_in_s(ctx, S.nxt)) ? Head::range : wide_next ? Head::wide_split : Head::whole;
+    }
+    S.s1_after = !S.early && S.sl_nxt;
+    return S;
+}
+
+struct DistRun {                       // the mutable state of one factorisation's enqueue
+    DistState* D; hipStream_t main, side, cs; const double* fwd_b;
+    bool sfree_rec[2][2] = {{false, false}, {false, false}};   // ev_sfree[b][j] / ev_pre have been recorded in this factorisation
+    bool pre_rec = false;
+    int64_t rest_panel = -1, rest_from = 0;     // an early panel's rows beyond its slices + its panel message (flush_rest)
+    std::vector<char> on_side;         // panel p was completed on the side stream
+    int64_t fwd_next = 0;              // first panel whose forward step is not enqueued yet
+};
+
+// Forward substitution of panel p across the ranks on `st` (all ranks: the segment sum -- one nb-long all-reduce; owner: the
+// panel's own part).  factored: what the owner waits for where the factorisation is still running beside it (panel p factored).
+int fwd_step(Ctx* ctx, DistState* D, int64_t p, hipStream_t st, hipEvent_t factored = nullptr) {
+    const Geo& g = ctx->g;
+    const int64_t c0 = g.panel_c0(p); const int64_t nbw = g.panel_w(p);
+    const bool own = g.owner(p) == g.rank;
+    double* v = D->vloc;
+    if (g.world > 1) {
+        DIST_HIP(hipMemcpyAsync(D->seg, v + c0, (size_t)nbw * sizeof(double), hipMemcpyDeviceToDevice, st));
+        int r = ex_allreduce(ctx, D, D->seg, (size_t)nbw, 0, st); if (r) return r;
+        if (own) DIST_HIP(hipMemcpyAsync(v + c0, D->seg, (size_t)nbw * sizeof(double), hipMemcpyDeviceToDevice, st));
+    }
+    if (own) {
+        if (factored) DIST_HIP(hipStreamWaitEvent(st, factored, 0));
+        int r = fwd_panel(ctx, p, v, st); if (r) return r;
+        r = diag_panel(ctx, p, v, st); if (r) return r;
+    }
+    return 0;
+}
+// ... the one that trails the factorisation on its own stream
+int fwd_trail(Ctx* ctx, const DistPlan& P, DistRun& R, int64_t p) {
+    return P.fwd ? fwd_step(ctx, R.D, p, R.D->fws, ctx->ev_done[(size_t)p]) : 0;
+}
+
+// ---- building blocks ------------------------------------------------------------------------------------------------
+// owner: panel p is complete on `st` -> forward-sweep event, pack the panel message, "factored" event
+int finish_panel(Ctx* ctx, const DistPlan& P, DistRun& R, int64_t p, hipStream_t st) {
+    DistState* D = R.D;
+    const int b = (int)(p & 1);
+    if (P.fwd) DIST_HIP(hipEventRecord(ctx->ev_done[(size_t)p], st));
+    if (P.msg_of(p) > 0) {
+        DIST_HIP(hipStreamWaitEvent(st, D->ev_free[b], 0));          // the previous message in this buffer has left / been unpacked
+        size_t sp; int r = span_begin(ctx, D, 1, st, &sp); if (r) return r;
+        { StreamScope sc(ctx, st); r = pyipm_newton_panel_pack(reinterpret_cast<pyipm_newton_ctx*>(ctx), p, D->msg[b]); }
+        if (r) return r;
+        r = span_end(ctx, D, sp, st); if (r) return r;
+    }
+    DIST_HIP(hipEventRecord(D->ev_fact[b], st));
+    hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, st, D->prog_dev + 2, (unsigned)(p + 1)); DIST_KCHECK();
+    return 0;
+}
+// owner: pack slice j of panel p on `st` (its rows of panel p + j are final there)
+int pack_s(Ctx* ctx, DistRun& R, int64_t p, int j, hipStream_t st) {
+    DistState* D = R.D;
+    if (slice_numel(ctx->g, p, j) == 0) return 0;
+    const int b = (int)(p & 1);
+    if (R.sfree_rec[b][j - 1]) DIST_HIP(hipStreamWaitEvent(st, D->ev_sfree[b][j - 1], 0));
+    int r = pack_slice(ctx, p, j, D->sbuf[b][j - 1], st); if (r) return r;
+    DIST_HIP(hipEventRecord(D->ev_spack[b][j - 1], st));
+    return 0;
+}
+// slice j of panel p on the wire: owner(p) -> owner(p + 1); without a point-to-point transport it travels as a broadcast
+// role: 0 = whatever this rank's part is, 1 = only if it is the sender, 2 = only if it is the receiver
+int xchg_s(Ctx* ctx, const DistPlan& P, DistRun& R, int64_t p, int j, int role) {
+    const Geo& g = ctx->g; DistState* D = R.D; const hipStream_t cs = R.cs, ps = P.ps;
+    const size_t cnt = slice_numel(g, p, j);
+    if (cnt == 0) return 0;
+    const int b = (int)(p & 1), src = g.owner(p), dst = g.owner(p + 1);
+    double* buf = D->sbuf[b][j - 1];
+    bool& free_rec = R.sfree_rec[b][j - 1];
+    const bool sender = g.rank == src && role != 2, receiver = g.rank == dst && role != 1;
+    if (P.p2p && !sender && !receiver) return 0;
+    if (!P.p2p) {
+        if (sender) DIST_HIP(hipStreamWaitEvent(cs, D->ev_spack[b][j - 1], 0));
+        else if (free_rec) DIST_HIP(hipStreamWaitEvent(cs, D->ev_sfree[b][j - 1], 0));
+        int r = tr_bcast(ctx, D, buf, cnt, src, cs); if (r) return r;
+        D->wire[WIRE_SLICES_AS_BCAST] += 1.0;
+        if (!receiver) { DIST_HIP(hipEventRecord(D->ev_sfree[b][j - 1], cs)); free_rec = true; }
+    } else if (sender) {
+        DIST_HIP(hipStreamWaitEvent(ps, D->ev_spack[b][j - 1], 0));
+        int r = tr_send(ctx, D, buf, cnt, dst, ps, true); if (r) return r;
+        DIST_HIP(hipEventRecord(D->ev_sfree[b][j - 1], ps)); free_rec = true;
+    } else if (receiver) {
+        if (free_rec) DIST_HIP(hipStreamWaitEvent(ps, D->ev_sfree[b][j - 1], 0));
+        int r = tr_recv(ctx, D, buf, cnt, src, ps, true); if (r) return r;
+    } else return 0;
+    if (receiver) DIST_HIP(hipEventRecord(D->ev_srecv[b][j - 1], P.p2p ? ps : cs));
+    if (sender || receiver) { D->wire[WIRE_SLICE_MSGS] += 1.0; D->wire[WIRE_SLICE_BYTES] += (double)(cnt * sizeof(double)); }
+    return 0;
+}
+// head update of panel q's columns from panel p (p < q, q owned) over rows [r0, r1): Lop = where L of panel p lives for those
+// rows (this rank's storage, the rebuilt panel, or a slice's L rows offset to global row numbers)
+int head_rows(Ctx* ctx, int64_t p, int64_t q, int64_t r0, int64_t r1, const double* Lop, int64_t ldl, hipStream_t st, bool small) {
+    const Geo& g = ctx->g;
+    if (r1 > g.Npad) r1 = g.Npad;
+    if (r1 <= r0) return 0;
+    const int K = (int)g.panel_w(p);
+    const int64_t c0q = g.panel_c0(q), nbwq = g.panel_w(q);
+    if (panel_in_s(ctx, p)) return 0;                              // (a slack-block source: handled by update_range, whole columns)
+    if (small || g.Npad - (c0q + nbwq) <= HEAD32_ROWS_DIST) {
+        int64_t pa0, pa1, pb0, pb1;
+        active_ranges(ctx, g.panel_c0(p), g.panel_c0(p) + K, &pa0, &pa1, &pb0, &pb1);
+        return launch_inpanel_update(ctx, st, dim3((unsigned)((r1 - r0) / 32), (unsigned)(nbwq / TB)), ctx->A, g.Npad, g.local_c0(q), Lop, ldl,
+                                     wbuf(ctx, p), g.Npad, c0q, K, r0, g.Npad, pa0, pa1, pb0, pb1, SIDE_PRIO);
+    }
+    return launch_update128(ctx, st, Lop, ldl, wbuf(ctx, p), K, r0, q / g.world, 1, {.row_end = r1, .src_c0 = g.panel_c0(p), .waves = HEAD_WAVES});
+}
+// the panel message of p: owner sends (its pack is behind ev_fact), everyone else joins
+int bcast_big(Ctx* ctx, const DistPlan& P, DistRun& R, int64_t p) {
+    DistState* D = R.D; const hipStream_t cs = R.cs;
+    const size_t bytes = P.msg_of(p);
+    if (!bytes) return 0;
+    const int b = (int)(p & 1);
+    if (ctx->debug_fault == 3 && p >= P.np / 2) {     // test hook: this panel's message "never completes" (the first panel from the middle on that HAS one: slack-block panels do not)
+        ctx->debug_fault = 0;
+        double tb = ctx->dist_timeout_s > 0 ? 3.0 * ctx->dist_timeout_s : 30.0; if (tb > 30.0) tb = 30.0;
+        hipLaunchKernelGGL(k_stall, dim3(1), dim3(64), 0, cs, (unsigned long long)(tb * 1.0e8));
+        DIST_KCHECK();
+    }
+    if (P.own(p)) DIST_HIP(hipStreamWaitEvent(cs, D->ev_fact[b], 0));
+    else DIST_HIP(hipStreamWaitEvent(cs, D->ev_free[b], 0));
+    size_t sp; int r = span_begin(ctx, D, 2, cs, &sp); if (r) return r;
+    r = ex_bcast(ctx, D, D->msg[b], bytes, ctx->g.owner(p), cs); if (r) return r;
+    r = span_end(ctx, D, sp, cs); if (r) return r;
+    DIST_HIP(hipEventRecord(D->ev_msg[b], cs));
+    if (P.own(p)) DIST_HIP(hipEventRecord(D->ev_free[b], cs));      // an owner's buffer is free once the message has left
+    D->bytes_sent += bytes; D->n_msgs++;
+    hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, cs, D->prog_dev + 0, (unsigned)(p + 1));      // progress word (bounded_wait)
+    DIST_KCHECK();
+    return 0;
+}
+// bulk update from panel p of the owned panels beyond `after`; with slices the panel this rank factors next goes first
+// (its own launch, then an event: that panel's early phase waits for nothing else of the main stream)
+int bulk_from(Ctx* ctx, const DistPlan& P, DistRun& R, int64_t p, int64_t after) {
+    int64_t nf = after + 1;
+    while (nf < P.np && !P.own(nf)) ++nf;
+    if (nf >= P.np) return 0;
+    if (P.slices_on && nf == after + 1) {               // (its early phase comes in the very next slot)
+        int r = update_range(ctx, p, nf, 1, R.main); if (r) return r;
+        DIST_HIP(hipEventRecord(R.D->ev_pre, R.main)); R.pre_rec = true;
+        return update_range(ctx, p, nf + 1, P.np, R.main);
+    }
+    return update_range(ctx, p, nf, P.np, R.main);
+}
+// an early panel's rows beyond its slices + its panel message (slot_next_panel leaves them; see there)
+int flush_rest(Ctx* ctx, const DistPlan& P, DistRun& R) {
+    if (R.rest_panel < 0) return 0;
+    const int64_t q = R.rest_panel; R.rest_panel = -1;
+    size_t sp; int r = span_begin(ctx, R.D, 4, R.side, &sp); if (r) return r;
+    r = panel_rows(ctx, q, R.rest_from, ctx->g.Npad, R.side); if (r) return r;
+    r = span_end(ctx, R.D, sp, R.side); if (r) return r;
+    return finish_panel(ctx, P, R, q, R.side);
+}
+// owner of k + 1, slice 2 of panel k has arrived in front of `st`: rebuild its L rows, free the buffer, head on its rows of panel k + 2
+int slice2_rows(Ctx* ctx, DistRun& R, const SlotPlan& S, const double* tiles_k, hipStream_t st) {
+    DistState* D = R.D;
+    int rc = unpack_slice(ctx, S.k, 2, D->sbuf[S.b][1], tiles_k, D->EL[1], st); if (rc) return rc;
+    DIST_HIP(hipEventRecord(D->ev_sfree[S.b][1], st)); R.sfree_rec[S.b][1] = true;
+    return head_rows(ctx, S.k, S.nxt, S.c2n, S.c3n, D->EL[1] - S.c2n, S.c3n - S.c2n, st, true);
+}
+
+// ---- the enqueue: set-up, panel 0, per slot (a) - (d), the tail ------------------------------------------------------------------
+// what the anorm all-reduce, the buffers and the events of this factorisation need before panel 0
+int dist_setup(Ctx* ctx, const DistPlan& P, DistRun& R) {
+    const Geo& g = ctx->g; DistState* D = R.D;
+    DIST_HIP(hipEventRecord(ctx->ev[0], R.main));
+    // every rank perturbs alike: the scale of a static pivot is the largest entry over ALL ranks' columns
+    int rc = ex_allreduce(ctx, D, reinterpret_cast<double*>(ctx->anorm), 1, 1, R.main); if (rc) return rc;
+    // the owner's stream starts behind everything the main stream has done to the matrix so far (the assembly, the reset of the
+    // statistics): with slices a panel's early phase waits for no other main-stream work
+    DIST_HIP(hipEventRecord(D->ev_head, R.main));
+    DIST_HIP(hipStreamWaitEvent(R.side, D->ev_head, 0));
+    if (P.msg_max > 0)
+        for (int b = 0; b < 2; ++b)
+            if (D->msg[b].reserve(P.msg_max / sizeof(double) + (size_t)P.W) != hipSuccess) {           // (slack: W equal pieces, sag_bcast)
+                ctx->err = "factor_dist: no memory for the panel messages"; return PYIPM_E_NOMEM; }
+    if (P.slices_on) {
+        if (P.slice_max > 0) {
+            bool got = true;
+            for (int b = 0; b < 2; ++b) for (int j = 0; j < 2; ++j) got = got && D->sbuf[b][j].reserve(P.slice_max) == hipSuccess;
+            for (int j = 0; j < 2; ++j) got = got && D->EL[j].reserve((size_t)g.nb * g.nb) == hipSuccess;
+            if (!got) { ctx->err = "factor_dist: no memory for the slice messages"; return PYIPM_E_NOMEM; }
+        }
+        for (int b = 0; b < 2; ++b) for (int j = 0; j < 2; ++j)
+            for (Event* e : {&D->ev_spack[b][j], &D->ev_srecv[b][j], &D->ev_sfree[b][j]}) DIST_HIP(e->ensure(hipEventDisableTiming));
+        for (Event* e : {&D->ev_pre, &D->ev_hr, &D->ev_hr2}) DIST_HIP(e->ensure(hipEventDisableTiming));
+    }
+    ctx->held.borrowed(Held::VLOC);
+    if (D->broken) { ctx->err = "an earlier distributed step timed out: this handle's streams may hold collectives that never complete -- destroy it"; return PYIPM_E_COMM; }
+    for (int k = 0; k < 3; ++k) D->prog_host[k] = 0u;
+    if (P.fwd) {
+        DIST_HIP(D->fws.ensure(hipStreamNonBlocking));
+        DIST_HIP(D->ev_fw.ensure(hipEventDisableTiming));
+        DIST_HIP(ensure_events(ctx->ev_done, (size_t)P.np, hipEventDisableTiming));
+        DIST_HIP(hipEventRecord(D->ev_fw, R.main));                     // the right-hand side was produced on the main stream
+        DIST_HIP(hipStreamWaitEvent(D->fws, D->ev_fw, 0));
+        { int r_ = launch_mask_owned(ctx, D->fws, D->vloc, R.fwd_b); if (r_) return r_; }
+    }
+    return 0;
+}
+// panel 0: its owner factors it whole on the main stream
+int panel0(Ctx* ctx, const DistPlan& P, DistRun& R) {
+    int rc;
+    if (P.own(0)) {
+        size_t sp; rc = span_begin(ctx, R.D, 0, R.main, &sp); if (rc) return rc;
+        rc = factor_panel(ctx, 0, R.main, false); if (rc) return rc;
+        if (P.sl(0)) { rc = pack_s(ctx, R, 0, 1, R.main); if (rc) return rc; rc = pack_s(ctx, R, 0, 2, R.main); if (rc) return rc; }
+        rc = span_end(ctx, R.D, sp, R.main); if (rc) return rc;
+        rc = finish_panel(ctx, P, R, 0, R.main); if (rc) return rc;
+    }
+    if (P.sl(0)) { rc = xchg_s(ctx, P, R, 0, 1, 0); if (rc) return rc; }
+    return 0;
+}
+// (a), owner of an early k + 1: slice 1 -> head on the diagonal block -> panel_chain, with or without the extra rows; the slice-2
+// rows; the pack of its own slice 1; panel k's tiles; the buffer-free events
+int chain_path(Ctx* ctx, const DistPlan& P, DistRun& R, const SlotPlan& S) {
+    const Geo& g = ctx->g; DistState* D = R.D; const hipStream_t side = R.side;
+    const int b = S.b; const int64_t k = S.k, nxt = S.nxt, ldE1 = S.c2n - S.c1n;
+    size_t sp_chain = (size_t)-1;
+    if (R.pre_rec) DIST_HIP(hipStreamWaitEvent(side, D->ev_pre, 0));   // the main stream's updates of panel k + 1's columns
+    DIST_HIP(hipStreamWaitEvent(side, D->ev_srecv[b][0], 0));
+    int rc = span_begin(ctx, D, 0, side, &sp_chain); if (rc) return rc;   // (chain path: work only, not the wait for a slice)
+    const double* tiles_k = D->sbuf[b][0] + ldE1 * g.panel_w(k);      // slice 1 carries the panel's tile inverses, tiles, flags
+    rc = unpack_slice(ctx, k, 1, D->sbuf[b][0], tiles_k, D->EL[0], side); if (rc) return rc;
+    rc = head_rows(ctx, k, nxt, S.c1n, S.c2n, D->EL[0] - S.c1n, ldE1, side, true); if (rc) return rc;
+    if (S.ext) {
+        // (on the collective stream, right behind the receive of slice 2: an idle stream woken through two events took
+        //  longer to get there than the launch it saves)
+        const hipStream_t xs = R.cs;
+        DIST_HIP(hipEventRecord(D->ev_x, side));                      // (behind unpack 1 / head 1: the tiles are read from the same buffer,
+        DIST_HIP(hipStreamWaitEvent(xs, D->ev_x, 0));                 //  EL[1]'s earlier readers are ordered)
+        if (R.pre_rec) DIST_HIP(hipStreamWaitEvent(xs, D->ev_pre, 0));
+        rc = slice2_rows(ctx, R, S, tiles_k, xs); if (rc) return rc;
+        D->xtoken += 1;
+        hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, xs, D->xflag, D->xtoken); DIST_KCHECK();
+        rc = panel_chain(ctx, nxt, side, S.c3n - S.c2n, D->xflag, D->xtoken); if (rc) return rc;
+        D->wire[WIRE_CHAINS_EXTRA_ROWS] += 1.0;
+        // (the slice-1 buffer's tiles are read by that unpack: it must have run before the buffer is freed below)
+        DIST_HIP(hipEventRecord(D->ev_x, xs));
+        DIST_HIP(hipStreamWaitEvent(side, D->ev_x, 0));
+    } else {
+        rc = panel_chain(ctx, nxt, side); if (rc) return rc;
+    }
+    if (S.c3n > S.c2n && !S.ext) {
+        rc = span_end(ctx, D, sp_chain, side); if (rc) return rc;
+        if (P.s2_late) { rc = xchg_s(ctx, P, R, k, 2, 2); if (rc) return rc; }
+        DIST_HIP(hipStreamWaitEvent(side, D->ev_srecv[b][1], 0));
+        rc = span_begin(ctx, D, 0, side, &sp_chain); if (rc) return rc;
+        rc = slice2_rows(ctx, R, S, tiles_k, side); if (rc) return rc;
+        rc = panel_rows(ctx, nxt, S.c2n, S.c3n, side); if (rc) return rc;
+    }
+    if (S.sl_nxt) { rc = pack_s(ctx, R, nxt, 1, side); if (rc) return rc; }
+    rc = span_end(ctx, D, sp_chain, side); if (rc) return rc;
+    // behind the chain path: panel k's tiles into the handle's arrays (the rest of its unpacking reads them there);
+    // only then may the slice-1 buffer be written again
+    rc = unpack_slice_tiles(ctx, k, tiles_k, side); if (rc) return rc;
+    DIST_HIP(hipEventRecord(D->ev_sfree[b][0], side)); R.sfree_rec[b][0] = true;
+    DIST_HIP(hipEventRecord(D->ev_hr2, side));
+    R.on_side[(size_t)nxt] = 1;
+    return 0;
+}
+// (a) ahead of the panel message of k.  An early slot: (1) slice 2 of panel k, (2) the early phase of panel k + 1 on its owner,
+// (3) slice 1 of panel k + 1, (4) the panel message of k -- in this order on every rank's collective stream
+int slot_ahead(Ctx* ctx, const DistPlan& P, DistRun& R, const SlotPlan& S) {
+    int rc;
+    if (S.early) {
+        rc = xchg_s(ctx, P, R, S.k, 2, P.s2_late ? 1 : 0); if (rc) return rc;
+        rc = flush_rest(ctx, P, R); if (rc) return rc;
+        if (S.own_nxt) { rc = chain_path(ctx, P, R, S); if (rc) return rc; }
+        if (S.sl_nxt) { rc = xchg_s(ctx, P, R, S.nxt, 1, 0); if (rc) return rc; }
+    }
+    return flush_rest(ctx, P, R);                                   // (a slot without slices: nothing to send first)
+}
+// (b) the panel message of k, and panel k becoming available on the main stream
+int slot_message(Ctx* ctx, const DistPlan& P, DistRun& R, const SlotPlan& S) {
+    DistState* D = R.D; const hipStream_t main = R.main;
+    int rc = bcast_big(ctx, P, R, S.k); if (rc) return rc;
+    if (S.own_k) {
+        if (R.on_side[(size_t)S.k]) DIST_HIP(hipStreamWaitEvent(main, D->ev_fact[S.b], 0));     // completed on the side stream
+    } else if (P.msg_of(S.k) > 0) {
+        DIST_HIP(hipStreamWaitEvent(main, D->ev_msg[S.b], 0));
+        size_t sp; rc = span_begin(ctx, D, 3, main, &sp); if (rc) return rc;
+        if (S.got_slices) DIST_HIP(hipStreamWaitEvent(main, D->ev_hr2, 0));      // panel k's tiles are in the handle's arrays
+        { StreamScope sc(ctx, main); rc = unpack_panel_from(ctx, S.k, D->msg[S.b], S.got_slices ? S.c3n : (int64_t)0, !S.got_slices, main); }
+        if (rc) return rc;
+        rc = span_end(ctx, D, sp, main); if (rc) return rc;
+        DIST_HIP(hipEventRecord(D->ev_free[S.b], main));
+    }
+    return 0;
+}
+// (c) panel k + 1 on its owner: the rest of an early panel, or the classic head + whole panel
+int slot_next_panel(Ctx* ctx, const DistPlan& P, DistRun& R, const SlotPlan& S) {
+    if (!S.own_nxt) return 0;
+    const Geo& g = ctx->g; DistState* D = R.D; const hipStream_t main = R.main, side = R.side;
+    const int64_t k = S.k, nxt = S.nxt;
+    const double* Lop = S.own_k ? ctx->A + g.local_c0(k) * g.Npad : ctx->Lbuf;
+    int rc;
+    if (S.early) {
+        // the rest of panel k + 1: the head from panel k on the rows beyond the slices (main stream: behind the unpack),
+        // then on the side stream its rows of panel k + 3 (slice 2 of panel k + 1 goes out in the next slot), the
+        // remaining rows, and the panel message
+        rc = head_rows(ctx, k, nxt, S.c3n, g.Npad, Lop, g.Npad, main, false); if (rc) return rc;
+        DIST_HIP(hipEventRecord(D->ev_hr, main));
+        DIST_HIP(hipStreamWaitEvent(side, D->ev_hr, 0));
+        size_t sp_rest; rc = span_begin(ctx, D, 4, side, &sp_rest); if (rc) return rc;
+        rc = panel_rows(ctx, nxt, S.c3n, S.c4n, side); if (rc) return rc;
+        if (S.sl_nxt) { rc = pack_s(ctx, R, nxt, 2, side); if (rc) return rc; }
+        rc = span_end(ctx, D, sp_rest, side); if (rc) return rc;
+        // the remaining rows and the panel message follow BEHIND the send of slice 2 on this stream: enqueued at the top
+        // of the next slot, right after that send (flush_rest)
+        R.rest_panel = nxt; R.rest_from = S.c4n;
+        return 0;
+    }
+    // classic: the whole head on the main stream, the whole panel on the side stream behind it
+    if (S.head == Head::range) {
+        rc = update_range(ctx, k, nxt, 1, main); if (rc) return rc;
+    } else if (S.head == Head::wide_split) {
+        // the tile chain of a wide panel needs the head only INSIDE the panel's diagonal block: that part first, the
+        // chain starts behind it; the rows below -- 97 % of the head's flops -- follow on ctx->rest, where the panel's
+        // rows kernels first read them (factor_block).  The same entries, the same products (round 4).
+        rc = ensure_rest_stream(ctx); if (rc) return rc;
+        rc = head_rows(ctx, k, nxt, S.c1n, S.c2n, Lop, g.Npad, main, true); if (rc) return rc;
+    } else {
+        rc = head_rows(ctx, k, nxt, S.c1n, g.Npad, Lop, g.Npad, main, false); if (rc) return rc;
+    }
+    DIST_HIP(hipEventRecord(D->ev_head, main));
+    DIST_HIP(hipStreamWaitEvent(side, D->ev_head, 0));
+    if (S.head == Head::wide_split) {
+        DIST_HIP(hipStreamWaitEvent(ctx->rest, D->ev_head, 0));       // (the main stream's earlier updates of these columns)
+        rc = head_rows(ctx, k, nxt, S.c2n, g.Npad, Lop, g.Npad, ctx->rest, false); if (rc) return rc;
+    }
+    size_t sp; rc = span_begin(ctx, D, 0, side, &sp); if (rc) return rc;
+    rc = factor_panel(ctx, nxt, side, false); if (rc) return rc;
+    if (S.sl_nxt) { rc = pack_s(ctx, R, nxt, 1, side); if (rc) return rc; rc = pack_s(ctx, R, nxt, 2, side); if (rc) return rc; }
+    rc = span_end(ctx, D, sp, side); if (rc) return rc;
+    rc = finish_panel(ctx, P, R, nxt, side); if (rc) return rc;
+    R.on_side[(size_t)nxt] = 1;
+    return 0;
+}
+// (d) the remainder: slice 1 of a classic k + 1, everyone's share of the bulk update of panel k, the progress word, the forward step
+int slot_remainder(Ctx* ctx, const DistPlan& P, DistRun& R, const SlotPlan& S) {
+    int rc;
+    if (S.s1_after) { rc = xchg_s(ctx, P, R, S.nxt, 1, 0); if (rc) return rc; }
+    rc = bulk_from(ctx, P, R, S.k, S.nxt); if (rc) return rc;
+    hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, R.main, R.D->prog_dev + 1, (unsigned)(S.k + 1)); DIST_KCHECK();
+    // last in the iteration: the host submits the next panel's chain first (in the chain-bound tail the GPU is
+    // waiting for exactly those launches; with the forward step submitted ahead of them the factorisation grew by as
+    // much as the sweep shrank)
+    rc = fwd_trail(ctx, P, R, S.k); if (rc) return rc;
+    R.fwd_next = S.k + 1;
+    return 0;
+}
+
+// ---- the tail ---------------------------------------------------------------------------------------------------------------------
+// join the helper streams (the last panel may have been factored on the side stream; messages in flight)
+int join_streams(Ctx* ctx, DistRun& R) {
+    DistState* D = R.D;
+    DIST_HIP(hipEventRecord(D->ev_join, R.side)); DIST_HIP(hipStreamWaitEvent(R.main, D->ev_join, 0));
+    DIST_HIP(hipEventRecord(D->ev_head, R.cs));   DIST_HIP(hipStreamWaitEvent(R.main, D->ev_head, 0));
+    if (ctx->rest) { DIST_HIP(hipEventRecord(D->ev_join, ctx->rest)); DIST_HIP(hipStreamWaitEvent(R.main, D->ev_join, 0)); }
+    return 0;
+}
+// the profile spans of the factorisation, summed by kind (span_begin)
+int sum_spans(Ctx* ctx, DistRun& R) {
+    DistState* D = R.D;
+    D->t_chain = D->t_pack = D->t_bcast = D->t_unpack = 0.0;
+    double t_rest = 0.0;
+    DIST_HIP(hipStreamSynchronize(R.cs)); DIST_HIP(hipStreamSynchronize(R.side));
+    for (auto& s : D->spans) {
+        float ms = 0.f; DIST_HIP(hipEventElapsedTime(&ms, s.a, s.b));
+        (s.kind == 0 ? D->t_chain : s.kind == 1 ? D->t_pack : s.kind == 2 ? D->t_bcast : s.kind == 3 ? D->t_unpack : t_rest) += ms;
+    }
+    ctx->t_panel = D->t_chain;
+    D->wire[WIRE_REST_MS] = t_rest;     // ms of the owner's rows work BEHIND the chain path (two-message protocol)
+    return 0;
+}
+// statistics over the ranks: counts add, extrema combine
+int reduce_stats_over_ranks(Ctx* ctx, DistState* D, hipStream_t main, pyipm_factor_stats* loc) {
+    if (ctx->g.world <= 1) return 0;
+    double h[8] = {(double)loc->n_neg, (double)loc->n_zero, (double)loc->n_2x2, (double)loc->n_pos, (double)loc->nonfinite,
+                   loc->d_max, loc->growth, -loc->d_min};
+    DIST_HIP(hipMemcpyAsync(D->small, h, sizeof(h), hipMemcpyHostToDevice, main));
+    int rc = ex_allreduce(ctx, D, D->small, 5, 0, main); if (rc) return rc;
+    rc = ex_allreduce(ctx, D, D->small + 5, 3, 1, main); if (rc) return rc;
+    DIST_HIP(hipMemcpyAsync(h, D->small, sizeof(h), hipMemcpyDeviceToHost, main));
+    DIST_HIP(hipStreamSynchronize(main));
+    loc->n_neg = (int64_t)h[0]; loc->n_zero = (int64_t)h[1]; loc->n_2x2 = (int64_t)h[2]; loc->n_pos = (int64_t)h[3];
+    loc->nonfinite = (int64_t)h[4]; loc->d_max = h[5]; loc->growth = h[6]; loc->d_min = -h[7];
+    return 0;
+}
+
 // fwd_b != NULL (step_dist): the forward substitution of that right-hand side (replicated, Npad) trails the factorisation on
 // its own stream -- y_p needs nothing but panel p factored on its owner and the segment sum of the panels before it -- and
 // the solve that follows starts at the backward sweep (Held::fwd_done).  The segment sums go through the collective stream
 // like every other exchange, at the same place of the loop on every rank.
-int factor_dist_geo(Ctx* ctx, pyipm_factor_stats* stats, const double* fwd_b);
+int factor_dist_geo(Ctx* ctx, pyipm_factor_stats* stats, const double* fwd_b) {
+    DistState* D; int rc = dist_state(ctx, &D); if (rc) return rc;
+    ctx->sched.clear();                                 // per-panel mode: uniform group map, dense panels
+    ctx->held.panel_phases_begun();
+    rc = factor_begin(ctx); if (rc) return rc;
+    D->used = 0; D->spans.clear(); D->bytes_sent = 0; D->n_msgs = 0;
+    for (int k = 0; k < WIRE_SLOTS; ++k) D->wire[k] = 0.0;
+    const DistPlan P = plan_dist(ctx, D, fwd_b != nullptr);
+    DistRun R{D, ctx->stream, D->side, D->cs, fwd_b};
+    R.on_side.assign((size_t)P.np, 0);
+    rc = dist_setup(ctx, P, R); if (rc) return rc;
+    rc = panel0(ctx, P, R); if (rc) return rc;
+    for (int64_t k = 0; k < P.np && P.below(k) > 0; ++k) {
+        const SlotPlan S = plan_slot(ctx, P, k);
+        rc = slot_ahead(ctx, P, R, S); if (rc) return rc;
+        rc = slot_message(ctx, P, R, S); if (rc) return rc;
+        rc = slot_next_panel(ctx, P, R, S); if (rc) return rc;
+        rc = slot_remainder(ctx, P, R, S); if (rc) return rc;
+    }
+    rc = flush_rest(ctx, P, R); if (rc) return rc;
+    for (int64_t p = R.fwd_next; p < P.np; ++p) { rc = fwd_trail(ctx, P, R, p); if (rc) return rc; }
+    if (P.fwd) {
+        DIST_HIP(hipEventRecord(D->ev_fw, D->fws)); DIST_HIP(hipStreamWaitEvent(R.main, D->ev_fw, 0));
+        ctx->held.forward_done_dist();
+    }
+    rc = join_streams(ctx, R); if (rc) return rc;
+    DIST_HIP(hipEventRecord(ctx->ev[1], R.main));
+    ctx->held.factor_enqueued();
+    rc = bounded_wait(ctx, D, R.main, P.np); if (rc) return rc;
+    pyipm_factor_stats loc;
+    rc = factor_end(ctx, &loc);
+    const int rc_nonfinite = rc;
+    if (rc && rc != PYIPM_E_NONFINITE) return rc;       // (known, DESIGN.md section 6: the peers are on their way into the all-reduces below)
+    {   float ms = 0.f; DIST_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1])); D->t_factor = ms; ctx->t_factor = ms; }
+    if (ctx->profile) { rc = sum_spans(ctx, R); if (rc) return rc; }
+    rc = reduce_stats_over_ranks(ctx, D, R.main, &loc); if (rc) return rc;
+    if (stats) *stats = loc;
+    if (loc.nonfinite) { ctx->err = "NaN/Inf met during factorisation"; return PYIPM_E_NONFINITE; }
+    return rc_nonfinite == PYIPM_E_NONFINITE ? PYIPM_E_NONFINITE : 0;
+}
 
 // The condensed option across ranks (round 3): the same per-panel schedule on the condensed geometry -- (n + me + |active
 // rows|) columns in the same 1-D block-cyclic map -- with the inertia of the eliminated (s, lambda_i) pairs added as in the
@@ -543,413 +1064,9 @@ int factor_dist(Ctx* ctx, pyipm_factor_stats* stats, const double* fwd_b = nullp
     return rc;
 }
 
-int factor_dist_geo(Ctx* ctx, pyipm_factor_stats* stats, const double* fwd_b) {
-    const Geo& g = ctx->g;
-    DistState* D; int rc = dist_state(ctx, &D); if (rc) return rc;
-    ctx->sched.clear();                                 // per-panel mode: uniform group map, dense panels
-    ctx->held.panel_phases_begun();
-    rc = factor_begin(ctx); if (rc) return rc;
-    D->used = 0; D->spans.clear(); D->bytes_sent = 0; D->n_msgs = 0;
-    for (int k = 0; k < 12; ++k) D->wire[k] = 0.0;
-    hipStream_t main = ctx->stream, side = D->side, cs = D->cs;
-    DIST_HIP(hipEventRecord(ctx->ev[0], main));
-    // every rank perturbs alike: the scale of a static pivot is the largest entry over ALL ranks' columns
-    rc = ex_allreduce(ctx, D, reinterpret_cast<double*>(ctx->anorm), 1, 1, main); if (rc) return rc;
-    // the owner's stream starts behind everything the main stream has done to the matrix so far (the assembly, the reset of the
-    // statistics): with slices a panel's early phase waits for no other main-stream work
-    DIST_HIP(hipEventRecord(D->ev_head, main));
-    DIST_HIP(hipStreamWaitEvent(side, D->ev_head, 0));
-    const int64_t np = g.npanels;
-    const int W = g.world;
-    const bool wire = W > 1 || D->selfmsg;
-    size_t need = 0;
-    if (wire) for (int64_t p = 0; p < np; ++p) { const size_t b = dist_msg_bytes(ctx, p); if (b > need) need = b; }
-    if (need > 0)
-        for (int b = 0; b < 2; ++b)
-            if (D->msg[b].reserve(need / sizeof(double) + (size_t)W) != hipSuccess) {                 // (slack: W equal pieces, sag_bcast)
-                ctx->err = "factor_dist: no memory for the panel messages"; return PYIPM_E_NOMEM; }
-    auto below = [&](int64_t p) { return g.Npad - (g.panel_c0(p) + g.panel_w(p)); };
-    auto own = [&](int64_t p) { return p >= 0 && p < np && g.owner(p) == g.rank; };
-    auto msg_of = [&](int64_t p) -> size_t { return (wire && p < np && below(p) > 0) ? dist_msg_bytes(ctx, p) : 0; };
-    // ---- the two-message protocol (round 5): slices ahead of the panel message --------------------------------------------
-    // sl(k): the rows of panel k that meet the diagonal block of panel k + 1 (slice 1, with the tile inverses) and the rows of
-    // panel k + 2 (slice 2) travel from owner(k) to owner(k + 1) point to point AHEAD of the panel message.  owner(k + 1) starts
-    // its tile chain on slice 1, runs the stages of its rows of panel k + 2 on slice 2 and hands ITS slice 1 on -- the chain of
-    // owners no longer waits for a panel message (hundreds of MB), its unpacking, or the rows work of the panel before: what
-    // it waits for is nb x nb.  The panel message itself is unchanged and follows for everybody's bulk update.  Decided from
-    // the geometry alone: every rank takes the same decision for every panel.
-    const bool slices_on = ctx->dist_slices && W > 1;
-    auto sl = [&](int64_t k) -> bool {
-        return slices_on && k >= 0 && k + 1 < np && msg_of(k) > 0 && g.owner(k + 1) != g.owner(k) && !panel_in_s(ctx, k) &&
-               panel_piecewise_ok(ctx, k + 1) && below(k + 1) >= 0;
-    };
-    const bool p2p = tr_has_p2p(D);
-    const hipStream_t ps = tr_slice_stream(D);          // where the point-to-point slices travel
-    if (slices_on) {
-        size_t smax = 0;
-        for (int64_t p = 0; p < np; ++p) for (int j = 1; j <= 2; ++j) { const size_t e = slice_numel(g, p, j); if (e > smax) smax = e; }
-        if (smax > 0) {
-            bool got = true;
-            for (int b = 0; b < 2; ++b) for (int j = 0; j < 2; ++j) got = got && D->sbuf[b][j].reserve(smax) == hipSuccess;
-            for (int j = 0; j < 2; ++j) got = got && D->EL[j].reserve((size_t)g.nb * g.nb) == hipSuccess;
-            if (!got) { ctx->err = "factor_dist: no memory for the slice messages"; return PYIPM_E_NOMEM; }
-        }
-        for (int b = 0; b < 2; ++b) for (int j = 0; j < 2; ++j)
-            for (Event* e : {&D->ev_spack[b][j], &D->ev_srecv[b][j], &D->ev_sfree[b][j]}) DIST_HIP(e->ensure(hipEventDisableTiming));
-        for (Event* e : {&D->ev_pre, &D->ev_hr, &D->ev_hr2}) DIST_HIP(e->ensure(hipEventDisableTiming));
-    }
-    bool sfree_rec[2][2] = {{false, false}, {false, false}};
-    bool pre_rec = false;
-    ctx->held.borrowed(Held::VLOC);
-    if (D->broken) { ctx->err = "an earlier distributed step timed out: this handle's streams may hold collectives that never complete -- destroy it"; return PYIPM_E_COMM; }
-    for (int k = 0; k < 3; ++k) D->prog_host[k] = 0u;
-    if (fwd_b) {
-        DIST_HIP(D->fws.ensure(hipStreamNonBlocking));
-        DIST_HIP(D->ev_fw.ensure(hipEventDisableTiming));
-        DIST_HIP(ensure_events(ctx->ev_done, (size_t)np, hipEventDisableTiming));
-        DIST_HIP(hipEventRecord(D->ev_fw, main));                       // the right-hand side was produced on the main stream
-        DIST_HIP(hipStreamWaitEvent(D->fws, D->ev_fw, 0));
-        { int r_ = launch_mask_owned(ctx, D->fws, D->vloc, fwd_b); if (r_) return r_; }
-    }
-    // forward substitution of panel p (all ranks: the segment sum; owner: the panel's own part)
-    auto fwd_step = [&](int64_t p) -> int {
-        if (!fwd_b) return 0;
-        const int64_t c0 = g.panel_c0(p); const int64_t nbw = g.panel_w(p);
-        double* v = D->vloc;
-        if (W > 1) {
-            DIST_HIP(hipMemcpyAsync(D->seg, v + c0, (size_t)nbw * sizeof(double), hipMemcpyDeviceToDevice, D->fws));
-            int r = ex_allreduce(ctx, D, D->seg, (size_t)nbw, 0, D->fws); if (r) return r;
-            if (own(p)) DIST_HIP(hipMemcpyAsync(v + c0, D->seg, (size_t)nbw * sizeof(double), hipMemcpyDeviceToDevice, D->fws));
-        }
-        if (own(p)) {
-            DIST_HIP(hipStreamWaitEvent(D->fws, ctx->ev_done[(size_t)p], 0));      // panel p factored
-            int r = fwd_panel(ctx, p, v, D->fws); if (r) return r;
-            r = diag_panel(ctx, p, v, D->fws); if (r) return r;
-        }
-        return 0;
-    };
-    // ---- building blocks ------------------------------------------------------------------------------------------------
-    // owner: panel p is complete on `st` -> forward-sweep event, pack the panel message, "factored" event
-    auto finish_panel = [&](int64_t p, hipStream_t st) -> int {
-        const int b = (int)(p & 1);
-        if (fwd_b) DIST_HIP(hipEventRecord(ctx->ev_done[(size_t)p], st));
-        if (msg_of(p) > 0) {
-            DIST_HIP(hipStreamWaitEvent(st, D->ev_free[b], 0));          // the previous message in this buffer has left / been unpacked
-            size_t sp; int r = span_begin(ctx, D, 1, st, &sp); if (r) return r;
-            { StreamScope sc(ctx, st); r = pyipm_newton_panel_pack(reinterpret_cast<pyipm_newton_ctx*>(ctx), p, D->msg[b]); }
-            if (r) return r;
-            r = span_end(ctx, D, sp, st); if (r) return r;
-        }
-        DIST_HIP(hipEventRecord(D->ev_fact[b], st));
-        hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, st, D->prog_dev + 2, (unsigned)(p + 1)); DIST_KCHECK();
-        return 0;
-    };
-    // owner: pack slice j of panel p on `st` (its rows of panel p + j are final there)
-    auto pack_s = [&](int64_t p, int j, hipStream_t st) -> int {
-        if (slice_numel(g, p, j) == 0) return 0;
-        const int b = (int)(p & 1);
-        if (sfree_rec[b][j - 1]) DIST_HIP(hipStreamWaitEvent(st, D->ev_sfree[b][j - 1], 0));
-        int r = pack_slice(ctx, p, j, D->sbuf[b][j - 1], st); if (r) return r;
-        DIST_HIP(hipEventRecord(D->ev_spack[b][j - 1], st));
-        return 0;
-    };
-    // slice j of panel p on the wire: owner(p) -> owner(p + 1); without a point-to-point transport it travels as a broadcast
-    // role: 0 = whatever this rank's part is, 1 = only if it is the sender, 2 = only if it is the receiver
-    auto xchg_s = [&](int64_t p, int j, int role) -> int {
-        const size_t cnt = slice_numel(g, p, j);
-        if (cnt == 0) return 0;
-        const int b = (int)(p & 1), src = g.owner(p), dst = g.owner(p + 1);
-        double* buf = D->sbuf[b][j - 1];
-        const bool sender = g.rank == src && role != 2, receiver = g.rank == dst && role != 1;
-        if (p2p && !sender && !receiver) return 0;
-        if (!p2p) {
-            if (sender) DIST_HIP(hipStreamWaitEvent(cs, D->ev_spack[b][j - 1], 0));
-            else if (sfree_rec[b][j - 1]) DIST_HIP(hipStreamWaitEvent(cs, D->ev_sfree[b][j - 1], 0));
-            int r = tr_bcast(ctx, D, buf, cnt, src, cs); if (r) return r;
-            D->wire[9] += 1.0;
-            if (!receiver) { DIST_HIP(hipEventRecord(D->ev_sfree[b][j - 1], cs)); sfree_rec[b][j - 1] = true; }
-        } else if (sender) {
-            DIST_HIP(hipStreamWaitEvent(ps, D->ev_spack[b][j - 1], 0));
-            int r = tr_send(ctx, D, buf, cnt, dst, ps, true); if (r) return r;
-            DIST_HIP(hipEventRecord(D->ev_sfree[b][j - 1], ps)); sfree_rec[b][j - 1] = true;
-        } else if (receiver) {
-            if (sfree_rec[b][j - 1]) DIST_HIP(hipStreamWaitEvent(ps, D->ev_sfree[b][j - 1], 0));
-            int r = tr_recv(ctx, D, buf, cnt, src, ps, true); if (r) return r;
-        } else return 0;
-        if (receiver) DIST_HIP(hipEventRecord(D->ev_srecv[b][j - 1], p2p ? ps : cs));
-        if (sender || receiver) { D->wire[7] += 1.0; D->wire[8] += (double)(cnt * sizeof(double)); }
-        return 0;
-    };
-    // head update of panel q's columns from panel p (p < q, q owned) over rows [r0, r1): Lop = where L of panel p lives for those
-    // rows (this rank's storage, the rebuilt panel, or a slice's L rows offset to global row numbers)
-    auto head_rows = [&](int64_t p, int64_t q, int64_t r0, int64_t r1, const double* Lop, int64_t ldl, hipStream_t st, bool small) -> int {
-        if (r1 > g.Npad) r1 = g.Npad;
-        if (r1 <= r0) return 0;
-        const int K = (int)g.panel_w(p);
-        const int64_t c0q = g.panel_c0(q), nbwq = g.panel_w(q);
-        if (panel_in_s(ctx, p)) return 0;                              // (a slack-block source: handled by update_range, whole columns)
-        if (small || g.Npad - (c0q + nbwq) <= HEAD32_ROWS_DIST) {
-            int64_t pa0, pa1, pb0, pb1;
-            active_ranges(ctx, g.panel_c0(p), g.panel_c0(p) + K, &pa0, &pa1, &pb0, &pb1);
-            return launch_inpanel_update(ctx, st, dim3((unsigned)((r1 - r0) / 32), (unsigned)(nbwq / TB)), ctx->A, g.Npad, g.local_c0(q), Lop, ldl,
-                                         wbuf(ctx, p), g.Npad, c0q, K, r0, g.Npad, pa0, pa1, pb0, pb1, SIDE_PRIO);
-        }
-        return launch_update128(ctx, st, Lop, ldl, wbuf(ctx, p), K, r0, q / W, 1, {.row_end = r1, .src_c0 = g.panel_c0(p), .waves = HEAD_WAVES});
-    };
-    // the panel message of p: owner sends (its pack is behind ev_fact), everyone else joins
-    auto bcast_big = [&](int64_t p) -> int {
-        const size_t bytes = msg_of(p);
-        if (!bytes) return 0;
-        const int b = (int)(p & 1);
-        if (ctx->debug_fault == 3 && p >= np / 2) {       // test hook: this panel's message "never completes" (the first panel from the middle on that HAS one: slack-block panels do not)
-            ctx->debug_fault = 0;
-            double tb = ctx->dist_timeout_s > 0 ? 3.0 * ctx->dist_timeout_s : 30.0; if (tb > 30.0) tb = 30.0;
-            hipLaunchKernelGGL(k_stall, dim3(1), dim3(64), 0, cs, (unsigned long long)(tb * 1.0e8));
-            DIST_KCHECK();
-        }
-        if (own(p)) DIST_HIP(hipStreamWaitEvent(cs, D->ev_fact[b], 0));
-        else DIST_HIP(hipStreamWaitEvent(cs, D->ev_free[b], 0));
-        size_t sp; int r = span_begin(ctx, D, 2, cs, &sp); if (r) return r;
-        r = ex_bcast(ctx, D, D->msg[b], bytes, g.owner(p), cs); if (r) return r;
-        r = span_end(ctx, D, sp, cs); if (r) return r;
-        DIST_HIP(hipEventRecord(D->ev_msg[b], cs));
-        if (own(p)) DIST_HIP(hipEventRecord(D->ev_free[b], cs));        // an owner's buffer is free once the message has left
-        D->bytes_sent += bytes; D->n_msgs++;
-        hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, cs, D->prog_dev + 0, (unsigned)(p + 1));      // progress word (bounded_wait)
-        DIST_KCHECK();
-        return 0;
-    };
-    // bulk update from panel p of the owned panels beyond `after`; with slices the panel this rank factors next goes first
-    // (its own launch, then an event: that panel's early phase waits for nothing else of the main stream)
-    auto bulk_from = [&](int64_t p, int64_t after) -> int {
-        int64_t nf = after + 1;
-        while (nf < np && !own(nf)) ++nf;
-        if (nf >= np) return 0;
-        if (slices_on && nf == after + 1) {                 // (its early phase comes in the very next slot)
-            int r = update_range(ctx, p, nf, 1, main); if (r) return r;
-            DIST_HIP(hipEventRecord(D->ev_pre, main)); pre_rec = true;
-            return update_range(ctx, p, nf + 1, np, main);
-        }
-        return update_range(ctx, p, nf, np, main);
-    };
-
-    // an early panel's rows beyond its slices + its panel message (see the slot loop)
-    int64_t rest_panel = -1, rest_from = 0;
-    auto flush_rest = [&]() -> int {
-        if (rest_panel < 0) return 0;
-        const int64_t q = rest_panel; rest_panel = -1;
-        size_t sp; int r = span_begin(ctx, D, 4, side, &sp); if (r) return r;
-        r = panel_rows(ctx, q, rest_from, g.Npad, side); if (r) return r;
-        r = span_end(ctx, D, sp, side); if (r) return r;
-        return finish_panel(q, side);
-    };
-    // ---- panel 0: its owner factors it whole on the main stream ------------------------------------------------------------
-    std::vector<char> on_side((size_t)np, 0);
-    if (own(0)) {
-        size_t sp; rc = span_begin(ctx, D, 0, main, &sp); if (rc) return rc;
-        rc = factor_panel(ctx, 0, main, false); if (rc) return rc;
-        if (sl(0)) { rc = pack_s(0, 1, main); if (rc) return rc; rc = pack_s(0, 2, main); if (rc) return rc; }
-        rc = span_end(ctx, D, sp, main); if (rc) return rc;
-        rc = finish_panel(0, main); if (rc) return rc;
-    }
-    if (sl(0)) { rc = xchg_s(0, 1, 0); if (rc) return rc; }
-    int64_t fwd_next = 0;                                               // first panel whose forward step is not enqueued yet
-    for (int64_t k = 0; k < np; ++k) {
-        if (below(k) <= 0) break;
-        const int b = (int)(k & 1);
-        const int64_t nxt = k + 1;
-        const bool early = sl(k);                                       // panel k + 1 is factored in pieces, on slices of panel k
-        const int64_t c1n = nxt < np ? g.panel_c0(nxt) : g.Npad, c2n = nxt + 1 < np ? g.panel_c0(nxt + 1) : g.Npad,
-                      c3n = nxt + 2 < np ? g.panel_c0(nxt + 2) : g.Npad;
-        size_t sp_chain = (size_t)-1;
-        if (early) {
-            // (1) slice 2 of panel k, (2) the early phase of panel k + 1 on its owner, (3) slice 1 of panel k + 1, (4) the panel
-            // message of k -- in this order on every rank's collective stream
-            // (slices on the owner's stream: the receiver posts its receive of slice 2 BEHIND its tile chain, below -- in front of
-            //  it the stream would sit waiting for a message the chain does not need)
-            const bool s2_late = p2p && ps == side;
-            rc = xchg_s(k, 2, s2_late ? 1 : 0); if (rc) return rc;
-            rc = flush_rest(); if (rc) return rc;
-            if (own(nxt)) {
-                const int64_t ldE1 = c2n - c1n;
-                if (pre_rec) DIST_HIP(hipStreamWaitEvent(side, D->ev_pre, 0));   // the main stream's updates of panel k + 1's columns
-                DIST_HIP(hipStreamWaitEvent(side, D->ev_srecv[b][0], 0));
-                rc = span_begin(ctx, D, 0, side, &sp_chain); if (rc) return rc;   // (chain path: work only, not the wait for a slice)
-                const double* tiles_k = D->sbuf[b][0] + ldE1 * g.panel_w(k);      // slice 1 carries the panel's tile inverses, tiles, flags
-                rc = unpack_slice(ctx, k, 1, D->sbuf[b][0], tiles_k, D->EL[0], side); if (rc) return rc;
-                rc = head_rows(k, nxt, c1n, c2n, D->EL[0] - c1n, ldE1, side, true); if (rc) return rc;
-                // (round 6) The rows of panel k + 2 -- what the NEXT owner's chain waits for as its slice 1 -- ride in the chain's own
-                // launch: their units apply every stage as the chain publishes it, instead of a k_panel_rest launch behind the chain
-                // (34 us + two launch boundaries per panel on the owners' path).  Their head comes from slice 2 of panel k, which is
-                // still on its way when the chain starts: it is unpacked and applied on the rows stream, and a word set behind it
-                // releases those units (bounded poll, as every poll of that kernel).  Not with slices posted on the owner's own
-                // stream behind the chain (s2_late): the receive would sit behind the kernel that waits for it.
-                const bool ext = c3n > c2n && !s2_late && ctx->dist_slices >= 2 && chain_extra_ok(ctx, nxt, c3n - c2n);
-                if (ext) {
-                    // (on the collective stream, right behind the receive of slice 2: an idle stream woken through two events took
-                    //  longer to get there than the launch it saves)
-                    const hipStream_t xs = cs;
-                    DIST_HIP(hipEventRecord(D->ev_x, side));                      // (behind unpack 1 / head 1: the tiles are read from the same buffer,
-                    DIST_HIP(hipStreamWaitEvent(xs, D->ev_x, 0));                 //  EL[1]'s earlier readers are ordered)
-                    if (pre_rec) DIST_HIP(hipStreamWaitEvent(xs, D->ev_pre, 0));
-                    rc = unpack_slice(ctx, k, 2, D->sbuf[b][1], tiles_k, D->EL[1], xs); if (rc) return rc;
-                    DIST_HIP(hipEventRecord(D->ev_sfree[b][1], xs)); sfree_rec[b][1] = true;
-                    rc = head_rows(k, nxt, c2n, c3n, D->EL[1] - c2n, c3n - c2n, xs, true); if (rc) return rc;
-                    D->xtoken += 1;
-                    hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, xs, D->xflag, D->xtoken); DIST_KCHECK();
-                    rc = panel_chain(ctx, nxt, side, c3n - c2n, D->xflag, D->xtoken); if (rc) return rc;
-                    D->wire[11] += 1.0;
-                    // (the slice-1 buffer's tiles are read by that unpack: it must have run before the buffer is freed below)
-                    DIST_HIP(hipEventRecord(D->ev_x, xs));
-                    DIST_HIP(hipStreamWaitEvent(side, D->ev_x, 0));
-                } else {
-                rc = panel_chain(ctx, nxt, side); if (rc) return rc;
-                }
-                if (c3n > c2n && !ext) {
-                    rc = span_end(ctx, D, sp_chain, side); if (rc) return rc;
-                    if (s2_late) { rc = xchg_s(k, 2, 2); if (rc) return rc; }
-                    DIST_HIP(hipStreamWaitEvent(side, D->ev_srecv[b][1], 0));
-                    rc = span_begin(ctx, D, 0, side, &sp_chain); if (rc) return rc;
-                    rc = unpack_slice(ctx, k, 2, D->sbuf[b][1], tiles_k, D->EL[1], side); if (rc) return rc;
-                    DIST_HIP(hipEventRecord(D->ev_sfree[b][1], side)); sfree_rec[b][1] = true;
-                    rc = head_rows(k, nxt, c2n, c3n, D->EL[1] - c2n, c3n - c2n, side, true); if (rc) return rc;
-                    rc = panel_rows(ctx, nxt, c2n, c3n, side); if (rc) return rc;
-                }
-                if (sl(nxt)) { rc = pack_s(nxt, 1, side); if (rc) return rc; }
-                rc = span_end(ctx, D, sp_chain, side); if (rc) return rc;
-                // behind the chain path: panel k's tiles into the handle's arrays (the rest of its unpacking reads them there);
-                // only then may the slice-1 buffer be written again
-                rc = unpack_slice_tiles(ctx, k, tiles_k, side); if (rc) return rc;
-                DIST_HIP(hipEventRecord(D->ev_sfree[b][0], side)); sfree_rec[b][0] = true;
-                DIST_HIP(hipEventRecord(D->ev_hr2, side));
-                on_side[(size_t)nxt] = 1;
-            }
-            if (sl(nxt)) { rc = xchg_s(nxt, 1, 0); if (rc) return rc; }
-        }
-        rc = flush_rest(); if (rc) return rc;                           // (a slot without slices: nothing to send first)
-        rc = bcast_big(k); if (rc) return rc;
-        // ---- main stream: panel k becomes available here ------------------------------------------------------------------
-        if (own(k)) {
-            if (on_side[(size_t)k]) DIST_HIP(hipStreamWaitEvent(main, D->ev_fact[b], 0));     // completed on the side stream
-        } else if (msg_of(k) > 0) {
-            DIST_HIP(hipStreamWaitEvent(main, D->ev_msg[b], 0));
-            size_t sp; rc = span_begin(ctx, D, 3, main, &sp); if (rc) return rc;
-            const bool got_slices = early && own(nxt);
-            if (got_slices) DIST_HIP(hipStreamWaitEvent(main, D->ev_hr2, 0));      // panel k's tiles are in the handle's arrays
-            { StreamScope sc(ctx, main); rc = unpack_panel_from(ctx, k, D->msg[b], got_slices ? c3n : (int64_t)0, !got_slices, main); }
-            if (rc) return rc;
-            rc = span_end(ctx, D, sp, main); if (rc) return rc;
-            DIST_HIP(hipEventRecord(D->ev_free[b], main));
-        }
-        if (nxt < np && own(nxt)) {
-            const bool mine_k = own(k);
-            const double* Lop = mine_k ? ctx->A + g.local_c0(k) * g.Npad : ctx->Lbuf;
-            if (early) {
-                // the rest of panel k + 1: the head from panel k on the rows beyond the slices (main stream: behind the unpack),
-                // then on the side stream its rows of panel k + 3 (slice 2 of panel k + 1 goes out in the next slot), the
-                // remaining rows, and the panel message
-                const int64_t c4n = nxt + 3 < np ? g.panel_c0(nxt + 3) : g.Npad;
-                rc = head_rows(k, nxt, c3n, g.Npad, Lop, g.Npad, main, false); if (rc) return rc;
-                DIST_HIP(hipEventRecord(D->ev_hr, main));
-                DIST_HIP(hipStreamWaitEvent(side, D->ev_hr, 0));
-                size_t sp_rest; rc = span_begin(ctx, D, 4, side, &sp_rest); if (rc) return rc;
-                rc = panel_rows(ctx, nxt, c3n, c4n, side); if (rc) return rc;
-                if (sl(nxt)) { rc = pack_s(nxt, 2, side); if (rc) return rc; }
-                rc = span_end(ctx, D, sp_rest, side); if (rc) return rc;
-                // the remaining rows and the panel message follow BEHIND the send of slice 2 on this stream: enqueued at the top
-                // of the next slot, right after that send (flush_rest)
-                rest_panel = nxt; rest_from = c4n;
-            } else {
-                // classic: the whole head on the main stream, the whole panel on the side stream behind it
-                const int64_t nbwn = g.panel_w(nxt);
-                const bool wide_next = ctx->tile_step && ctx->wide_sub >= 128 &&
-                                       ctx->wide_sub % 128 == 0 && nbwn > ctx->wide_sub && nbwn / TB <= 32 && c1n + nbwn < g.Npad &&
-                                       !panel_in_s(ctx, nxt) && !panel_in_s(ctx, k) && nbwn % 32 == 0;
-                if (panel_in_s(ctx, k) || panel_in_s(ctx, nxt)) {
-                    rc = update_range(ctx, k, nxt, 1, main); if (rc) return rc;
-                    DIST_HIP(hipEventRecord(D->ev_head, main));
-                    DIST_HIP(hipStreamWaitEvent(side, D->ev_head, 0));
-                } else if (wide_next) {
-                    // the tile chain of a wide panel needs the head only INSIDE the panel's diagonal block: that part first, the
-                    // chain starts behind it; the rows below -- 97 % of the head's flops -- follow on ctx->rest, where the panel's
-                    // rows kernels first read them (factor_block).  The same entries, the same products (round 4).
-                    rc = ensure_rest_stream(ctx); if (rc) return rc;
-                    rc = head_rows(k, nxt, c1n, c2n, Lop, g.Npad, main, true); if (rc) return rc;
-                    DIST_HIP(hipEventRecord(D->ev_head, main));
-                    DIST_HIP(hipStreamWaitEvent(side, D->ev_head, 0));
-                    DIST_HIP(hipStreamWaitEvent(ctx->rest, D->ev_head, 0));       // (the main stream's earlier updates of these columns)
-                    rc = head_rows(k, nxt, c2n, g.Npad, Lop, g.Npad, ctx->rest, false); if (rc) return rc;
-                } else {
-                    rc = head_rows(k, nxt, c1n, g.Npad, Lop, g.Npad, main, false); if (rc) return rc;
-                    DIST_HIP(hipEventRecord(D->ev_head, main));
-                    DIST_HIP(hipStreamWaitEvent(side, D->ev_head, 0));
-                }
-                size_t sp; rc = span_begin(ctx, D, 0, side, &sp); if (rc) return rc;
-                rc = factor_panel(ctx, nxt, side, false); if (rc) return rc;
-                if (sl(nxt)) { rc = pack_s(nxt, 1, side); if (rc) return rc; rc = pack_s(nxt, 2, side); if (rc) return rc; }
-                rc = span_end(ctx, D, sp, side); if (rc) return rc;
-                rc = finish_panel(nxt, side); if (rc) return rc;
-                on_side[(size_t)nxt] = 1;
-            }
-        }
-        if (!early && sl(nxt)) { rc = xchg_s(nxt, 1, 0); if (rc) return rc; }       // (classic panel k + 1: its slice 1 follows the panel message of k)
-        rc = bulk_from(k, nxt); if (rc) return rc;                                // everyone's share of the bulk update of panel k
-        hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, main, D->prog_dev + 1, (unsigned)(k + 1)); DIST_KCHECK();
-        // last in the iteration: the host submits the next panel's chain first (in the chain-bound tail the GPU is
-        // waiting for exactly those launches; with the forward step submitted ahead of them the factorisation grew by as
-        // much as the sweep shrank)
-        rc = fwd_step(k); if (rc) return rc;
-        fwd_next = k + 1;
-    }
-    rc = flush_rest(); if (rc) return rc;
-    for (int64_t p = fwd_next; p < np; ++p) { rc = fwd_step(p); if (rc) return rc; }
-    if (fwd_b) {
-        DIST_HIP(hipEventRecord(D->ev_fw, D->fws)); DIST_HIP(hipStreamWaitEvent(main, D->ev_fw, 0));
-        ctx->held.forward_done_dist();
-    }
-    // join the helper streams (the last panel may have been factored on the side stream; messages in flight)
-    DIST_HIP(hipEventRecord(D->ev_join, side)); DIST_HIP(hipStreamWaitEvent(main, D->ev_join, 0));
-    DIST_HIP(hipEventRecord(D->ev_head, cs));   DIST_HIP(hipStreamWaitEvent(main, D->ev_head, 0));
-    if (ctx->rest) { DIST_HIP(hipEventRecord(D->ev_join, ctx->rest)); DIST_HIP(hipStreamWaitEvent(main, D->ev_join, 0)); }
-    DIST_HIP(hipEventRecord(ctx->ev[1], main));
-    ctx->held.factor_enqueued();
-    rc = bounded_wait(ctx, D, main, np); if (rc) return rc;
-    pyipm_factor_stats loc;
-    rc = factor_end(ctx, &loc);
-    const int rc_nonfinite = rc;
-    if (rc && rc != PYIPM_E_NONFINITE) return rc;
-    {   float ms = 0.f; DIST_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1])); D->t_factor = ms; ctx->t_factor = ms; }
-    if (ctx->profile) {
-        D->t_chain = D->t_pack = D->t_bcast = D->t_unpack = 0.0;
-        double t_rest = 0.0;
-        DIST_HIP(hipStreamSynchronize(cs)); DIST_HIP(hipStreamSynchronize(side));
-        for (auto& s : D->spans) {
-            float ms = 0.f; DIST_HIP(hipEventElapsedTime(&ms, s.a, s.b));
-            (s.kind == 0 ? D->t_chain : s.kind == 1 ? D->t_pack : s.kind == 2 ? D->t_bcast : s.kind == 3 ? D->t_unpack : t_rest) += ms;
-        }
-        ctx->t_panel = D->t_chain;
-        D->wire[10] = t_rest;           // ms of the owner's rows work BEHIND the chain path (two-message protocol)
-    }
-    // statistics over the ranks: counts add, extrema combine
-    if (W > 1) {
-        double h[8] = {(double)loc.n_neg, (double)loc.n_zero, (double)loc.n_2x2, (double)loc.n_pos, (double)loc.nonfinite,
-                       loc.d_max, loc.growth, -loc.d_min};
-        DIST_HIP(hipMemcpyAsync(D->small, h, sizeof(h), hipMemcpyHostToDevice, main));
-        rc = ex_allreduce(ctx, D, D->small, 5, 0, main); if (rc) return rc;
-        rc = ex_allreduce(ctx, D, D->small + 5, 3, 1, main); if (rc) return rc;
-        DIST_HIP(hipMemcpyAsync(h, D->small, sizeof(h), hipMemcpyDeviceToHost, main));
-        DIST_HIP(hipStreamSynchronize(main));
-        loc.n_neg = (int64_t)h[0]; loc.n_zero = (int64_t)h[1]; loc.n_2x2 = (int64_t)h[2]; loc.n_pos = (int64_t)h[3];
-        loc.nonfinite = (int64_t)h[4]; loc.d_max = h[5]; loc.growth = h[6]; loc.d_min = -h[7];
-    }
-    if (stats) *stats = loc;
-    if (loc.nonfinite) { ctx->err = "NaN/Inf met during factorisation"; return PYIPM_E_NONFINITE; }
-    return rc_nonfinite == PYIPM_E_NONFINITE ? PYIPM_E_NONFINITE : 0;
-}
-
 // x := Hc^{-1} b across the ranks.  b, x: Npad device vectors, replicated (b on entry, x on return).
 // Forward: rank r keeps vloc_r with sum_r vloc_r = b - (updates applied so far); the owner of panel p needs the SUM of
-// the segment [c0, c1) -- one nb-long all-reduce -- resolves it and pushes its update into its own vloc.  No vector
+// the segment [c0, c1) -- one nb-long all-reduce -- resolves it and pushes its update into its own vloc (fwd_step).  No vector
 // travels.  Backward: the owner needs every x below, so each resolved segment is broadcast (nb doubles).
 int solve_dist_once(Ctx* ctx, DistState* D, const double* b, double* x, bool forward_done = false) {
     const Geo& g = ctx->g;
@@ -958,19 +1075,7 @@ int solve_dist_once(Ctx* ctx, DistState* D, const double* b, double* x, bool for
     if (!forward_done) {
         { int r_ = launch_mask_owned(ctx, st, v, b); if (r_) return r_; }
     }
-    for (int64_t p = 0; p < g.npanels && !forward_done; ++p) {
-        const int64_t c0 = g.panel_c0(p); const int64_t nbw = g.panel_w(p);
-        const bool own = g.owner(p) == g.rank;
-        if (g.world > 1) {
-            DIST_HIP(hipMemcpyAsync(D->seg, v + c0, (size_t)nbw * sizeof(double), hipMemcpyDeviceToDevice, st));
-            int rc = ex_allreduce(ctx, D, D->seg, (size_t)nbw, 0, st); if (rc) return rc;
-            if (own) DIST_HIP(hipMemcpyAsync(v + c0, D->seg, (size_t)nbw * sizeof(double), hipMemcpyDeviceToDevice, st));
-        }
-        if (own) {
-            int rc = fwd_panel(ctx, p, v); if (rc) return rc;
-            rc = diag_panel(ctx, p, v); if (rc) return rc;
-        }
-    }
+    for (int64_t p = 0; p < g.npanels && !forward_done; ++p) { int rc = fwd_step(ctx, D, p, st); if (rc) return rc; }
     for (int64_t p = g.npanels - 1; p >= 0; --p) {
         const int64_t c0 = g.panel_c0(p); const int64_t nbw = g.panel_w(p);
         if (g.owner(p) == g.rank) { int rc = bwd_panel(ctx, p, v); if (rc) return rc; }
@@ -1099,7 +1204,7 @@ int pyipm_newton_dist_wire(pyipm_newton_ctx* h, double out[12]) try {
     PYIPM_ENTER("dist_wire", 0)
     if (!out) return PYIPM_E_BADARG;
     DistState* D; int rc = dist_state(ctx, &D); if (rc) return rc;
-    for (int k = 0; k < 12; ++k) out[k] = D->wire[k];
+    for (int k = 0; k < WIRE_SLOTS; ++k) out[k] = D->wire[k];
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 

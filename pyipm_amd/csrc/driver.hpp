@@ -97,6 +97,7 @@ int solve_inplace(Ctx* ctx, double* v, bool forward_done = false);
 int solve_plain(Ctx* ctx, double* v, bool forward_done, int nrhs = 1, int64_t vstride = 0, double* part = nullptr,
                 int64_t pstride = 0);
 int ensure_rest_stream(Ctx* ctx);
+bool panel_is_wide(const Ctx* ctx, int64_t p);
 bool panel_piecewise_ok(const Ctx* ctx, int64_t p);
 int panel_chain(Ctx* ctx, int64_t p, hipStream_t stream, int64_t xrows = 0, const unsigned* xword = nullptr, unsigned xwant = 0);
 bool chain_extra_ok(const Ctx* ctx, int64_t p, int64_t xrows);

@@ -472,8 +472,7 @@ int factor_panel(Ctx* ctx, int64_t p, hipStream_t stream, bool apply_pending) {
     // source columns allows, so a mixed group needs all of them written.
     if (ctx->skip_zeros && g.world == 1 && g.mi > 0 && ctx->sched.in_x_panel(p)) slack_hole(g, &hole0, &hole1);
     else panel_hole(ctx, p, &hole0, &hole1);            // per-panel mode (any number of ranks)
-    if (ctx->tile_step && !ctx->sched.active() && ctx->wide_sub >= 128 && ctx->wide_sub % 128 == 0 &&
-        nbw > ctx->wide_sub && nt <= 32 && c0 + nbw < g.Npad)
+    if (ctx->tile_step && !ctx->sched.active() && panel_is_wide(ctx, p) && nt <= 32 && c0 + nbw < g.Npad)
         return factor_wide_panel(ctx, p, stream);
     if (ctx->tile_step && nt <= 16) {
         // stepped schedule: launch t inverts tile t (after eliminating tile t - 1 from the rows of the diagonal block), one
@@ -767,12 +766,16 @@ int factor_wide_panel(Ctx* ctx, int64_t p, hipStream_t stream) {
 // arrived (a slice message, nb x nb); the rows below follow when their operands do.  A panel's rows below its diagonal block
 // do not interact, so factoring it in pieces -- the tile chain, then the stages of any row range -- runs the same kernels on
 // every entry in the same order as factor_panel does in one go: the same bits (tests/test_gpu_dist.py, tools/rank_replay.py).
+// is panel p wider than `wide_sub` columns (factored and swept as a block of sub-panels that wide)?  The width alone: every
+// site adds what else it needs (factor_panel: per-panel mode, at most 32 tiles, rows below; panel_piecewise_ok: 32 against 16
+// tiles; panel_rows: nothing; the distributed driver's classic head, plan_slot: also the slack block and the 32-row grid).
+bool panel_is_wide(const Ctx* ctx, int64_t p) {
+    return ctx->wide_sub >= 128 && ctx->wide_sub % 128 == 0 && ctx->g.panel_w(p) > ctx->wide_sub;
+}
 bool panel_piecewise_ok(const Ctx* ctx, int64_t p) {
-    const Geo& g = ctx->g;
     if (!ctx->tile_step || panel_in_s(ctx, p)) return false;
-    const int nbw = (int)g.panel_w(p), nt = nbw / TB;
-    const bool wide = ctx->wide_sub >= 128 && ctx->wide_sub % 128 == 0 && nbw > ctx->wide_sub;
-    return wide ? (nt <= 32) : (nt <= 16);
+    const int nt = (int)ctx->g.panel_w(p) / TB;
+    return panel_is_wide(ctx, p) ? (nt <= 32) : (nt <= 16);
 }
 // the tile steps of panel p's diagonal block (all that needs is the diagonal block up to date)
 int panel_chain(Ctx* ctx, int64_t p, hipStream_t stream, int64_t xrows, const unsigned* xword, unsigned xwant) {
@@ -808,8 +811,7 @@ int panel_rows(Ctx* ctx, int64_t p, int64_t r0, int64_t r1, hipStream_t stream) 
     double* W = wbuf(ctx, p);
     int64_t hole0 = 0, hole1 = 0;
     panel_hole(ctx, p, &hole0, &hole1);
-    const bool wide = ctx->wide_sub >= 128 && ctx->wide_sub % 128 == 0 && nbw > ctx->wide_sub;
-    if (!wide) {
+    if (!panel_is_wide(ctx, p)) {
         hipLaunchKernelGGL(k_panel_rest, dim3((unsigned)((r1 - r0) / TB)), dim3(256), 0, stream, ctx->A, g.Npad, c0, lc0, nt, r0,
                            W, g.Npad, ctx->Dinv + (c0 / TB) * TT, ctx->Tsv + (c0 / TB) * TT, ctx->Tflag + c0 / TB,
                            ctx->block_refine, hole0, hole1, &ctx->dstats->growth_bits);

@@ -98,74 +98,63 @@ class DistNewton(object):
         def view(ptr, count):
             return torch.as_tensor(_RawDeviceArray(ptr, count), device=core.device)
 
-        def bcast(user, ptr, nbytes, root, stream):
-            try:
-                t = view(ptr, nbytes // 8)
-                torch.cuda.synchronize(core.device)                     # the library enqueued the producer on `stream`
-                h = t.cpu()
-                dist.broadcast(h, src=root if self.group is None else dist.get_global_rank(self.group, root), group=self.group)
-                if self.rank != root:
-                    t.copy_(h)
-                    torch.cuda.synchronize(core.device)
-                return 0
-            except Exception as e:                                      # nothing may propagate through the C frames
-                self._cb_error = e
-                return 1
+        def grank(r):
+            return r if self.group is None else dist.get_global_rank(self.group, r)
 
+        def callback(fn):
+            """The frame of every exchange callback: nothing may propagate through the C frames, so an exception is stored
+            (_native re-raises it) and the library is told 1."""
+            def cb(*args):
+                try:
+                    fn(*args)
+                    return 0
+                except Exception as e:
+                    self._cb_error = e
+                    return 1
+            return cb
+
+        @callback
+        def bcast(user, ptr, nbytes, root, stream):
+            t = view(ptr, nbytes // 8)
+            torch.cuda.synchronize(core.device)                         # the library enqueued the producer on `stream`
+            self._collective(t, lambda h: dist.broadcast(h, src=grank(root), group=self.group), back=self.rank != root, stage=True)
+            if self.rank != root:
+                torch.cuda.synchronize(core.device)
+
+        @callback
         def allreduce(user, ptr, count, op, stream):
-            try:
-                t = view(ptr, count)
-                torch.cuda.synchronize(core.device)
-                h = t.cpu()
-                dist.all_reduce(h, op=dist.ReduceOp.MAX if op else dist.ReduceOp.SUM, group=self.group)
-                t.copy_(h)
-                torch.cuda.synchronize(core.device)
-                return 0
-            except Exception as e:
-                self._cb_error = e
-                return 1
+            t = view(ptr, count)
+            torch.cuda.synchronize(core.device)
+            self._collective(t, lambda h: dist.all_reduce(h, op=dist.ReduceOp.MAX if op else dist.ReduceOp.SUM, group=self.group),
+                             stage=True)
+            torch.cuda.synchronize(core.device)
 
         core.set_exchange(BCAST_FN(bcast), ALLREDUCE_FN(allreduce))
         if not self._p2p:
             return
         from .newton import ALLGATHER_FN, RECV_FN, SEND_FN
 
-        def grank(r):
-            return r if self.group is None else dist.get_global_rank(self.group, r)
-
+        @callback
         def send(user, ptr, nbytes, peer, stream):
-            try:
-                torch.cuda.synchronize(core.device)
-                dist.send(view(ptr, nbytes // 8).cpu(), dst=grank(peer), group=self.group)
-                return 0
-            except Exception as e:
-                self._cb_error = e
-                return 1
+            torch.cuda.synchronize(core.device)
+            dist.send(view(ptr, nbytes // 8).cpu(), dst=grank(peer), group=self.group)
 
+        @callback
         def recv(user, ptr, nbytes, peer, stream):
-            try:
-                h = torch.empty(nbytes // 8, dtype=torch.float64)
-                dist.recv(h, src=grank(peer), group=self.group)
-                view(ptr, nbytes // 8).copy_(h)
-                torch.cuda.synchronize(core.device)
-                return 0
-            except Exception as e:
-                self._cb_error = e
-                return 1
+            h = torch.empty(nbytes // 8, dtype=torch.float64)
+            dist.recv(h, src=grank(peer), group=self.group)
+            view(ptr, nbytes // 8).copy_(h)
+            torch.cuda.synchronize(core.device)
 
+        @callback
         def allgather(user, sptr, rptr, nbytes_per_rank, stream):
-            try:
-                n = nbytes_per_rank // 8
-                torch.cuda.synchronize(core.device)
-                h = view(sptr, n).cpu()                                   # (taken before anything is written: send may lie inside recv)
-                outs = [torch.empty_like(h) for _ in range(self.world)]
-                dist.all_gather(outs, h, group=self.group)
-                view(rptr, n * self.world).copy_(torch.cat(outs))
-                torch.cuda.synchronize(core.device)
-                return 0
-            except Exception as e:
-                self._cb_error = e
-                return 1
+            n = nbytes_per_rank // 8
+            torch.cuda.synchronize(core.device)
+            h = view(sptr, n).cpu()                                   # (taken before anything is written: send may lie inside recv)
+            outs = [torch.empty_like(h) for _ in range(self.world)]
+            dist.all_gather(outs, h, group=self.group)
+            view(rptr, n * self.world).copy_(torch.cat(outs))
+            torch.cuda.synchronize(core.device)
 
         core.set_exchange_p2p(SEND_FN(send), RECV_FN(recv), ALLGATHER_FN(allgather), serialize=self._serialize)
         if self._selftest:
@@ -179,16 +168,21 @@ class DistNewton(object):
         c0 = p * self.nb
         return c0, min(c0 + self.nb, self.Npad)
 
+    def _collective(self, t, collective, back=True, stage=None):
+        """Run `collective` on t -- when staging, on a host copy of it (device tensors cannot ride a gloo group), which goes
+        back into t where `back` says so."""
+        if not (self.stage if stage is None else stage):
+            collective(t)
+            return
+        h = t.cpu()
+        collective(h)
+        if back:
+            t.copy_(h)
+
     def _bcast(self, t, src):
         if self.world == 1:
             return
-        if self.stage:
-            h = t.cpu()
-            self.dist.broadcast(h, src=src, group=self.group)
-            if self.rank != src:
-                t.copy_(h)
-        else:
-            self.dist.broadcast(t, src=src, group=self.group)
+        self._collective(t, lambda x: self.dist.broadcast(x, src=src, group=self.group), back=self.rank != src)
         self.bytes_broadcast += t.numel() * t.element_size()
 
     def _msgbuf(self, numel):
@@ -228,13 +222,7 @@ class DistNewton(object):
     def _sync_anorm(self):
         """Every rank perturbs alike: the scale of a static pivot is the largest assembled entry over ALL ranks."""
         if self.world > 1 and hasattr(self.core, "anorm"):
-            t = self.core.anorm()
-            if self.stage:
-                h = t.cpu()
-                self.dist.all_reduce(h, op=self.dist.ReduceOp.MAX, group=self.group)
-                t.copy_(h)
-            else:
-                self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX, group=self.group)
+            self._collective(self.core.anorm(), lambda x: self.dist.all_reduce(x, op=self.dist.ReduceOp.MAX, group=self.group))
 
     def _factor_lockstep(self):
         core = self.core
@@ -354,12 +342,7 @@ class DistNewton(object):
     def _allreduce_sum(self, t):
         if self.world == 1:
             return
-        if self.stage:
-            h = t.cpu()
-            self.dist.all_reduce(h, op=self.dist.ReduceOp.SUM, group=self.group)
-            t.copy_(h)
-        else:
-            self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM, group=self.group)
+        self._collective(t, lambda x: self.dist.all_reduce(x, op=self.dist.ReduceOp.SUM, group=self.group))
 
     def residual(self):
         """g = -grad, complete on every rank."""

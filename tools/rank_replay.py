@@ -278,7 +278,8 @@ def main():
                        "link_model_ms": state["link_ms"], "messages": dts[med]["messages"], "bytes": dts[med]["bytes"],
                        "owned_panels": len([p for p in range(npanels) if p % W == r]),
                        "rows_behind_the_chain_ms": wrs[med][10], "slice_messages": int(wrs[med][7]), "slice_bytes": int(wrs[med][8]),
-                       "slice_link_model_ms": state["slice_link_ms"]}
+                       "slice_link_model_ms": state["slice_link_ms"],
+                       "wire_counters": [int(v) for i, v in enumerate(wrs[med]) if i != 10]}
                 if verify:
                     local = core.kkt_storage()
                     same, lc = True, 0
