@@ -34,7 +34,9 @@
  *   call that returns data to the HOST — a PYIPM_MEM_HOST output, pyipm_factor_stats, step lengths,
  *   timings — synchronises the stream before returning, and host INPUT buffers are never read after
  *   the call returns (the library stages them).  Device input blocks passed to stage_blocks are NOT
- *   copied: their pointers are retained until the next stage_blocks / destroy.
+ *   copied: their pointers are retained until the next stage_blocks / destroy.  Their CONTENTS must
+ *   not change between two stage_blocks calls: the handle keeps what it factored of them (below).
+ *   Restaging the same pointers is how a caller announces new contents.
  */
 #ifndef PYIPM_NEWTON_H
 #define PYIPM_NEWTON_H
@@ -190,6 +192,27 @@ int pyipm_newton_kkt_matvec(pyipm_newton_ctx* ctx, const double* v, double* y, i
  * without regularisation retries (the host loop re-issues assemble/factor with new shifts). */
 int pyipm_newton_step(pyipm_newton_ctx* ctx, double delta, double delta_c, int refine,
                       double* dz, pyipm_factor_stats* stats, int memkind);
+/* Reuse of the x-block factorisation.  In the order x | s | lambda_e | lambda_i the panels of the x block hold d2L + delta I,
+ * Je' and Ji': the staged blocks and delta, nothing of s, lda or mu.  On a single-rank handle in the full form, step() and
+ * the pair assemble() / factor() therefore factor the groups of panels inside the x block once per stage_blocks: the first
+ * factorisation after it RECORDS (a full factorisation that also copies the columns behind those groups, as they stand once
+ * the last of them has been applied, into a snapshot the handle allocates outside its workspace: (N - n)^2 doubles at the
+ * most, none for the panels inside the slack block); every later one with the same delta and delta_c REUSES: its assembly
+ * writes the slack columns and restores the snapshot, its factorisation runs the forward substitution over the kept panels
+ * and factors the multiplier block alone.  Bit for bit the result of a full factorisation.  Between a reusing assemble() and
+ * its factor() the x columns of the storage hold the kept factor, not the matrix; every entry point that looks at the storage
+ * as a matrix or writes into it (kkt_storage, the per-panel phases, set_option, stage_vectors, set_stream with another stream)
+ * completes the assembly first and drops what was kept.  stage_blocks, a failed factorisation and one with other shifts
+ * drop it too; other shifts are recorded only when they come twice in a row (a shift loop never pays for a snapshot).  A
+ * caller that restages before every step (an NLP loop) pays for one snapshot per handle: recording stops when blocks are
+ * restaged before anything reused them and resumes with the second factorisation of the same blocks.  Once kkt_storage has
+ * handed the pointer out every factorisation is a full one until set_option("keep_zeros") is called again (the holder may
+ * write anywhere).  PYIPM_REUSE_X=0 in the environment at create time switches all of it off; so does a snapshot that cannot
+ * be allocated, silently.  Condensed, batched, provider and multi-rank handles, lookahead = 0 and systems whose first
+ * group reaches beyond the x block never reuse.
+ * out[0] = factorisations of this handle that reused, [1] = that recorded, [2] = bytes of the snapshot, [3] = the last one:
+ * 0 full, 1 recording, 2 reusing.  With PYIPM_GROUP_TRACE set every factorisation says which kind it is. */
+int pyipm_newton_reuse_info(pyipm_newton_ctx* ctx, int64_t out[4]);
 
 /* SURVEY.md section 8(f) rank 3 -- the derivative provider of the QP family on the device.  For
  *   min 1/2 x'Qx + c'x  s.t.  Ax = b,  Gx - h >= 0

@@ -43,6 +43,7 @@ constexpr int64_t BULK_BN_ROWS = 20480;       // 128 x 256 tiles only for launch
                                               // block per CU, every register) its kernels wait twice as long for a slot -- exposed panel 6.0
                                               // instead of 5.3 ms with the threshold at persist_rows, the step 0.8 % slower
 constexpr int BULK_BN_MIN_K = 512;            // ... and with at least this K (shorter ones keep 128 x 128: twice the blocks)
+constexpr int PX_HDR = 32;                    // doubles in front of the prefix snapshot: DevStats, then the assembly's maximum
 constexpr int TILE_FREE_CUS = 64;             // k_tile_step8: CUs assumed free beside a persistent bulk launch (units per block: 1 while the launch fits)
 
 // Block-cyclic 1D column distribution by panels of width nb.
@@ -149,6 +150,23 @@ struct Held {
                                           // so every assembly is a full one until set_option("keep_zeros") is called again
     bool rc_warm_valid[2] = {false, false};   // rc_warm[k] holds the vector the last adaptive condition estimate ended with
     bool ev_assemble_valid = false, ev_solve_valid = false;   // events 2-3 / 4-5 have been recorded (last_timings)
+    // The reusable x-block prefix: columns [0, cB) of the storage hold L of the groups inside the x block,
+    // the tile inverses and flags of those columns are theirs, and the handle's snapshot holds the columns behind them as
+    // they were when the last of those groups had been applied -- all of it a function of the staged blocks, delta and delta_c.
+    bool px_valid = false;
+    double px_delta = 0.0, px_delta_c = 0.0;   // ... the shifts it was recorded with
+    int64_t px_groups = 0, px_cB = 0;          // ... and the schedule: groups of the prefix, first column behind them
+    // The recording policy: whoever restages the blocks before any step reused them is an NLP loop and stops paying for
+    // snapshots; a second step on the same blocks starts them again.
+    bool px_record = true;
+    int px_steps = 0;                          // fused steps since the blocks were staged
+    bool px_reused = false;                    // ... one of them reused the prefix
+    double px_last_delta = 0.0, px_last_delta_c = 0.0;   // shifts of the last factorisation (a shift loop changes them every time: no snapshot)
+    // What the last assembly decided for the factorisation that follows it (0 full, 1 recording, 2 reusing) and its boundary.
+    // 2 with `assembled`: the storage holds L of the prefix in columns [0, cB), the matrix behind them -- whoever looks at the
+    // storage as a matrix first has it completed (storage_whole).
+    int px_plan = 0; int64_t px_plan_groups = 0, px_plan_cB = 0;
+    bool partial() const { return assembled && px_plan == 2; }
 
     enum : unsigned { V0 = 1, V1 = 2, V2 = 4, VLOC = 8 };
     // Somebody writes work vectors of the handle.  v0 / v1 carry a pending fused forward pass and its right-hand side, vloc the
@@ -163,6 +181,8 @@ struct Held {
     // stage_blocks_owned has never said so (forget = false): on a single-rank handle merit_ray / rcond after it see the old ones.
     void blocks_staged(bool forget = true) {
         have_blocks = true;
+        if (px_steps > 0 && !px_reused) px_record = false;
+        px_valid = false; px_steps = 0; px_reused = false;
         if (forget) { ray_valid = false; rc_warm_cold(); }
     }
     // g = -grad belongs to the vectors staged before, and so does the merit function along the kept ray.
@@ -171,7 +191,21 @@ struct Held {
     void residual_formed() { have_rhs = true; forward_pending = false; }
     // Assembly, in two halves around its launches.  The condensed system lives in the same storage with another layout, so the
     // zeros are gone as soon as it starts.
-    void assemble_begun(bool condensed) { if (condensed) zeros_clean = false; else cond_active = false; }
+    // A whole assembly overwrites the x columns: the prefix is gone.
+    void assemble_begun(bool condensed) { if (condensed) zeros_clean = false; else cond_active = false; px_valid = false; px_plan = 0; }
+    void assembly_planned(int plan, int64_t groups, int64_t cB) { px_plan = plan; px_plan_groups = groups; px_plan_cB = cB; }
+    // The slack columns re-assembled and the snapshot restored behind a valid prefix: a matrix again, its zeros as they were.
+    void prefix_reassembled() { assembled = true; factored = false; forward_pending = false; }
+    // Anything that may change the schedule or the order on the stream (set_option, set_stream), and a step that failed.
+    void prefix_dropped() { px_valid = false; if (px_plan == 1) px_plan = 0; }
+    // An assembly of a step starts / its factorisation is done.  A second one on the same blocks: the caller is no NLP loop.
+    void step_begun() { if (px_steps >= 1) px_record = true; }
+    void step_factored(bool recorded, bool reused, double delta, double delta_c, int64_t groups, int64_t cB) {
+        ++px_steps; px_last_delta = delta; px_last_delta_c = delta_c; px_plan = 0;
+        if (reused) px_reused = true;
+        if (recorded) { px_valid = true; px_delta = delta; px_delta_c = delta_c; px_groups = groups; px_cB = cB; }
+    }
+
     // The zeros of a full single-rank assembly survive a factorisation of finite numbers (every update that reaches them adds an
     // exact zero); whatever else may write into the storage clears the flag.  The storage holds a matrix, no factor.
     void assemble_done(bool condensed, bool single_rank) {
@@ -180,18 +214,18 @@ struct Held {
     }
     void assemble_timed() { ev_assemble_valid = true; }
     // The owner of the storage wrote a matrix into it (the L-BFGS Gram system): full layout, no residual of this handle's.
-    void matrix_written() { assembled = true; factored = false; have_rhs = false; forward_pending = false; cond_active = false; }
+    void matrix_written() { px_valid = false; px_plan = 0; assembled = true; factored = false; have_rhs = false; forward_pending = false; cond_active = false; }
     void step_batched_begun(bool condensed) { cond_active = condensed; }
     // rhs = g of every problem (backward_error_batched reads it).  v2 is the staging copy of a HOST output: the directions of the
     // problems that took part (step_lengths_batched with dz = NULL reads it); a device output is the caller's tensor alone.
     void step_batched_enqueued(bool host_out) { have_rhs = true; ev_assemble_valid = true; have_direction = host_out; }
     // Factorisation.  Per-panel phases (the caller or the distributed driver drives the panels): no promise about what gets written.
-    void panel_phases_begun() { zeros_clean = false; }
+    void panel_phases_begun() { zeros_clean = false; px_valid = false; }
     void factor_begun() { forward_fused = false; }
     void forward_fused_under_factor() { forward_fused = true; }
     void forward_done_dist() { fwd_done = true; }
     void factor_enqueued() { assembled = false; }                  // the storage now holds the factor
-    void factor_invalid() { zeros_clean = false; }                 // a chain poll timed out: anything may be in the storage
+    void factor_invalid() { zeros_clean = false; px_valid = false; }               // a chain poll timed out: anything may be in the storage
     void factor_read_back(bool nonfinite) { factored = true; if (nonfinite) zeros_clean = false; }
     void factor_timed_out() { factored = false; }                  // distributed step: the device never completed it
     // The factorisation call returns rc.  Failed: the zeros are no longer clean.  keep_forward: a fused forward pass stays
@@ -211,10 +245,10 @@ struct Held {
     void rc_warm_cold() { rc_warm_valid[0] = rc_warm_valid[1] = false; }      // another or a shifted matrix, or a new buffer
     void rc_warm_kept(int phase, bool good) { rc_warm_valid[phase] = good; }
     // A holder of the pointer may write through it, now or later.
-    void storage_handed_out() { zeros_clean = false; storage_exported = true; }
+    void storage_handed_out() { zeros_clean = false; storage_exported = true; px_valid = false; }   // (... into the x columns too: no reuse either)
     void keep_zeros_set() { zeros_clean = false; storage_exported = false; }
     // An exception unwound out of the middle of a schedule: the half-done state is dropped.
-    void quiesced() { factored = false; forward_pending = false; forward_fused = false; zeros_clean = false; }
+    void quiesced() { factored = false; forward_pending = false; forward_fused = false; zeros_clean = false; px_valid = false; }
 };
 
 struct DistState;                                       // dist_impl.hpp
@@ -298,6 +332,12 @@ struct Ctx {
     double* fwd_vec = nullptr;            // vector the fused forward substitution runs on
     double t_gram = 0;                    // ms of the Ji Sigma Ji' launch (profile)
     bool provider_only = false;           // pyipm_newton_create_provider: staged blocks + vectors, products and residuals; no factorisation
+    // reuse of the x-block factorisation while the staged blocks stay (Held::px_*)
+    int reuse_x = 1;                      // PYIPM_REUSE_X=0 at create time switches it off; so does a snapshot that could not be allocated
+    DevBuf<double> snap;                  // the snapshot, outside the workspace (allocated by the first recording step): PX_HDR doubles
+                                          // (DevStats and the assembly's maximum as they stood at the boundary), then the column ranges
+    int64_t n_reused = 0, n_recorded = 0; // fused steps of this handle that reused the prefix / recorded one
+    int last_step_kind = 0;               // 0 full, 1 recording, 2 reusing
     DevBuf<char> ws;                      // the workspace: the caller's (adopted) or the library's; capacity = the bytes the geometry needs
     // carved from workspace
     double *A = nullptr, *Wbuf = nullptr, *Lbuf = nullptr, *Dinv = nullptr;

@@ -34,8 +34,11 @@ enum : unsigned {
     G_FACTOR_ABLE = 4,   // not a provider-only handle
     G_ONE_RANK = 8,      // world == 1
     G_FACTORED = 16,     // a factor is in the storage
-    G_DEVICE = 32,       // makes the handle's device current (last: a refusal costs no HIP call)
+    G_DEVICE = 32,       // makes the handle's device current (a refusal costs no HIP call)
+    G_STORAGE = 64,      // the entry looks at the KKT storage as a matrix, writes into it or changes what a pending factorisation was
+                         // planned with: an assembly that kept the x-block prefix is completed first, the prefix dropped (with G_DEVICE)
 };
+int storage_whole(Ctx* ctx);        // pyipm_newton.hip
 inline int need_factor(Ctx* ctx, const char* name) {
     if (ctx->held.factored) return 0;
     ctx->err = std::string(name) + ": factor first"; return PYIPM_E_BADARG;
@@ -49,6 +52,7 @@ inline int enter(pyipm_newton_ctx* h, const char* name, unsigned need, Ctx** out
     if ((need & G_ONE_RANK) && ctx->g.world != 1) { ctx->err = std::string(name) + "(): single-rank entry point"; return PYIPM_E_BADARG; }
     if (need & G_FACTORED) { int rc = need_factor(ctx, name); if (rc) return rc; }
     if (need & G_DEVICE) PYIPM_HIP(hipSetDevice(ctx->device));
+    if (need & G_STORAGE) return storage_whole(ctx);
     return 0;
 }
 #define PYIPM_ENTER(name_, need_)  Ctx* ctx; { const int rc_ = enter(h, name_, need_, &ctx); if (rc_) return rc_; }
@@ -108,7 +112,7 @@ int unpack_slice(Ctx* ctx, int64_t p, int j, const double* buf, const double* ti
 int unpack_slice_tiles(Ctx* ctx, int64_t p, const double* tiles, hipStream_t st);
 int unpack_panel_from(Ctx* ctx, int64_t p, const double* buf, int64_t row_from, bool with_tiles, hipStream_t st);
 int factor_end(Ctx* ctx, pyipm_factor_stats* stats);
-int factor_dispatch(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward);
+int factor_dispatch(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward, int px = 0);   // px: factor_all (pyipm_newton_step alone passes one)
 int cond_reduce(Ctx* ctx, const double* b, double* vc);
 int cond_expand(Ctx* ctx, const double* vc, double* v);
 int kkt_matvec_dev(Ctx* ctx, const double* v, double* y);

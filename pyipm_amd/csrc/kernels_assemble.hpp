@@ -67,8 +67,10 @@ __global__ __launch_bounds__(256) void k_assemble(
     double eps, double delta, double delta_c, unsigned long long* __restrict__ anorm_bits, int nt_store, int sharded,
     int zeros_in_place,      // the storage still holds the zeros of an earlier assembly wherever nothing can ever fill in
     int64_t lc_off,          // first local column of this launch (the assembly may come as two launches, see assemble_dev)
-    int tri_nbx)             // > 0 (single rank, lc_off == 0): a 1-D grid over the patches on or below the diagonal only -- the 2-D
+    int tri_nbx,             // > 0 (single rank, lc_off == 0): a 1-D grid over the patches on or below the diagonal only -- the 2-D
                              // grid launches as many patches above it, 65000 workgroups at N = 32768 that start only to return
+    int64_t jc0, int64_t jc1)   // only the global columns [jc0, jc1) are stored (and counted in the maximum); a whole assembly: [0, Npad).
+                             // A step that reuses the x-block prefix re-assembles the slack columns alone (reassemble_slack)
 {
     int64_t bx = blockIdx.x, by = blockIdx.y;
     if (tri_nbx > 0) {
@@ -117,7 +119,7 @@ __global__ __launch_bounds__(256) void k_assemble(
         const int64_t j = j0 + c;
         const int64_t jr = sharded ? lc_base + c : j;  // row-sharded blocks are laid out in local column order
         dbl2_t v; v.x = 0.0; v.y = 0.0;
-        if (c < ncol && i + 1 >= j) {
+        if (c < ncol && i + 1 >= j && j >= jc0 && j < jc1) {
             if (vec_h && j < g.n && i + 1 < g.n && i >= j) {
                 v = *reinterpret_cast<const dbl2_t*>(&d2L[jr * ldh + i]);
                 if (i == j) v.x += delta;
@@ -132,7 +134,7 @@ __global__ __launch_bounds__(256) void k_assemble(
     #pragma unroll
     for (int c = 0; c < 16; ++c) {
         const int64_t j = j0 + c, lc = lc_base + c;
-        if (c >= ncol || i + 1 < j) continue;         // both rows above the diagonal: not stored
+        if (c >= ncol || i + 1 < j || j < jc0 || j >= jc1) continue;   // both rows above the diagonal, or a column this launch leaves alone: not stored
         const dbl2_t v = val[c];
         {   // the scale of a static pivot leaves Sigma = lambda_i / (s + eps) out: late in an interior-point run those entries span
             // 1e-10 .. 1e+10 while the rows a static pivot lands in (zero Hessian rows: LPs, linear variables) keep the scale of
@@ -151,6 +153,19 @@ __global__ __launch_bounds__(256) void k_assemble(
         }
     }
     anorm_publish(anorm_bits, amax);
+}
+
+// dst[i + c ldd] = src[i + c lds] for i < rows (even, both 16-byte aligned), c < cols: the snapshot of the columns behind the
+// x-block prefix, out of the KKT storage and back into it (prefix_save / prefix_restore).  grid (cols, row chunks).
+__global__ __launch_bounds__(256) void k_copy_cols(double* __restrict__ dst, int64_t ldd, const double* __restrict__ src, int64_t lds,
+                                                   int64_t rows, int64_t cols)
+{
+    const int64_t c = blockIdx.x;
+    if (c >= cols) return;
+    const double* __restrict__ s = src + c * lds;
+    double* __restrict__ d = dst + c * ldd;
+    for (int64_t i = ((int64_t)blockIdx.y * 256 + threadIdx.x) * 2; i + 1 < rows; i += (int64_t)gridDim.y * 512)
+        *reinterpret_cast<dbl2_t*>(d + i) = *reinterpret_cast<const dbl2_t*>(s + i);
 }
 
 // ---- wave-level helpers -------------------------------------------------------------------

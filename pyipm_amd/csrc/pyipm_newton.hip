@@ -1604,7 +1604,7 @@ int assemble_condensed(Ctx* ctx, double delta, double delta_c) {
         asm_grid(gc, &grid, &tri);
         PYIPM_HIP(hipMemsetAsync(ctx->anorm, 0, sizeof(unsigned long long), ctx->stream));
         hipLaunchKernelGGL(k_assemble, grid, dim3(256), 0, ctx->stream, ctx->A, gc.Npad, gc, ctx->d2L, ctx->ld_d2L,
-                           Jx, ldx, (const double*)nullptr, (int64_t)0, ctx->s, ctx->lda, ctx->eps, delta, delta_c, ctx->anorm, 0, 0, 0, (int64_t)0, tri);
+                           Jx, ldx, (const double*)nullptr, (int64_t)0, ctx->s, ctx->lda, ctx->eps, delta, delta_c, ctx->anorm, 0, 0, 0, (int64_t)0, tri, (int64_t)0, gc.Npad);
         PYIPM_KCHECK();
         if (na > 0) {
             hipLaunchKernelGGL(k_cond_fix_diag, grid1(na), dim3(256), 0, ctx->stream, ctx->A, gc.Npad, g.n + g.me,
@@ -1671,7 +1671,7 @@ int assemble_dev(Ctx* ctx, double delta, double delta_c) {
         asm_grid(g, &grid, &tri);
         hipLaunchKernelGGL(k_assemble, grid, dim3(256), 0, ctx->stream, ctx->A, g.Npad, g, ctx->d2L, ctx->ld_d2L,
                            ctx->Je, ctx->ld_Je, ctx->Ji, ctx->ld_Ji, ctx->s, ctx->lda, ctx->eps, delta, delta_c, ctx->anorm, 0, ctx->sharded,
-                           zip, (int64_t)0, tri);
+                           zip, (int64_t)0, tri, (int64_t)0, g.Npad);
         PYIPM_KCHECK();
     }
     ctx->held.assemble_done(false, g.world == 1);
@@ -1713,6 +1713,144 @@ GroupSched plan_groups(const Geo& g, int group, int tail_group, bool tail_group_
     }
     s.first_.push_back(np);
     return s;
+}
+
+// ---- the reusable x-block prefix -------------------------------------------------------------------------
+// The x-block panels hold d2L + delta I, Je', Ji': what stage_blocks staged and delta, nothing of s, lda or mu.  Groups [0, gB)
+// -- gB the first group that does not lie inside the x block -- are the prefix; once all of their contributions have reached
+// the columns [cB, Npad) behind them and nothing else has, those columns are a function of the blocks, delta, delta_c and the
+// geometry (minus the panels wholly inside the slack block: no x column reaches them, they are re-assembled).  A RECORDING step
+// is a full factorisation that copies them, the statistics and the assembly's maximum as they stand at that point into the
+// snapshot; a REUSING step re-assembles the slack columns, restores the rest from the snapshot, seeds the statistics and
+// factors from group gB on.  Only pyipm_newton_step does either: nobody can look at the matrix between its phases.
+enum { PX_FULL = 0, PX_RECORD = 1, PX_REUSE = 2 };
+static int64_t prefix_groups(const GroupSched& sc) {
+    int64_t gB = 0;
+    while (gB < sc.ngroups() && sc.in_x(gB)) ++gB;
+    return gB;
+}
+// The column ranges of the snapshot, [c0, c1) each with the rows [c0, Npad): what lies behind column cB except the panels wholly
+// inside the slack block.  Returns the snapshot's doubles (header included).
+struct PxRange { int64_t c0, c1, off; };
+static size_t prefix_ranges(const Geo& g, int64_t cB, PxRange out[2], int* count) {
+    int64_t s0 = 0, s1 = 0;                                  // the panels wholly inside the slack block: columns [s0, s1)
+    if (g.mi > 0) {
+        s0 = (g.n + g.nb - 1) / g.nb * g.nb; if (s0 < cB) s0 = cB;
+        s1 = (g.n + g.mi) / g.nb * g.nb;
+    }
+    const int64_t cut[2][2] = {{cB, s1 > s0 ? s0 : g.Npad}, {s1 > s0 ? s1 : g.Npad, g.Npad}};
+    size_t tot = PX_HDR; *count = 0;
+    for (int k = 0; k < 2; ++k) {
+        if (cut[k][1] <= cut[k][0]) continue;
+        out[*count] = PxRange{cut[k][0], cut[k][1], (int64_t)tot};
+        tot += (size_t)(cut[k][1] - cut[k][0]) * (size_t)(g.Npad - cut[k][0]);
+        ++*count;
+    }
+    return tot;
+}
+static_assert(sizeof(DevStats) <= 16 * sizeof(double) && PX_HDR > 16, "the snapshot's header holds DevStats, then the maximum");
+static int prefix_copy(Ctx* ctx, int64_t cB, bool save) {
+    const Geo& g = ctx->g;
+    PxRange r[2]; int nr = 0;
+    const size_t tot = prefix_ranges(g, cB, r, &nr);
+    if (tot > ctx->snap.capacity()) { ctx->err = "prefix snapshot: buffer too small"; return PYIPM_E_BADARG; }
+    double* hdr = ctx->snap.get();
+    const hipMemcpyKind dd = hipMemcpyDeviceToDevice;
+    if (save) {
+        PYIPM_HIP(hipMemcpyAsync(hdr, ctx->dstats, sizeof(DevStats), dd, ctx->stream));
+        PYIPM_HIP(hipMemcpyAsync(hdr + 16, ctx->anorm, sizeof(unsigned long long), dd, ctx->stream));
+    } else {
+        PYIPM_HIP(hipMemcpyAsync(ctx->anorm, hdr + 16, sizeof(unsigned long long), dd, ctx->stream));
+    }
+    for (int k = 0; k < nr; ++k) {
+        const int64_t rows = g.Npad - r[k].c0, cols = r[k].c1 - r[k].c0;
+        double* a = ctx->A + r[k].c0 + r[k].c0 * g.Npad;       // (single rank: local = global columns)
+        double* b = ctx->snap.get() + r[k].off;
+        const dim3 grid((unsigned)cols, (unsigned)((rows + 2047) / 2048));
+        if (save) hipLaunchKernelGGL(k_copy_cols, grid, dim3(256), 0, ctx->stream, b, rows, (const double*)a, g.Npad, rows, cols);
+        else      hipLaunchKernelGGL(k_copy_cols, grid, dim3(256), 0, ctx->stream, a, g.Npad, (const double*)b, rows, rows, cols);
+        PYIPM_KCHECK();
+    }
+    return 0;
+}
+// What kind of step the fused entry point runs now.  Reuse applies to the full form on one rank with a lookahead schedule and at
+// least one group inside the x block; everything else is a full step, as it always was.
+static int prefix_mode(Ctx* ctx, double delta, double delta_c, int64_t* gB_out, int64_t* cB_out) {
+    const Geo& g = ctx->g;
+    Held& h = ctx->held;
+    *gB_out = 0; *cB_out = 0;
+    if (!ctx->reuse_x || g.world != 1 || ctx->batched || ctx->provider_only || (ctx->condensed && g.mi > 0) || !ctx->lookahead ||
+        h.storage_exported) return PX_FULL;                    // (a holder of the storage pointer may write into the x columns at any time)
+    const GroupSched sc = plan_groups(g, ctx->group, ctx->tail_group, ctx->tail_group_user, ctx->skip_zeros != 0, ctx->lookahead);
+    const int64_t gB = prefix_groups(sc);
+    if (gB == 0 || gB >= sc.ngroups()) return PX_FULL;
+    const int64_t cB = g.panel_c0(sc.first(gB));
+    *gB_out = gB; *cB_out = cB;
+    if (h.px_valid && delta == h.px_delta && delta_c == h.px_delta_c && gB == h.px_groups && cB == h.px_cB && ctx->snap) return PX_REUSE;
+    // the first factorisation of these blocks records; a later one only with the shifts of the one before it (a shift loop
+    // changes them every time and never gets as far as reusing)
+    if (!h.px_record || (h.px_steps > 0 && (delta != h.px_last_delta || delta_c != h.px_last_delta_c))) return PX_FULL;
+    PxRange r[2]; int nr = 0;
+    const size_t tot = prefix_ranges(g, cB, r, &nr);
+    if (ctx->snap.capacity() < tot) {
+        if (ctx->snap.reserve(tot) != hipSuccess) {              // no room for it: the handle goes on without the feature
+            (void)hipGetLastError();
+            ctx->reuse_x = 0;
+            return PX_FULL;
+        }
+        if (getenv("PYIPM_POISON_WORKSPACE")) (void)hipMemsetAsync(ctx->snap, 0xFF, tot * sizeof(double), ctx->stream);
+    }
+    return PX_RECORD;
+}
+// The assembly of a reusing step (events 2 and 3 around it): the slack columns -- Sigma, -I -- from the staged vectors, the
+// columns of the snapshot from the snapshot.  Columns [0, cB) keep L of the prefix.
+static int reassemble_slack(Ctx* ctx, int64_t cB) {
+    const Geo& g = ctx->g;
+    PYIPM_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
+    int rc = prefix_copy(ctx, cB, false); if (rc) return rc;
+    if (g.mi > 0) {
+        const int zip = (ctx->keep_zeros && !ctx->held.storage_exported && ctx->held.zeros_clean) ? 1 : 0;
+        const int64_t lc0 = g.n / 16 * 16;
+        const dim3 grid((unsigned)((g.Npad + 511) / 512), (unsigned)((g.n + g.mi - lc0 + 15) / 16));
+        hipLaunchKernelGGL(k_assemble, grid, dim3(256), 0, ctx->stream, ctx->A, g.Npad, g, ctx->d2L, ctx->ld_d2L,
+                           ctx->Je, ctx->ld_Je, ctx->Ji, ctx->ld_Ji, ctx->s, ctx->lda, ctx->eps, ctx->delta, ctx->delta_c, ctx->anorm, 0, 0,
+                           zip, lc0, 0, g.n, g.n + g.mi);
+        PYIPM_KCHECK();
+    }
+    PYIPM_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
+    ctx->held.prefix_reassembled();
+    ctx->held.assemble_timed();
+    return 0;
+}
+
+// The assembly of a step or of pyipm_newton_assemble, with the decision what the factorisation behind it does (Held::px_plan).
+// The separate phases take part: between a reusing assembly and its factorisation the storage holds L of the prefix in the x
+// columns, and every entry point that looks at the storage as a matrix completes it first (G_STORAGE, storage_whole).
+int assemble_planned(Ctx* ctx, double delta, double delta_c) {
+    if (!ctx->held.have_blocks || !ctx->held.have_vectors || ctx->provider_only) return assemble_timed(ctx, delta, delta_c);   // (its refusals)
+    ctx->held.step_begun();
+    int64_t gB = 0, cB = 0;
+    const int px = prefix_mode(ctx, delta, delta_c, &gB, &cB);
+    const int rc = px == PX_REUSE ? reassemble_slack(ctx, cB) : assemble_timed(ctx, delta, delta_c);
+    if (rc) return rc;
+    ctx->held.assembly_planned(ctx->held.cond_active ? (int)PX_FULL : px, gB, cB);
+    return 0;
+}
+// ... and its factorisation, with the bookkeeping of what was recorded or reused.
+int factor_planned(Ctx* ctx, pyipm_factor_stats* stats, bool fuse) {
+    const int px = ctx->held.assembled ? ctx->held.px_plan : (int)PX_FULL;
+    const int64_t gB = ctx->held.px_plan_groups, cB = ctx->held.px_plan_cB;
+    const double delta = ctx->delta, delta_c = ctx->delta_c;
+    const int rc = factor_dispatch(ctx, stats, fuse, px);
+    if (rc) { ctx->held.prefix_dropped(); ctx->held.px_plan = 0; return rc; }       // a failed factorisation: the next one runs in full
+    ctx->held.step_factored(px == PX_RECORD, px == PX_REUSE, delta, delta_c, gB, cB);
+    ctx->last_step_kind = px; ctx->n_recorded += px == PX_RECORD; ctx->n_reused += px == PX_REUSE;
+    return 0;
+}
+int storage_whole(Ctx* ctx) {
+    if (ctx->held.partial()) { const int rc = assemble_timed(ctx, ctx->delta, ctx->delta_c); if (rc) return rc; }
+    ctx->held.prefix_dropped();
+    return 0;
 }
 
 // diagnostics (PYIPM_GROUP_TRACE=1): where each group's chain, head and bulk update begin and end on the device, without a
@@ -1891,7 +2029,11 @@ static GroupStep plan_step(const Ctx* ctx, const FactorRun& run, int64_t grp) {
 // (enqueue_slack_first); group 0 on the main stream; then per group grp, as plan_step decided: head (group grp -> the lookahead
 // target) on hs, group grp + 1 on cs, bulk update (group grp -> everything behind the target) on the main stream beside it --
 // one-group lookahead.  lookahead = 0: bulk update, then the next group, all on the main stream.
-int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
+// px (pyipm_newton_step only): PX_RECORD -- neither of the two shortcuts that blur the point where the prefix is complete (the slack
+// panels up front, the lookahead across the slack block; nor group 0 panel by panel): the last prefix group's bulk update covers
+// every column behind it, the snapshot follows on the main stream, group gB after it.  PX_REUSE -- the loop starts at group gB,
+// the forward substitution runs over the prefix panels first.  The same products in the same order per entry: the same bits.
+int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false, int px = PX_FULL) {
     const Geo& g = ctx->g;
     if (g.world != 1) { ctx->err = "factor(): single-rank entry point; use the per-panel phases when world > 1"; return PYIPM_E_BADARG; }
     if (!ctx->held.assembled) { ctx->err = "factor: assemble first"; return PYIPM_E_BADARG; }
@@ -1908,8 +2050,14 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
     ctx->sched = plan_groups(g, ctx->group, ctx->tail_group, ctx->tail_group_user, ctx->skip_zeros != 0, ctx->lookahead);
     const GroupSched& sc = ctx->sched;
     const int64_t np = g.npanels, ngroups = sc.ngroups();
-    const FactorRun run{fuse_forward, ctx->lookahead >= 2 && ngroups > 2 && chain_group(ctx, 0) && sc.fast(1), slack_first_applies(ctx)};
+    const bool rec = px == PX_RECORD, reuse = px == PX_REUSE;
+    const int64_t gB = px ? prefix_groups(sc) : 0, g0 = reuse ? gB : 0;           // g0: the first group this factorisation runs
+    if (px && (gB == 0 || gB >= ngroups || !ctx->lookahead)) { ctx->err = "factor: no reusable prefix in this schedule"; return PYIPM_E_BADARG; }
+    const FactorRun run{fuse_forward, !px && ctx->lookahead >= 2 && ngroups > 2 && chain_group(ctx, 0) && sc.fast(1),
+                        !rec && slack_first_applies(ctx)};
     GroupTrace tr;
+    if (tr.on()) fprintf(stderr, "[pyipm group trace] %s step%s\n", rec ? "recording" : reuse ? "reusing" : "full",
+                         reuse ? ": the x-block prefix is kept" : "");
     ctx->held.factor_begun();
     if (fuse_forward) {
         PYIPM_HIP(ctx->fwd.ensure(hipStreamNonBlocking));
@@ -1917,15 +2065,41 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
         PYIPM_HIP(hipEventRecord(ctx->ev_head, ctx->stream));          // v0 = rhs copy was enqueued on the main stream
         PYIPM_HIP(hipStreamWaitEvent(ctx->fwd, ctx->ev_head, 0));
     }
-    rc = factor_begin(ctx); if (rc) return rc;
+    if (reuse) {                            // the statistics as the prefix left them, not zero
+        PYIPM_HIP(hipMemcpyAsync(ctx->dstats, ctx->snap.get(), sizeof(DevStats), hipMemcpyDeviceToDevice, ctx->stream));
+        ctx->n_trailing = 0; ctx->trailing_flops = 0.0; ctx->trailing_area = 0.0;
+    } else {
+        rc = factor_begin(ctx); if (rc) return rc;
+    }
     if (run.slack_first) { rc = enqueue_slack_first(ctx, run, ctx->stream); if (rc) return rc; }
-    tr.mark("chain+rows begin", 0, ctx->stream);
-    rc = run_group(ctx, run, 0, ctx->stream); if (rc) return rc;
-    tr.mark("chain+rows end", 0, ctx->stream);
+    if (reuse && fuse_forward) {            // the new right-hand side through the prefix panels: L and the tile inverses are there
+        for (int64_t q = 0; q < sc.first(gB); ++q) {
+            rc = fwd_panel(ctx, q, ctx->fwd_vec, ctx->fwd); if (rc) return rc;
+            rc = diag_panel(ctx, q, ctx->fwd_vec, ctx->fwd); if (rc) return rc;
+        }
+    }
+    if (reuse && run.slack_first && sc.fast(g0)) PYIPM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_sfast, 0));   // (as in front of any slack group)
+    tr.mark("chain+rows begin", g0, ctx->stream);
+    rc = run_group(ctx, run, g0, ctx->stream); if (rc) return rc;
+    tr.mark("chain+rows end", g0, ctx->stream);
+    if (reuse) PYIPM_HIP(hipEventRecord(ctx->ev_main, ctx->stream));      // group g0 ran on the main stream: its head on the side stream waits for this
     if (tr.on()) fprintf(stderr, "[pyipm group trace] %lld groups\n", (long long)ngroups);
     bool across_prev = false;
-    for (int64_t grp = 0; grp + 1 < ngroups; ++grp) {
+    for (int64_t grp = g0; grp + 1 < ngroups; ++grp) {
         const int64_t p0 = sc.first(grp), n0 = sc.size(grp);            // the source: its contribution goes to everything behind it
+        if (rec && grp + 1 == gB) {
+            // the last group of the prefix (complete on the main stream: group 0 ran there, every later one was joined behind its
+            // chain): one update of everything behind it, the snapshot, then group gB -- all on the main stream, no lookahead
+            tr.mark("bulk begin", grp, ctx->stream);
+            rc = timed_update(ctx, p0, n0, p0 + n0, np - (p0 + n0)); if (rc) return rc;
+            tr.mark("bulk end", grp, ctx->stream);
+            rc = prefix_copy(ctx, g.panel_c0(sc.first(gB)), true); if (rc) return rc;
+            tr.mark("snapshot end", grp, ctx->stream);
+            rc = run_group(ctx, run, gB, ctx->stream); if (rc) return rc;
+            PYIPM_HIP(hipEventRecord(ctx->ev_main, ctx->stream));
+            across_prev = false;
+            continue;
+        }
         if (!ctx->lookahead) {
             rc = timed_update(ctx, p0, n0, p0 + n0, np - (p0 + n0)); if (rc) return rc;
             rc = run_group(ctx, run, grp + 1, ctx->stream); if (rc) return rc;
@@ -1993,8 +2167,8 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false) {
 // factor_all on whichever system assemble() built; inertia reported for the FULL KKT matrix either way:
 // every eliminated (s_k, lambda_i_k) pair [[Sigma_k, -1], [-1, 0]] has determinant -1, i.e. one positive
 // and one negative eigenvalue whatever the sign of Sigma_k.
-int factor_dispatch(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward) {
-    if (!ctx->held.cond_active) { ctx->fwd_vec = ctx->v0; return factor_all(ctx, stats, fuse_forward); }
+int factor_dispatch(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward, int px) {
+    if (!ctx->held.cond_active) { ctx->fwd_vec = ctx->v0; return factor_all(ctx, stats, fuse_forward, px); }
     pyipm_factor_stats local; if (!stats) stats = &local;
     int rc;
     ctx->fwd_vec = ctx->vc;
@@ -2164,6 +2338,7 @@ static int create_impl(pyipm_newton_ctx** out, int64_t n, int64_t me, int64_t mi
             ctx->group = default_group(world, nb);
             { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) ctx->num_cus = ncu; }
             ctx->provider_only = provider_only;
+            { const char* e = getenv("PYIPM_REUSE_X"); if (e && e[0] == '0') ctx->reuse_x = 0; }
         },
         [&](Ctx* ctx, char* base) { return carve_workspace(ctx, g, base, provider_only); },
         2 /* [0] max |entry|, [1] "assembly pending" */, true);
@@ -2405,6 +2580,10 @@ int pyipm_newton_destroy(pyipm_newton_ctx* h) try {
 
 int pyipm_newton_set_stream(pyipm_newton_ctx* h, void* stream) try {
     PYIPM_ENTER("set_stream", 0)
+    if (ctx->stream != (hipStream_t)stream) {                // (what the old stream still runs is not ordered before the new one)
+        PYIPM_HIP(hipSetDevice(ctx->device));
+        const int rc = storage_whole(ctx); if (rc) return rc;
+    }
     ctx->stream = (hipStream_t)stream;
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
@@ -2438,6 +2617,7 @@ int pyipm_newton_stage_vectors(pyipm_newton_ctx* h, const double* df, const doub
                                const double* s, const double* lda, double mu, double eps, int memkind) try {
     PYIPM_ENTER("stage_vectors", G_DEVICE) const Geo& g = ctx->g;
     int rc;
+    if (ctx->held.partial()) { rc = storage_whole(ctx); if (rc) return rc; }      // (a pending partial assembly is completed from the vectors it was made of)
     const size_t B = (size_t)ctx->batch;          // batched handles: every vector is [batch][len], contiguous
     rc = put_vec(ctx, ctx->df, df, B * g.n, memkind); if (rc) return rc;
     rc = put_vec(ctx, ctx->ce, ce, B * g.me, memkind); if (rc) return rc;
@@ -2457,7 +2637,7 @@ int pyipm_newton_residual(pyipm_newton_ctx* h, double* g_out, int memkind) try {
 
 int pyipm_newton_assemble(pyipm_newton_ctx* h, double delta, double delta_c) try {
     PYIPM_ENTER("assemble", G_SINGLE | G_DEVICE)
-    return assemble_timed(ctx, delta, delta_c);
+    return assemble_planned(ctx, delta, delta_c);
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_factor(pyipm_newton_ctx* h, pyipm_factor_stats* stats) try {
@@ -2466,7 +2646,7 @@ int pyipm_newton_factor(pyipm_newton_ctx* h, pyipm_factor_stats* stats) try {
     // factorisation; solve(rhs = NULL) then only runs the block-diagonal and backward parts
     const bool fuse = ctx->fuse_forward && ctx->held.have_rhs && ctx->g.world == 1 && ctx->held.assembled;
     if (fuse) { int rc = solve_prepare(ctx, nullptr, PYIPM_MEM_DEVICE, true); if (rc) return rc; }
-    int rc = factor_dispatch(ctx, stats, fuse);
+    int rc = factor_planned(ctx, stats, fuse);
     ctx->held.factor_returned(rc, fuse);
     return rc;
 } PYIPM_CATCH_H(h)
@@ -2701,20 +2881,35 @@ int pyipm_newton_provider_stats(pyipm_newton_ctx* h, double out[4]) try {
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
-int pyipm_newton_step(pyipm_newton_ctx* h, double delta, double delta_c, int refine, double* dz,
-                      pyipm_factor_stats* stats, int memkind) try {
-    PYIPM_ENTER("step", G_SINGLE | G_DEVICE)
-    if (!dz) { ctx->err = "step: null output"; return PYIPM_E_BADARG; }
+// The fused step.  While the staged blocks, delta and delta_c stay what they were it keeps the factor of the x-block groups
+// (prefix_mode: full, recording or reusing).
+static int step_fused(Ctx* ctx, double delta, double delta_c, int refine, double* dz, pyipm_factor_stats* stats, int memkind) {
     int rc = residual_dev(ctx); if (rc) return rc;
-    rc = assemble_timed(ctx, delta, delta_c); if (rc) return rc;
+    rc = assemble_planned(ctx, delta, delta_c); if (rc) return rc;
     const bool fuse = ctx->fuse_forward != 0;
     if (fuse) { rc = solve_prepare(ctx, nullptr, memkind, true); if (rc) return rc; }     // v0 = v1 = g before factoring
-    rc = factor_dispatch(ctx, stats, fuse);
+    rc = factor_planned(ctx, stats, fuse);
     ctx->held.factor_returned(rc, false);                    // (the solve below consumes the fused pass at once)
     if (rc) return rc;
     PYIPM_HIP(hipEventRecord(ctx->ev[4], ctx->stream));
     if (!fuse) { rc = solve_prepare(ctx, nullptr, memkind); if (rc) return rc; }
     return solve_finish(ctx, kLocalOps, dz, 1, refine, memkind, fuse && ctx->held.forward_fused);
+}
+
+int pyipm_newton_step(pyipm_newton_ctx* h, double delta, double delta_c, int refine, double* dz,
+                      pyipm_factor_stats* stats, int memkind) try {
+    PYIPM_ENTER("step", G_SINGLE | G_DEVICE)
+    if (!dz) { ctx->err = "step: null output"; return PYIPM_E_BADARG; }
+    const int rc = step_fused(ctx, delta, delta_c, refine, dz, stats, memkind);
+    if (rc) ctx->held.prefix_dropped();                      // a failed step: the next one runs in full
+    return rc;
+} PYIPM_CATCH_H(h)
+
+int pyipm_newton_reuse_info(pyipm_newton_ctx* h, int64_t out[4]) try {
+    PYIPM_ENTER("reuse_info", 0)
+    if (!out) return PYIPM_E_BADARG;
+    out[0] = ctx->n_reused; out[1] = ctx->n_recorded; out[2] = (int64_t)(ctx->snap.capacity() * sizeof(double)); out[3] = ctx->last_step_kind;
+    return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_step_lengths(pyipm_newton_ctx* h, double tau, const double* dz_in, double* alpha_s, double* alpha_l) try {
@@ -2835,7 +3030,7 @@ int pyipm_newton_merit_ray(pyipm_newton_ctx* h, const double* dz, double nu, dou
 
 // ---- per-panel phases -----------------------------------------------------------------------------
 int pyipm_newton_factor_begin(pyipm_newton_ctx* h) try {
-    PYIPM_ENTER("factor_begin", G_SINGLE | G_DEVICE)
+    PYIPM_ENTER("factor_begin", G_SINGLE | G_DEVICE | G_STORAGE)
     if (!ctx->held.assembled) { ctx->err = "factor_begin: assemble first"; return PYIPM_E_BADARG; }
     if (ctx->held.cond_active) { ctx->err = "per-panel phases do not apply to the condensed system; use factor()"; return PYIPM_E_BADARG; }
     ctx->sched.clear();                                 // per-panel phases: uniform group map, dense panels
@@ -2848,17 +3043,17 @@ int pyipm_newton_factor_end(pyipm_newton_ctx* h, pyipm_factor_stats* stats) try 
     return factor_end(ctx, stats);
 } PYIPM_CATCH_H(h)
 int pyipm_newton_factor_panel(pyipm_newton_ctx* h, int64_t p) try {
-    PYIPM_ENTER("factor_panel", G_SINGLE | G_DEVICE)
+    PYIPM_ENTER("factor_panel", G_SINGLE | G_DEVICE | G_STORAGE)
     return factor_panel(ctx, p, ctx->stream, false);
 } PYIPM_CATCH_H(h)
 int pyipm_newton_trailing_update(pyipm_newton_ctx* h, int64_t p) try {
-    PYIPM_ENTER("trailing_update", G_SINGLE | G_DEVICE)
+    PYIPM_ENTER("trailing_update", G_SINGLE | G_DEVICE | G_STORAGE)
     if (p < 0 || p >= ctx->g.npanels) return PYIPM_E_BADARG;
     return trailing_update(ctx, p);
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_trailing_update_range(pyipm_newton_ctx* h, int64_t p, int64_t first, int64_t count) try {
-    PYIPM_ENTER("trailing_update_range", G_SINGLE | G_DEVICE)
+    PYIPM_ENTER("trailing_update_range", G_SINGLE | G_DEVICE | G_STORAGE)
     const Geo& g = ctx->g;
     if (p < 0 || p >= g.npanels || first <= p || count < 0) return PYIPM_E_BADARG;
     if (g.panel_c0(p) + g.panel_w(p) >= g.Npad) return PYIPM_OK;
@@ -2885,7 +3080,7 @@ size_t pyipm_newton_panel_msg_bytes(pyipm_newton_ctx* h, int64_t p) try {
 } PYIPM_CATCH_SIZE
 
 int pyipm_newton_panel_pack(pyipm_newton_ctx* h, int64_t p, double* buf) try {
-    PYIPM_ENTER("panel_pack", G_SINGLE | G_DEVICE) const Geo& g = ctx->g;
+    PYIPM_ENTER("panel_pack", G_SINGLE | G_DEVICE | G_STORAGE) const Geo& g = ctx->g;
     if (!buf) return PYIPM_E_BADARG;
     if (p < 0 || p >= g.npanels || g.owner(p) != g.rank) { ctx->err = "panel_pack: not the owner"; return PYIPM_E_BADARG; }
     int64_t h0, h1;
@@ -2910,7 +3105,7 @@ int pyipm_newton_panel_pack(pyipm_newton_ctx* h, int64_t p, double* buf) try {
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_panel_unpack(pyipm_newton_ctx* h, int64_t p, const double* buf) try {
-    PYIPM_ENTER("panel_unpack", G_SINGLE | G_DEVICE) const Geo& g = ctx->g;
+    PYIPM_ENTER("panel_unpack", G_SINGLE | G_DEVICE | G_STORAGE) const Geo& g = ctx->g;
     if (!buf) return PYIPM_E_BADARG;
     if (p < 0 || p >= g.npanels || g.owner(p) == g.rank) { ctx->err = "panel_unpack: owner does not unpack"; return PYIPM_E_BADARG; }
     { int rc = unpack_panel_from(ctx, p, buf, 0, /*with_tiles=*/true, ctx->stream); if (rc) return rc; }
@@ -2938,7 +3133,7 @@ int pyipm_newton_bwd_panel(pyipm_newton_ctx* h, int64_t p, double* v) try {
 
 // ---- introspection --------------------------------------------------------------------------------
 int pyipm_newton_kkt_storage(pyipm_newton_ctx* h, double** ptr, int64_t* ld, int64_t* ncols) try {
-    PYIPM_ENTER("kkt_storage", 0)
+    PYIPM_ENTER("kkt_storage", G_DEVICE | G_STORAGE)
     if (ptr) { *ptr = ctx->A; ctx->held.storage_handed_out(); }
     if (ld) *ld = ctx->held.cond_active ? ctx->gc.Npad : ctx->g.Npad;
     if (ncols) *ncols = ctx->held.cond_active ? ctx->gc.ncols_local : ctx->g.ncols_local;
@@ -2988,7 +3183,7 @@ int pyipm_newton_trailing_bytes(pyipm_newton_ctx* h, double out[4]) try {
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_set_option(pyipm_newton_ctx* h, const char* name, double value) try {
-    PYIPM_ENTER("set_option", 0)
+    PYIPM_ENTER("set_option", G_DEVICE | G_STORAGE)          // (any option may change the schedule or the numbers)
     if (!name) return PYIPM_E_BADARG;
     if (!strcmp(name, "expert")) { ctx->expert = (int)value != 0; return PYIPM_OK; }
     {   // expert switches (include/pyipm_newton.h): measurement knobs, test hooks, parked experiments

@@ -89,6 +89,7 @@ def load_library(path: str | None = None):
         "pyipm_newton_rcond": (c_int, [ctxp, c_int, c_int, POINTER(c_double)]),
         "pyipm_newton_kkt_matvec": (c_int, [ctxp, c_void_p, c_void_p, c_int]),
         "pyipm_newton_step": (c_int, [ctxp, c_double, c_double, c_int, c_void_p, POINTER(FactorStats), c_int]),
+        "pyipm_newton_reuse_info": (c_int, [ctxp, POINTER(c_int64)]),
         "pyipm_newton_step_lengths": (c_int, [ctxp, c_double, c_void_p, POINTER(c_double), POINTER(c_double)]),
         "pyipm_newton_merit_info": (c_int, [ctxp, c_void_p, POINTER(c_double)]),
         "pyipm_newton_dots": (c_int, [ctxp, c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int64), POINTER(c_double)]),
@@ -383,6 +384,14 @@ class NewtonCore(object):
                                         ctypes.byref(st), MEM_DEVICE)
         self._ck(rc, st.as_dict())
         return dz, st.as_dict()
+
+    def reuse_info(self):
+        """Steps of this handle that reused the x-block prefix / recorded one, the snapshot's bytes and the kind of the last
+        step (``pyipm_newton_reuse_info``)."""
+        o = (c_int64 * 4)()
+        self._ck(self.lib.pyipm_newton_reuse_info(self.h, o))
+        return {"reused": int(o[0]), "recorded": int(o[1]), "snapshot_bytes": int(o[2]),
+                "last": ("full", "recording", "reusing")[int(o[3])]}
 
     def step_lengths(self, tau, dz=None):
         """Fraction-to-the-boundary step lengths (alpha_s, alpha_l) for the direction of the last solve, or for ``dz``
