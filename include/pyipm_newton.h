@@ -210,6 +210,9 @@ int pyipm_newton_step(pyipm_newton_ctx* ctx, double delta, double delta_c, int r
  * write anywhere).  PYIPM_REUSE_X=0 in the environment at create time switches all of it off; so does a snapshot that cannot
  * be allocated, silently.  Condensed, batched, provider and multi-rank handles, lookahead = 0 and systems whose first
  * group reaches beyond the x block never reuse.
+ * A reusing step sends its right-hand side through the kept panels in one launch (k_fwd_prefix) where the one-launch sweeps apply
+ * (sweep_persist, one rank, panels of at most 256 columns); PYIPM_FWD_PREFIX=0 at create time keeps the launches per panel,
+ * PYIPM_FWD_PREFIX=W (W >= 2) sets the workgroups of that launch (default 96).  The same bits either way.
  * out[0] = factorisations of this handle that reused, [1] = that recorded, [2] = bytes of the snapshot, [3] = the last one:
  * 0 full, 1 recording, 2 reusing.  With PYIPM_GROUP_TRACE set every factorisation says which kind it is. */
 int pyipm_newton_reuse_info(pyipm_newton_ctx* ctx, int64_t out[4]);

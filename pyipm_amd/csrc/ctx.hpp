@@ -337,6 +337,12 @@ struct Ctx {
     DevBuf<double> snap;                  // the snapshot, outside the workspace (allocated by the first recording step): PX_HDR doubles
                                           // (DevStats and the assembly's maximum as they stood at the boundary), then the column ranges
     int64_t n_reused = 0, n_recorded = 0; // fused steps of this handle that reused the prefix / recorded one
+    int fwd_prefix = 1;                   // a reusing step's forward substitution through the kept panels in one launch (k_fwd_prefix);
+    int fwd_prefix_wgs = 96;              // PYIPM_FWD_PREFIX=0 at create time keeps the per-panel launches, =W (>= 2) sets its workgroups
+    DevBuf<unsigned> fwdp_sync;           // ... its flags, progress words and error word (its own: the main stream's sweeps use sweep_sync)
+    static constexpr int FWDP_ERRW = 4096 + 8192;   // ... the error word's place (at most 4096 panels and 8192 chunks: solve_plain's one_launch)
+    bool fwdp_used = false;               // ... it ran since the error word was last read (factor_end)
+    int occ_fwd_prefix = 0;               // ... resident workgroups per CU (occupancy query, cached)
     int last_step_kind = 0;               // 0 full, 1 recording, 2 reusing
     DevBuf<char> ws;                      // the workspace: the caller's (adopted) or the library's; capacity = the bytes the geometry needs
     // carved from workspace

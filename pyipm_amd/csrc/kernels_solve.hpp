@@ -637,6 +637,124 @@ __global__ __launch_bounds__(512, 4) void k_fwd_sweep(const double* __restrict__
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The forward substitution through the KEPT panels [0, P0) of a reusing step in one launch.  Their L is
+// complete before the step begins, so nothing orders this sweep but itself; per panel the per-panel path spends three dependent
+// launches (k_fwd_diag, k_fwd_gemv, k_diag_apply), 64 x 3 of them in front of every panel the step does factor.  The result
+// is, bit for bit, what those launches leave in v before k_diag_apply (which follows as ONE launch over the prefix tiles: the
+// row owners read y, not z) -- k_fwd_sweep's is not: its eight waves split a panel's columns into eight partial sums.  Here
+//   * workgroup 0 is the chain: for panel s it waits until the panel's chunks carry the contributions of panels 0 .. s - 1,
+//     resolves the diagonal block in k_fwd_diag's order (a lane per row, the 64 columns of tile u ascending from 0.0, then
+//     y -= acc), stores y and raises flag[s]; the operands of the first step are requested before it waits;
+//   * every other workgroup owns 64-row chunks for the whole launch, strided over the grid; the rows that lie inside the slack
+//     hole of x columns whatever the panel own nothing.  Wave j takes the panel's columns k = j (mod 4) ascending -- one of
+//     k_fwd_gemv's four accumulators each, 512 contiguous bytes per load, requested BEFORE flag[s] is polled (L does not
+//     depend on y); the four sums meet in shared memory and wave 0 applies v -= (acc0 + acc1) + (acc2 + acc3).  A chunk whose
+//     256-row launch block of k_fwd_gemv (counted from the panel's end) lies outside the active ranges is not touched, as there.
+// Hand-over as in the sweeps above: relaxed agent-scope atomics for all that crosses workgroups, s_waitcnt for order, every poll
+// with a timeout, a sticky error word; on error the prefix rows of v become NaN.  256 threads; P0 panels of nb <= 256 columns.
+__global__ __launch_bounds__(256) void k_fwd_prefix(const double* __restrict__ A, SweepGeo sg, int P0, double* v, unsigned* sync,
+                                                    unsigned* err, unsigned long long timeout)
+{
+    __shared__ double ys[4 * TB];
+    __shared__ double ps[4][TB];
+    __shared__ int ok_s;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nb = sg.nb, cpp = nb / TB;                        // chunks (= tiles) per panel
+    const int nchunks = (int)(sg.Npad / TB);
+    unsigned* flag = sync; unsigned* prog = sync + P0;          // prog[c]: panels applied to the 64-row chunk c
+    if (tid == 0) ok_s = 1;
+    __syncthreads();
+    if (blockIdx.x == 0) {
+        for (int s = 0; s < P0; ++s) {
+            const int64_t c0 = (int64_t)s * nb;
+            const bool below0 = tid >= TB && tid < nb;          // rows of the tiles behind tile 0
+            double lt[TB];
+            if (below0) {
+                const double* col = A + (c0 + tid) + c0 * sg.ld;
+                #pragma unroll
+                for (int k = 0; k < TB; ++k) lt[k] = col[(int64_t)k * sg.ld];
+            }
+            if (s > 0 && tid < cpp && !sweep_wait(prog + s * cpp + tid, (unsigned)s, err, timeout)) ok_s = 0;
+            __syncthreads();
+            if (!ok_s) break;
+            if (tid < nb) ys[tid] = ld_agent(v + c0 + tid);
+            for (int u = 0; u + 1 < cpp; ++u) {
+                __syncthreads();
+                if (tid >= (u + 1) * TB && tid < nb) {
+                    double acc = 0.0;
+                    if (u == 0) {
+                        #pragma unroll
+                        for (int k = 0; k < TB; ++k) acc = fma(lt[k], ys[k], acc);
+                    } else {
+                        const double* col = A + (c0 + tid) + (c0 + (int64_t)u * TB) * sg.ld;
+                        #pragma unroll
+                        for (int k = 0; k < TB; ++k) acc = fma(col[(int64_t)k * sg.ld], ys[u * TB + k], acc);
+                    }
+                    ys[tid] -= acc;
+                }
+            }
+            __syncthreads();
+            if (tid < nb) st_agent(v + c0 + tid, ys[tid]);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            if (tid == 0) __hip_atomic_store(flag + s, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        __syncthreads();
+        if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)
+            for (int64_t i = tid; i < (int64_t)P0 * nb; i += 256) st_agent(v + i, __builtin_nan(""));
+        return;
+    }
+    // ---- row owners: the chunks below panel 0 without the hole, numbered m = 0 .. nlog - 1; mine are m = blockIdx - 1 + k (gridDim - 1) ----
+    // the hole: chunks whose launch block of k_fwd_gemv lies inside the slack rows wherever the panel ends (blocks begin up to
+    // 192 rows above the chunk and end up to 256 rows below its first row)
+    int h0 = nchunks, hl = 0;
+    if (sg.skip && sg.mi >= 512) {
+        const int a = (int)((sg.n + 192 + TB - 1) / TB), b = (int)((sg.n + sg.mi - 256) / TB) + 1;
+        if (b > a) { h0 = a; hl = b - a; }
+    }
+    const int nown = (int)gridDim.x - 1, nlog = nchunks - cpp - hl;
+    const int kc = nb / 4;                                      // columns per wave: 16, 32, 48 or 64
+    for (int s = 0; s < P0; ++s) {
+        const int64_t c0 = (int64_t)s * nb, row_begin = c0 + nb;
+        int m = (int)blockIdx.x - 1;
+        if (m < s * cpp) m += ((s * cpp - m + nown - 1) / nown) * nown;      // my first chunk below panel s (those all lie above the hole)
+        if (m >= nlog) return;                                  // nothing below this panel is mine, now or later
+        bool have_y = false;
+        for (; m < nlog; m += nown) {
+            int c = cpp + m; if (c >= h0) c += hl;
+            const int64_t r0 = (int64_t)c * TB;
+            const int64_t i0 = row_begin + (r0 - row_begin) / 256 * 256;     // the chunk's launch block of k_fwd_gemv
+            if (!sweep_active(sg, c0, c0 + nb, i0, i0 + 256)) continue;      // (the same for every thread of the workgroup)
+            double la[TB];
+            #pragma unroll
+            for (int j = 0; j < TB; ++j) la[j] = (j < kc) ? A[(r0 + lane) + (c0 + wave + 4 * j) * sg.ld] : 0.0;
+            if (!have_y) {
+                // (all four waves agree before anyone leaves: a wave returning alone would leave the others at the barrier)
+                if (!sweep_wait(flag + s, 1u, err, timeout)) ok_s = 0;
+                __syncthreads();
+                if (!ok_s) return;
+                if (tid < nb) ys[tid] = ld_agent(v + c0 + tid);
+                __syncthreads();
+                have_y = true;
+            }
+            double acc = 0.0;
+            #pragma unroll
+            for (int j = 0; j < TB; ++j) if (j < kc) acc = fma(la[j], ys[wave + 4 * j], acc);
+            ps[wave][lane] = acc;
+            __syncthreads();
+            if (wave == 0) {
+                const double t4 = (ps[0][lane] + ps[1][lane]) + (ps[2][lane] + ps[3][lane]);
+                double* vp = v + r0 + lane;
+                st_agent(vp, ld_agent(vp) - t4);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (lane == 0) __hip_atomic_store(prog + c, (unsigned)(s + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            __syncthreads();
+        }
+    }
+}
+
 // v[i] = b[i] on the rows of the panels this rank owns, 0 elsewhere: the ranks' vectors sum to b (distributed sweeps)
 __global__ __launch_bounds__(256) void k_mask_owned(double* __restrict__ v, const double* __restrict__ b, Geo g)
 {

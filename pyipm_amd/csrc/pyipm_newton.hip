@@ -1073,6 +1073,9 @@ int factor_end(Ctx* ctx, pyipm_factor_stats* stats) {
     unsigned* const chain_errw = ctx->chain_sync ? ctx->chain_sync + (size_t)Ctx::CHAIN_SLOTS * Ctx::CHAIN_WORDS : nullptr;
     if (ctx->chain_used && chain_errw)
         PYIPM_HIP(hipMemcpyAsync(&chain_err, chain_errw, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    int fwdp_err = 0;                                       // (the main stream has joined ctx->fwd by now: this step's launch is behind us)
+    if (ctx->fwdp_used && ctx->fwdp_sync)
+        PYIPM_HIP(hipMemcpyAsync(&fwdp_err, ctx->fwdp_sync + Ctx::FWDP_ERRW, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     PYIPM_HIP(hipStreamSynchronize(ctx->stream));
     ctx->chain_used = false;
     if (chain_err) {
@@ -1087,6 +1090,13 @@ int factor_end(Ctx* ctx, pyipm_factor_stats* stats) {
         ctx->err = "backward sweep (k_bwd_sweep): a poll timed out in an earlier solve; its result was NaN"; return PYIPM_E_HIP;
     }
     ctx->sweep_used = false;
+    if (fwdp_err) {
+        PYIPM_HIP(hipMemsetAsync(ctx->fwdp_sync + Ctx::FWDP_ERRW, 0, sizeof(unsigned), ctx->stream));
+        ctx->err = "forward sweep over the kept panels (k_fwd_prefix): a poll timed out; the direction was NaN "
+                   "(PYIPM_FWD_PREFIX=0 runs it panel by panel)";
+        return PYIPM_E_HIP;
+    }
+    ctx->fwdp_used = false;
     if (ctx->profile) {
         // time during which SOME update launch ran: the launches of the main stream are serial, a lookahead head on the
         // side stream may overlap the bulk update that follows it -- union of the intervals, not their sum
@@ -1268,6 +1278,51 @@ int solve_plain(Ctx* ctx, double* v, bool forward_done, int nrhs, int64_t vstrid
         return 0;
     }
     for (int64_t p = g.npanels - 1; p >= 0; --p) { int rc = bwd_panel(ctx, p, v, nrhs, vstride, part, pstride); if (rc) return rc; }
+    return 0;
+}
+
+// The forward substitution of a reusing step through the kept panels [0, P0) (k_fwd_prefix + one k_diag_apply over their tiles) on
+// `stream`, in place of P0 x (k_fwd_diag, k_fwd_gemv, k_diag_apply): the same bits.  Applies where solve_plain's one-launch sweeps
+// do; the caller keeps the per-panel loop otherwise.  The sync words are this launch's own (the main stream's sweeps use
+// ctx->sweep_sync, and a solve may still be running there): flags, a progress word per chunk -- zeroed on the same stream in front
+// of every launch -- and the error word behind them, zeroed once on that stream and sticky (factor_end reads it).
+static bool fwd_prefix_applies(const Ctx* ctx, int64_t P0) {
+    const Geo& g = ctx->g;
+    return ctx->fwd_prefix && ctx->sweep_persist && P0 >= 1 && g.world == 1 && g.nb <= 4 * TB && g.nb % TB == 0 && g.npanels >= 2 &&
+           g.npanels <= 4096 && g.Npad % 8 == 0 && g.Npad / TB <= 8192 && sub_width(ctx, (int)g.nb) == (int)g.nb &&
+           P0 * g.nb <= g.n;
+}
+static int fwd_prefix(Ctx* ctx, int64_t P0, double* v, hipStream_t stream) {
+    const Geo& g = ctx->g;
+    if (!ctx->fwdp_sync) {
+        PYIPM_HIP(ctx->fwdp_sync.reserve(Ctx::FWDP_ERRW + 1));
+        PYIPM_HIP(hipMemsetAsync(ctx->fwdp_sync + Ctx::FWDP_ERRW, 0, sizeof(unsigned), stream));
+    }
+    SweepGeo sg;
+    sg.Npad = g.Npad; sg.ld = g.Npad; sg.n = g.n; sg.mi = g.mi; sg.me = g.me; sg.nb = g.nb; sg.npanels = (int)g.npanels;
+    sg.skip = (ctx->skip_zeros && g.mi > 0) ? 1 : 0;
+    const int64_t nchunks = g.Npad / TB;
+    PYIPM_HIP(hipMemsetAsync(ctx->fwdp_sync, 0, (size_t)(P0 + nchunks) * sizeof(unsigned), stream));
+    // every workgroup must be resident (they wait for each other): at most what an occupancy query of THIS build says the GPU holds;
+    // and a guest beside the factorisation, whose chains and heads run meanwhile: fwd_prefix_wgs workgroups (profiles/fwd_prefix_ab.json)
+    if (ctx->occ_fwd_prefix <= 0) {
+        int occ = 0;
+        PYIPM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_fwd_prefix, 256, 0));
+        if (occ < 1) { ctx->err = "k_fwd_prefix does not fit a compute unit"; return PYIPM_E_HIP; }
+        ctx->occ_fwd_prefix = occ;
+    }
+    int64_t blocks = 1 + (nchunks - g.nb / TB);
+    if (blocks > (int64_t)ctx->occ_fwd_prefix * ctx->num_cus) blocks = (int64_t)ctx->occ_fwd_prefix * ctx->num_cus;
+    if (blocks > ctx->fwd_prefix_wgs) blocks = ctx->fwd_prefix_wgs;
+    if (ctx->sweep_max_blocks > 0 && blocks > ctx->sweep_max_blocks) blocks = ctx->sweep_max_blocks;      // (test hook: several chunks per owner)
+    if (blocks < 2) blocks = 2;
+    hipLaunchKernelGGL(k_fwd_prefix, dim3((unsigned)blocks), dim3(256), 0, stream, ctx->A, sg, (int)P0, v, ctx->fwdp_sync,
+                       ctx->fwdp_sync + Ctx::FWDP_ERRW, (unsigned long long)2.0e8);                               // polls give up after 2 s (100 MHz clock)
+    PYIPM_KCHECK();
+    hipLaunchKernelGGL(k_diag_apply, dim3((unsigned)(P0 * g.nb / TB), 1), dim3(64), 0, stream, ctx->Dinv, ctx->Tsv, ctx->Tflag,
+                       ctx->block_refine, (int64_t)0, (int64_t)0, v, (int64_t)0);
+    PYIPM_KCHECK();
+    ctx->fwdp_used = true;
     return 0;
 }
 
@@ -2073,10 +2128,16 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false, i
     }
     if (run.slack_first) { rc = enqueue_slack_first(ctx, run, ctx->stream); if (rc) return rc; }
     if (reuse && fuse_forward) {            // the new right-hand side through the prefix panels: L and the tile inverses are there
-        for (int64_t q = 0; q < sc.first(gB); ++q) {
-            rc = fwd_panel(ctx, q, ctx->fwd_vec, ctx->fwd); if (rc) return rc;
-            rc = diag_panel(ctx, q, ctx->fwd_vec, ctx->fwd); if (rc) return rc;
+        const int64_t P0 = sc.first(gB);
+        if (fwd_prefix_applies(ctx, P0)) {  // ... in one launch (k_fwd_prefix), or panel by panel
+            rc = fwd_prefix(ctx, P0, ctx->fwd_vec, ctx->fwd); if (rc) return rc;
+        } else {
+            for (int64_t q = 0; q < P0; ++q) {
+                rc = fwd_panel(ctx, q, ctx->fwd_vec, ctx->fwd); if (rc) return rc;
+                rc = diag_panel(ctx, q, ctx->fwd_vec, ctx->fwd); if (rc) return rc;
+            }
         }
+        tr.mark("fwd prefix end (before group)", gB, ctx->fwd);
     }
     if (reuse && run.slack_first && sc.fast(g0)) PYIPM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_sfast, 0));   // (as in front of any slack group)
     tr.mark("chain+rows begin", g0, ctx->stream);
@@ -2144,6 +2205,7 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false, i
         across_prev = st.across;
     }
     if (fuse_forward) {                     // join: the main stream continues after the forward pass
+        tr.mark("fwd stream end (before group)", ngroups, ctx->fwd);
         PYIPM_HIP(hipEventRecord(ctx->ev_fwd, ctx->fwd));
         PYIPM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_fwd, 0));
         ctx->held.forward_fused_under_factor();
@@ -2339,6 +2401,7 @@ static int create_impl(pyipm_newton_ctx** out, int64_t n, int64_t me, int64_t mi
             { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) ctx->num_cus = ncu; }
             ctx->provider_only = provider_only;
             { const char* e = getenv("PYIPM_REUSE_X"); if (e && e[0] == '0') ctx->reuse_x = 0; }
+            { const char* e = getenv("PYIPM_FWD_PREFIX"); if (e) { const int w = atoi(e); if (w <= 0) ctx->fwd_prefix = 0; else if (w >= 2) ctx->fwd_prefix_wgs = w; } }
         },
         [&](Ctx* ctx, char* base) { return carve_workspace(ctx, g, base, provider_only); },
         2 /* [0] max |entry|, [1] "assembly pending" */, true);
