@@ -637,6 +637,108 @@ __global__ __launch_bounds__(512, 4) void k_fwd_sweep(const double* __restrict__
     }
 }
 
+constexpr int FWDP_RESIDENT = 16;       // chunks of v a row owner of k_fwd_prefix keeps on chip (tests/test_gpu_fwd_prefix_resident.py states it too)
+// A row owner of k_fwd_prefix (see there): the chunks below panel 0 without the hole, numbered m = 0 .. nlog - 1; mine are
+// m = blockIdx - 1 + k (gridDim - 1).  KC = nb / 4: the columns of a panel that one wave takes.
+template <int KC>
+__device__ __forceinline__ void fwd_prefix_owner(const double* __restrict__ A, const SweepGeo& sg, int P0, double* v, unsigned* flag,
+                                                 unsigned* prog, unsigned* err, unsigned long long timeout, double* ys,
+                                                 double (*ps)[4][TB], double (*vres)[TB], int* ok_s)
+{
+    constexpr int Q = KC / 4;                                   // a quarter of them
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nb = sg.nb, cpp = nb / TB, nchunks = (int)(sg.Npad / TB);
+    // the hole: chunks whose launch block of k_fwd_gemv lies inside the slack rows wherever the panel ends (blocks begin up to
+    // 192 rows above the chunk and end up to 256 rows below its first row)
+    int h0 = nchunks, hl = 0;
+    if (sg.skip && sg.mi >= 512) {
+        const int a = (int)((sg.n + 192 + TB - 1) / TB), b = (int)((sg.n + sg.mi - 256) / TB) + 1;
+        if (b > a) { h0 = a; hl = b - a; }
+    }
+    const int nown = (int)gridDim.x - 1, nlog = nchunks - cpp - hl, m0 = (int)blockIdx.x - 1;
+    // a visit = (panel s, my chunk m below it), panels ascending, my chunks ascending inside a panel, the inactive ones left out
+    auto chunk_of = [&](int m) { const int c = cpp + m; return c >= h0 ? c + hl : c; };
+    auto visit_at = [&](int& s, int& m) -> bool {              // the first visit at or behind (s, m); the same for every thread
+        for (; s < P0; ++s, m = m0) {
+            if (m < s * cpp) m += ((s * cpp - m + nown - 1) / nown) * nown;  // my first chunk below panel s (those all lie above the hole)
+            const int64_t row_begin = (int64_t)(s + 1) * nb;
+            for (; m < nlog; m += nown) {
+                const int64_t r0 = (int64_t)chunk_of(m) * TB;
+                const int64_t i0 = row_begin + (r0 - row_begin) / 256 * 256;     // the chunk's launch block of k_fwd_gemv
+                if (sweep_active(sg, (int64_t)s * nb, row_begin, i0, i0 + 256)) return true;
+            }
+        }
+        return false;
+    };
+    // L of a visit: la is a ring of four quarters, and a quarter is requested for the NEXT visit as soon as this visit has used
+    // it (L does not depend on y) -- a visit's columns are on their way one visit ahead, whatever flag[s] says
+    double la[KC];
+    auto request = [&](int q, int s, int m) {
+        const double* src = A + ((int64_t)chunk_of(m) * TB + lane) + ((int64_t)s * nb + wave) * sg.ld;
+        #pragma unroll
+        for (int j = Q * q; j < Q * q + Q; ++j) la[j] = ld_agent(src + (int64_t)(4 * j) * sg.ld);   // (an atomic load stays where it is written: a plain one sinks to its use, a visit later)
+    };
+    unsigned dirty = 0, seen = 0;                               // (wave 0) slots of vres that hold what v does not; slots loaded once
+    int s = 0, m = m0;
+    bool more = visit_at(s, m);
+    if (!more) return;
+    #pragma unroll
+    for (int q = 0; q < 4; ++q) request(q, s, m);
+    int ys_of = -1, par = 0;
+    while (more) {
+        int sn = s, mn = m + nown;
+        const bool more_n = visit_at(sn, mn);
+        const int sr = more_n ? sn : s, mr = more_n ? mn : m;  // (behind the last visit: the same columns once more, unused -- no branch among the loads)
+        if (ys_of != s) {
+            // (all four waves agree before anyone leaves: a wave returning alone would leave the others at the barrier)
+            if (!sweep_wait(flag + s, 1u, err, timeout)) *ok_s = 0;
+            __syncthreads();
+            if (!*ok_s) return;
+            if (tid < nb) ys[tid] = ld_agent(v + (int64_t)s * nb + tid);
+            __syncthreads();
+            ys_of = s;
+        }
+        double acc = 0.0;
+        #pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            #pragma unroll
+            for (int j = Q * q; j < Q * q + Q; ++j) acc = fma(la[j], ys[wave + 4 * j], acc);
+            request(q, sr, mr);
+        }
+        ps[par][wave][lane] = acc;
+        __syncthreads();
+        // (ps has two halves: wave 0 reads this one while the others fill the next visit's; ys changes only behind a barrier that wave 0 joins)
+        if (wave == 0) {
+            const double t4 = (ps[par][0][lane] + ps[par][1][lane]) + (ps[par][2][lane] + ps[par][3][lane]);
+            const int c = chunk_of(m), k = (m - m0) / nown;     // my k-th chunk: resident in slot k while k < FWDP_RESIDENT
+            double* vp = v + (int64_t)c * TB + lane;
+            const bool res = k < FWDP_RESIDENT;
+            double x;
+            if (res && ((seen >> k) & 1u)) x = vres[k][lane]; else x = ld_agent(vp);
+            x -= t4;
+            // final for its reader: a chunk of panel p after panel p - 1 (the chain waits for prog[c] >= p); a chunk below the prefix
+            // after the last kept panel (the end of this workgroup's visits); a chunk without a slot goes home after every visit
+            const bool fin = c < P0 * cpp && s + 1 == c / cpp;
+            if (!res || fin) {
+                st_agent(vp, x);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (lane == 0) __hip_atomic_store(prog + c, (unsigned)(s + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (res) dirty &= ~(1u << k);
+            } else {
+                vres[k][lane] = x;
+                dirty |= 1u << k;
+            }
+            if (res) seen |= 1u << k;
+        }
+        par ^= 1;
+        s = sn; m = mn; more = more_n;
+    }
+    if (wave == 0) {                                            // what is still resident: the chunks below the prefix
+        for (int k = 0; k < FWDP_RESIDENT; ++k)
+            if ((dirty >> k) & 1u) st_agent(v + (int64_t)chunk_of(m0 + k * nown) * TB + lane, vres[k][lane]);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // The forward substitution through the KEPT panels [0, P0) of a reusing step in one launch.  Their L is
 // complete before the step begins, so nothing orders this sweep but itself; per panel the per-panel path spends three dependent
@@ -648,16 +750,22 @@ __global__ __launch_bounds__(512, 4) void k_fwd_sweep(const double* __restrict__
 //     y -= acc), stores y and raises flag[s]; the operands of the first step are requested before it waits;
 //   * every other workgroup owns 64-row chunks for the whole launch, strided over the grid; the rows that lie inside the slack
 //     hole of x columns whatever the panel own nothing.  Wave j takes the panel's columns k = j (mod 4) ascending -- one of
-//     k_fwd_gemv's four accumulators each, 512 contiguous bytes per load, requested BEFORE flag[s] is polled (L does not
-//     depend on y); the four sums meet in shared memory and wave 0 applies v -= (acc0 + acc1) + (acc2 + acc3).  A chunk whose
-//     256-row launch block of k_fwd_gemv (counted from the panel's end) lies outside the active ranges is not touched, as there.
+//     k_fwd_gemv's four accumulators each, 512 contiguous bytes per load, requested one VISIT ahead, a quarter of them at a
+//     time as the registers come free (L does not depend on y, so neither flag[s] nor a panel's end holds the requests back);
+//     the four sums meet in shared memory and wave 0 applies v -= (acc0 + acc1) + (acc2 + acc3).  A chunk whose 256-row launch
+//     block of k_fwd_gemv (counted from the panel's end) lies outside the active ranges is not touched, as there.
+//   * an owner keeps the rows of v of its first FWDP_RESIDENT chunks in shared memory from a chunk's first active visit on: the
+//     subtractions are the same, panel after panel, but the chunk goes to global memory, and prog[c] is raised, only when it is
+//     final for its reader -- a chunk of panel p after panel p - 1 (the chain), a chunk below the prefix when the owner's visits
+//     end (the kernels behind this launch).  An owner's further chunks make the global round trip on every visit.
 // Hand-over as in the sweeps above: relaxed agent-scope atomics for all that crosses workgroups, s_waitcnt for order, every poll
-// with a timeout, a sticky error word; on error the prefix rows of v become NaN.  256 threads; P0 panels of nb <= 256 columns.
+// with a timeout, a sticky error word; on error the prefix rows of v become NaN.  256 threads; P0 panels of 128 or 256 columns.
 __global__ __launch_bounds__(256) void k_fwd_prefix(const double* __restrict__ A, SweepGeo sg, int P0, double* v, unsigned* sync,
                                                     unsigned* err, unsigned long long timeout)
 {
     __shared__ double ys[4 * TB];
-    __shared__ double ps[4][TB];
+    __shared__ double ps[2][4][TB];
+    __shared__ double vres[FWDP_RESIDENT][TB];                  // (wave 0 of a row owner: lane l keeps row l of its k-th chunk)
     __shared__ int ok_s;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nb = sg.nb, cpp = nb / TB;                        // chunks (= tiles) per panel
@@ -683,13 +791,15 @@ __global__ __launch_bounds__(256) void k_fwd_prefix(const double* __restrict__ A
                 __syncthreads();
                 if (tid >= (u + 1) * TB && tid < nb) {
                     double acc = 0.0;
-                    if (u == 0) {
+                    #pragma unroll
+                    for (int k = 0; k < TB; ++k) acc = fma(lt[k], ys[u * TB + k], acc);
+                    if (tid >= (u + 2) * TB) {
+                        // the next step's 64 columns, all requested at once and across its barrier (atomic loads stay where they are
+                        // written: as plain ones each was loaded in front of its own fma, 64 dependent round trips a step)
+                        const double* col = A + c0 + (c0 + (int64_t)(u + 1) * TB) * sg.ld;   // (the same for every thread: a scalar base per column)
+                        __builtin_amdgcn_sched_barrier(0);      // (behind the sums: the requests reuse their registers)
                         #pragma unroll
-                        for (int k = 0; k < TB; ++k) acc = fma(lt[k], ys[k], acc);
-                    } else {
-                        const double* col = A + (c0 + tid) + (c0 + (int64_t)u * TB) * sg.ld;
-                        #pragma unroll
-                        for (int k = 0; k < TB; ++k) acc = fma(col[(int64_t)k * sg.ld], ys[u * TB + k], acc);
+                        for (int k = 0; k < TB; ++k) lt[k] = ld_agent(col + (int64_t)k * sg.ld + tid);
                     }
                     ys[tid] -= acc;
                 }
@@ -705,54 +815,11 @@ __global__ __launch_bounds__(256) void k_fwd_prefix(const double* __restrict__ A
             for (int64_t i = tid; i < (int64_t)P0 * nb; i += 256) st_agent(v + i, __builtin_nan(""));
         return;
     }
-    // ---- row owners: the chunks below panel 0 without the hole, numbered m = 0 .. nlog - 1; mine are m = blockIdx - 1 + k (gridDim - 1) ----
-    // the hole: chunks whose launch block of k_fwd_gemv lies inside the slack rows wherever the panel ends (blocks begin up to
-    // 192 rows above the chunk and end up to 256 rows below its first row)
-    int h0 = nchunks, hl = 0;
-    if (sg.skip && sg.mi >= 512) {
-        const int a = (int)((sg.n + 192 + TB - 1) / TB), b = (int)((sg.n + sg.mi - 256) / TB) + 1;
-        if (b > a) { h0 = a; hl = b - a; }
-    }
-    const int nown = (int)gridDim.x - 1, nlog = nchunks - cpp - hl;
-    const int kc = nb / 4;                                      // columns per wave: 16, 32, 48 or 64
-    for (int s = 0; s < P0; ++s) {
-        const int64_t c0 = (int64_t)s * nb, row_begin = c0 + nb;
-        int m = (int)blockIdx.x - 1;
-        if (m < s * cpp) m += ((s * cpp - m + nown - 1) / nown) * nown;      // my first chunk below panel s (those all lie above the hole)
-        if (m >= nlog) return;                                  // nothing below this panel is mine, now or later
-        bool have_y = false;
-        for (; m < nlog; m += nown) {
-            int c = cpp + m; if (c >= h0) c += hl;
-            const int64_t r0 = (int64_t)c * TB;
-            const int64_t i0 = row_begin + (r0 - row_begin) / 256 * 256;     // the chunk's launch block of k_fwd_gemv
-            if (!sweep_active(sg, c0, c0 + nb, i0, i0 + 256)) continue;      // (the same for every thread of the workgroup)
-            double la[TB];
-            #pragma unroll
-            for (int j = 0; j < TB; ++j) la[j] = (j < kc) ? A[(r0 + lane) + (c0 + wave + 4 * j) * sg.ld] : 0.0;
-            if (!have_y) {
-                // (all four waves agree before anyone leaves: a wave returning alone would leave the others at the barrier)
-                if (!sweep_wait(flag + s, 1u, err, timeout)) ok_s = 0;
-                __syncthreads();
-                if (!ok_s) return;
-                if (tid < nb) ys[tid] = ld_agent(v + c0 + tid);
-                __syncthreads();
-                have_y = true;
-            }
-            double acc = 0.0;
-            #pragma unroll
-            for (int j = 0; j < TB; ++j) if (j < kc) acc = fma(la[j], ys[wave + 4 * j], acc);
-            ps[wave][lane] = acc;
-            __syncthreads();
-            if (wave == 0) {
-                const double t4 = (ps[0][lane] + ps[1][lane]) + (ps[2][lane] + ps[3][lane]);
-                double* vp = v + r0 + lane;
-                st_agent(vp, ld_agent(vp) - t4);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                if (lane == 0) __hip_atomic_store(prog + c, (unsigned)(s + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            __syncthreads();
-        }
-    }
+    // ---- row owners ----
+    // (the columns per wave at compile time: no test per column.  Panels are 128 or 256 columns wide here: a handle's nb is a
+    //  multiple of 128, and fwd_prefix_applies asks for it too)
+    if (cpp == 2) fwd_prefix_owner<32>(A, sg, P0, v, flag, prog, err, timeout, ys, ps, vres, &ok_s);
+    else fwd_prefix_owner<64>(A, sg, P0, v, flag, prog, err, timeout, ys, ps, vres, &ok_s);
 }
 
 // v[i] = b[i] on the rows of the panels this rank owns, 0 elsewhere: the ranks' vectors sum to b (distributed sweeps)

@@ -1288,7 +1288,7 @@ int solve_plain(Ctx* ctx, double* v, bool forward_done, int nrhs, int64_t vstrid
 // of every launch -- and the error word behind them, zeroed once on that stream and sticky (factor_end reads it).
 static bool fwd_prefix_applies(const Ctx* ctx, int64_t P0) {
     const Geo& g = ctx->g;
-    return ctx->fwd_prefix && ctx->sweep_persist && P0 >= 1 && g.world == 1 && g.nb <= 4 * TB && g.nb % TB == 0 && g.npanels >= 2 &&
+    return ctx->fwd_prefix && ctx->sweep_persist && P0 >= 1 && g.world == 1 && g.nb <= 4 * TB && g.nb % (2 * TB) == 0 && g.npanels >= 2 &&
            g.npanels <= 4096 && g.Npad % 8 == 0 && g.Npad / TB <= 8192 && sub_width(ctx, (int)g.nb) == (int)g.nb &&
            P0 * g.nb <= g.n;
 }
@@ -1304,7 +1304,7 @@ static int fwd_prefix(Ctx* ctx, int64_t P0, double* v, hipStream_t stream) {
     const int64_t nchunks = g.Npad / TB;
     PYIPM_HIP(hipMemsetAsync(ctx->fwdp_sync, 0, (size_t)(P0 + nchunks) * sizeof(unsigned), stream));
     // every workgroup must be resident (they wait for each other): at most what an occupancy query of THIS build says the GPU holds;
-    // and a guest beside the factorisation, whose chains and heads run meanwhile: fwd_prefix_wgs workgroups (profiles/fwd_prefix_ab.json)
+    // and a guest beside the factorisation, whose chains and heads run meanwhile: fwd_prefix_wgs workgroups (profiles/fwd_prefix_resident_ab.json)
     if (ctx->occ_fwd_prefix <= 0) {
         int occ = 0;
         PYIPM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_fwd_prefix, 256, 0));
