@@ -251,6 +251,34 @@ struct Held {
     void quiesced() { factored = false; forward_pending = false; forward_fused = false; zeros_clean = false; px_valid = false; }
 };
 
+// The words of a device-driven launch (k_tile_chain, k_fwd_sweep / k_bwd_sweep, k_fwd_prefix): `words` flags and progress words
+// in the layout its kernel indexes, and behind them, as the last word of the allocation, the sticky error word a poll that
+// timed out sets.  factor_end reads the error word of every owner that launched since it last did, and reports `message`.
+constexpr unsigned long long POLL_TIMEOUT = 200000000ull;   // a poll gives up after 2 s (100 MHz clock)
+struct PollWords {
+    DevBuf<unsigned> buf;
+    size_t words; const char* message;
+    bool used = false;                    // a launch ran since the error word was last read
+    PollWords(size_t words_, const char* message_) : words(words_), message(message_) {}
+    unsigned* err() const { return buf + words; }
+    hipError_t allocate() { return buf.reserve(words + 1); }
+    hipError_t ensure(hipStream_t st) {   // first use: allocated, the error word zeroed on `st`
+        if (buf) return hipSuccess;
+        const hipError_t e = allocate();
+        return e != hipSuccess ? e : clear_err(st);
+    }
+    hipError_t arm(size_t n, hipStream_t st) { return hipMemsetAsync(buf, 0, n * sizeof(unsigned), st); }   // the first n words := 0 in front of a launch on `st`
+    // The first n words := 0 for launches on ANY stream.  The fill is ordered on the NULL stream and the kernels poll from
+    // non-blocking streams, which are not ordered behind it: k_chain_wait met the words of an earlier handle's life in this memory
+    // -- larger epochs: "done" -- and let the rows kernels run ahead of the chain (tools/chain_stress.py).  So: wait for the fill.
+    hipError_t zero_and_wait(size_t n) {
+        const hipError_t e = hipMemset(buf, 0, n * sizeof(unsigned));
+        return e != hipSuccess ? e : hipDeviceSynchronize();
+    }
+    hipError_t fetch_err(int* host, hipStream_t st) const { return hipMemcpyAsync(host, err(), sizeof(int), hipMemcpyDeviceToHost, st); }
+    hipError_t clear_err(hipStream_t st) { return hipMemsetAsync(err(), 0, sizeof(unsigned), st); }
+};
+
 struct DistState;                                       // dist_impl.hpp
 struct DistDelete { void operator()(DistState*) const; };   // (pyipm_dist.hip: the type is complete there)
 
@@ -295,12 +323,12 @@ struct Ctx {
     int tile_step = 1;                    // stepped panel schedule (kernels_panel.hpp): one launch per diagonal tile (the rows inside the
                                           // diagonal block), one for the rows below it; panels of at most 4 tiles; same bits
     int sweep_max_blocks = 0;             // test hook: cap on the workgroups of the one-launch sweeps (0 = as many as the GPU holds)
-    int occ_fwd_sweep = 0, occ_bwd_sweep = 0;   // resident workgroups per CU of the one-launch sweeps (occupancy query, cached)
+    int occ_fwd_sweep = 0, occ_bwd_sweep = 0, occ_fwd_prefix = 0;   // resident workgroups per CU of the one-launch sweeps (occupancy query, cached)
     int sweep_persist = 1;                // single rank, one right-hand side: the backward sweep as ONE device-driven launch (k_bwd_sweep)
     DevBuf<double> sweep_buf;             // ... the near sums as the column owners hand them to workgroup 0 (Npad doubles, NaN = not there yet)
     DevBuf<double> ms_buf;                // solve_many: its column blocks, partials and refinement vectors (allocated on first use, grown on demand)
-    DevBuf<unsigned> sweep_sync;          // ... its flags and counters (3 npanels + 1 words, zeroed before every sweep)
-    bool sweep_used = false;              // ... a sweep ran since the error word was last read (solve_info / factor_end look at it)
+    PollWords sweep_words{3 * 4096,       // ... its flags and counters (at most 3 npanels words, zeroed before every sweep)
+                          "backward sweep (k_bwd_sweep): a poll timed out in an earlier solve; its result was NaN"};
     int dist_slices = 2;                  // distributed schedule: the two-message protocol (slices ahead of the panel message: the next owner's tile
                                           // chain starts on an nb x nb message); 0 = one message per panel (rounds 1-4); collective
     double dist_timeout_s = 300.0;        // distributed step: bound on the host's wait for the device (dist_impl.hpp:bounded_wait); <= 0: none
@@ -339,10 +367,9 @@ struct Ctx {
     int64_t n_reused = 0, n_recorded = 0; // fused steps of this handle that reused the prefix / recorded one
     int fwd_prefix = 1;                   // a reusing step's forward substitution through the kept panels in one launch (k_fwd_prefix);
     int fwd_prefix_wgs = 96;              // PYIPM_FWD_PREFIX=0 at create time keeps the per-panel launches, =W (>= 2) sets its workgroups
-    DevBuf<unsigned> fwdp_sync;           // ... its flags, progress words and error word (its own: the main stream's sweeps use sweep_sync)
-    static constexpr int FWDP_ERRW = 4096 + 8192;   // ... the error word's place (at most 4096 panels and 8192 chunks: solve_plain's one_launch)
-    bool fwdp_used = false;               // ... it ran since the error word was last read (factor_end)
-    int occ_fwd_prefix = 0;               // ... resident workgroups per CU (occupancy query, cached)
+    PollWords fwdp_words{4096 + 8192,     // ... its own flags and progress words (at most 4096 panels and 8192 chunks: sweeps_in_one_launch)
+                         "forward sweep over the kept panels (k_fwd_prefix): a poll timed out; the direction was NaN "
+                         "(PYIPM_FWD_PREFIX=0 runs it panel by panel)"};
     int last_step_kind = 0;               // 0 full, 1 recording, 2 reusing
     DevBuf<char> ws;                      // the workspace: the caller's (adopted) or the library's; capacity = the bytes the geometry needs
     // carved from workspace
@@ -392,11 +419,12 @@ struct Ctx {
     bool chain_lds_set = false;
     int chain_cpy = 5;                    // ... column tiles per unit and stage a row tile is split for
     static constexpr int CHAIN_SLOTS = 8, CHAIN_WORDS = 160;
-    DevBuf<unsigned> chain_sync;          // ... progress words (CHAIN_SLOTS regions used round robin, epoch-stamped) + the sticky error word
+    PollWords chain_words{CHAIN_SLOTS * CHAIN_WORDS,   // ... progress words: CHAIN_SLOTS regions used round robin, epoch-stamped
+                          "tile chain (k_tile_chain): a poll timed out -- a workgroup of the chain did not become resident; this factorisation "
+                          "is invalid (set_option(\"tile_chain\", 0) runs one launch per tile)"};
     unsigned chain_epoch = 0;
     ChainGeo chain_last = {};             // ... the last chain launch (factor_block hands it to k_chain_wait)
     unsigned long long* chain_dbg = nullptr; int chain_dbg_launch = 0;   // diagnostics only (option debug_chain_ptr)
-    bool chain_used = false;              // ... a chain launch ran since the error word was last read (factor_end)
     int64_t tile8_rows = 12288;           // ... used by the single-rank schedule for the first group and where at most this many rows are left
     int bc_per_problem = 1;               // batched condensed form: the Gram part by one workgroup per problem where n = 64 .. 256 allows it
     int block_refine = 2;                 // refinement steps of L T = S in the panel scaling and of T z = y in the solves

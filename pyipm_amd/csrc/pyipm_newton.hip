@@ -2,6 +2,7 @@
 // gfx950 only; no CUDA path, no CPU fallback.  Host-side orchestration of the HIP kernels in
 // kernels_*.hpp.  Replaces /root/reference/pyipm.py:1717-1725 (see the header for the mapping).
 #include "driver.hpp"
+#include "sub_walk.hpp"
 #include "kernels_assemble.hpp"
 #include "kernels_factor.hpp"
 #include "kernels_panel.hpp"
@@ -544,18 +545,15 @@ int launch_tile_steps(Ctx* ctx, hipStream_t chain, int64_t gc0, int64_t glc0, in
     if (tb <= ta) return 0;
     if (tb - ta >= 2 && chain_applies(ctx, gc0, nT)) {
         // the steps [ta, tb) as ONE launch of persistent workgroups (kernels_chain.hpp): no launch boundary between two tiles
-        if (!ctx->chain_sync) {
-            PYIPM_HIP(ctx->chain_sync.reserve((size_t)(Ctx::CHAIN_SLOTS * Ctx::CHAIN_WORDS + 1)));
-            PYIPM_HIP(hipMemset(ctx->chain_sync, 0, (size_t)(Ctx::CHAIN_SLOTS * Ctx::CHAIN_WORDS + 1) * sizeof(unsigned)));
-            // (the fill is ordered on the NULL stream; k_chain_wait polls these words from a non-blocking stream: it met the words of
-            //  an earlier handle's life in this memory -- larger epochs: "done" -- and let the rows kernels run ahead of the chain, on
-            //  the first step of a handle only: tools/chain_stress.py.  Once per handle: wait for the fill.)
-            PYIPM_HIP(hipDeviceSynchronize());
+        PollWords& cw = ctx->chain_words;
+        if (!cw.buf) {                                   // once per handle: every word, the error word too
+            PYIPM_HIP(cw.allocate());
+            PYIPM_HIP(cw.zero_and_wait(cw.words + 1));
             ctx->chain_epoch = 0;
         }
         if (ctx->chain_epoch >= (1u << 24)) {            // the words' epochs must stay ordered: start over (every 16 M launches)
             PYIPM_HIP(hipDeviceSynchronize());
-            PYIPM_HIP(hipMemset(ctx->chain_sync, 0, (size_t)(Ctx::CHAIN_SLOTS * Ctx::CHAIN_WORDS) * sizeof(unsigned)));
+            PYIPM_HIP(cw.zero_and_wait(cw.words));
             ctx->chain_epoch = 0;
         }
         ChainGeo cg;
@@ -563,9 +561,9 @@ int launch_tile_steps(Ctx* ctx, hipStream_t chain, int64_t gc0, int64_t glc0, in
         cg.nR = nT + ((ta == 0 && tb == nT) ? nX : 0); cg.xword = xword; cg.xwant = xwant;
         ctx->chain_epoch += 1;
         cg.base = ctx->chain_epoch * 64u;
-        cg.sync = ctx->chain_sync + (size_t)(ctx->chain_epoch % Ctx::CHAIN_SLOTS) * Ctx::CHAIN_WORDS;
-        cg.err = ctx->chain_sync + (size_t)Ctx::CHAIN_SLOTS * Ctx::CHAIN_WORDS;
-        cg.timeout = (unsigned long long)2.0e8;          // 2 s (100 MHz clock)
+        cg.sync = cw.buf + (size_t)(ctx->chain_epoch % Ctx::CHAIN_SLOTS) * Ctx::CHAIN_WORDS;
+        cg.err = cw.err();
+        cg.timeout = POLL_TIMEOUT;
         cg.dbg = nullptr;
         if (ctx->chain_dbg && ctx->chain_dbg_launch < 64) cg.dbg = ctx->chain_dbg + (size_t)(ctx->chain_dbg_launch++) * CHAIN_DBG_WORDS;
         const unsigned nblk = 1u + (unsigned)chain_units(ta, nT, cg.cpy, cg.nR);
@@ -580,7 +578,7 @@ int launch_tile_steps(Ctx* ctx, hipStream_t chain, int64_t gc0, int64_t glc0, in
                            ctx->Tflag + gc0 / TB, ctx->refine_cond, ctx->block_refine, ctx->dstats, g.N, ctx->pivtol_rel, ctx->anorm,
                            g.n + g.mi, ctx->tile_blocked, cg, ctx->dbg_buf);
         PYIPM_KCHECK();
-        ctx->chain_used = true;
+        cw.used = true;
         ctx->chain_last = cg;
         return 0;
     }
@@ -1066,37 +1064,19 @@ pyipm_factor_stats to_stats(const DevStats& z) {
 int factor_end(Ctx* ctx, pyipm_factor_stats* stats) {
     DevStats z;
     PYIPM_HIP(hipMemcpyAsync(&z, ctx->dstats, sizeof(z), hipMemcpyDeviceToHost, ctx->stream));
-    int sweep_err = 0;
-    if (ctx->sweep_used && ctx->sweep_sync)
-        PYIPM_HIP(hipMemcpyAsync(&sweep_err, ctx->sweep_sync + 3 * 4096, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    int chain_err = 0;
-    unsigned* const chain_errw = ctx->chain_sync ? ctx->chain_sync + (size_t)Ctx::CHAIN_SLOTS * Ctx::CHAIN_WORDS : nullptr;
-    if (ctx->chain_used && chain_errw)
-        PYIPM_HIP(hipMemcpyAsync(&chain_err, chain_errw, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    int fwdp_err = 0;                                       // (the main stream has joined ctx->fwd by now: this step's launch is behind us)
-    if (ctx->fwdp_used && ctx->fwdp_sync)
-        PYIPM_HIP(hipMemcpyAsync(&fwdp_err, ctx->fwdp_sync + Ctx::FWDP_ERRW, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    // the error words of the device-driven launches, in the order they are reported in.  (prefix sweep: the main stream has joined
+    // ctx->fwd by now, this step's launch is behind us.)  `used` falls once the word has been read, whatever it held.
+    PollWords* const pw[3] = {&ctx->chain_words, &ctx->sweep_words, &ctx->fwdp_words};
+    int perr[3] = {0, 0, 0};
+    for (int k = 0; k < 3; ++k) if (pw[k]->used && pw[k]->buf) PYIPM_HIP(pw[k]->fetch_err(&perr[k], ctx->stream));
     PYIPM_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->chain_used = false;
-    if (chain_err) {
-        PYIPM_HIP(hipMemsetAsync(chain_errw, 0, sizeof(unsigned), ctx->stream));
-        ctx->held.factor_invalid();
-        ctx->err = "tile chain (k_tile_chain): a poll timed out -- a workgroup of the chain did not become resident; this factorisation is invalid "
-                   "(set_option(\"tile_chain\", 0) runs one launch per tile)";
-        return PYIPM_E_HIP;
+    for (int k = 0; k < 3; ++k) pw[k]->used = false;
+    for (int k = 0; k < 3; ++k) {
+        if (!perr[k]) continue;
+        PYIPM_HIP(pw[k]->clear_err(ctx->stream));
+        if (pw[k] == &ctx->chain_words) ctx->held.factor_invalid();
+        ctx->err = pw[k]->message; return PYIPM_E_HIP;
     }
-    if (sweep_err) {
-        PYIPM_HIP(hipMemsetAsync(ctx->sweep_sync + 3 * 4096, 0, sizeof(unsigned), ctx->stream));
-        ctx->err = "backward sweep (k_bwd_sweep): a poll timed out in an earlier solve; its result was NaN"; return PYIPM_E_HIP;
-    }
-    ctx->sweep_used = false;
-    if (fwdp_err) {
-        PYIPM_HIP(hipMemsetAsync(ctx->fwdp_sync + Ctx::FWDP_ERRW, 0, sizeof(unsigned), ctx->stream));
-        ctx->err = "forward sweep over the kept panels (k_fwd_prefix): a poll timed out; the direction was NaN "
-                   "(PYIPM_FWD_PREFIX=0 runs it panel by panel)";
-        return PYIPM_E_HIP;
-    }
-    ctx->fwdp_used = false;
     if (ctx->profile) {
         // time during which SOME update launch ran: the launches of the main stream are serial, a lookahead head on the
         // side stream may overlap the bulk update that follows it -- union of the intervals, not their sum
@@ -1145,26 +1125,32 @@ int factor_end(Ctx* ctx, pyipm_factor_stats* stats) {
 static int sub_width(const Ctx* ctx, int pw) {
     return (ctx->wide_sub >= TB && ctx->wide_sub % TB == 0 && pw > ctx->wide_sub) ? ctx->wide_sub : pw;
 }
+// One sub-panel of a walk: nbw columns at global column c0 (local lc0), `below` rows under them and, where there are any, the row
+// ranges in which L of these columns can be non-zero (active_ranges).  for_sub_panels: body(SweepSub) for the sub-panels of panel p
+// at sub-width sw, first to last or last first (walk_sub, sub_walk.hpp); the first non-zero return ends the walk.
+struct SweepSub { int64_t c0, lc0; int nbw; int64_t below, a0, a1, b0, b1; };
+template <class F>
+static int for_sub_panels(const Ctx* ctx, int64_t p, int sw, bool last_first, F body) {
+    const Geo& g = ctx->g;
+    return walk_sub((int)g.panel_w(p), sw, last_first, [&](int off, int nbw) {
+        SweepSub s = {g.panel_c0(p) + off, g.local_c0(p) + off, nbw, g.Npad - (g.panel_c0(p) + off + nbw), 0, 0, 0, 0};
+        if (s.below > 0) active_ranges(ctx, s.c0, s.c0 + nbw, &s.a0, &s.a1, &s.b0, &s.b1);
+        return body(s);
+    });
+}
 int fwd_panel(Ctx* ctx, int64_t p, double* v, hipStream_t stream, int nrhs, int64_t vstride) {
     if (!stream) stream = ctx->stream;
     const Geo& g = ctx->g;
-    const int64_t pc0 = g.panel_c0(p), plc0 = g.local_c0(p);
-    const int pw = (int)g.panel_w(p), sw = sub_width(ctx, pw);
-    for (int off = 0; off < pw; off += sw) {
-    const int64_t c0 = pc0 + off, lc0 = plc0 + off;
-    const int nbw = pw - off < sw ? pw - off : sw;
-    hipLaunchKernelGGL(k_fwd_diag, dim3(1, nrhs), dim3(nbw), nbw * sizeof(double), stream, ctx->A, g.Npad, lc0, c0, nbw, v, vstride);
-    PYIPM_KCHECK();
-    const int64_t below = g.Npad - (c0 + nbw);
-    if (below > 0) {
-        int64_t a0, a1, b0, b1;
-        active_ranges(ctx, c0, c0 + nbw, &a0, &a1, &b0, &b1);
-        hipLaunchKernelGGL(k_fwd_gemv, dim3(grid1(below).x, nrhs), dim3(256), nbw * sizeof(double), stream, ctx->A, g.Npad, lc0, c0,
-                           nbw, c0 + nbw, g.Npad, v, vstride, a0, a1, b0, b1);
+    return for_sub_panels(ctx, p, sub_width(ctx, (int)g.panel_w(p)), false, [&](const SweepSub& s) {
+        hipLaunchKernelGGL(k_fwd_diag, dim3(1, nrhs), dim3(s.nbw), s.nbw * sizeof(double), stream, ctx->A, g.Npad, s.lc0, s.c0, s.nbw, v, vstride);
         PYIPM_KCHECK();
-    }
-    }
-    return 0;
+        if (s.below > 0) {
+            hipLaunchKernelGGL(k_fwd_gemv, dim3(grid1(s.below).x, nrhs), dim3(256), s.nbw * sizeof(double), stream, ctx->A, g.Npad, s.lc0, s.c0,
+                               s.nbw, s.c0 + s.nbw, g.Npad, v, vstride, s.a0, s.a1, s.b0, s.b1);
+            PYIPM_KCHECK();
+        }
+        return 0;
+    });
 }
 
 int diag_panel(Ctx* ctx, int64_t p, double* v, hipStream_t stream, int nrhs, int64_t vstride) {
@@ -1182,147 +1168,134 @@ int diag_panel(Ctx* ctx, int64_t p, double* v, hipStream_t stream, int nrhs, int
 int bwd_panel(Ctx* ctx, int64_t p, double* v, int nrhs, int64_t vstride, double* part, int64_t pstride) {
     const Geo& g = ctx->g;
     if (!part) part = ctx->partial;
-    const int64_t pc0 = g.panel_c0(p), plc0 = g.local_c0(p);
-    const int pw = (int)g.panel_w(p), sw = sub_width(ctx, pw);
-    for (int off = ((pw - 1) / sw) * sw; off >= 0; off -= sw) {        // sub-panels of a wide panel, last first (see fwd_panel)
-    const int64_t c0 = pc0 + off, lc0 = plc0 + off;
-    const int nbw = pw - off < sw ? pw - off : sw;
-    const int64_t below = g.Npad - (c0 + nbw);
-    int nchunk = 0;
-    if (below > 0) {
-        nchunk = (int)((below + ROWCHUNK - 1) / ROWCHUNK);
-        int64_t a0, a1, b0, b1;
-        active_ranges(ctx, c0, c0 + nbw, &a0, &a1, &b0, &b1);
-        hipLaunchKernelGGL(k_bwd_dot, dim3(nbw, nchunk, nrhs), dim3(256), 0, ctx->stream, ctx->A, g.Npad, lc0, g.nb,
-                           c0 + nbw, g.Npad, v, part, vstride, pstride, a0, a1, b0, b1);
+    return for_sub_panels(ctx, p, sub_width(ctx, (int)g.panel_w(p)), true, [&](const SweepSub& s) {      // last first (see fwd_panel)
+        int nchunk = 0;
+        if (s.below > 0) {
+            nchunk = (int)((s.below + ROWCHUNK - 1) / ROWCHUNK);
+            hipLaunchKernelGGL(k_bwd_dot, dim3(s.nbw, nchunk, nrhs), dim3(256), 0, ctx->stream, ctx->A, g.Npad, s.lc0, g.nb,
+                               s.c0 + s.nbw, g.Npad, v, part, vstride, pstride, s.a0, s.a1, s.b0, s.b1);
+            PYIPM_KCHECK();
+        }
+        if (s.nbw <= 4 * TB)                                // on 1024 threads through shared memory; wider panels: thread k walks down column k
+            hipLaunchKernelGGL(k_bwd_diag4, dim3(1, nrhs), dim3(1024), 0, ctx->stream, ctx->A, g.Npad, s.lc0, s.c0, s.nbw,
+                               g.nb, part, nchunk, v, vstride, pstride);
+        else
+            hipLaunchKernelGGL(k_bwd_diag, dim3(1, nrhs), dim3(s.nbw), s.nbw * sizeof(double), ctx->stream, ctx->A, g.Npad, s.lc0, s.c0, s.nbw,
+                               g.nb, part, nchunk, v, vstride, pstride);
         PYIPM_KCHECK();
-    }
-    if (nbw <= 4 * TB)                                  // on 1024 threads through shared memory; wider panels: thread k walks down column k
-        hipLaunchKernelGGL(k_bwd_diag4, dim3(1, nrhs), dim3(1024), 0, ctx->stream, ctx->A, g.Npad, lc0, c0, nbw,
-                           g.nb, part, nchunk, v, vstride, pstride);
-    else
-        hipLaunchKernelGGL(k_bwd_diag, dim3(1, nrhs), dim3(nbw), nbw * sizeof(double), ctx->stream, ctx->A, g.Npad, lc0, c0, nbw,
-                           g.nb, part, nchunk, v, vstride, pstride);
+        return 0;
+    });
+}
+
+// ---- the one-launch sweeps: k_fwd_sweep, k_bwd_sweep (solve_plain), k_fwd_prefix (a reusing step) -------------------------------
+// what the three ask of the handle and its geometry; each caller adds its own terms
+static bool sweeps_in_one_launch(const Ctx* ctx) {
+    const Geo& g = ctx->g;
+    return ctx->sweep_persist && g.world == 1 && g.nb <= 4 * TB && g.nb % TB == 0 && g.npanels >= 2 && g.npanels <= 4096 &&
+           g.Npad % 8 == 0 && g.Npad / TB <= 8192;
+}
+static SweepGeo sweep_geo(const Ctx* ctx) {
+    const Geo& g = ctx->g;
+    SweepGeo sg;
+    sg.Npad = g.Npad; sg.ld = g.Npad; sg.n = g.n; sg.mi = g.mi; sg.me = g.me; sg.nb = g.nb; sg.npanels = (int)g.npanels;
+    sg.skip = (ctx->skip_zeros && g.mi > 0) ? 1 : 0;
+    return sg;
+}
+// Every workgroup of a sweep must be resident (they wait for each other): the grid comes from an occupancy query of THIS build of
+// the kernel, not from an assumption about its registers / shared memory.  *occ: resident workgroups per CU, cached.
+// must_fit: the message of the error where none fits (NULL: the caller clamps).
+template <class K>
+static int resident_per_cu(Ctx* ctx, int* occ, K kernel, int threads, const char* must_fit) {
+    if (*occ <= 0) PYIPM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, kernel, threads, 0));
+    if (*occ < 1 && must_fit) { ctx->err = must_fit; return PYIPM_E_HIP; }
+    return 0;
+}
+// ... `want` workgroups, at most `resident` per CU, at most `cap`, at most the test hook's, at least `floor`
+static unsigned sweep_grid(const Ctx* ctx, int64_t want, int resident, int64_t floor, int64_t cap = INT64_MAX) {
+    int64_t blocks = std::min(std::min(want, (int64_t)resident * ctx->num_cus), cap);
+    if (ctx->sweep_max_blocks > 0 && blocks > ctx->sweep_max_blocks) blocks = ctx->sweep_max_blocks;      // (test hook: several chunks per owner)
+    return (unsigned)std::max(blocks, floor);
+}
+
+// forward sweep in one launch (k_fwd_sweep: workgroup 0 on the diagonal blocks, the others on their 64-row chunks), then
+// inv(T) y for all tiles at once
+static int fwd_sweep(Ctx* ctx, double* v) {
+    const Geo& g = ctx->g;
+    PollWords& sw = ctx->sweep_words;
+    PYIPM_HIP(sw.ensure(ctx->stream));
+    PYIPM_HIP(sw.arm((size_t)(g.npanels + g.Npad / TB), ctx->stream));
+    { int rc = resident_per_cu(ctx, &ctx->occ_fwd_sweep, k_fwd_sweep, 512, nullptr); if (rc) return rc; }
+    const int occ = ctx->occ_fwd_sweep < 1 ? 1 : (ctx->occ_fwd_sweep > 2 ? 2 : ctx->occ_fwd_sweep);
+    hipLaunchKernelGGL(k_fwd_sweep, dim3(sweep_grid(ctx, 1 + (g.Npad / TB - g.nb / TB), occ, 2)), dim3(512), 0, ctx->stream,
+                       ctx->A, sweep_geo(ctx), v, sw.buf.get(), sw.err(), POLL_TIMEOUT);
     PYIPM_KCHECK();
-    }
+    hipLaunchKernelGGL(k_diag_apply, dim3((unsigned)(g.Npad / TB), 1), dim3(64), 0, ctx->stream, ctx->Dinv, ctx->Tsv, ctx->Tflag,
+                       ctx->block_refine, (int64_t)0, (int64_t)0, v, (int64_t)0);
+    PYIPM_KCHECK();
+    sw.used = true;
+    return 0;
+}
+// the whole backward sweep in one launch (k_bwd_sweep): workgroup 0 on the diagonal blocks, every other wave on its columns
+static int bwd_sweep(Ctx* ctx, double* v) {
+    const Geo& g = ctx->g;
+    PollWords& sw = ctx->sweep_words;
+    PYIPM_HIP(ctx->sweep_buf.reserve((size_t)g.Npad));
+    PYIPM_HIP(sw.ensure(ctx->stream));
+    PYIPM_HIP(sw.arm((size_t)(2 * g.npanels + 4096), ctx->stream));     // flags, near counts, a progress word per owner wave
+    PYIPM_HIP(hipMemsetAsync(ctx->sweep_buf, 0xFF, (size_t)g.Npad * sizeof(double), ctx->stream));      // NaN: "not there yet"
+    const int64_t nearb = (g.nb / 8 + 15) / 16;                  // workgroups that only do the next panel's columns
+    { int rc = resident_per_cu(ctx, &ctx->occ_bwd_sweep, k_bwd_sweep, 1024, "k_bwd_sweep does not fit a compute unit"); if (rc) return rc; }
+    // one workgroup per CU by design, whatever would fit.  The cap: a progress word per owner WAVE, (blocks - 1 - nearb) x 16 of them,
+    // inside the 4096 words zeroed above (on a part with more than 257 CUs the words beyond them would keep last sweep's
+    // counts and workgroup 0 would stop waiting)
+    const unsigned blocks = sweep_grid(ctx, 1 + nearb + (g.Npad / 8 + 15) / 16, 1, 2 + nearb, 1 + nearb + 4096 / 16);
+    hipLaunchKernelGGL(k_bwd_sweep, dim3(blocks), dim3(1024), 0, ctx->stream, ctx->A, sweep_geo(ctx), v, sw.buf.get(), sw.err(),
+                       POLL_TIMEOUT, ctx->sweep_buf.get(), ctx->dbg_buf);
+    PYIPM_KCHECK();
+    sw.used = true;
     return 0;
 }
 
 // x := M^{-1} x in place for the factored matrix of the current geometry (single-rank path)
-int solve_plain(Ctx* ctx, double* v, bool forward_done, int nrhs, int64_t vstride, double* part,
-                int64_t pstride) {
+int solve_plain(Ctx* ctx, double* v, bool forward_done, int nrhs, int64_t vstride, double* part, int64_t pstride) {
     const Geo& g = ctx->g;
-    const bool one_launch = ctx->sweep_persist && nrhs == 1 && g.world == 1 && g.nb <= 4 * TB && g.nb % TB == 0 && g.npanels >= 2 &&
-                            g.npanels <= 4096 && g.Npad % 8 == 0 && g.Npad / TB <= 8192;
-    if (one_launch) {
-        PYIPM_HIP(ctx->sweep_buf.reserve((size_t)g.Npad));
-        if (!ctx->sweep_sync) {
-            PYIPM_HIP(ctx->sweep_sync.reserve(3 * 4096 + 1));
-            PYIPM_HIP(hipMemsetAsync(ctx->sweep_sync + 3 * 4096, 0, sizeof(unsigned), ctx->stream));      // the error word: sticky
-        }
-    }
-    SweepGeo sg;
-    sg.Npad = g.Npad; sg.ld = g.Npad; sg.n = g.n; sg.mi = g.mi; sg.me = g.me; sg.nb = g.nb; sg.npanels = (int)g.npanels;
-    sg.skip = (ctx->skip_zeros && g.mi > 0) ? 1 : 0;
+    const bool one_launch = sweeps_in_one_launch(ctx) && nrhs == 1;
     if (!forward_done && one_launch) {
-        // forward sweep in one launch (k_fwd_sweep: workgroup 0 on the diagonal blocks, the others on their 64-row chunks),
-        // then inv(T) y for all tiles at once
-        const int P = (int)g.npanels;
-        PYIPM_HIP(hipMemsetAsync(ctx->sweep_sync, 0, (size_t)(P + g.Npad / TB) * sizeof(unsigned), ctx->stream));
-        int64_t blocks = 1 + (g.Npad / TB - g.nb / TB);
-        // every workgroup of a sweep must be resident (they wait for each other): the grid comes from an occupancy query of
-        // THIS build of the kernel, not from an assumption about its registers / shared memory
-        if (ctx->occ_fwd_sweep <= 0) {
-            int occ = 0;
-            PYIPM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_fwd_sweep, 512, 0));
-            ctx->occ_fwd_sweep = occ < 1 ? 1 : (occ > 2 ? 2 : occ);
-        }
-        if (blocks > (int64_t)ctx->occ_fwd_sweep * ctx->num_cus) blocks = (int64_t)ctx->occ_fwd_sweep * ctx->num_cus;
-        if (ctx->sweep_max_blocks > 0 && blocks > ctx->sweep_max_blocks) blocks = ctx->sweep_max_blocks;      // (test hook: several chunks per owner)
-        if (blocks < 2) blocks = 2;
-        hipLaunchKernelGGL(k_fwd_sweep, dim3((unsigned)blocks), dim3(512), 0, ctx->stream, ctx->A, sg, v, ctx->sweep_sync,
-                           ctx->sweep_sync + 3 * 4096, (unsigned long long)2.0e8);
-        PYIPM_KCHECK();
-        hipLaunchKernelGGL(k_diag_apply, dim3((unsigned)(g.Npad / TB), 1), dim3(64), 0, ctx->stream, ctx->Dinv, ctx->Tsv, ctx->Tflag,
-                           ctx->block_refine, (int64_t)0, (int64_t)0, v, (int64_t)0);
-        PYIPM_KCHECK();
-        ctx->sweep_used = true;
+        int rc = fwd_sweep(ctx, v); if (rc) return rc;
     } else if (!forward_done) {
         for (int64_t p = 0; p < g.npanels; ++p) { int rc = fwd_panel(ctx, p, v, nullptr, nrhs, vstride); if (rc) return rc; }
         for (int64_t p = 0; p < g.npanels; ++p) { int rc = diag_panel(ctx, p, v, nullptr, nrhs, vstride); if (rc) return rc; }
     }
-    if (one_launch) {
-        // the whole backward sweep in one launch (k_bwd_sweep): workgroup 0 on the diagonal blocks, every other wave on its columns
-        const int P = (int)g.npanels;
-        PYIPM_HIP(hipMemsetAsync(ctx->sweep_sync, 0, (size_t)(2 * P + 4096) * sizeof(unsigned), ctx->stream));     // flags, near counts, a progress word per owner wave
-        PYIPM_HIP(hipMemsetAsync(ctx->sweep_buf, 0xFF, (size_t)g.Npad * sizeof(double), ctx->stream));      // NaN: "not there yet"
-        const int64_t groups = g.Npad / 8;
-        const int64_t nearb = (g.nb / 8 + 15) / 16;                  // workgroups that only do the next panel's columns
-        int64_t blocks = 1 + nearb + (groups + 15) / 16;
-        if (ctx->occ_bwd_sweep <= 0) {
-            int occ = 0;
-            PYIPM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_bwd_sweep, 1024, 0));
-            if (occ < 1) { ctx->err = "k_bwd_sweep does not fit a compute unit"; return PYIPM_E_HIP; }
-            ctx->occ_bwd_sweep = 1;                                  // (one workgroup per CU by design, whatever would fit)
-        }
-        if (blocks > ctx->num_cus) blocks = ctx->num_cus;
-        // a progress word per owner WAVE, (blocks - 1 - nearb) x 16 of them, inside the 4096 words zeroed above (on a part
-        // with more than 257 CUs the words beyond them would keep last sweep's counts and workgroup 0 would stop waiting)
-        if ((blocks - 1 - nearb) * 16 > 4096) blocks = 1 + nearb + 4096 / 16;
-        if (ctx->sweep_max_blocks > 0 && blocks > ctx->sweep_max_blocks) blocks = ctx->sweep_max_blocks;
-        if (blocks < 2 + nearb) blocks = 2 + nearb;
-        hipLaunchKernelGGL(k_bwd_sweep, dim3((unsigned)blocks), dim3(1024), 0, ctx->stream, ctx->A, sg, v, ctx->sweep_sync,
-                           ctx->sweep_sync + 3 * 4096, (unsigned long long)2.0e8, ctx->sweep_buf, ctx->dbg_buf);                       // polls give up after 2 s (100 MHz clock)
-        PYIPM_KCHECK();
-        ctx->sweep_used = true;
-        return 0;
-    }
+    if (one_launch) return bwd_sweep(ctx, v);
     for (int64_t p = g.npanels - 1; p >= 0; --p) { int rc = bwd_panel(ctx, p, v, nrhs, vstride, part, pstride); if (rc) return rc; }
     return 0;
 }
 
 // The forward substitution of a reusing step through the kept panels [0, P0) (k_fwd_prefix + one k_diag_apply over their tiles) on
 // `stream`, in place of P0 x (k_fwd_diag, k_fwd_gemv, k_diag_apply): the same bits.  Applies where solve_plain's one-launch sweeps
-// do; the caller keeps the per-panel loop otherwise.  The sync words are this launch's own (the main stream's sweeps use
-// ctx->sweep_sync, and a solve may still be running there): flags, a progress word per chunk -- zeroed on the same stream in front
-// of every launch -- and the error word behind them, zeroed once on that stream and sticky (factor_end reads it).
+// do; the caller keeps the per-panel loop otherwise.  The words are this launch's own (a solve may still be running on the main
+// stream with ctx->sweep_words): flags and a progress word per chunk, zeroed on the same stream in front of every launch.
 static bool fwd_prefix_applies(const Ctx* ctx, int64_t P0) {
     const Geo& g = ctx->g;
-    return ctx->fwd_prefix && ctx->sweep_persist && P0 >= 1 && g.world == 1 && g.nb <= 4 * TB && g.nb % (2 * TB) == 0 && g.npanels >= 2 &&
-           g.npanels <= 4096 && g.Npad % 8 == 0 && g.Npad / TB <= 8192 && sub_width(ctx, (int)g.nb) == (int)g.nb &&
+    return ctx->fwd_prefix && sweeps_in_one_launch(ctx) && P0 >= 1 && g.nb % (2 * TB) == 0 && sub_width(ctx, (int)g.nb) == (int)g.nb &&
            P0 * g.nb <= g.n;
 }
 static int fwd_prefix(Ctx* ctx, int64_t P0, double* v, hipStream_t stream) {
     const Geo& g = ctx->g;
-    if (!ctx->fwdp_sync) {
-        PYIPM_HIP(ctx->fwdp_sync.reserve(Ctx::FWDP_ERRW + 1));
-        PYIPM_HIP(hipMemsetAsync(ctx->fwdp_sync + Ctx::FWDP_ERRW, 0, sizeof(unsigned), stream));
-    }
-    SweepGeo sg;
-    sg.Npad = g.Npad; sg.ld = g.Npad; sg.n = g.n; sg.mi = g.mi; sg.me = g.me; sg.nb = g.nb; sg.npanels = (int)g.npanels;
-    sg.skip = (ctx->skip_zeros && g.mi > 0) ? 1 : 0;
+    PollWords& fw = ctx->fwdp_words;
     const int64_t nchunks = g.Npad / TB;
-    PYIPM_HIP(hipMemsetAsync(ctx->fwdp_sync, 0, (size_t)(P0 + nchunks) * sizeof(unsigned), stream));
-    // every workgroup must be resident (they wait for each other): at most what an occupancy query of THIS build says the GPU holds;
-    // and a guest beside the factorisation, whose chains and heads run meanwhile: fwd_prefix_wgs workgroups (profiles/fwd_prefix_resident_ab.json)
-    if (ctx->occ_fwd_prefix <= 0) {
-        int occ = 0;
-        PYIPM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_fwd_prefix, 256, 0));
-        if (occ < 1) { ctx->err = "k_fwd_prefix does not fit a compute unit"; return PYIPM_E_HIP; }
-        ctx->occ_fwd_prefix = occ;
-    }
-    int64_t blocks = 1 + (nchunks - g.nb / TB);
-    if (blocks > (int64_t)ctx->occ_fwd_prefix * ctx->num_cus) blocks = (int64_t)ctx->occ_fwd_prefix * ctx->num_cus;
-    if (blocks > ctx->fwd_prefix_wgs) blocks = ctx->fwd_prefix_wgs;
-    if (ctx->sweep_max_blocks > 0 && blocks > ctx->sweep_max_blocks) blocks = ctx->sweep_max_blocks;      // (test hook: several chunks per owner)
-    if (blocks < 2) blocks = 2;
-    hipLaunchKernelGGL(k_fwd_prefix, dim3((unsigned)blocks), dim3(256), 0, stream, ctx->A, sg, (int)P0, v, ctx->fwdp_sync,
-                       ctx->fwdp_sync + Ctx::FWDP_ERRW, (unsigned long long)2.0e8);                               // polls give up after 2 s (100 MHz clock)
+    PYIPM_HIP(fw.ensure(stream));
+    PYIPM_HIP(fw.arm((size_t)(P0 + nchunks), stream));
+    { int rc = resident_per_cu(ctx, &ctx->occ_fwd_prefix, k_fwd_prefix, 256, "k_fwd_prefix does not fit a compute unit"); if (rc) return rc; }
+    // a guest beside the factorisation, whose chains and heads run meanwhile: fwd_prefix_wgs workgroups (profiles/fwd_prefix_resident_ab.json)
+    const unsigned blocks = sweep_grid(ctx, 1 + (nchunks - g.nb / TB), ctx->occ_fwd_prefix, 2, ctx->fwd_prefix_wgs);
+    hipLaunchKernelGGL(k_fwd_prefix, dim3(blocks), dim3(256), 0, stream, ctx->A, sweep_geo(ctx), (int)P0, v, fw.buf.get(), fw.err(),
+                       POLL_TIMEOUT);
     PYIPM_KCHECK();
     hipLaunchKernelGGL(k_diag_apply, dim3((unsigned)(P0 * g.nb / TB), 1), dim3(64), 0, stream, ctx->Dinv, ctx->Tsv, ctx->Tflag,
                        ctx->block_refine, (int64_t)0, (int64_t)0, v, (int64_t)0);
     PYIPM_KCHECK();
-    ctx->fwdp_used = true;
+    fw.used = true;
     return 0;
 }
 
@@ -1383,52 +1356,44 @@ int solve_inplace(Ctx* ctx, double* v, bool forward_done) {
 int solve_many_plain(Ctx* ctx, double* V, int64_t ldv, int64_t kpad, double* part) {
     const Geo& g = ctx->g;
     const hipStream_t st = ctx->stream;
-    auto ms_width = [&](int pw) { return std::min(sub_width(ctx, pw), (int)MS_SUBW); };     // (the in-panel kernels' limit)
+    auto ms_width = [&](int64_t p) { return std::min(sub_width(ctx, (int)g.panel_w(p)), (int)MS_SUBW); };     // (the in-panel kernels' limit)
     for (int64_t p = 0; p < g.npanels; ++p) {
-        const int pw = (int)g.panel_w(p), sw = ms_width(pw);
-        for (int off = 0; off < pw; off += sw) {
-            const int64_t c0 = g.panel_c0(p) + off, lc0 = g.local_c0(p) + off;
-            const int nbw = pw - off < sw ? pw - off : sw;
+        int rc = for_sub_panels(ctx, p, ms_width(p), false, [&](const SweepSub& s) {
             hipLaunchKernelGGL(k_ms_fwd_diag, dim3((unsigned)(kpad / MS_CW)), dim3(512), 0, st,
-                               ctx->A, g.Npad, lc0, c0, nbw, V, ldv);
+                               ctx->A, g.Npad, s.lc0, s.c0, s.nbw, V, ldv);
             PYIPM_KCHECK();
-            const int64_t below = g.Npad - (c0 + nbw);
-            if (below > 0) {
-                int64_t a0, a1, b0, b1;
-                active_ranges(ctx, c0, c0 + nbw, &a0, &a1, &b0, &b1);
-                hipLaunchKernelGGL(k_ms_fwd_gemm, dim3((unsigned)(kpad / MS_KB), (unsigned)(below / TB)), dim3(256), 0, st,
-                                   ctx->A, g.Npad, lc0, c0, nbw, c0 + nbw, V, ldv, a0, a1, b0, b1);
+            if (s.below > 0) {
+                hipLaunchKernelGGL(k_ms_fwd_gemm, dim3((unsigned)(kpad / MS_KB), (unsigned)(s.below / TB)), dim3(256), 0, st,
+                                   ctx->A, g.Npad, s.lc0, s.c0, s.nbw, s.c0 + s.nbw, V, ldv, s.a0, s.a1, s.b0, s.b1);
                 PYIPM_KCHECK();
             }
-        }
+            return 0;
+        });
+        if (rc) return rc;
     }
     hipLaunchKernelGGL(k_ms_diag, dim3((unsigned)(kpad / MS_CW), (unsigned)(g.Npad / TB)), dim3(256), 0, st, ctx->Dinv, ctx->Tsv,
                        ctx->Tflag, ctx->block_refine, V, ldv);
     PYIPM_KCHECK();
     for (int64_t p = g.npanels - 1; p >= 0; --p) {
-        const int pw = (int)g.panel_w(p), sw = ms_width(pw);
-        for (int off = ((pw - 1) / sw) * sw; off >= 0; off -= sw) {
-            const int64_t c0 = g.panel_c0(p) + off, lc0 = g.local_c0(p) + off;
-            const int nbw = pw - off < sw ? pw - off : sw;
-            const int64_t below = g.Npad - (c0 + nbw);
+        int rc = for_sub_panels(ctx, p, ms_width(p), true, [&](const SweepSub& s) {
             const double* sums = nullptr;
-            if (below > 0) {
-                const int nchunk = (int)((below + MS_RCH - 1) / MS_RCH);
-                int64_t a0, a1, b0, b1;
-                active_ranges(ctx, c0, c0 + nbw, &a0, &a1, &b0, &b1);
-                hipLaunchKernelGGL(k_ms_bwd_part, dim3((unsigned)(kpad / MS_KB), (unsigned)(nbw / TB), (unsigned)nchunk), dim3(256), 0, st,
-                                   ctx->A, g.Npad, lc0, nbw, c0 + nbw, g.Npad, V, ldv, part, kpad, a0, a1, b0, b1);
+            if (s.below > 0) {
+                const int nchunk = (int)((s.below + MS_RCH - 1) / MS_RCH);
+                hipLaunchKernelGGL(k_ms_bwd_part, dim3((unsigned)(kpad / MS_KB), (unsigned)(s.nbw / TB), (unsigned)nchunk), dim3(256), 0, st,
+                                   ctx->A, g.Npad, s.lc0, s.nbw, s.c0 + s.nbw, g.Npad, V, ldv, part, kpad, s.a0, s.a1, s.b0, s.b1);
                 PYIPM_KCHECK();
-                const int64_t nelem = kpad * nbw;
+                const int64_t nelem = kpad * s.nbw;
                 double* red = part + (size_t)nchunk * (size_t)nelem;
                 hipLaunchKernelGGL(k_ms_bwd_reduce, dim3((unsigned)(nelem / 64)), dim3(256), 0, st, part, nchunk, nelem, red);
                 PYIPM_KCHECK();
                 sums = red;
             }
             hipLaunchKernelGGL(k_ms_bwd_diag, dim3((unsigned)(kpad / MS_CW)), dim3(512), 0, st,
-                               ctx->A, g.Npad, lc0, c0, nbw, sums, V, ldv);
+                               ctx->A, g.Npad, s.lc0, s.c0, s.nbw, sums, V, ldv);
             PYIPM_KCHECK();
-        }
+            return 0;
+        });
+        if (rc) return rc;
     }
     return 0;
 }

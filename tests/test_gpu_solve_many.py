@@ -79,6 +79,21 @@ def test_columns_match_x_true_and_solve(shape):
     core.close()
 
 
+def test_ragged_last_sub_panel_of_a_wide_panel():
+    """nb = 384 at wide_sub = 256: every panel is swept as sub-panels of 256 + 128 columns, forward and last first, by the
+    per-panel sweeps of solve (sweep_persist = 0) and by solve_many.  N = 768: two such panels."""
+    m = Manufactured(448, 64, 128, seed=7)
+    core, _ = _factored(m, nb=384, wide_sub=256, sweep_persist=0)
+    X, B = _rhs(m, 3)
+    x0 = core.solve(B[:, 0], flip=False).cpu().numpy()
+    assert _colerr(x0[:, None], X[:, :1])[0] <= 1e-10
+    Xs = core.solve_many(B, flip=False).cpu().numpy()
+    assert Xs.shape == (m.N, 3)
+    assert _colerr(Xs, X).max() <= 1e-10
+    assert _colerr(Xs[:, :1], x0[:, None])[0] <= 1e-12
+    core.close()
+
+
 def test_flip_negates_exactly_the_multiplier_rows():
     m = Manufactured(403, 57, 99, seed=5)
     core, _ = _factored(m)
