@@ -434,6 +434,38 @@ int pyipm_newton_step_batched_each(pyipm_newton_ctx* ctx, const double* mu, cons
  * alpha: [batch][2], host or device per memkind (host: synchronises).  Needs stage_vectors. */
 int pyipm_newton_step_lengths_batched(pyipm_newton_ctx* ctx, double tau, const double* dz, double* alpha, int memkind);
 
+/* The batch as a solver: what a line search and a barrier loop over the whole batch need between two steps, per problem and
+ * without leaving the device -- the batched counterparts of block_products / _t, merit_info and merit_ray above.  Plain
+ * launches, one workgroup or one wave per problem; every sum runs over a fixed partition in a fixed order given by the
+ * problem's sizes alone, so the bits of problem b depend neither on the batch size nor on b's place in the batch, and those of
+ * one ray value neither on K nor on the value's place in the call.
+ * PYIPM_E_BADARG for all four: not a batched handle, what the entry reads (blocks; vectors) not staged, a required pointer NULL.
+ *
+ * block_products_batched -- the provider of the QP family (pyipm.py:855-954: df = Qx + c, ce = Ax - b, ci = Gx - h) for every
+ *   problem: Qv[b] = sym(triu(d2L_b)) v_b (n), JeTv[b] = Je_b' v_b (me), JiTv[b] = Ji_b' v_b (mi) from the staged blocks, ONE
+ *   pass over each block (only the UPPER triangle of d2L is read).  v: [batch][n]; any output may be NULL.  DEVICE pointers.
+ * block_products_t_batched -- the J lambda terms of self.grad (pyipm.py:655-668): out[b] = Je_b le_b + Ji_b li_b (n);
+ *   le [batch][me] / li [batch][mi], either may be NULL.  DEVICE pointers.
+ * Both return once their launch is enqueued on the handle's stream. */
+int pyipm_newton_block_products_batched(pyipm_newton_ctx* ctx, const double* v, double* Qv, double* JeTv, double* JiTv);
+int pyipm_newton_block_products_t_batched(pyipm_newton_ctx* ctx, const double* le, const double* li, double* out);
+/* merit_info_batched -- out[b][16] = the quantities of pyipm_newton_merit_info for problem b over the staged vectors
+ *   ([batch][len]) and the directions dz: the host passes of phi / dphi (pyipm.py:670-721), the merit-parameter update
+ *   (:1727-1735), the KKT report (:958-991) and the barrier update (:1804-1814), for the whole batch in one launch.
+ *   dz: DEVICE [batch][N], multiplier block sign-flipped as the steps return it; NULL = the directions of the last step where
+ *   the handle keeps them (a step with host output), else none: entries 2, 3, 11, 12 are NaN.  Entries 5 and 6 come from the
+ *   residual g = -grad the last step left (each problem's with its own mu of that step): NaN before any step since
+ *   stage_vectors.  Entry 10 is NaN when mi == 0.  out: host (synchronises) or device (asynchronous) per memkind.
+ * merit_ray_batched -- out[b][k] = phi_b(x + a dx, s + a ds) - phi_b(x, s) for a = alphas[b][k], K <= 1024 candidates per problem
+ *   in one launch (pyipm.py:1534-1548: every backtracking candidate alpha tau^k of every problem's search), term by term as
+ *   pyipm_newton_merit_ray, with each problem's own nu[b], mu[b].  g1 = df . dx, g2 = dx' Q dx, Je' dx, Ji' dx are formed from the
+ *   staged blocks for every call (nothing of a direction is kept); quad != NULL: quad[b] is taken for g2 and d2L is not read.
+ *   dz as above, but required (NULL without kept directions: PYIPM_E_BADARG).  nu, mu, quad: [batch]; alphas, out:
+ *   [batch][K]; all five host or device per memkind (host: staged, synchronises).  PYIPM_E_BADARG also for K < 1 or K > 1024. */
+int pyipm_newton_merit_info_batched(pyipm_newton_ctx* ctx, const double* dz, double* out, int memkind);
+int pyipm_newton_merit_ray_batched(pyipm_newton_ctx* ctx, const double* dz, const double* nu, const double* mu, const double* quad,
+                                   const double* alphas, int K, double* out, int memkind);
+
 /* ---- introspection for tests / bench ------------------------------------------------------ */
 
 /* Device pointer + leading dimension of the local KKT storage (column-major lower).  The caller may write through the
@@ -550,8 +582,9 @@ int pyipm_newton_set_option(pyipm_newton_ctx* ctx, const char* name, double valu
  * pyipm_newton_step_lengths in place: a caller built against the older header would have passed a host pointer where the
  * device direction goes).  A binding checks pyipm_newton_abi_version() == PYIPM_NEWTON_ABI_VERSION of the header it was
  * written against before any other call (pyipm_amd/newton.py does).  7: step_batched_each, step_lengths_batched; the
- * workspace of a batched handle grew by the per-problem parameters. */
-#define PYIPM_NEWTON_ABI_VERSION 7
+ * workspace of a batched handle grew by the per-problem parameters.  8: block_products_batched, block_products_t_batched,
+ * merit_info_batched, merit_ray_batched. */
+#define PYIPM_NEWTON_ABI_VERSION 8
 int pyipm_newton_abi_version(void);
 
 /* fp64 MFMA peak micro-benchmark: register-resident v_mfma_f64_16x16x4_f64 only.

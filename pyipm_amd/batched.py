@@ -214,6 +214,77 @@ class BatchedNewton(object):
         self._ck(self.lib.pyipm_newton_step_lengths_batched(self.h, float(tau), ptr(dz), ptr(al), MEM_DEVICE))
         return al
 
+    # -- the provider's products and the merit pieces of every problem (pyipm_newton_*_batched; device tensors in and out) -----
+    def _staged_handle(self, who):
+        if self.h is None:
+            raise NewtonError("%s: stage a batch first (stage / step_all)" % who)
+        self._ck(self.lib.pyipm_newton_set_stream(self.h, c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)))
+
+    def _direction(self, dz, who):
+        if dz is None:
+            dz = self._last_out
+            if dz is None:
+                raise NewtonError("%s: no direction (step first, or pass dz)" % who)
+        return to_device(dz, self.device, (self.batch, self.N))
+
+    def products_all(self, v, want=(True, True, True)):
+        """(Q_b v_b, Je_b' v_b, Ji_b' v_b) of every problem for v (B, n), from the staged blocks in one launch
+        (``pyipm_newton_block_products_batched``): device tensors (B, n), (B, me), (B, mi); entries not wanted (or of an empty
+        block) are None."""
+        self._staged_handle("products_all")
+        t, B = self.torch, self.batch
+        v = to_device(v, self.device, (B, self.n))
+        mk = lambda k, on: t.empty((B, k), dtype=t.float64, device=self.device) if (on and k) else None    # noqa: E731
+        q, e, i = mk(self.n, want[0]), mk(self.me, want[1]), mk(self.mi, want[2])
+        self._ck(self.lib.pyipm_newton_block_products_batched(self.h, ptr(v), ptr(q), ptr(e), ptr(i)))
+        return q, e, i
+
+    def products_t_all(self, le=None, li=None):
+        """Je_b le_b + Ji_b li_b (B, n) of every problem (``pyipm_newton_block_products_t_batched``); le (B, me) / li (B, mi),
+        either may be None."""
+        self._staged_handle("products_t_all")
+        t, B = self.torch, self.batch
+        le = to_device(le, self.device, (B, self.me)) if (le is not None and self.me) else None
+        li = to_device(li, self.device, (B, self.mi)) if (li is not None and self.mi) else None
+        out = t.empty((B, self.n), dtype=t.float64, device=self.device)
+        self._ck(self.lib.pyipm_newton_block_products_t_batched(self.h, ptr(le), ptr(li), ptr(out)))
+        return out
+
+    MERIT_KEYS = ("ce_l1", "cis_l1", "df_dx", "ds_over_s", "sum_log_s", "kkt_x", "kkt_s", "kkt_ce", "kkt_ci", "comp_sum",
+                  "comp_min", "dx_norm", "ds_norm")              # columns 0 .. 12 of merit_info_all (NewtonCore.MERIT_KEYS)
+
+    def merit_info_all(self, dz=None, use_last=True):
+        """The 16 quantities of ``NewtonCore.merit_info`` for every problem (``pyipm_newton_merit_info_batched``): device tensor
+        (B, 16), columns as MERIT_KEYS.  ``dz`` (B, N): the directions; None = what the last step returned, or none at all
+        (``use_last=False``, or no step yet): the direction columns are NaN."""
+        self._staged_handle("merit_info_all")
+        if dz is None and use_last:
+            dz = self._last_out
+        if dz is not None:
+            dz = to_device(dz, self.device, (self.batch, self.N))
+        out = self.torch.empty((self.batch, 16), dtype=self.torch.float64, device=self.device)
+        self._ck(self.lib.pyipm_newton_merit_info_batched(self.h, ptr(dz), ptr(out), MEM_DEVICE))
+        return out
+
+    def merit_ray_all(self, alphas, nu, mu, dz=None, quad=None):
+        """phi_b(x + a dx, s + a ds) - phi_b(x, s) for every a in ``alphas[b]`` ((B, K), K <= 1024) with each problem's own
+        ``nu``, ``mu`` (scalars or (B,)): device tensor (B, K) (``pyipm_newton_merit_ray_batched``: one launch for every
+        candidate of every problem).  ``dz``: None = what the last step returned; ``quad`` (B,): dx'Q dx given by the caller."""
+        self._staged_handle("merit_ray_all")
+        t, B = self.torch, self.batch
+        dz = self._direction(dz, "merit_ray_all")
+        alphas = to_device(alphas, self.device)
+        if alphas.dim() != 2 or alphas.shape[0] != B:
+            raise NewtonError("merit_ray_all: alphas must be (B, K)")
+        alphas = alphas.to(t.float64).contiguous()
+        K = int(alphas.shape[1])
+        pn, pm = self._per_problem(nu, t.float64), self._per_problem(mu, t.float64)
+        pq = None if quad is None else self._per_problem(quad, t.float64)
+        out = t.empty((B, K), dtype=t.float64, device=self.device)
+        self._ck(self.lib.pyipm_newton_merit_ray_batched(self.h, ptr(dz), ptr(pn), ptr(pm), ptr(pq), ptr(alphas), K, ptr(out),
+                                                         MEM_DEVICE))
+        return out
+
     n_factor = 0                           # passes over the batch (direction_all)
     n_inertia_retries = 0                  # problem x shifted pass whose inertia was still wrong (delta *= 10, pyipm.py:1399-1403)
     _shift_info = None
@@ -225,7 +296,7 @@ class BatchedNewton(object):
         return self._shift_info
 
     def direction_all(self, d2L, Je, Ji, df, ce, ci, s, lda, mu, delta=0.0, eta=1e-4, beta=0.4, reg_coef=None, delta0=None,
-                      max_shift_tries=60):
+                      max_shift_tries=60, active=None):
         """``reghess`` + solve (pyipm.py:1373-1406, 1717-1725) per problem of the batch, in the order ``HipNewtonBackend.direction``
         uses; ``mu`` and ``delta`` (the delta each problem persists from its last call) are scalars or (B,).
         Pass 1: no shifts, every problem.  A problem fails when its inertia is wrong (n_neg != me + mi), a NaN / Inf was met, or
@@ -234,6 +305,8 @@ class BatchedNewton(object):
         me > 0) and delta0 / max(delta / 2, delta0), and are stepped again ALONE (``active``) with delta *= 10 until their
         inertia is right; the others keep the bits of pass 1.  With ``condensed`` pass 1 is condensed, a problem that misses
         the guard fails too, and the retry passes run in the full form.
+        ``active`` ((B,) flags; None = all): only these problems take part -- the others sit every pass out (their rows of dz
+        are NaN, their statistics those of their last step, their delta unchanged).
         Returns (dz, delta (B,) float64, list of statistics): delta as the reference persists it, unchanged without a shift."""
         torch = self.torch
         me, mi, need = self.me, self.mi, self.me + self.mi
@@ -244,7 +317,8 @@ class BatchedNewton(object):
         mu_v = np.broadcast_to(np.asarray(mu, dtype=np.float64), (B,)).copy()
         delta_v = np.broadcast_to(np.asarray(delta, dtype=np.float64), (B,)).copy()
         dc_v, zero = np.zeros(B), np.zeros(B)
-        out, st = self.step_each(mu_v, zero, zero)
+        part = np.ones(B, dtype=bool) if active is None else np.asarray(active).astype(bool).reshape(B)
+        out, st = self.step_each(mu_v, zero, zero, None if active is None else part.astype(np.int32))
         self.n_factor += 1
         stats = list(st)
 
@@ -260,6 +334,7 @@ class BatchedNewton(object):
         if cond and self.guard:
             be = self.last_backward_errors = self.backward_errors(out)
             failed |= ((be > self.condensed_tol) | ~torch.isfinite(be)).cpu().numpy()
+        failed &= part
         passes = np.zeros(B, dtype=np.int64)
         fail = np.flatnonzero(failed)
         for b in fail:

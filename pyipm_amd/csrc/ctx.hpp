@@ -292,6 +292,8 @@ struct Ctx {
     // of step_batched_each land before that launch ([3][batch] doubles, [batch] flags); b_alpha: staging of host step lengths
     double *b_mu = nullptr, *b_delta = nullptr, *b_delta_c = nullptr, *b_in = nullptr, *b_alpha = nullptr;
     int *b_act = nullptr, *b_in_act = nullptr;
+    DevBuf<double> b_merit_buf;           // merit pieces of a batched handle (outside the workspace, allocated on first use, grown on demand):
+                                          // [info B x 16 | gq B x 2 | dce B x me | dci B x mi | nu, mu, quad B each | alphas B x K | ray out B x K]
     int device = 0;
     hipStream_t stream = nullptr;         // the caller's: not owned
     Stream side;                          // panel lookahead stream (created on first factor)

@@ -11,6 +11,7 @@
 #include "ctx.hpp"
 #include "kernels_assemble.hpp"
 #include "kernels_factor.hpp"
+#include "kernels_merit.hpp"
 
 namespace pyipm {
 
@@ -862,6 +863,233 @@ __global__ __launch_bounds__(256) void k_b_step_lengths(double* __restrict__ out
         al = fmin(al, __shfl_xor(al, off, 64));
     }
     if (lane == 0) { out[2 * b] = as; out[2 * b + 1] = al; }
+}
+
+// ---- the batch as a solver: the provider's products and the merit pieces of every problem ----------------
+// Plain launches, one workgroup (products) or one wave (reductions) per problem: no waits, polls or atomics between
+// workgroups.  Every sum runs over a fixed partition in a fixed order that depends on the problem's sizes alone, so the bits
+// of problem b depend neither on the batch size nor on b's place in the batch, and those of one ray value neither on K nor on
+// the value's place in the call.
+
+// All-lanes minimum of a wave (no order to fix: a minimum is exact).
+__device__ __forceinline__ double wave_min(double v) {
+    #pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+// One problem's products with its blocks, by its workgroup of 256 threads:  sym(triu(d2L)) v  (qv: n),  Je' v  (ev: me),
+// Ji' v  (iv: mi); a NULL output is not formed and its block not read.  ONE pass over the row-major rows, every entry read
+// once and coalesced: wave w takes the rows j = w, w + 4, ...; of row j of d2L it reads the part i >= j -- the row part
+// sum_i H[j][i] v[i] crosses the wave by shuffles, the mirrored part H[j][i] v[j] (i > j) is added to the wave's own
+// accumulator of column i in shared memory (one lane per column, rows in ascending order), and the rows of Je / Ji feed their
+// column accumulators the same way.  Then column c = its row part + the four waves' accumulators in the order (0 + 1) + (2 + 3).
+// gq != NULL (the ray's preparation): qv is not stored; gq[0] = df . v and gq[1] = v' Q v are (quad != NULL: gq[1] = *quad).
+// Dynamic shared memory: (2 n + 4 (n + me + mi)) doubles <= 48 KB (n + me + mi <= 1023).
+__device__ __forceinline__ void b_products_problem(const BatchPtrs& bp, const Geo& g, int64_t b, const double* __restrict__ vb,
+                                                   double* __restrict__ qv, double* __restrict__ ev, double* __restrict__ iv,
+                                                   double* __restrict__ gq, const double* __restrict__ dfb, const double* __restrict__ quad,
+                                                   double* lds)
+{
+    __shared__ double red[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool want_q = qv != nullptr || (gq != nullptr && quad == nullptr);
+    const int64_t n = g.n, nq = want_q ? n : 0, me = ev ? g.me : 0, mi = iv ? g.mi : 0, W = nq + me + mi;
+    double* vs = lds;                       // v of this problem
+    double* rowp = vs + n;                  // row parts of Q v
+    double* col = rowp + n;                 // [4][W]: per wave [Q columns | Je columns | Ji columns]
+    for (int64_t i = tid; i < n; i += 256) vs[i] = vb[i];
+    for (int64_t i = tid; i < 4 * W; i += 256) col[i] = 0.0;
+    __syncthreads();
+    double* mine = col + wave * W;
+    const double* H = want_q ? bp.d2L + b * bp.sH : nullptr;
+    const double* Je = me ? bp.Je + b * bp.sJe : nullptr;
+    const double* Ji = mi ? bp.Ji + b * bp.sJi : nullptr;
+    for (int64_t j = wave; j < n; j += 4) {
+        const double vj = vs[j];
+        if (want_q) {
+            const double* r = H + j * bp.ldh;
+            double acc = 0.0;
+            #pragma unroll 4
+            for (int64_t i = (j & ~(int64_t)63) + lane; i < n; i += 64) {
+                if (i < j) continue;
+                const double h = r[i];
+                acc = fma(h, vs[i], acc);
+                if (i > j) mine[i] = fma(h, vj, mine[i]);
+            }
+            acc = wave_sum(acc);
+            if (lane == 0) rowp[j] = acc;
+        }
+        if (me) {
+            const double* r = Je + j * bp.ldje;
+            #pragma unroll 4
+            for (int64_t a = lane; a < me; a += 64) mine[nq + a] = fma(r[a], vj, mine[nq + a]);
+        }
+        if (mi) {
+            const double* r = Ji + j * bp.ldji;
+            #pragma unroll 4
+            for (int64_t a = lane; a < mi; a += 64) mine[nq + me + a] = fma(r[a], vj, mine[nq + me + a]);
+        }
+    }
+    __syncthreads();
+    double g1 = 0.0, g2 = 0.0;
+    for (int64_t c = tid; c < W; c += 256) {
+        const double t = (col[c] + col[W + c]) + (col[2 * W + c] + col[3 * W + c]);
+        if (c < nq) {
+            const double q = rowp[c] + t;
+            if (qv) qv[c] = q;
+            if (gq) g2 = fma(vs[c], q, g2);
+        }
+        else if (c < nq + me) ev[c - nq] = t;
+        else iv[c - nq - me] = t;
+    }
+    if (gq) {
+        for (int64_t i = tid; i < n; i += 256) g1 = fma(dfb[i], vs[i], g1);
+        g1 = merit_block_sum(g1, red);
+        g2 = merit_block_sum(g2, red);
+        if (tid == 0) { gq[0] = g1; gq[1] = quad ? *quad : g2; }
+    }
+}
+
+// (Q v, Je' v, Ji' v) of every problem: grid B, 256 threads.  v: [B][n]; outputs [B][n], [B][me], [B][mi], any of them NULL.
+__global__ __launch_bounds__(256) void k_b_products(BatchPtrs bp, Geo g, const double* __restrict__ v, double* __restrict__ Qv,
+                                                    double* __restrict__ JeTv, double* __restrict__ JiTv)
+{
+    extern __shared__ double lds[];
+    const int64_t b = blockIdx.x;
+    b_products_problem(bp, g, b, v + b * g.n, Qv ? Qv + b * g.n : nullptr, (JeTv && g.me) ? JeTv + b * g.me : nullptr,
+                       (JiTv && g.mi) ? JiTv + b * g.mi : nullptr, nullptr, nullptr, nullptr, lds);
+}
+
+// out_b = Je_b le_b + Ji_b li_b (n) of every problem; le [B][me] / li [B][mi], either may be NULL.  grid B, 256 threads: a wave
+// takes four rows per trip (their loads in flight together, as k_bc_prep), the lanes stride along the row-major rows.
+__global__ __launch_bounds__(256) void k_b_products_t(BatchPtrs bp, Geo g, const double* __restrict__ le, const double* __restrict__ li,
+                                                      double* __restrict__ out)
+{
+    const int64_t b = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t n = g.n, me = le ? g.me : 0, mi = li ? g.mi : 0;
+    const double* leb = me ? le + b * g.me : nullptr;
+    const double* lib = mi ? li + b * g.mi : nullptr;
+    const double* Je = me ? bp.Je + b * bp.sJe : nullptr;
+    const double* Ji = mi ? bp.Ji + b * bp.sJi : nullptr;
+    for (int64_t j0 = (int64_t)wave * 4; j0 < n; j0 += 16) {
+        double acc[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int64_t a = lane; a < me; a += 64) {
+            const double la = leb[a];
+            #pragma unroll
+            for (int q = 0; q < 4; ++q) if (j0 + q < n) acc[q] = fma(Je[(j0 + q) * bp.ldje + a], la, acc[q]);
+        }
+        for (int64_t a = lane; a < mi; a += 64) {
+            const double la = lib[a];
+            #pragma unroll
+            for (int q = 0; q < 4; ++q) if (j0 + q < n) acc[q] = fma(Ji[(j0 + q) * bp.ldji + a], la, acc[q]);
+        }
+        #pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] = wave_sum(acc[q]);
+        if (lane < 4 && j0 + lane < n)
+            out[b * n + j0 + lane] = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
+    }
+}
+
+// The 16 quantities of k_merit_info / pyipm_newton_merit_info for every problem, out[b][16] as the single entry point returns
+// them (5 - 8, 11, 12 as norms): ONE WAVE per problem, four problems per block, grid ceil(B / 4), as k_b_step_lengths.  The lanes
+// stride over the staged vectors [B][len], the sums cross the wave by shuffles.  dz: [B][N] or NULL (2, 3, 11, 12 = NaN);
+// have_g: bp.rhs holds g = -grad of the staged vectors (a step left it; else 5, 6 = NaN) -- 5 is read from it, 6 is formed from
+// the problem's own bp.pmu[b], the barrier parameter its g was formed with.  mi = 0: 10 = NaN.
+__global__ __launch_bounds__(256) void k_b_merit_info(double* __restrict__ out, BatchPtrs bp, Geo g, const double* __restrict__ dz,
+                                                      int have_g, double eps, int B)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;                                      // (wave-uniform)
+    const int64_t n = g.n, me = g.me, mi = g.mi;
+    const double* df = bp.df + b * n;
+    const double* ce = bp.ce + b * me;
+    const double* ci = bp.ci + b * mi;
+    const double* s = bp.s + b * mi;
+    const double* lda = bp.lda + b * (me + mi);
+    const double* d = dz ? dz + b * g.N : nullptr;
+    const double* gr = have_g ? bp.rhs + b * bp.sV : nullptr;
+    const double mu = have_g ? bp.pmu[b] : 0.0;
+    double q[13];
+    #pragma unroll
+    for (int k = 0; k < 13; ++k) q[k] = 0.0;
+    q[10] = 1.0e308;
+    for (int64_t i = lane; i < n; i += 64) {
+        if (d) { const double x = d[i]; q[2] = fma(df[i], x, q[2]); q[11] = fma(x, x, q[11]); }
+        if (gr) { const double v = gr[i]; q[5] = fma(v, v, q[5]); }
+    }
+    for (int64_t i = lane; i < me; i += 64) {
+        const double c = ce[i];
+        q[0] += fabs(c); q[7] = fma(c, c, q[7]);
+    }
+    for (int64_t i = lane; i < mi; i += 64) {
+        const double si = s[i], r = ci[i] - si, li = lda[me + i];
+        q[1] += fabs(r); q[8] = fma(r, r, q[8]);
+        q[4] += log(si);
+        const double sl = si * li;
+        q[9] += sl; q[10] = fmin(q[10], sl);
+        if (d) { const double x = d[n + i]; q[3] += x / (si + eps); q[12] = fma(x, x, q[12]); }
+        if (gr) { const double v = (li - mu / (si + eps)) * si; q[6] = fma(v, v, q[6]); }
+    }
+    #pragma unroll
+    for (int k = 0; k < 13; ++k) q[k] = (k == 10) ? wave_min(q[k]) : wave_sum(q[k]);
+    if (lane == 0) {
+        const double nan = __builtin_nan("");
+        double* o = out + b * MERIT_NQ;
+        o[0] = q[0]; o[1] = q[1]; o[2] = d ? q[2] : nan; o[3] = d ? q[3] : nan; o[4] = q[4];
+        o[5] = gr ? sqrt(q[5]) : nan; o[6] = gr ? sqrt(q[6]) : nan; o[7] = sqrt(q[7]); o[8] = sqrt(q[8]);
+        o[9] = q[9]; o[10] = mi ? q[10] : nan; o[11] = d ? sqrt(q[11]) : nan; o[12] = d ? sqrt(q[12]) : nan;
+        o[13] = o[14] = o[15] = 0.0;
+    }
+}
+
+// What the ray of problem b needs once per direction (grid B, 256 threads; b_products_problem on v = dx_b):
+// gq[b] = (df . dx, dx' Q dx or quad[b]), dce[b] = Je' dx, dci[b] = Ji' dx.  dz: [B][N].
+__global__ __launch_bounds__(256) void k_b_ray_prep(BatchPtrs bp, Geo g, const double* __restrict__ dz, const double* __restrict__ quad,
+                                                    double* __restrict__ gq, double* __restrict__ dce, double* __restrict__ dci)
+{
+    extern __shared__ double lds[];
+    const int64_t b = blockIdx.x;
+    b_products_problem(bp, g, b, dz + b * g.N, nullptr, g.me ? dce + b * g.me : nullptr, g.mi ? dci + b * g.mi : nullptr,
+                       gq + 2 * b, bp.df + b * g.n, quad ? quad + b : nullptr, lds);
+}
+
+// out[b][k] = phi(x + a dx, s + a ds) - phi(x, s) of problem b for a = alphas[b][k], term by term as k_merit_ray (abs_change,
+// log1p), with the problem's own nu[b], mu[b]: ONE WAVE per (candidate, problem), four candidates per block, grid
+// (ceil(K / 4), B).  A value is the work of its wave alone: lanes stride over me and mi, the three sums cross the wave by shuffles.
+__global__ __launch_bounds__(256) void k_b_merit_ray(double* __restrict__ out, const double* __restrict__ alphas, int K, BatchPtrs bp, Geo g,
+                                                     const double* __restrict__ gq, const double* __restrict__ dce,
+                                                     const double* __restrict__ dci, const double* __restrict__ dz,
+                                                     const double* __restrict__ nu, const double* __restrict__ mu)
+{
+    const int lane = threadIdx.x & 63;
+    const int k = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    const int64_t b = blockIdx.y;
+    if (k >= K) return;                                      // (wave-uniform)
+    const int64_t me = g.me, mi = g.mi;
+    const double a = alphas[b * K + k];
+    const double* ce = bp.ce + b * me;
+    const double* ci = bp.ci + b * mi;
+    const double* s = bp.s + b * mi;
+    const double* ds = dz + b * g.N + g.n;
+    const double* de = dce + b * me;
+    const double* di = dci + b * mi;
+    double se = 0.0, si = 0.0, sl = 0.0;
+    for (int64_t i = lane; i < me; i += 64) se += abs_change(ce[i], de[i], a);
+    for (int64_t i = lane; i < mi; i += 64) {
+        const double s0 = s[i], d = ds[i], r = ci[i] - s0, dr = di[i] - d;
+        si += abs_change(r, dr, a);
+        sl += log1p(a * (d / s0));
+    }
+    se = wave_sum(se); si = wave_sum(si); sl = wave_sum(sl);
+    if (lane == 0) {
+        double v = a * gq[2 * b] + (0.5 * a * a) * gq[2 * b + 1];
+        if (me) v = v + nu[b] * se;
+        if (mi) v = v + nu[b] * si - mu[b] * sl;
+        out[b * K + k] = v;
+    }
 }
 
 }  // namespace pyipm

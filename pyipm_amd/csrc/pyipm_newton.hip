@@ -2592,6 +2592,102 @@ int pyipm_newton_backward_error_batched(pyipm_newton_ctx* h, const double* dz, d
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
+// ---- the batch as a solver: provider products and merit pieces of every problem (kernels_batched.hpp) ----
+// Scratch of the four entries below, outside the workspace (as solve_many's): the fixed part and room for K candidates.
+struct BatchMerit { double *info, *gq, *dce, *dci, *nu, *mu, *quad, *alphas, *out; };
+static int batch_merit_scratch(Ctx* ctx, int K, BatchMerit* m) {
+    const Geo& g = ctx->g;
+    const size_t B = (size_t)ctx->batch, fixed = B * (size_t)(MERIT_NQ + 2 + g.me + g.mi + 3);
+    const size_t need = fixed + 2 * B * (size_t)K;
+    if (ctx->b_merit_buf.capacity() < need) {
+        PYIPM_HIP(ctx->b_merit_buf.reserve(need));
+        if (getenv("PYIPM_POISON_WORKSPACE")) PYIPM_HIP(hipMemsetAsync(ctx->b_merit_buf, 0xFF, need * sizeof(double), ctx->stream));   // as the workspace
+    }
+    double* p = ctx->b_merit_buf;
+    m->info = p; p += B * MERIT_NQ;
+    m->gq = p; p += B * 2;
+    m->dce = p; p += B * (size_t)g.me;
+    m->dci = p; p += B * (size_t)g.mi;
+    m->nu = p; p += B; m->mu = p; p += B; m->quad = p; p += B;
+    m->alphas = p; p += B * (size_t)K; m->out = p;
+    return 0;
+}
+static size_t batch_products_lds(const Geo& g) { return (size_t)(2 * g.n + 4 * (g.n + g.me + g.mi)) * sizeof(double); }
+
+int pyipm_newton_block_products_batched(pyipm_newton_ctx* h, const double* v, double* Qv, double* JeTv, double* JiTv) try {
+    PYIPM_ENTER("block_products_batched", G_BATCHED | G_DEVICE) const Geo& g = ctx->g;
+    if (!v) { ctx->err = "block_products_batched: null v"; return PYIPM_E_BADARG; }
+    if (!ctx->held.have_blocks) { ctx->err = "block_products_batched: stage blocks first"; return PYIPM_E_BADARG; }
+    if (!Qv && !(JeTv && g.me) && !(JiTv && g.mi)) return PYIPM_OK;
+    hipLaunchKernelGGL(k_b_products, dim3((unsigned)ctx->batch), dim3(256), batch_products_lds(g), ctx->stream, batch_ptrs(ctx), g, v, Qv, JeTv, JiTv);
+    PYIPM_KCHECK();
+    return PYIPM_OK;
+} PYIPM_CATCH_H(h)
+
+int pyipm_newton_block_products_t_batched(pyipm_newton_ctx* h, const double* le, const double* li, double* out) try {
+    PYIPM_ENTER("block_products_t_batched", G_BATCHED | G_DEVICE) const Geo& g = ctx->g;
+    if (!out) { ctx->err = "block_products_t_batched: null output"; return PYIPM_E_BADARG; }
+    if (!ctx->held.have_blocks) { ctx->err = "block_products_t_batched: stage blocks first"; return PYIPM_E_BADARG; }
+    hipLaunchKernelGGL(k_b_products_t, dim3((unsigned)ctx->batch), dim3(256), 0, ctx->stream, batch_ptrs(ctx), g, le, li, out);
+    PYIPM_KCHECK();
+    return PYIPM_OK;
+} PYIPM_CATCH_H(h)
+
+int pyipm_newton_merit_info_batched(pyipm_newton_ctx* h, const double* dz, double* out, int memkind) try {
+    PYIPM_ENTER("merit_info_batched", G_BATCHED | G_DEVICE) const Geo& g = ctx->g;
+    if (!out) { ctx->err = "merit_info_batched: null output"; return PYIPM_E_BADARG; }
+    if (memkind != PYIPM_MEM_DEVICE && memkind != PYIPM_MEM_HOST) { ctx->err = "merit_info_batched: bad memkind"; return PYIPM_E_BADARG; }
+    if (!ctx->held.have_vectors) { ctx->err = "merit_info_batched: stage vectors first"; return PYIPM_E_BADARG; }
+    const int B = ctx->batch;
+    BatchMerit m;
+    if (memkind == PYIPM_MEM_HOST) { int rc = batch_merit_scratch(ctx, 0, &m); if (rc) return rc; }
+    const double* d = dz ? dz : (ctx->held.have_direction ? ctx->v2 : nullptr);
+    double* dev = (memkind == PYIPM_MEM_DEVICE) ? out : m.info;
+    hipLaunchKernelGGL(k_b_merit_info, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, ctx->stream, dev, batch_ptrs(ctx), g, d,
+                       ctx->held.have_rhs ? 1 : 0, ctx->eps, B);
+    PYIPM_KCHECK();
+    if (memkind == PYIPM_MEM_HOST) {
+        PYIPM_HIP(hipMemcpyAsync(out, dev, (size_t)B * MERIT_NQ * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        PYIPM_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return PYIPM_OK;
+} PYIPM_CATCH_H(h)
+
+int pyipm_newton_merit_ray_batched(pyipm_newton_ctx* h, const double* dz, const double* nu, const double* mu, const double* quad,
+                                   const double* alphas, int K, double* out, int memkind) try {
+    PYIPM_ENTER("merit_ray_batched", G_BATCHED | G_DEVICE) const Geo& g = ctx->g;
+    if (!nu || !mu || !alphas || !out) { ctx->err = "merit_ray_batched: null nu / mu / alphas / out"; return PYIPM_E_BADARG; }
+    if (K < 1 || K > 1024) { ctx->err = "merit_ray_batched: 1 <= K <= 1024"; return PYIPM_E_BADARG; }
+    if (memkind != PYIPM_MEM_DEVICE && memkind != PYIPM_MEM_HOST) { ctx->err = "merit_ray_batched: bad memkind"; return PYIPM_E_BADARG; }
+    if (!ctx->held.have_vectors || !ctx->held.have_blocks) { ctx->err = "merit_ray_batched: stage blocks and vectors first"; return PYIPM_E_BADARG; }
+    const double* d = dz ? dz : (ctx->held.have_direction ? ctx->v2 : nullptr);
+    if (!d) { ctx->err = "merit_ray_batched: the handle keeps the directions of a step with host output only -- pass dz"; return PYIPM_E_BADARG; }
+    const size_t B = (size_t)ctx->batch;
+    const bool host = memkind == PYIPM_MEM_HOST;
+    BatchMerit m;
+    { int rc = batch_merit_scratch(ctx, host ? K : 0, &m); if (rc) return rc; }
+    if (host) {
+        PYIPM_HIP(hipMemcpyAsync(m.nu, nu, B * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        PYIPM_HIP(hipMemcpyAsync(m.mu, mu, B * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        if (quad) PYIPM_HIP(hipMemcpyAsync(m.quad, quad, B * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        PYIPM_HIP(hipMemcpyAsync(m.alphas, alphas, B * (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        nu = m.nu; mu = m.mu; if (quad) quad = m.quad; alphas = m.alphas;
+    }
+    const BatchPtrs bp = batch_ptrs(ctx);
+    // the products of the direction with the blocks, formed for every call: nothing of a direction is kept between two calls
+    hipLaunchKernelGGL(k_b_ray_prep, dim3((unsigned)B), dim3(256), batch_products_lds(g), ctx->stream, bp, g, d, quad, m.gq, m.dce, m.dci);
+    PYIPM_KCHECK();
+    double* dev = host ? m.out : out;
+    hipLaunchKernelGGL(k_b_merit_ray, dim3((unsigned)((K + 3) / 4), (unsigned)B), dim3(256), 0, ctx->stream, dev, alphas, K, bp, g,
+                       m.gq, m.dce, m.dci, d, nu, mu);
+    PYIPM_KCHECK();
+    if (host) {
+        PYIPM_HIP(hipMemcpyAsync(out, dev, B * (size_t)K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        PYIPM_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return PYIPM_OK;
+} PYIPM_CATCH_H(h)
+
 // Teardown is an order, not a list: stuck collectives aborted, every stream of the handle drained, the communicators gone --
 // after that nothing on the device refers to what the handle owns, and ~Ctx may release its members in any order.
 int pyipm_newton_destroy(pyipm_newton_ctx* h) try {

@@ -48,7 +48,7 @@ class NewtonError(RuntimeError):
 _lib = None
 
 
-ABI_VERSION = 7          # PYIPM_NEWTON_ABI_VERSION of include/pyipm_newton.h this file's signatures were written against
+ABI_VERSION = 8          # PYIPM_NEWTON_ABI_VERSION of include/pyipm_newton.h this file's signatures were written against
 
 
 def load_library(path: str | None = None):
@@ -121,6 +121,10 @@ def load_library(path: str | None = None):
         "pyipm_newton_stats_batched": (c_int, [ctxp, POINTER(FactorStats)]),
         "pyipm_newton_step_batched_each": (c_int, [ctxp, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
         "pyipm_newton_step_lengths_batched": (c_int, [ctxp, c_double, c_void_p, c_void_p, c_int]),
+        "pyipm_newton_block_products_batched": (c_int, [ctxp, c_void_p, c_void_p, c_void_p, c_void_p]),
+        "pyipm_newton_block_products_t_batched": (c_int, [ctxp, c_void_p, c_void_p, c_void_p]),
+        "pyipm_newton_merit_info_batched": (c_int, [ctxp, c_void_p, c_void_p, c_int]),
+        "pyipm_newton_merit_ray_batched": (c_int, [ctxp, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int]),
         "pyipm_mfma_f64_peak": (c_int, [c_int, c_int, POINTER(c_double)]),
         "pyipm_newton_block_products": (c_int, [ctxp, c_void_p, c_void_p, c_void_p, c_void_p]),
         "pyipm_newton_block_products_t": (c_int, [ctxp, c_void_p, c_void_p, c_void_p]),
