@@ -104,7 +104,15 @@ int pyipm_newton_geometry(pyipm_newton_ctx* ctx, int64_t out[8]);
 
 /* Constant-per-iteration blocks: Hessian of the Lagrangian and the constraint Jacobians.
  * Device pointers are retained (caller keeps them alive until re-staged); host pointers are
- * copied into library-owned staging and not retained.  Je/Ji may be NULL when me/mi == 0. */
+ * copied into library-owned staging and not retained.  Je/Ji may be NULL when me/mi == 0.
+ * Layout of a retained device block (tests/test_gpu_strided_blocks.py): row-major, row r at ptr + r * ld doubles,
+ * any ld >= the block's width, each block with its own.  The base needs the alignment of a double (8 bytes) and no
+ * more, and ld may be odd.  Of d2L only the upper triangle (column >= row) is used; the entries below the diagonal
+ * and the ld - width doubles that pad every row may hold anything, NaN included: no result depends on them, and no
+ * result depends on ld or on the base address -- every one is bit for bit that of the packed block.  The extent that
+ * must be readable is (rows - 1) * ld + width doubles.  pyipm_newton_stage_blocks_batched: the same for every problem,
+ * whose block b starts at ptr + b * stride doubles (stride >= rows * ld; the members may lie in any order in memory
+ * as long as that holds).  ld < width is PYIPM_E_BADARG. */
 int pyipm_newton_stage_blocks(pyipm_newton_ctx* ctx, const double* d2L, int64_t ld_d2L,
                               const double* Je, int64_t ld_Je, const double* Ji, int64_t ld_Ji,
                               int memkind);

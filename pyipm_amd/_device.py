@@ -23,6 +23,22 @@ def to_device(a, device, shape=None, contiguous=True):
     return t.contiguous() if contiguous else t
 
 
+def rows_to_device(a, device, shape):
+    """``a`` as an fp64 tensor of ``shape`` ((rows, width) or (batch, rows, width)) on ``device``, with its strides in doubles
+    but the last: (ld,) or (batch stride, ld).  A torch tensor that already has that dtype, device and shape, dense rows
+    (``stride(-1) == 1``) that do not overlap (``stride(-2) >= width``) and batch members that do not either
+    (``stride(0) >= rows * stride(1)``) is handed on as it is, no copy: the library takes a leading dimension and a batch stride
+    for the blocks it retains.  Every other layout is made contiguous as ``to_device`` does."""
+    import torch
+    shape = tuple(int(k) for k in shape)
+    if isinstance(a, torch.Tensor) and a.dtype == torch.float64 and a.device == device and tuple(a.shape) == shape:
+        st = tuple(int(k) for k in a.stride())
+        if st[-1] == 1 and st[-2] >= shape[-1] and (len(shape) == 2 or st[0] >= shape[1] * st[1]):
+            return a, st[:-1]
+    t = to_device(a, device, shape)
+    return t, ((shape[-1],) if len(shape) == 2 else (shape[1] * shape[2], shape[2]))
+
+
 def ptr(t):
     return c_void_p(0) if t is None else c_void_p(t.data_ptr())
 

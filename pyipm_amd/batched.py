@@ -13,7 +13,7 @@ from ctypes import c_void_p
 
 import numpy as np
 
-from ._device import alloc_workspace, ptr, to_device
+from ._device import alloc_workspace, ptr, rows_to_device, to_device
 from .newton import ERRORS, MEM_DEVICE, FactorStats, NewtonError, load_library
 
 
@@ -154,14 +154,21 @@ class BatchedNewton(object):
         B = int(d2L.shape[0])
         if self.h is None or B != self.batch:
             self._create(B)
-        blocks = (dev(d2L, (B, n, n)), dev(Je, (B, n, me)) if me else None, dev(Ji, (B, n, mi)) if mi else None)
+
+        def rows(a, width):                    # a row- and batch-strided device view as it is: (tensor, batch stride, ld)
+            if not width:
+                return None, 0, 0
+            t, (sb, ld) = rows_to_device(a, self.device, (B, n, width))
+            return t, sb, ld
+
+        (H, sH, ldh), (E, sE, lde), (I, sI, ldi) = rows(d2L, n), rows(Je, me), rows(Ji, mi)
+        blocks = (H, E, I)
         vecs = (dev(df, (B, n)), dev(ce, (B, me)) if me else None, dev(ci, (B, mi)) if mi else None,
                 dev(s, (B, mi)) if mi else None, dev(lda, (B, me + mi)) if (me + mi) else None)
         self._keep = (blocks, vecs)            # the library retains the block pointers
 
         self._ck(self.lib.pyipm_newton_set_stream(self.h, c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
-        self._ck(self.lib.pyipm_newton_stage_blocks_batched(self.h, ptr(blocks[0]), n, n * n, ptr(blocks[1]), me, n * me,
-                                                            ptr(blocks[2]), mi, n * mi))
+        self._ck(self.lib.pyipm_newton_stage_blocks_batched(self.h, ptr(H), ldh, sH, ptr(E), lde, sE, ptr(I), ldi, sI))
         self._ck(self.lib.pyipm_newton_stage_vectors(self.h, ptr(vecs[0]), ptr(vecs[1]), ptr(vecs[2]), ptr(vecs[3]),
                                                      ptr(vecs[4]), float(mu), float(eps), MEM_DEVICE))
         self._eps = float(eps)

@@ -12,7 +12,7 @@ from ctypes import POINTER, c_char_p, c_double, c_int, c_int64, c_size_t, c_void
 
 import numpy as np
 
-from ._device import RawDeviceArray, ptr, to_device
+from ._device import RawDeviceArray, ptr, rows_to_device, to_device
 from .newton import ERRORS, MEM_DEVICE, MEM_HOST, NewtonError, load_library
 
 
@@ -136,6 +136,13 @@ class LbfgsCore(object):
     def _dev(self, a, shape):
         return to_device(a, self.device, shape)
 
+    def _rows(self, a, shape):
+        """A 2-D operand and its leading dimension: a row-strided device view as it is (``_device.rows_to_device``)."""
+        if a is None:
+            return None, max(shape[1], 1)
+        t, (ld,) = rows_to_device(a, self.device, shape)
+        return t, ld
+
     _ptr = staticmethod(ptr)
 
     def set_option(self, name, value):
@@ -157,10 +164,9 @@ class LbfgsCore(object):
         n, me, mi = self.n, self.me, self.mi
         if me + mi == 0:
             return
-        Je = self._dev(Je, (n, me)) if me else None
-        Ji = self._dev(Ji, (n, mi)) if mi else None
-        self._ck(self.lib.pyipm_lbfgs_stage_jacobian(self.h, self._ptr(Je), max(me, 1), self._ptr(Ji), max(mi, 1),
-                                                     MEM_DEVICE))
+        Je, lde = self._rows(Je if me else None, (n, me))
+        Ji, ldi = self._rows(Ji if mi else None, (n, mi))
+        self._ck(self.lib.pyipm_lbfgs_stage_jacobian(self.h, self._ptr(Je), lde, self._ptr(Ji), ldi, MEM_DEVICE))
         self.torch.cuda.current_stream(self.device).synchronize()      # Je / Ji temporaries may die now
 
     def direction(self, g, s, lda, zeta, S, Y, SS, L, D, reg=0.0, eps=float(np.finfo(np.float64).eps), flip=False):
@@ -171,15 +177,15 @@ class LbfgsCore(object):
         g = self._dev(g, (N,))
         s = self._dev(s, (mi,)) if mi else None
         lda = self._dev(lda, (me + mi,)) if (me + mi) else None
-        Sd = self._dev(S, (n, m)) if m else None
-        Yd = self._dev(Y, (n, m)) if m else None
+        Sd, lds = self._rows(S if m else None, (n, m))
+        Yd, ldy = self._rows(Y if m else None, (n, m))
         small = [np.ascontiguousarray(np.asarray(a, dtype=np.float64)).reshape(m, m) if m else None for a in (SS, L, D)]
         dz = torch.empty(N, dtype=torch.float64, device=self.device)
         st = LbfgsStats()
         hp = lambda a: c_void_p(0) if a is None else a.ctypes.data_as(c_void_p)     # noqa: E731
         self._ck(self.lib.pyipm_lbfgs_set_stream(self.h, c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
         self._ck(self.lib.pyipm_lbfgs_direction(self.h, self._ptr(g), self._ptr(s), self._ptr(lda), float(zeta), m,
-                                                self._ptr(Sd), max(m, 1), self._ptr(Yd), max(m, 1), hp(small[0]),
+                                                self._ptr(Sd), lds, self._ptr(Yd), ldy, hp(small[0]),
                                                 hp(small[1]), hp(small[2]), float(reg), float(eps), self._ptr(dz),
                                                 1 if flip else 0, MEM_DEVICE, ctypes.byref(st)))
         return dz, st.as_dict()

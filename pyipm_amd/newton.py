@@ -15,7 +15,7 @@ from ctypes import POINTER, c_char_p, c_double, c_int, c_int64, c_size_t, c_void
 
 import numpy as np
 
-from ._device import RawDeviceArray as _RawDeviceArray, alloc_workspace, ptr, to_device  # noqa: F401  (dist.py, tools/rank_replay.py)
+from ._device import RawDeviceArray as _RawDeviceArray, alloc_workspace, ptr, rows_to_device, to_device  # noqa: F401  (dist.py, tools/rank_replay.py)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PYIPM_NEWTON_LIB") or os.path.join(_HERE, "libpyipm_newton.so")
@@ -247,6 +247,13 @@ class NewtonCore(object):
     def _dev(self, a, shape=None, contiguous=True):
         return to_device(a, self.device, shape, contiguous)
 
+    def _rows(self, a, shape):
+        """A staged block and its leading dimension: a row-strided device view as it is (``_device.rows_to_device``)."""
+        if a is None:
+            return None, max(shape[1], 1)
+        t, (ld,) = rows_to_device(a, self.device, shape)
+        return t, ld
+
     _ptr = staticmethod(ptr)
 
     on_device = True
@@ -284,15 +291,16 @@ class NewtonCore(object):
 
     # -- staging -----------------------------------------------------------------------------
     def stage_blocks(self, d2L, Je=None, Ji=None):
-        """d2L (n,n) row-major (upper triangle read), Je (n,me), Ji (n,mi)."""
+        """d2L (n,n) row-major (upper triangle read), Je (n,me), Ji (n,mi).  A device tensor whose rows are dense and
+        ``stride(0) >= width`` apart is retained as it is, with that leading dimension; anything else is copied packed."""
         self._use_current_stream()
         n, me, mi = self.n, self.me, self.mi
-        d2L = self._dev(d2L, (n, n)) if (d2L is not None or not self.provider_only) else None
-        Je = self._dev(Je, (n, me)) if me else None
-        Ji = self._dev(Ji, (n, mi)) if mi else None
+        d2L, ldh = self._rows(d2L, (n, n))
+        Je, lde = self._rows(Je if me else None, (n, me))
+        Ji, ldi = self._rows(Ji if mi else None, (n, mi))
         self._keep.update(d2L=d2L, Je=Je, Ji=Ji)
-        self._ck(self.lib.pyipm_newton_stage_blocks(self.h, self._ptr(d2L), n, self._ptr(Je), max(me, 1),
-                                                    self._ptr(Ji), max(mi, 1), MEM_DEVICE))
+        self._ck(self.lib.pyipm_newton_stage_blocks(self.h, self._ptr(d2L), ldh, self._ptr(Je), lde,
+                                                    self._ptr(Ji), ldi, MEM_DEVICE))
 
     def stage_vectors(self, df, ce=None, ci=None, s=None, lda=None, mu=0.2, eps=float(np.finfo(np.float64).eps)):
         self._use_current_stream()
@@ -517,12 +525,12 @@ class NewtonCore(object):
         self._use_current_stream()
         n, me, mi = self.n, self.me, self.mi
         r = len(self.owned_rows())
-        d2L = self._dev(d2L_rows, (r, n))
-        Je = self._dev(Je_rows, (r, me)) if me else None
-        Ji = self._dev(Ji_rows, (r, mi)) if mi else None
+        d2L, ldh = self._rows(d2L_rows, (r, n))
+        Je, lde = self._rows(Je_rows if me else None, (r, me))
+        Ji, ldi = self._rows(Ji_rows if mi else None, (r, mi))
         self._keep.update(d2L=d2L, Je=Je, Ji=Ji)
-        self._ck(self.lib.pyipm_newton_stage_blocks_owned(self.h, self._ptr(d2L), n, self._ptr(Je), max(me, 1),
-                                                          self._ptr(Ji), max(mi, 1), MEM_DEVICE))
+        self._ck(self.lib.pyipm_newton_stage_blocks_owned(self.h, self._ptr(d2L), ldh, self._ptr(Je), lde,
+                                                          self._ptr(Ji), ldi, MEM_DEVICE))
 
     def set_exchange(self, bcast_cb, allreduce_cb):
         """ctypes callbacks (BCAST_FN / ALLREDUCE_FN); kept alive with the handle."""
