@@ -221,8 +221,15 @@ int pyipm_newton_step(pyipm_newton_ctx* ctx, double delta, double delta_c, int r
  * A reusing step sends its right-hand side through the kept panels in one launch (k_fwd_prefix) where the one-launch sweeps apply
  * (sweep_persist, one rank, panels of at most 256 columns); PYIPM_FWD_PREFIX=0 at create time keeps the launches per panel,
  * PYIPM_FWD_PREFIX=W (W >= 2) sets the workgroups of that launch (default 96).  The same bits either way.
- * out[0] = factorisations of this handle that reused, [1] = that recorded, [2] = bytes of the snapshot, [3] = the last one:
- * 0 full, 1 recording, 2 reusing.  With PYIPM_GROUP_TRACE set every factorisation says which kind it is. */
+ * With me > 0 and mi > 0 a reusing step also keeps the groups of the schedule that lie wholly inside the lambda_e columns (at
+ * least one such group, at least one group behind them; a group that straddles a border of lambda_e is factored): the slack
+ * columns couple to lambda_i only, so those groups depend on the blocks and the shifts alone.  A second snapshot holds their W and
+ * what lies behind them; the diagonal blocks of the lambda_i columns are recomputed every step (the slack term changes them).
+ * The same bits.  Whatever drops the prefix drops them too; PYIPM_REUSE_LAM_E=0 at create time, or a second snapshot that cannot
+ * be allocated (silently), leaves the x prefix alone.
+ * out[0] = factorisations of this handle that reused, [1] = that recorded, [2] = bytes of the snapshots (both), [3] = the last
+ * one: 0 full, 1 recording, 2 reusing (whichever groups it kept).  With PYIPM_GROUP_TRACE set every factorisation says which kind
+ * it is and how many groups it recorded or kept. */
 int pyipm_newton_reuse_info(pyipm_newton_ctx* ctx, int64_t out[4]);
 
 /* SURVEY.md section 8(f) rank 3 -- the derivative provider of the QP family on the device.  For

@@ -156,6 +156,11 @@ struct Held {
     bool px_valid = false;
     double px_delta = 0.0, px_delta_c = 0.0;   // ... the shifts it was recorded with
     int64_t px_groups = 0, px_cB = 0;          // ... and the schedule: groups of the prefix, first column behind them
+    // The second level: the groups [px_gS, px_gE) wholly inside the lambda_e columns are kept as well (their L, tile inverses, saved
+    // tiles and flags in place; their W rows below the boundary and the state of everything behind them in the second snapshot).
+    // Only ever consulted together with px_valid and written by every recording step: whatever drops the prefix drops it too.
+    bool px_e_valid = false;
+    int64_t px_gS = 0, px_gE = 0;
     // The recording policy: whoever restages the blocks before any step reused them is an NLP loop and stops paying for
     // snapshots; a second step on the same blocks starts them again.
     bool px_record = true;
@@ -166,6 +171,7 @@ struct Held {
     // 2 with `assembled`: the storage holds L of the prefix in columns [0, cB), the matrix behind them -- whoever looks at the
     // storage as a matrix first has it completed (storage_whole).
     int px_plan = 0; int64_t px_plan_groups = 0, px_plan_cB = 0;
+    bool px_plan_e = false; int64_t px_plan_gS = 0, px_plan_gE = 0;   // ... with the lambda_e groups [gS, gE) recorded / kept as well
     bool partial() const { return assembled && px_plan == 2; }
 
     enum : unsigned { V0 = 1, V1 = 2, V2 = 4, VLOC = 8 };
@@ -193,17 +199,23 @@ struct Held {
     // zeros are gone as soon as it starts.
     // A whole assembly overwrites the x columns: the prefix is gone.
     void assemble_begun(bool condensed) { if (condensed) zeros_clean = false; else cond_active = false; px_valid = false; px_plan = 0; }
-    void assembly_planned(int plan, int64_t groups, int64_t cB) { px_plan = plan; px_plan_groups = groups; px_plan_cB = cB; }
+    void assembly_planned(int plan, int64_t groups, int64_t cB, bool e, int64_t gS, int64_t gE) {
+        px_plan = plan; px_plan_groups = groups; px_plan_cB = cB;
+        px_plan_e = plan != 0 && e; px_plan_gS = gS; px_plan_gE = gE;
+    }
     // The slack columns re-assembled and the snapshot restored behind a valid prefix: a matrix again, its zeros as they were.
     void prefix_reassembled() { assembled = true; factored = false; forward_pending = false; }
     // Anything that may change the schedule or the order on the stream (set_option, set_stream), and a step that failed.
-    void prefix_dropped() { px_valid = false; if (px_plan == 1) px_plan = 0; }
+    void prefix_dropped() { px_valid = false; px_e_valid = false; if (px_plan == 1) px_plan = 0; }
     // An assembly of a step starts / its factorisation is done.  A second one on the same blocks: the caller is no NLP loop.
     void step_begun() { if (px_steps >= 1) px_record = true; }
     void step_factored(bool recorded, bool reused, double delta, double delta_c, int64_t groups, int64_t cB) {
         ++px_steps; px_last_delta = delta; px_last_delta_c = delta_c; px_plan = 0;
         if (reused) px_reused = true;
-        if (recorded) { px_valid = true; px_delta = delta; px_delta_c = delta_c; px_groups = groups; px_cB = cB; }
+        if (recorded) {
+            px_valid = true; px_delta = delta; px_delta_c = delta_c; px_groups = groups; px_cB = cB;
+            px_e_valid = px_plan_e; px_gS = px_plan_gS; px_gE = px_plan_gE;
+        }
     }
 
     // The zeros of a full single-rank assembly survive a factorisation of finite numbers (every update that reaches them adds an
@@ -366,6 +378,12 @@ struct Ctx {
     int reuse_x = 1;                      // PYIPM_REUSE_X=0 at create time switches it off; so does a snapshot that could not be allocated
     DevBuf<double> snap;                  // the snapshot, outside the workspace (allocated by the first recording step): PX_HDR doubles
                                           // (DevStats and the assembly's maximum as they stood at the boundary), then the column ranges
+    int reuse_lam_e = 1;                  // the second level (the lambda_e groups kept too); PYIPM_REUSE_LAM_E=0 at create time switches it
+                                          // off, a second snapshot that could not be allocated does so for the handle
+    DevBuf<double> snap_e;                // the second snapshot: PX_HDR doubles (the record in front of the lambda_e groups, then their own),
+                                          // W of the lambda_e groups in the rows below cE, the square [cE, Npad) as it stood behind them
+    DevBuf<unsigned> diag_tiles;          // tile list of k_update<64>: the 128-row diagonal blocks of the columns [cE, Npad)
+    std::vector<unsigned> diag_tiles_host; int64_t diag_tiles_n = -1;   // ... its host copy and the (Npad - cE) / 128 it was built for
     int64_t n_reused = 0, n_recorded = 0; // fused steps of this handle that reused the prefix / recorded one
     int fwd_prefix = 1;                   // a reusing step's forward substitution through the kept panels in one launch (k_fwd_prefix);
     int fwd_prefix_wgs = 96;              // PYIPM_FWD_PREFIX=0 at create time keeps the per-panel launches, =W (>= 2) sets its workgroups

@@ -168,6 +168,36 @@ __global__ __launch_bounds__(256) void k_copy_cols(double* __restrict__ dst, int
         *reinterpret_cast<dbl2_t*>(d + i) = *reinterpret_cast<const dbl2_t*>(s + i);
 }
 
+// The square of the columns and rows [c0, c0 + n) of the storage (ld) against a dense n x n copy of it (second snapshot of a
+// step that keeps the lambda_e groups).  save: storage -> copy.  Otherwise copy -> storage WITHOUT the 128-row diagonal block of
+// each column, which the reusing step recomputes.  The whole square, as the first snapshot: which rows above its diagonal block
+// a group's head and chain kernels touch is not settled.  grid (n, chunks), 256 threads, two rows per
+// thread (n and c0 are multiples of 128).
+__global__ __launch_bounds__(256) void k_copy_square(double* __restrict__ A, int64_t ld, double* __restrict__ B, int64_t n, int64_t c0, int save)
+{
+    const int64_t c = blockIdx.x;
+    if (c >= n) return;
+    const int64_t j = c0 + c;
+    const int64_t d0 = (j & ~(int64_t)127) - c0;
+    double* __restrict__ a = A + c0 + j * ld;
+    double* __restrict__ b = B + c * n;
+    for (int64_t i = ((int64_t)blockIdx.y * 256 + threadIdx.x) * 2; i + 1 < n; i += (int64_t)gridDim.y * 512) {
+        if (save) *reinterpret_cast<dbl2_t*>(b + i) = *reinterpret_cast<const dbl2_t*>(a + i);
+        else if (i < d0 || i >= d0 + 128) *reinterpret_cast<dbl2_t*>(a + i) = *reinterpret_cast<const dbl2_t*>(b + i);
+    }
+}
+// The 128-row diagonal blocks of the columns [c0, c0 + n) of the storage from a column range of the first snapshot (columns from
+// global column s0 on, rows from s0 on, leading dimension lds).  grid (n), 64 threads.
+__global__ __launch_bounds__(64) void k_copy_diag_blocks(double* __restrict__ A, int64_t ld, const double* __restrict__ S, int64_t lds,
+                                                         int64_t s0, int64_t c0, int64_t n)
+{
+    const int64_t c = blockIdx.x;
+    if (c >= n) return;
+    const int64_t j = c0 + c, d = j & ~(int64_t)127;
+    const int i = threadIdx.x * 2;
+    *reinterpret_cast<dbl2_t*>(A + d + i + j * ld) = *reinterpret_cast<const dbl2_t*>(S + (d - s0) + i + (j - s0) * lds);
+}
+
 // ---- wave-level helpers -------------------------------------------------------------------
 __device__ __forceinline__ double wave_sum(double v) {
     #pragma unroll

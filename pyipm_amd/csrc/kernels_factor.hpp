@@ -122,6 +122,15 @@ __global__ __launch_bounds__(64) void k_init_stats(DevStats* __restrict__ st) {
     }
 }
 
+// One record merged into another (one thread): counts add, minima and maxima combine -- with the atomics the tile kernels use,
+// so kernels of other streams may be adding to `st` meanwhile.
+__global__ __launch_bounds__(64) void k_merge_stats(DevStats* __restrict__ st, const DevStats* __restrict__ src) {
+    if (threadIdx.x == 0) {
+        stats_add(st, src->n_neg, src->n_zero, src->n_2x2, src->n_pos, src->nonfinite, src->d_min, src->d_max);
+        atomicMax(&st->growth_bits, src->growth_bits);
+    }
+}
+
 // Shared-memory scratch of one tile inversion (a 256-thread workgroup).
 struct TileScratch {
     double stage[TB][TB + 1];

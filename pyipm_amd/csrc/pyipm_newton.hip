@@ -1769,7 +1769,8 @@ static size_t prefix_ranges(const Geo& g, int64_t cB, PxRange out[2], int* count
     return tot;
 }
 static_assert(sizeof(DevStats) <= 16 * sizeof(double) && PX_HDR > 16, "the snapshot's header holds DevStats, then the maximum");
-static int prefix_copy(Ctx* ctx, int64_t cB, bool save) {
+// (c_end > 0, restoring: only the columns in front of c_end -- a step that keeps the lambda_e groups too)
+static int prefix_copy(Ctx* ctx, int64_t cB, bool save, int64_t c_end = 0) {
     const Geo& g = ctx->g;
     PxRange r[2]; int nr = 0;
     const size_t tot = prefix_ranges(g, cB, r, &nr);
@@ -1783,7 +1784,8 @@ static int prefix_copy(Ctx* ctx, int64_t cB, bool save) {
         PYIPM_HIP(hipMemcpyAsync(ctx->anorm, hdr + 16, sizeof(unsigned long long), dd, ctx->stream));
     }
     for (int k = 0; k < nr; ++k) {
-        const int64_t rows = g.Npad - r[k].c0, cols = r[k].c1 - r[k].c0;
+        const int64_t rows = g.Npad - r[k].c0, cols = (c_end > 0 && c_end < r[k].c1 ? c_end : r[k].c1) - r[k].c0;
+        if (cols <= 0) continue;
         double* a = ctx->A + r[k].c0 + r[k].c0 * g.Npad;       // (single rank: local = global columns)
         double* b = ctx->snap.get() + r[k].off;
         const dim3 grid((unsigned)cols, (unsigned)((rows + 2047) / 2048));
@@ -1793,12 +1795,72 @@ static int prefix_copy(Ctx* ctx, int64_t cB, bool save) {
     }
     return 0;
 }
+// ---- the second level: the lambda_e groups -----------------------------------------------------------------
+// The slack columns couple to lambda_i only, so behind the x groups the lambda_e columns depend on the staged blocks, delta and
+// delta_c alone: the groups [gS, gE) that lie wholly inside the columns [n + mi, n + mi + me) are kept like the prefix.  gS is the
+// first group behind the slack block, gE the first one that does not lie wholly inside lambda_e, cS / cE their first columns; a
+// group that straddles either border is factored.  What changes behind cE from step to step are the diagonal entries of the
+// lambda_i block (the slack term), and an FMA chain rounds by its running value: a reusing step takes the 128-row diagonal blocks
+// behind cE as the prefix left them (first snapshot), lets the groups it factors in front of gS and the slack kernels apply
+// their terms, applies the kept groups with k_update over a list of those blocks alone (diag_update; the saved W), in group
+// order -- the products every entry of a block received in the recording step, in that order -- and takes everything else behind cE
+// from the second snapshot.
+struct LamE { bool ok = false; int64_t gS = 0, gE = 0, cS = 0, cE = 0; };
+static LamE lam_e_groups(const Geo& g, const GroupSched& sc, int64_t gB) {
+    LamE e;
+    const int64_t ng = sc.ngroups(), e0 = g.n + g.mi, e1 = e0 + g.me;
+    if (g.me <= 0 || g.mi <= 0 || gB <= 0 || gB >= ng) return e;
+    auto c0 = [&](int64_t grp) { return grp >= ng ? g.Npad : g.panel_c0(sc.first(grp)); };
+    int64_t gS = gB; while (gS < ng && c0(gS) < e0) ++gS;
+    int64_t gE = gS; while (gE < ng && c0(gE + 1) <= e1) ++gE;
+    if (gE == gS || gE >= ng) return e;                       // no whole group inside lambda_e, or none behind it
+    e.ok = true; e.gS = gS; e.gE = gE; e.cS = c0(gS); e.cE = c0(gE);
+    return e;
+}
+// The second snapshot: PX_HDR doubles, W of the columns [cS, cE) in the rows [cE, Npad) (leading dimension Npad - cE), the square.
+static size_t lam_e_doubles(const Geo& g, const LamE& e) {
+    const size_t rows = (size_t)(g.Npad - e.cE);
+    return PX_HDR + rows * (size_t)(e.cE - e.cS) + rows * rows;
+}
+static double* lam_e_w(const Ctx* ctx, const LamE& e, int64_t c) { return ctx->snap_e.get() + PX_HDR + (c - e.cS) * (ctx->g.Npad - e.cE); }
+static double* lam_e_square(const Ctx* ctx, const LamE& e) { return lam_e_w(ctx, e, e.cE); }
+// K source columns from global column src_c0 on (L at Lop; -S at W, whose first row is global row w_row0 <= cE: row r of column
+// k at W[(r - w_row0) + k ldw]) applied to the 128-row diagonal blocks of the columns [cE, Npad): k_update<64> (the instance of
+// the narrow bulk launches) over a list of those tiles.  k_update addresses its W operand by global row; the address of "row 0"
+// it is handed is computed on integers (a pointer in front of the buffer is never formed; no tile of the list reads there).
+static int diag_update(Ctx* ctx, hipStream_t st, const double* Lop, const double* W, int64_t w_row0, int64_t ldw, int K, int64_t src_c0,
+                       int64_t cE) {
+    const double* const Wop = reinterpret_cast<const double*>(reinterpret_cast<uintptr_t>(W) - (uintptr_t)w_row0 * sizeof(double));
+    const Geo& g = ctx->g;
+    const int64_t nrt = (g.Npad - cE) / BM;
+    if (nrt <= 0 || K <= 0) return 0;
+    if (ctx->diag_tiles_n != nrt) {
+        ctx->diag_tiles_host.clear();
+        for (int64_t r = 0; r < nrt; ++r) for (int h = 0; h < BM / 64; ++h)
+            ctx->diag_tiles_host.push_back((unsigned)r | ((unsigned)(r * (BM / 64) + h) << 16));
+        PYIPM_HIP(ctx->diag_tiles.reserve(ctx->diag_tiles_host.size()));
+        PYIPM_HIP(hipMemcpyAsync(ctx->diag_tiles.get(), ctx->diag_tiles_host.data(), ctx->diag_tiles_host.size() * sizeof(unsigned),
+                                 hipMemcpyHostToDevice, st));
+        ctx->diag_tiles_n = nrt;
+    }
+    UpdGeo u;
+    u.row_begin = cE; u.Npad = g.Npad; u.first_lp = cE / g.nb; u.sub0 = 0;
+    u.nb = g.nb; u.world = 1; u.rank = 0; u.nrt = (int)nrt; u.nct = (int)(nrt * (BM / 64));
+    u.prio = 0; u.rt_min0 = 0; u.rt_step = 0; u.dbg = ctx->dbg_buf; u.ks_cstride = 0;
+    active_ranges(ctx, src_c0, src_c0 + K, &u.a0, &u.a1, &u.b0, &u.b1);
+    u.tiles = ctx->diag_tiles.get();
+    hipLaunchKernelGGL((k_update<64, true, 8>), dim3((unsigned)ctx->diag_tiles_host.size()), dim3(512), 0, st, ctx->A, g.Npad, Lop, g.Npad,
+                       Wop, ldw, K, u);
+    PYIPM_KCHECK();
+    return 0;
+}
+
 // What kind of step the fused entry point runs now.  Reuse applies to the full form on one rank with a lookahead schedule and at
 // least one group inside the x block; everything else is a full step, as it always was.
-static int prefix_mode(Ctx* ctx, double delta, double delta_c, int64_t* gB_out, int64_t* cB_out) {
+static int prefix_mode(Ctx* ctx, double delta, double delta_c, int64_t* gB_out, int64_t* cB_out, LamE* e_out) {
     const Geo& g = ctx->g;
     Held& h = ctx->held;
-    *gB_out = 0; *cB_out = 0;
+    *gB_out = 0; *cB_out = 0; *e_out = LamE();
     if (!ctx->reuse_x || g.world != 1 || ctx->batched || ctx->provider_only || (ctx->condensed && g.mi > 0) || !ctx->lookahead ||
         h.storage_exported) return PX_FULL;                    // (a holder of the storage pointer may write into the x columns at any time)
     const GroupSched sc = plan_groups(g, ctx->group, ctx->tail_group, ctx->tail_group_user, ctx->skip_zeros != 0, ctx->lookahead);
@@ -1806,7 +1868,11 @@ static int prefix_mode(Ctx* ctx, double delta, double delta_c, int64_t* gB_out, 
     if (gB == 0 || gB >= sc.ngroups()) return PX_FULL;
     const int64_t cB = g.panel_c0(sc.first(gB));
     *gB_out = gB; *cB_out = cB;
-    if (h.px_valid && delta == h.px_delta && delta_c == h.px_delta_c && gB == h.px_groups && cB == h.px_cB && ctx->snap) return PX_REUSE;
+    const LamE le = ctx->reuse_lam_e ? lam_e_groups(g, sc, gB) : LamE();
+    if (h.px_valid && delta == h.px_delta && delta_c == h.px_delta_c && gB == h.px_groups && cB == h.px_cB && ctx->snap) {
+        if (le.ok && h.px_e_valid && le.gS == h.px_gS && le.gE == h.px_gE && ctx->snap_e.capacity() >= lam_e_doubles(g, le)) *e_out = le;
+        return PX_REUSE;
+    }
     // the first factorisation of these blocks records; a later one only with the shifts of the one before it (a shift loop
     // changes them every time and never gets as far as reusing)
     if (!h.px_record || (h.px_steps > 0 && (delta != h.px_last_delta || delta_c != h.px_last_delta_c))) return PX_FULL;
@@ -1820,14 +1886,40 @@ static int prefix_mode(Ctx* ctx, double delta, double delta_c, int64_t* gB_out, 
         }
         if (getenv("PYIPM_POISON_WORKSPACE")) (void)hipMemsetAsync(ctx->snap, 0xFF, tot * sizeof(double), ctx->stream);
     }
+    if (le.ok) {
+        const size_t tot_e = lam_e_doubles(g, le);
+        if (ctx->snap_e.capacity() < tot_e) {
+            if (ctx->snap_e.reserve(tot_e) != hipSuccess) {          // no room for the second one: the first level alone
+                (void)hipGetLastError();
+                ctx->reuse_lam_e = 0;
+                return PX_RECORD;
+            }
+            if (getenv("PYIPM_POISON_WORKSPACE")) (void)hipMemsetAsync(ctx->snap_e, 0xFF, tot_e * sizeof(double), ctx->stream);
+        }
+        *e_out = le;
+    }
     return PX_RECORD;
 }
 // The assembly of a reusing step (events 2 and 3 around it): the slack columns -- Sigma, -I -- from the staged vectors, the
 // columns of the snapshot from the snapshot.  Columns [0, cB) keep L of the prefix.
-static int reassemble_slack(Ctx* ctx, int64_t cB) {
+// With the lambda_e groups kept (e.ok): of the first snapshot the columns in front of cS and the diagonal blocks behind cE as the
+// prefix left them, of the second one everything else behind cE; the columns [cS, cE) keep L.
+static int reassemble_slack(Ctx* ctx, int64_t cB, const LamE& e) {
     const Geo& g = ctx->g;
     PYIPM_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
-    int rc = prefix_copy(ctx, cB, false); if (rc) return rc;
+    int rc = prefix_copy(ctx, cB, false, e.ok ? e.cS : 0); if (rc) return rc;
+    if (e.ok) {
+        PxRange r[2]; int nr = 0;
+        (void)prefix_ranges(g, cB, r, &nr);
+        if (nr < 1 || r[nr - 1].c0 > e.cE || r[nr - 1].c1 != g.Npad) { ctx->err = "prefix snapshot: the lambda_i columns are not in its last range"; return PYIPM_E_BADARG; }
+        const int64_t ne = g.Npad - e.cE, s0 = r[nr - 1].c0;
+        hipLaunchKernelGGL(k_copy_diag_blocks, dim3((unsigned)ne), dim3(64), 0, ctx->stream, ctx->A, g.Npad,
+                           (const double*)(ctx->snap.get() + r[nr - 1].off), g.Npad - s0, s0, e.cE, ne);
+        PYIPM_KCHECK();
+        hipLaunchKernelGGL(k_copy_square, dim3((unsigned)ne, (unsigned)((ne + 2047) / 2048)), dim3(256), 0, ctx->stream, ctx->A, g.Npad,
+                           lam_e_square(ctx, e), ne, e.cE, 0);
+        PYIPM_KCHECK();
+    }
     if (g.mi > 0) {
         const int zip = (ctx->keep_zeros && !ctx->held.storage_exported && ctx->held.zeros_clean) ? 1 : 0;
         const int64_t lc0 = g.n / 16 * 16;
@@ -1849,11 +1941,11 @@ static int reassemble_slack(Ctx* ctx, int64_t cB) {
 int assemble_planned(Ctx* ctx, double delta, double delta_c) {
     if (!ctx->held.have_blocks || !ctx->held.have_vectors || ctx->provider_only) return assemble_timed(ctx, delta, delta_c);   // (its refusals)
     ctx->held.step_begun();
-    int64_t gB = 0, cB = 0;
-    const int px = prefix_mode(ctx, delta, delta_c, &gB, &cB);
-    const int rc = px == PX_REUSE ? reassemble_slack(ctx, cB) : assemble_timed(ctx, delta, delta_c);
+    int64_t gB = 0, cB = 0; LamE le;
+    const int px = prefix_mode(ctx, delta, delta_c, &gB, &cB, &le);
+    const int rc = px == PX_REUSE ? reassemble_slack(ctx, cB, le) : assemble_timed(ctx, delta, delta_c);
     if (rc) return rc;
-    ctx->held.assembly_planned(ctx->held.cond_active ? (int)PX_FULL : px, gB, cB);
+    ctx->held.assembly_planned(ctx->held.cond_active ? (int)PX_FULL : px, gB, cB, le.ok, le.gS, le.gE);
     return 0;
 }
 // ... and its factorisation, with the bookkeeping of what was recorded or reused.
@@ -2071,13 +2163,27 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false, i
     const GroupSched& sc = ctx->sched;
     const int64_t np = g.npanels, ngroups = sc.ngroups();
     const bool rec = px == PX_RECORD, reuse = px == PX_REUSE;
-    const int64_t gB = px ? prefix_groups(sc) : 0, g0 = reuse ? gB : 0;           // g0: the first group this factorisation runs
+    const int64_t gB = px ? prefix_groups(sc) : 0;
     if (px && (gB == 0 || gB >= ngroups || !ctx->lookahead)) { ctx->err = "factor: no reusable prefix in this schedule"; return PYIPM_E_BADARG; }
+    // the second level (what the assembly planned): the lambda_e groups [gS, gE) are recorded / kept as well
+    const LamE le = (px && ctx->held.px_plan_e) ? lam_e_groups(g, sc, gB) : LamE();
+    if (px && ctx->held.px_plan_e && !(le.ok && le.gS == ctx->held.px_plan_gS && le.gE == ctx->held.px_plan_gE && ctx->snap_e)) {
+        ctx->err = "factor: the schedule changed behind the assembly of a step that keeps the lambda_e groups"; return PYIPM_E_BADARG;
+    }
+    const int64_t g0 = reuse ? (le.ok ? le.gE : gB) : 0;                           // g0: the first group of the lookahead loop
+    // (second snapshot's header: the record in front of the lambda_e groups, then their own; gS > gB always -- group gB begins in
+    //  front of column n + mi)
+    DevStats* const st_before = le.ok ? (DevStats*)ctx->snap_e.get() : nullptr;
+    DevStats* const st_lam_e = le.ok ? (DevStats*)(ctx->snap_e.get() + 16) : nullptr;
     const FactorRun run{fuse_forward, !px && ctx->lookahead >= 2 && ngroups > 2 && chain_group(ctx, 0) && sc.fast(1),
                         !rec && slack_first_applies(ctx)};
     GroupTrace tr;
-    if (tr.on()) fprintf(stderr, "[pyipm group trace] %s step%s\n", rec ? "recording" : reuse ? "reusing" : "full",
-                         reuse ? ": the x-block prefix is kept" : "");
+    if (tr.on()) {
+        fprintf(stderr, "[pyipm group trace] %s step%s\n", rec ? "recording" : reuse ? "reusing" : "full",
+                reuse ? ": the x-block prefix is kept" : "");
+        if (px) fprintf(stderr, "[pyipm group trace] %s %lld groups: x prefix [0, %lld), lambda_e [%lld, %lld)\n", rec ? "records" : "keeps",
+                        (long long)(gB + (le.ok ? le.gE - le.gS : 0)), (long long)gB, (long long)le.gS, (long long)le.gE);
+    }
     ctx->held.factor_begun();
     if (fuse_forward) {
         PYIPM_HIP(ctx->fwd.ensure(hipStreamNonBlocking));
@@ -2087,6 +2193,7 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false, i
     }
     if (reuse) {                            // the statistics as the prefix left them, not zero
         PYIPM_HIP(hipMemcpyAsync(ctx->dstats, ctx->snap.get(), sizeof(DevStats), hipMemcpyDeviceToDevice, ctx->stream));
+        if (le.ok) { hipLaunchKernelGGL(k_merge_stats, dim3(1), dim3(64), 0, ctx->stream, ctx->dstats, (const DevStats*)st_lam_e); PYIPM_KCHECK(); }
         ctx->n_trailing = 0; ctx->trailing_flops = 0.0; ctx->trailing_area = 0.0;
     } else {
         rc = factor_begin(ctx); if (rc) return rc;
@@ -2104,15 +2211,77 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false, i
         }
         tr.mark("fwd prefix end (before group)", gB, ctx->fwd);
     }
+    if (reuse && le.ok) {
+        // The groups between the prefix and the kept lambda_e groups (the slack group, a group that straddles a border), one after
+        // the other on the main stream.  What they reach behind themselves that this step still needs: the columns in front of cS
+        // (none inside the slack block: a slack column takes nothing from the columns before it) and the diagonal blocks behind cE.
+        for (int64_t grp = gB; grp < le.gS; ++grp) {
+            const int64_t p0 = sc.first(grp), n0 = sc.size(grp);
+            if (run.slack_first && sc.fast(grp)) PYIPM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_sfast, 0));
+            tr.mark("chain+rows begin", grp, ctx->stream);
+            rc = run_group(ctx, run, grp, ctx->stream); if (rc) return rc;
+            tr.mark("chain+rows end", grp, ctx->stream);
+            if (sc.fast(grp)) { rc = timed_update(ctx, p0, n0, p0 + n0, np - (p0 + n0)); if (rc) return rc; continue; }   // (k_s_schur: diagonal entries)
+            for (int64_t t = grp + 1; t < le.gS; ++t)
+                if (!sc.fast(t)) { rc = timed_update(ctx, p0, n0, sc.first(t), sc.size(t)); if (rc) return rc; }
+            int K = 0; for (int64_t q = p0; q < p0 + n0; ++q) K += (int)g.panel_w(q);
+            rc = diag_update(ctx, ctx->stream, ctx->A + g.local_c0(p0) * g.Npad, wbuf(ctx, p0), 0, g.Npad, K, g.panel_c0(p0), le.cE); if (rc) return rc;
+        }
+        // ... the kept groups: their forward substitution waits for nothing, their products go to the diagonal blocks
+        tr.mark("diagonal blocks begin", le.gS, ctx->stream);
+        for (int64_t grp = le.gS; grp < le.gE; ++grp) {
+            const int64_t p0 = sc.first(grp), n0 = sc.size(grp), c0 = g.panel_c0(p0);
+            if (fuse_forward)
+                for (int64_t q = p0; q < p0 + n0; ++q) {
+                    rc = fwd_panel(ctx, q, ctx->fwd_vec, ctx->fwd); if (rc) return rc;
+                    rc = diag_panel(ctx, q, ctx->fwd_vec, ctx->fwd); if (rc) return rc;
+                }
+            rc = diag_update(ctx, ctx->stream, ctx->A + g.local_c0(p0) * g.Npad, lam_e_w(ctx, le, c0), le.cE, g.Npad - le.cE,
+                             (int)(g.panel_c0(sc.first(grp + 1)) - c0), c0, le.cE); if (rc) return rc;
+        }
+        tr.mark("diagonal blocks end", le.gE, ctx->stream);
+    }
     if (reuse && run.slack_first && sc.fast(g0)) PYIPM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_sfast, 0));   // (as in front of any slack group)
     tr.mark("chain+rows begin", g0, ctx->stream);
     rc = run_group(ctx, run, g0, ctx->stream); if (rc) return rc;
     tr.mark("chain+rows end", g0, ctx->stream);
     if (reuse) PYIPM_HIP(hipEventRecord(ctx->ev_main, ctx->stream));      // group g0 ran on the main stream: its head on the side stream waits for this
     if (tr.on()) fprintf(stderr, "[pyipm group trace] %lld groups\n", (long long)ngroups);
+    // A recording step isolates the lambda_e groups' own statistics: the record so far is set aside and reset in front of group gS
+    // (on the stream that group runs on, behind everything that came before it), merged back behind group gE - 1.
+    auto stats_aside = [&](hipStream_t S) -> int {
+        PYIPM_HIP(hipMemcpyAsync(st_before, ctx->dstats, sizeof(DevStats), hipMemcpyDeviceToDevice, S));
+        hipLaunchKernelGGL(k_init_stats, dim3(1), dim3(64), 0, S, ctx->dstats); PYIPM_KCHECK();
+        return 0;
+    };
     bool across_prev = false;
     for (int64_t grp = g0; grp + 1 < ngroups; ++grp) {
         const int64_t p0 = sc.first(grp), n0 = sc.size(grp);            // the source: its contribution goes to everything behind it
+        if (rec && le.ok && grp >= le.gS && grp < le.gE) {
+            // a lambda_e group, complete on the main stream: its W in the rows behind cE, before the buffer is recycled
+            const int64_t c0 = g.panel_c0(p0), rows = g.Npad - le.cE, cols = g.panel_c0(sc.first(grp + 1)) - c0;
+            hipLaunchKernelGGL(k_copy_cols, dim3((unsigned)cols, (unsigned)((rows + 2047) / 2048)), dim3(256), 0, ctx->stream,
+                               lam_e_w(ctx, le, c0), rows, (const double*)(wbuf(ctx, p0) + le.cE), g.Npad, rows, cols);
+            PYIPM_KCHECK();
+        }
+        if (rec && le.ok && grp + 1 == le.gE) {
+            // the last lambda_e group: as behind the prefix -- one update of everything behind it, the groups' own record, the
+            // second snapshot, then group gE, all on the main stream
+            tr.mark("bulk begin", grp, ctx->stream);
+            rc = timed_update(ctx, p0, n0, p0 + n0, np - (p0 + n0)); if (rc) return rc;
+            tr.mark("bulk end", grp, ctx->stream);
+            PYIPM_HIP(hipMemcpyAsync(st_lam_e, ctx->dstats, sizeof(DevStats), hipMemcpyDeviceToDevice, ctx->stream));
+            hipLaunchKernelGGL(k_merge_stats, dim3(1), dim3(64), 0, ctx->stream, ctx->dstats, (const DevStats*)st_before); PYIPM_KCHECK();
+            const int64_t ne = g.Npad - le.cE;
+            hipLaunchKernelGGL(k_copy_square, dim3((unsigned)ne, (unsigned)((ne + 2047) / 2048)), dim3(256), 0, ctx->stream, ctx->A, g.Npad,
+                               lam_e_square(ctx, le), ne, le.cE, 1);
+            PYIPM_KCHECK();
+            tr.mark("second snapshot end", grp, ctx->stream);
+            rc = run_group(ctx, run, le.gE, ctx->stream); if (rc) return rc;
+            PYIPM_HIP(hipEventRecord(ctx->ev_main, ctx->stream));
+            across_prev = false;
+            continue;
+        }
         if (rec && grp + 1 == gB) {
             // the last group of the prefix (complete on the main stream: group 0 ran there, every later one was joined behind its
             // chain): one update of everything behind it, the snapshot, then group gB -- all on the main stream, no lookahead
@@ -2155,6 +2324,7 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false, i
         tr.mark("chain+rows begin", grp + 1, st.cs);
         if (run.slack_first && st.nxt_fast)                              // its kernels ran up front: whoever follows on cs (= the main
             PYIPM_HIP(hipStreamWaitEvent(st.cs, ctx->ev_sfast, 0));      // stream: k_s_schur too) is ordered behind them
+        if (rec && le.ok && grp + 1 == le.gS) { rc = stats_aside(st.cs); if (rc) return rc; }
         rc = run_group(ctx, run, grp + 1, st.cs); if (rc) return rc;
         tr.mark("chain+rows end", grp + 1, st.cs);
         PYIPM_HIP(hipEventRecord(ctx->ev_panel, st.cs));
@@ -2366,6 +2536,7 @@ static int create_impl(pyipm_newton_ctx** out, int64_t n, int64_t me, int64_t mi
             { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) ctx->num_cus = ncu; }
             ctx->provider_only = provider_only;
             { const char* e = getenv("PYIPM_REUSE_X"); if (e && e[0] == '0') ctx->reuse_x = 0; }
+            { const char* e = getenv("PYIPM_REUSE_LAM_E"); if (e && e[0] == '0') ctx->reuse_lam_e = 0; }
             { const char* e = getenv("PYIPM_FWD_PREFIX"); if (e) { const int w = atoi(e); if (w <= 0) ctx->fwd_prefix = 0; else if (w >= 2) ctx->fwd_prefix_wgs = w; } }
         },
         [&](Ctx* ctx, char* base) { return carve_workspace(ctx, g, base, provider_only); },
@@ -3032,7 +3203,7 @@ int pyipm_newton_step(pyipm_newton_ctx* h, double delta, double delta_c, int ref
 int pyipm_newton_reuse_info(pyipm_newton_ctx* h, int64_t out[4]) try {
     PYIPM_ENTER("reuse_info", 0)
     if (!out) return PYIPM_E_BADARG;
-    out[0] = ctx->n_reused; out[1] = ctx->n_recorded; out[2] = (int64_t)(ctx->snap.capacity() * sizeof(double)); out[3] = ctx->last_step_kind;
+    out[0] = ctx->n_reused; out[1] = ctx->n_recorded; out[2] = (int64_t)((ctx->snap.capacity() + ctx->snap_e.capacity()) * sizeof(double)); out[3] = ctx->last_step_kind;
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
