@@ -220,7 +220,10 @@ int pyipm_newton_step(pyipm_newton_ctx* ctx, double delta, double delta_c, int r
  * group reaches beyond the x block never reuse.
  * A reusing step sends its right-hand side through the kept panels in one launch (k_fwd_prefix) where the one-launch sweeps apply
  * (sweep_persist, one rank, panels of at most 256 columns); PYIPM_FWD_PREFIX=0 at create time keeps the launches per panel,
- * PYIPM_FWD_PREFIX=W (W >= 2) sets the workgroups of that launch (default 96).  The same bits either way.
+ * PYIPM_FWD_PREFIX=W (W >= 2) sets the workgroups of that launch (default 96).  The same bits either way.  The kept panels behind
+ * the prefix (the closed-form slack panels, the kept lambda_e groups below) follow in a second launch of the same kind
+ * (k_fwd_range) under the same conditions; PYIPM_FWD_RANGE=0 at create time keeps their launches per panel, =W (W >= 2) sets its
+ * workgroups (default 32).  The same bits either way.
  * With me > 0 and mi > 0 a reusing step also keeps the groups of the schedule that lie wholly inside the lambda_e columns (at
  * least one such group, at least one group behind them; a group that straddles a border of lambda_e is factored): the slack
  * columns couple to lambda_i only, so those groups depend on the blocks and the shifts alone.  A second snapshot holds their W and

@@ -337,7 +337,7 @@ struct Ctx {
     int tile_step = 1;                    // stepped panel schedule (kernels_panel.hpp): one launch per diagonal tile (the rows inside the
                                           // diagonal block), one for the rows below it; panels of at most 4 tiles; same bits
     int sweep_max_blocks = 0;             // test hook: cap on the workgroups of the one-launch sweeps (0 = as many as the GPU holds)
-    int occ_fwd_sweep = 0, occ_bwd_sweep = 0, occ_fwd_prefix = 0;   // resident workgroups per CU of the one-launch sweeps (occupancy query, cached)
+    int occ_fwd_sweep = 0, occ_bwd_sweep = 0, occ_fwd_prefix = 0, occ_fwd_range = 0;   // resident workgroups per CU of the one-launch sweeps (occupancy query, cached)
     int sweep_persist = 1;                // single rank, one right-hand side: the backward sweep as ONE device-driven launch (k_bwd_sweep)
     DevBuf<double> sweep_buf;             // ... the near sums as the column owners hand them to workgroup 0 (Npad doubles, NaN = not there yet)
     DevBuf<double> ms_buf;                // solve_many: its column blocks, partials and refinement vectors (allocated on first use, grown on demand)
@@ -390,6 +390,14 @@ struct Ctx {
     PollWords fwdp_words{4096 + 8192,     // ... its own flags and progress words (at most 4096 panels and 8192 chunks: sweeps_in_one_launch)
                          "forward sweep over the kept panels (k_fwd_prefix): a poll timed out; the direction was NaN "
                          "(PYIPM_FWD_PREFIX=0 runs it panel by panel)"};
+    int fwd_range = 1;                    // ... and through the other kept panels (slack, lambda_e groups) in a second launch (k_fwd_range);
+    int fwd_range_wgs = 32;               // PYIPM_FWD_RANGE=0 at create time keeps their per-panel launches, =W (>= 2) sets its workgroups
+                                          // (32: a guest beside the first lambda_i chain and its head -- 16 .. 48 measure alike, 96 costs
+                                          //  0.1 ms of the step: profiles/fwd_range_ab.json)
+    int64_t fwd_range_key[8] = {-1, -1, -1, -1, -1, -1, -1, -1}, fwd_range_owned = 0;   // ... the chunks its owners share, and what they were counted for
+    PollWords fwdr_words{4096 + 8192,     // ... its own flags and progress words
+                         "forward sweep over the kept slack and lambda_e panels (k_fwd_range): a poll timed out; the direction was NaN "
+                         "(PYIPM_FWD_RANGE=0 runs it panel by panel)"};
     int last_step_kind = 0;               // 0 full, 1 recording, 2 reusing
     DevBuf<char> ws;                      // the workspace: the caller's (adopted) or the library's; capacity = the bytes the geometry needs
     // carved from workspace

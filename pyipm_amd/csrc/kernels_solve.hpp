@@ -12,6 +12,7 @@
 // last grid dimension (v + index*vstride); single-vector callers launch that dimension as 1 with stride 0.
 #pragma once
 #include "ctx.hpp"
+#include "fwd_range_plan.hpp"
 
 namespace pyipm {
 
@@ -822,6 +823,183 @@ __global__ __launch_bounds__(256) void k_fwd_prefix(const double* __restrict__ A
     else fwd_prefix_owner<64>(A, sg, P0, v, flag, prog, err, timeout, ys, ps, vres, &ok_s);
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_fwd_range: k_fwd_prefix's launch over the panels [Pa, Pb) of a reusing step's OTHER kept panels -- the closed-form slack panels
+// and the kept lambda_e groups, behind the prefix launch: flag[s - Pa], columns from s nb, the same chain,
+// the same owners (four waves = k_fwd_gemv's four sums, the ring of quarters, the resident chunks), panels ascending -- per row
+// the products of the per-panel launches in their order, the same bits.  A kernel of its own beside k_fwd_prefix, whose
+// instruction stream stays what it was.  In such a range not every panel reaches every chunk below it (a slack panel reaches its
+// lambda_i rows only), so what the chain waits for, which visit of an owner is final and which chunks have an owner at all come
+// from ONE statement of "the last panel of [Pa, s) that reaches chunk c" (fwd_range_plan.hpp): the chain waits for exactly the
+// value the final visit stores, or not at all; a chunk nobody reaches has no owner.  With Pa = 0 inside the x block that
+// statement is k_fwd_prefix's rule (tests/test_fwd_range_plan.py replays both).
+constexpr int FWDR_MAXOWN = 1024;       // chunks one row owner can hold the numbers of: fwd_range_grid (pyipm_newton.hip) launches only
+                                        // grids that stay inside -- the guard at the store below never drops a chunk of such a launch
+__device__ __forceinline__ FwdPlanGeo plan_geo(const SweepGeo& sg) { return FwdPlanGeo{sg.Npad, sg.n, sg.mi, sg.me, sg.nb, sg.skip}; }
+// A row owner: the chunks some panel of [Pa, Pb) reaches (fwd_plan_owned), numbered ascending m = 0 .. nlog - 1; mine are
+// m = blockIdx - 1 + k (gridDim - 1), their chunk numbers kept in `mine`.  KC = nb / 4: the columns of a panel that one wave takes.
+template <int KC>
+__device__ __forceinline__ void fwd_range_owner(const double* __restrict__ A, const SweepGeo& sg, int Pa, int Pb, double* v, unsigned* flag,
+                                                unsigned* prog, unsigned* err, unsigned long long timeout, double* ys,
+                                                double (*ps)[4][TB], double (*vres)[TB], int* ok_s, unsigned short* mine, int* wcnt)
+{
+    constexpr int Q = KC / 4;                                   // a quarter of them
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nb = sg.nb, cpp = nb / TB, nchunks = (int)(sg.Npad / TB);
+    const FwdPlanGeo pg = plan_geo(sg);
+    const int nown = (int)gridDim.x - 1, m0 = (int)blockIdx.x - 1;
+    // number the owned chunks, 256 candidates a round: a chunk's number is the count of owned chunks in front of it
+    int nlog = 0;
+    for (int cb = (Pa + 1) * cpp; cb < nchunks; cb += 256) {
+        const int c = cb + tid;
+        const bool own = c < nchunks && fwd_plan_owned(pg, Pa, Pb, c);
+        const unsigned long long bal = __ballot(own);
+        if (lane == 0) wcnt[wave] = __popcll(bal);
+        __syncthreads();
+        int mnum = nlog + __popcll(bal & ((1ull << lane) - 1ull));
+        for (int w = 0; w < 4; ++w) { if (w < wave) mnum += wcnt[w]; nlog += wcnt[w]; }
+        if (own && mnum % nown == m0 && mnum / nown < FWDR_MAXOWN) mine[mnum / nown] = (unsigned short)c;   // (the host guarantees the bound)
+        __syncthreads();
+    }
+    // a visit = (panel s, my chunk m below it that the panel reaches), panels ascending, my chunks ascending inside a panel
+    auto chunk_of = [&](int m) -> int { return (int)mine[(m - m0) / nown]; };
+    auto visit_at = [&](int& s, int& m) -> bool {              // the first visit at or behind (s, m); the same for every thread
+        for (; s < Pb; ++s, m = m0)
+            for (; m < nlog; m += nown) if (fwd_plan_visit(pg, s, chunk_of(m))) return true;
+        return false;
+    };
+    // L of a visit: la is a ring of four quarters, and a quarter is requested for the NEXT visit as soon as this visit has used
+    // it (L does not depend on y) -- a visit's columns are on their way one visit ahead, whatever flag[s] says
+    double la[KC];
+    auto request = [&](int q, int s, int m) {
+        const double* src = A + ((int64_t)chunk_of(m) * TB + lane) + ((int64_t)s * nb + wave) * sg.ld;
+        #pragma unroll
+        for (int j = Q * q; j < Q * q + Q; ++j) la[j] = ld_agent(src + (int64_t)(4 * j) * sg.ld);   // (an atomic load stays where it is written)
+    };
+    unsigned dirty = 0, seen = 0;                               // (wave 0) slots of vres that hold what v does not; slots loaded once
+    int s = Pa, m = m0;
+    bool more = visit_at(s, m);
+    if (!more) return;
+    #pragma unroll
+    for (int q = 0; q < 4; ++q) request(q, s, m);
+    int ys_of = -1, par = 0;
+    while (more) {
+        int sn = s, mn = m + nown;
+        const bool more_n = visit_at(sn, mn);
+        const int sr = more_n ? sn : s, mr = more_n ? mn : m;  // (behind the last visit: the same columns once more, unused -- no branch among the loads)
+        if (ys_of != s) {
+            // (all four waves agree before anyone leaves: a wave returning alone would leave the others at the barrier)
+            if (!sweep_wait(flag + (s - Pa), 1u, err, timeout)) *ok_s = 0;
+            __syncthreads();
+            if (!*ok_s) return;
+            if (tid < nb) ys[tid] = ld_agent(v + (int64_t)s * nb + tid);
+            __syncthreads();
+            ys_of = s;
+        }
+        double acc = 0.0;
+        #pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            #pragma unroll
+            for (int j = Q * q; j < Q * q + Q; ++j) acc = fma(la[j], ys[wave + 4 * j], acc);
+            request(q, sr, mr);
+        }
+        ps[par][wave][lane] = acc;
+        __syncthreads();
+        // (ps has two halves: wave 0 reads this one while the others fill the next visit's; ys changes only behind a barrier that wave 0 joins)
+        if (wave == 0) {
+            const double t4 = (ps[par][0][lane] + ps[par][1][lane]) + (ps[par][2][lane] + ps[par][3][lane]);
+            const int c = chunk_of(m), k = (m - m0) / nown;     // my k-th chunk: resident in slot k while k < FWDP_RESIDENT
+            double* vp = v + (int64_t)c * TB + lane;
+            const bool res = k < FWDP_RESIDENT;
+            double x;
+            if (res && ((seen >> k) & 1u)) x = vres[k][lane]; else x = ld_agent(vp);
+            x -= t4;
+            // final for its reader: a chunk of a panel of the range after the last panel that reaches it (the chain waits for exactly
+            // that value of prog[c]); a chunk below the range when the owner's visits end; a chunk without a slot goes home every visit
+            const bool fin = fwd_plan_final(pg, Pa, Pb, s, c);
+            if (!res || fin) {
+                st_agent(vp, x);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (lane == 0) __hip_atomic_store(prog + c, (unsigned)(s + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (res) dirty &= ~(1u << k);
+            } else {
+                vres[k][lane] = x;
+                dirty |= 1u << k;
+            }
+            if (res) seen |= 1u << k;
+        }
+        par ^= 1;
+        s = sn; m = mn; more = more_n;
+    }
+    if (wave == 0) {                                            // what is still resident: the chunks below the range
+        for (int k = 0; k < FWDP_RESIDENT; ++k)
+            if ((dirty >> k) & 1u) st_agent(v + (int64_t)chunk_of(m0 + k * nown) * TB + lane, vres[k][lane]);
+    }
+}
+
+// Hand-over as in k_fwd_prefix: relaxed agent-scope atomics for all that crosses workgroups, s_waitcnt for order, every poll with a
+// timeout, a sticky error word; on error the range's rows of v become NaN.  256 threads; panels of 128 or 256 columns.
+__global__ __launch_bounds__(256) void k_fwd_range(const double* __restrict__ A, SweepGeo sg, int Pa, int Pb, double* v, unsigned* sync,
+                                                   unsigned* err, unsigned long long timeout)
+{
+    __shared__ double ys[4 * TB];
+    __shared__ double ps[2][4][TB];
+    __shared__ double vres[FWDP_RESIDENT][TB];                  // (wave 0 of a row owner: lane l keeps row l of its k-th chunk)
+    __shared__ unsigned short mine[FWDR_MAXOWN];                // (a row owner: the chunks that are its own, ascending)
+    __shared__ int wcnt[4];
+    __shared__ int ok_s;
+    const int tid = threadIdx.x;
+    const int nb = sg.nb, cpp = nb / TB;                        // chunks (= tiles) per panel
+    unsigned* flag = sync; unsigned* prog = sync + (Pb - Pa);   // flag[s - Pa]; prog[c]: s + 1 of the last panel s stored into the 64-row chunk c
+    if (tid == 0) ok_s = 1;
+    __syncthreads();
+    if (blockIdx.x == 0) {
+        for (int s = Pa; s < Pb; ++s) {
+            const int64_t c0 = (int64_t)s * nb;
+            const bool below0 = tid >= TB && tid < nb;          // rows of the tiles behind tile 0
+            double lt[TB];
+            if (below0) {
+                const double* col = A + (c0 + tid) + c0 * sg.ld;
+                #pragma unroll
+                for (int k = 0; k < TB; ++k) lt[k] = col[(int64_t)k * sg.ld];
+            }
+            if (tid < cpp) {                                    // the last panel that reaches this chunk has stored it -- or nobody does
+                const int p = fwd_plan_chain_waits(plan_geo(sg), Pa, s, s * cpp + tid);
+                if (p >= 0 && !sweep_wait(prog + s * cpp + tid, (unsigned)(p + 1), err, timeout)) ok_s = 0;
+            }
+            __syncthreads();
+            if (!ok_s) break;
+            if (tid < nb) ys[tid] = ld_agent(v + c0 + tid);
+            for (int u = 0; u + 1 < cpp; ++u) {
+                __syncthreads();
+                if (tid >= (u + 1) * TB && tid < nb) {
+                    double acc = 0.0;
+                    #pragma unroll
+                    for (int k = 0; k < TB; ++k) acc = fma(lt[k], ys[u * TB + k], acc);
+                    if (tid >= (u + 2) * TB) {
+                        // the next step's 64 columns, all requested at once and across its barrier (see k_fwd_prefix)
+                        const double* col = A + c0 + (c0 + (int64_t)(u + 1) * TB) * sg.ld;
+                        __builtin_amdgcn_sched_barrier(0);
+                        #pragma unroll
+                        for (int k = 0; k < TB; ++k) lt[k] = ld_agent(col + (int64_t)k * sg.ld + tid);
+                    }
+                    ys[tid] -= acc;
+                }
+            }
+            __syncthreads();
+            if (tid < nb) st_agent(v + c0 + tid, ys[tid]);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            if (tid == 0) __hip_atomic_store(flag + (s - Pa), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        __syncthreads();
+        if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)
+            for (int64_t i = (int64_t)Pa * nb + tid; i < (int64_t)Pb * nb; i += 256) st_agent(v + i, __builtin_nan(""));
+        return;
+    }
+    if (cpp == 2) fwd_range_owner<32>(A, sg, Pa, Pb, v, flag, prog, err, timeout, ys, ps, vres, &ok_s, mine, wcnt);
+    else fwd_range_owner<64>(A, sg, Pa, Pb, v, flag, prog, err, timeout, ys, ps, vres, &ok_s, mine, wcnt);
+}
 // v[i] = b[i] on the rows of the panels this rank owns, 0 elsewhere: the ranks' vectors sum to b (distributed sweeps)
 __global__ __launch_bounds__(256) void k_mask_owned(double* __restrict__ v, const double* __restrict__ b, Geo g)
 {

@@ -1064,14 +1064,15 @@ pyipm_factor_stats to_stats(const DevStats& z) {
 int factor_end(Ctx* ctx, pyipm_factor_stats* stats) {
     DevStats z;
     PYIPM_HIP(hipMemcpyAsync(&z, ctx->dstats, sizeof(z), hipMemcpyDeviceToHost, ctx->stream));
-    // the error words of the device-driven launches, in the order they are reported in.  (prefix sweep: the main stream has joined
+    // the error words of the device-driven launches, in the order they are reported in.  (prefix and range sweeps: the main stream has joined
     // ctx->fwd by now, this step's launch is behind us.)  `used` falls once the word has been read, whatever it held.
-    PollWords* const pw[3] = {&ctx->chain_words, &ctx->sweep_words, &ctx->fwdp_words};
-    int perr[3] = {0, 0, 0};
-    for (int k = 0; k < 3; ++k) if (pw[k]->used && pw[k]->buf) PYIPM_HIP(pw[k]->fetch_err(&perr[k], ctx->stream));
+    constexpr int NPW = 4;
+    PollWords* const pw[NPW] = {&ctx->chain_words, &ctx->sweep_words, &ctx->fwdp_words, &ctx->fwdr_words};
+    int perr[NPW] = {0, 0, 0, 0};
+    for (int k = 0; k < NPW; ++k) if (pw[k]->used && pw[k]->buf) PYIPM_HIP(pw[k]->fetch_err(&perr[k], ctx->stream));
     PYIPM_HIP(hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 3; ++k) pw[k]->used = false;
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < NPW; ++k) pw[k]->used = false;
+    for (int k = 0; k < NPW; ++k) {
         if (!perr[k]) continue;
         PYIPM_HIP(pw[k]->clear_err(ctx->stream));
         if (pw[k] == &ctx->chain_words) ctx->held.factor_invalid();
@@ -1294,6 +1295,44 @@ static int fwd_prefix(Ctx* ctx, int64_t P0, double* v, hipStream_t stream) {
     PYIPM_KCHECK();
     hipLaunchKernelGGL(k_diag_apply, dim3((unsigned)(P0 * g.nb / TB), 1), dim3(64), 0, stream, ctx->Dinv, ctx->Tsv, ctx->Tflag,
                        ctx->block_refine, (int64_t)0, (int64_t)0, v, (int64_t)0);
+    PYIPM_KCHECK();
+    fw.used = true;
+    return 0;
+}
+
+// The other kept panels of a reusing step, [Pa, Pb) behind the prefix -- the closed-form slack panels and the kept lambda_e groups --
+// in one launch of their own (k_fwd_range + one k_diag_apply over their tiles) in place of (Pb - Pa) x 3 dependent launches: the
+// same bits (panels ascending, k_fwd_gemv's sums).  Its words are its own: the prefix launch in front of it may still be polling its.
+// fwd_range_grid: the workgroups of that launch, 0 where it does not apply (every owner must be able to number its chunks).
+static unsigned fwd_range_grid(Ctx* ctx, int64_t Pa, int64_t Pb) {
+    const Geo& g = ctx->g;
+    if (!ctx->fwd_range || Pb <= Pa || Pb >= g.npanels) return 0;
+    if (resident_per_cu(ctx, &ctx->occ_fwd_range, k_fwd_range, 256, nullptr) || ctx->occ_fwd_range < 1) return 0;
+    const SweepGeo sg = sweep_geo(ctx);
+    // the owned chunks of the range: a function of the geometry and the range alone, counted once and kept (the enqueue path of
+    // every reusing step comes through here)
+    const int64_t key[8] = {sg.Npad, sg.n, sg.mi, sg.me, sg.nb, sg.skip, Pa, Pb};
+    if (memcmp(key, ctx->fwd_range_key, sizeof(key)) != 0) {
+        const FwdPlanGeo pg{sg.Npad, sg.n, sg.mi, sg.me, sg.nb, sg.skip};
+        int64_t owned = 0;
+        for (int64_t c = (Pa + 1) * (g.nb / TB); c < g.Npad / TB; ++c) owned += fwd_plan_owned(pg, (int)Pa, (int)Pb, (int)c) ? 1 : 0;
+        memcpy(ctx->fwd_range_key, key, sizeof(key)); ctx->fwd_range_owned = owned;
+    }
+    const int64_t owned = ctx->fwd_range_owned;
+    const unsigned blocks = sweep_grid(ctx, 1 + owned, ctx->occ_fwd_range, 2, ctx->fwd_range_wgs);
+    // (k_fwd_range's owners hold the numbers of at most FWDR_MAXOWN chunks each: a grid that would give one more is not launched)
+    return (owned + blocks - 2) / (blocks - 1) <= FWDR_MAXOWN ? blocks : 0;
+}
+static int fwd_range(Ctx* ctx, int64_t Pa, int64_t Pb, unsigned blocks, double* v, hipStream_t stream) {
+    const Geo& g = ctx->g;
+    PollWords& fw = ctx->fwdr_words;
+    PYIPM_HIP(fw.ensure(stream));
+    PYIPM_HIP(fw.arm((size_t)((Pb - Pa) + g.Npad / TB), stream));
+    hipLaunchKernelGGL(k_fwd_range, dim3(blocks), dim3(256), 0, stream, ctx->A, sweep_geo(ctx), (int)Pa, (int)Pb, v, fw.buf.get(), fw.err(),
+                       POLL_TIMEOUT);
+    PYIPM_KCHECK();
+    hipLaunchKernelGGL(k_diag_apply, dim3((unsigned)((Pb - Pa) * g.nb / TB), 1), dim3(64), 0, stream, ctx->Dinv, ctx->Tsv, ctx->Tflag,
+                       ctx->block_refine, Pa * g.nb / TB, Pa * g.nb, v, (int64_t)0);
     PYIPM_KCHECK();
     fw.used = true;
     return 0;
@@ -1998,6 +2037,7 @@ struct FactorRun {                     // what holds for one whole factorisation
     bool early0;                       // group 0 goes to the columns beyond it panel by panel (panel_done)
     bool slack_first;                  // the closed-form panels of the slack block were enqueued up front (enqueue_slack_first) ...
     bool done_early(const Ctx* ctx, int64_t q) const { return slack_first && ctx->sched.fast_panel(q); }   // ... panel q was
+    int64_t fr_a = 0, fr_b = 0;        // panels [fr_a, fr_b): their forward substitution runs in one launch of its own (fwd_range), not here
 };
 
 // Panel q of group grp is complete once `used` reaches this point.  The fused forward substitution takes it up.
@@ -2013,7 +2053,7 @@ struct FactorRun {                     // what holds for one whole factorisation
 // (n, me, mi = 3072, 512, 1024: 2.99 -> 3.08 ms): not applied there.  Fewer, persistent blocks per piece (64 ... 192
 // of them) only made the last piece longer.
 static int panel_done(Ctx* ctx, const FactorRun& run, int64_t grp, int64_t q, hipStream_t used) {
-    if (run.fuse_forward) {
+    if (run.fuse_forward && !(q >= run.fr_a && q < run.fr_b)) {
         if (!run.done_early(ctx, q)) PYIPM_HIP(hipEventRecord(ctx->ev_done[q], used));      // (else: recorded behind its kernel)
         PYIPM_HIP(hipStreamWaitEvent(ctx->fwd, ctx->ev_done[q], 0));
         int r2 = fwd_panel(ctx, q, ctx->fwd_vec, ctx->fwd); if (r2) return r2;
@@ -2175,8 +2215,18 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false, i
     //  front of column n + mi)
     DevStats* const st_before = le.ok ? (DevStats*)ctx->snap_e.get() : nullptr;
     DevStats* const st_lam_e = le.ok ? (DevStats*)(ctx->snap_e.get() + 16) : nullptr;
-    const FactorRun run{fuse_forward, !px && ctx->lookahead >= 2 && ngroups > 2 && chain_group(ctx, 0) && sc.fast(1),
-                        !rec && slack_first_applies(ctx)};
+    FactorRun run{fuse_forward, !px && ctx->lookahead >= 2 && ngroups > 2 && chain_group(ctx, 0) && sc.fast(1),
+                  !rec && slack_first_applies(ctx)};
+    // The kept panels behind the prefix in one launch (fwd_range): the slack panels and the lambda_e groups where every group in
+    // [gB, gS) is closed-form and was enqueued up front, the lambda_e groups alone where one of them is factored this step.
+    int64_t frA = 0, frB = 0; unsigned fr_blocks = 0; bool fr_slack = false;
+    if (reuse && fuse_forward && le.ok && fwd_prefix_applies(ctx, sc.first(gB))) {
+        fr_slack = run.slack_first;
+        for (int64_t grp = gB; grp < le.gS; ++grp) fr_slack = fr_slack && sc.fast(grp);
+        frA = sc.first(fr_slack ? gB : le.gS); frB = sc.first(le.gE);
+        fr_blocks = fwd_range_grid(ctx, frA, frB);
+        if (fr_blocks) { run.fr_a = frA; run.fr_b = frB; }
+    }
     GroupTrace tr;
     if (tr.on()) {
         fprintf(stderr, "[pyipm group trace] %s step%s\n", rec ? "recording" : reuse ? "reusing" : "full",
@@ -2210,6 +2260,11 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false, i
             }
         }
         tr.mark("fwd prefix end (before group)", gB, ctx->fwd);
+        if (fr_blocks && fr_slack) {        // ... and on through the slack panels (complete at ev_sfast) and the kept lambda_e groups
+            PYIPM_HIP(hipStreamWaitEvent(ctx->fwd, ctx->ev_sfast, 0));
+            rc = fwd_range(ctx, frA, frB, fr_blocks, ctx->fwd_vec, ctx->fwd); if (rc) return rc;
+            tr.mark("fwd kept range end", gB, ctx->fwd);
+        }
     }
     if (reuse && le.ok) {
         // The groups between the prefix and the kept lambda_e groups (the slack group, a group that straddles a border), one after
@@ -2229,9 +2284,13 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false, i
         }
         // ... the kept groups: their forward substitution waits for nothing, their products go to the diagonal blocks
         tr.mark("diagonal blocks begin", le.gS, ctx->stream);
+        if (fr_blocks && !fr_slack) {       // (one launch behind the panels of [gB, gS), which went panel by panel)
+            rc = fwd_range(ctx, frA, frB, fr_blocks, ctx->fwd_vec, ctx->fwd); if (rc) return rc;
+            tr.mark("fwd kept range end", le.gS, ctx->fwd);
+        }
         for (int64_t grp = le.gS; grp < le.gE; ++grp) {
             const int64_t p0 = sc.first(grp), n0 = sc.size(grp), c0 = g.panel_c0(p0);
-            if (fuse_forward)
+            if (fuse_forward && !fr_blocks)
                 for (int64_t q = p0; q < p0 + n0; ++q) {
                     rc = fwd_panel(ctx, q, ctx->fwd_vec, ctx->fwd); if (rc) return rc;
                     rc = diag_panel(ctx, q, ctx->fwd_vec, ctx->fwd); if (rc) return rc;
@@ -2538,6 +2597,7 @@ static int create_impl(pyipm_newton_ctx** out, int64_t n, int64_t me, int64_t mi
             { const char* e = getenv("PYIPM_REUSE_X"); if (e && e[0] == '0') ctx->reuse_x = 0; }
             { const char* e = getenv("PYIPM_REUSE_LAM_E"); if (e && e[0] == '0') ctx->reuse_lam_e = 0; }
             { const char* e = getenv("PYIPM_FWD_PREFIX"); if (e) { const int w = atoi(e); if (w <= 0) ctx->fwd_prefix = 0; else if (w >= 2) ctx->fwd_prefix_wgs = w; } }
+            { const char* e = getenv("PYIPM_FWD_RANGE"); if (e) { const int w = atoi(e); if (w <= 0) ctx->fwd_range = 0; else if (w >= 2) ctx->fwd_range_wgs = w; } }
         },
         [&](Ctx* ctx, char* base) { return carve_workspace(ctx, g, base, provider_only); },
         2 /* [0] max |entry|, [1] "assembly pending" */, true);
