@@ -484,6 +484,50 @@ int pyipm_newton_merit_info_batched(pyipm_newton_ctx* ctx, const double* dz, dou
 int pyipm_newton_merit_ray_batched(pyipm_newton_ctx* ctx, const double* dz, const double* nu, const double* mu, const double* quad,
                                    const double* alphas, int K, double* out, int memkind);
 
+/* The kept factors of a batch as a solver: after a step every problem holds its factor, its own shifts and (condensed form) its
+ * active set; these three entries work against them as solve / solve_many, kkt_matvec and rcond do on a single-system handle
+ * -- refinement against the blocks, the rcond <= eps test of reghess (pyipm.py:1379-1381), extra right-hand sides
+ * (pyipm.py:18-20, 911-914).  Plain launches, no atomics or waits between workgroups, every sum over a partition and in an
+ * order the problem's sizes alone decide: the bits of a column depend neither on k, nor on its place among the columns, nor on
+ * the batch size or the problem's place in the batch.  None of them writes the factor, the kept residual, the statistics or a
+ * kept host-output direction: a following backward_error_batched, step_lengths_batched(dz = NULL) or step returns the bits
+ * it would have returned without the call.  The factors, shifts and active sets are those of a step's blocks AND vectors
+ * (a condensed solve rebuilds Sigma from the staged s, lda): staging blocks or vectors again drops them -- all three entries
+ * then return PYIPM_E_BADARG until the next step.  Scratch is the library's own buffer outside the workspace, grown on demand
+ * (pyipm_newton_workspace_bytes_batched is unchanged).
+ *
+ * solve_batched -- x = inv(Hc_b) rhs for k columns per problem (pyipm.py:1718-1725 for any right-hand side) against the factor
+ *   of the last step each problem took part in: the matrix with THAT problem's shifts, full or condensed as that step was (a
+ *   condensed factor: each column is reduced as the step reduces its residual, the sweeps run over n + me + |A| rows, the full
+ *   [dx|ds|dle|dli] is recovered).  Column j of problem b: rhs + b stride_rhs + j ld_rhs (doubles), likewise x; ld >= N, entries
+ *   N .. ld - 1 are not written; x may BE rhs (same pointer, ld and stride: solved in place -- with refine > 0 the library keeps
+ *   a copy of the right-hand sides for the residuals); any other overlap of the two device blocks is PYIPM_E_BADARG.  active: batch flags or
+ *   NULL = every problem; a problem with active[b] == 0 (or one no step has factored yet) costs workgroups that return at
+ *   once, its columns of x are NOT written.  flip != 0: rows n + mi .. N - 1 negated (the reference's multiplier sign).
+ *   refine > 0: that many steps R = B - Hc X; X += solve(R) with Hc from the blocks (kkt_matvec_batched's kernel);
+ *   refine < 0 (adaptive on a single system): PYIPM_E_BADARG -- a column's bits never depend on its neighbours.
+ *   k == 0 returns 0.  Device pointers: asynchronous on the handle's stream; host pointers are staged and the call synchronises.
+ *   PYIPM_E_BADARG: not a batched handle, no step yet, a NULL pointer, ld < N, k < 0 or k > 65535, refine < 0.
+ * kkt_matvec_batched -- y = Hc_b v for k columns per problem from the staged blocks (never the factor), with the problem's own
+ *   delta / delta_c of its last step and Sigma = lda / (s + eps) of the staged vectors (pyipm.py:824-842); raw sign, no flip.
+ *   The blocks are read once per chunk of 8 columns.  y must not overlap v.  Needs staged blocks and vectors and one step.
+ * rcond_batched -- out[b][4] = the quantities of pyipm_newton_rcond for problem b (pyipm.py:1379-1381): the min|w| estimate from
+ *   it_inv inverse iterations (solve_batched's kernel), the max|w| estimate from it_pow power iterations (kkt_matvec_batched's
+ *   kernel), their ratio, and the static-pivot magnitude sqrt(eps) max|Hc_b|.  0 = the defaults 3 / 6; negative (adaptive)
+ *   counts: PYIPM_E_BADARG.  Start vectors as pyipm_newton_rcond's; norms and normalisation by one wave per problem in a
+ *   fixed order.  Where a problem's factor holds static pivots (n_zero > 0) it is the factor of a matrix perturbed at the
+ *   level of the fourth quantity, and inverse iteration alone finds THAT matrix' smallest eigenvalue; there the iterate x is
+ *   taken back to the unperturbed blocks, x' = x - inv(factored)(Hc x), and |Hc x'| / |x'| (an upper bound of min|w| of Hc
+ *   for any x') replaces the estimate where it is smaller: a singular Hc_b reads as singular (rcond at rounding level)
+ *   although its factor is not.  active as above (rows of out of the others are not written).  Full form only: PYIPM_E_BADARG when the
+ *   handle's last step was condensed; NaN for a problem that still holds a condensed factor from an earlier step.
+ *   out: host (synchronises) or device per memkind, and active with it. */
+int pyipm_newton_solve_batched(pyipm_newton_ctx* ctx, int64_t k, const double* rhs, int64_t ld_rhs, int64_t stride_rhs,
+                               double* x, int64_t ld_x, int64_t stride_x, const int32_t* active, int flip, int refine, int memkind);
+int pyipm_newton_kkt_matvec_batched(pyipm_newton_ctx* ctx, int64_t k, const double* v, int64_t ld_v, int64_t stride_v,
+                                    double* y, int64_t ld_y, int64_t stride_y, int memkind);
+int pyipm_newton_rcond_batched(pyipm_newton_ctx* ctx, int it_inv, int it_pow, const int32_t* active, double* out, int memkind);
+
 /* ---- introspection for tests / bench ------------------------------------------------------ */
 
 /* Device pointer + leading dimension of the local KKT storage (column-major lower).  The caller may write through the
@@ -601,7 +645,8 @@ int pyipm_newton_set_option(pyipm_newton_ctx* ctx, const char* name, double valu
  * device direction goes).  A binding checks pyipm_newton_abi_version() == PYIPM_NEWTON_ABI_VERSION of the header it was
  * written against before any other call (pyipm_amd/newton.py does).  7: step_batched_each, step_lengths_batched; the
  * workspace of a batched handle grew by the per-problem parameters.  8: block_products_batched, block_products_t_batched,
- * merit_info_batched, merit_ray_batched. */
+ * merit_info_batched, merit_ray_batched.  (Still 8: solve_batched, kkt_matvec_batched, rcond_batched -- entries added, no
+ * argument list, layout or workspace size changed.) */
 #define PYIPM_NEWTON_ABI_VERSION 8
 int pyipm_newton_abi_version(void);
 

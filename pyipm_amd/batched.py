@@ -292,6 +292,66 @@ class BatchedNewton(object):
                                                          MEM_DEVICE))
         return out
 
+    # -- the kept factors as a solver (pyipm_newton_solve_batched / kkt_matvec_batched / rcond_batched) ----------------------
+    def _columns(self, a, who):
+        """(B, N) or (B, k, N) as a contiguous float64 device tensor (B, k, N), and whether it came without the k axis."""
+        t = to_device(a, self.device)
+        flat = t.dim() == 2
+        if flat:
+            t = t.unsqueeze(1)
+        if t.dim() != 3 or t.shape[0] != self.batch or t.shape[2] != self.N:
+            raise NewtonError("%s: expected (B, N) or (B, k, N) with B = %d, N = %d" % (who, self.batch, self.N))
+        return t.to(self.torch.float64).contiguous(), flat
+
+    def solve_all(self, rhs, flip=True, refine=0, active=None, out=None):
+        """``inv(Hc_b) rhs_b`` for every problem against the factor its last step left -- the matrix with that problem's own
+        shifts, full or condensed as that step was.  ``rhs``: (B, N) or (B, k, N); returns a device tensor of the same shape
+        (``out``: a contiguous float64 tensor of that shape to write into; it may be ``rhs`` itself: solved in place).  ``flip``: rows n + mi .. negated, as the steps
+        return directions.  ``refine``: that many steps ``R = B - Hc X; X += solve(R)`` against the blocks (>= 0).
+        ``active`` ((B,) flags; None = all): the rows of the other problems are not written (NaN in a new tensor)."""
+        self._staged_handle("solve_all")
+        t = self.torch
+        r, flat = self._columns(rhs, "solve_all")
+        k = int(r.shape[1])
+        pa = None if active is None else self._per_problem(active, t.int32)
+        if out is None:
+            x = t.empty_like(r)
+            if pa is not None:
+                x.fill_(float("nan"))
+        else:
+            if tuple(out.shape) != tuple(rhs.shape) or out.dtype != t.float64 or not out.is_contiguous() or out.device != self.device:
+                raise NewtonError("solve_all: out must be a contiguous float64 device tensor of rhs' shape")
+            x = out.unsqueeze(1) if flat else out
+        N = self.N
+        self._ck(self.lib.pyipm_newton_solve_batched(self.h, k, ptr(r), N, k * N, ptr(x), N, k * N, ptr(pa), int(bool(flip)),
+                                                     int(refine), MEM_DEVICE))
+        return out if out is not None else (x.squeeze(1) if flat else x)
+
+    def kkt_matvec_all(self, v):
+        """``Hc_b v_b`` for every problem from the staged blocks (never the factor), with each problem's own shifts of its last
+        step and Sigma of the staged vectors; raw sign.  ``v``: (B, N) or (B, k, N); a device tensor of the same shape."""
+        self._staged_handle("kkt_matvec_all")
+        vv, flat = self._columns(v, "kkt_matvec_all")
+        k, N = int(vv.shape[1]), self.N
+        y = self.torch.empty_like(vv)
+        self._ck(self.lib.pyipm_newton_kkt_matvec_batched(self.h, k, ptr(vv), N, k * N, ptr(y), N, k * N, MEM_DEVICE))
+        return y.squeeze(1) if flat else y
+
+    RCOND_KEYS = ("w_min", "w_max", "rcond", "static_pivot")     # columns of rcond_all (NewtonCore.rcond's four)
+
+    def rcond_all(self, it_inv=0, it_pow=0, active=None):
+        """The condition estimate of every problem (``pyipm_newton_rcond_batched``): device tensor (B, 4), columns as
+        RCOND_KEYS -- min|w| from ``it_inv`` inverse iterations with the kept factor, max|w| from ``it_pow`` power iterations
+        with the blocks (0 = 3 / 6), their ratio, and the magnitude of a static pivot.  Where a factor holds static pivots
+        the min|w| estimate is corrected against the unperturbed blocks, so a singular member reads as singular.  Full form
+        only.  ``active``: the rows of the other problems are NaN."""
+        self._staged_handle("rcond_all")
+        t = self.torch
+        pa = None if active is None else self._per_problem(active, t.int32)
+        out = t.full((self.batch, 4), float("nan"), dtype=t.float64, device=self.device)
+        self._ck(self.lib.pyipm_newton_rcond_batched(self.h, int(it_inv), int(it_pow), ptr(pa), ptr(out), MEM_DEVICE))
+        return out
+
     n_factor = 0                           # passes over the batch (direction_all)
     n_inertia_retries = 0                  # problem x shifted pass whose inertia was still wrong (delta *= 10, pyipm.py:1399-1403)
     _shift_info = None

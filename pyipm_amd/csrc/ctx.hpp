@@ -139,6 +139,8 @@ struct Held {
     bool have_rhs = false;                // rhs holds g = -grad of the staged vectors
     bool assembled = false, factored = false;
     bool cond_active = false;             // the current assembled / factored matrix is the condensed one
+    bool batch_stepped = false;           // batched handle: a step has been enqueued -- the problems that took part hold a factor, their
+                                          // shifts and (condensed) their active sets; nothing of the solve_batched family writes any of it
     bool forward_fused = false;           // the last factor_all ran a forward substitution under itself
     bool forward_pending = false;         // v1 = the staged right-hand side, v0 (vc: condensed) = its forward pass: solve(rhs = NULL) starts at the diagonal
     bool fwd_done = false;                // the same for the distributed driver: its vloc holds the forward pass.  A field of its own: it
@@ -190,9 +192,10 @@ struct Held {
         if (px_steps > 0 && !px_reused) px_record = false;
         px_valid = false; px_steps = 0; px_reused = false;
         if (forget) { ray_valid = false; rc_warm_cold(); }
+        batch_stepped = false;            // (the kept factors, shifts and active sets belong to the blocks and vectors of their step)
     }
     // g = -grad belongs to the vectors staged before, and so does the merit function along the kept ray.
-    void vectors_staged() { have_vectors = true; have_rhs = false; ray_valid = false; }
+    void vectors_staged() { have_vectors = true; have_rhs = false; ray_valid = false; batch_stepped = false; }
     // rhs is rewritten: a forward pass that ran on the old one is worthless.
     void residual_formed() { have_rhs = true; forward_pending = false; }
     // Assembly, in two halves around its launches.  The condensed system lives in the same storage with another layout, so the
@@ -230,7 +233,7 @@ struct Held {
     void step_batched_begun(bool condensed) { cond_active = condensed; }
     // rhs = g of every problem (backward_error_batched reads it).  v2 is the staging copy of a HOST output: the directions of the
     // problems that took part (step_lengths_batched with dz = NULL reads it); a device output is the caller's tensor alone.
-    void step_batched_enqueued(bool host_out) { have_rhs = true; ev_assemble_valid = true; have_direction = host_out; }
+    void step_batched_enqueued(bool host_out) { have_rhs = true; ev_assemble_valid = true; have_direction = host_out; batch_stepped = true; }
     // Factorisation.  Per-panel phases (the caller or the distributed driver drives the panels): no promise about what gets written.
     void panel_phases_begun() { zeros_clean = false; px_valid = false; }
     void factor_begun() { forward_fused = false; }
@@ -306,6 +309,11 @@ struct Ctx {
     int *b_act = nullptr, *b_in_act = nullptr;
     DevBuf<double> b_merit_buf;           // merit pieces of a batched handle (outside the workspace, allocated on first use, grown on demand):
                                           // [info B x 16 | gq B x 2 | dce B x me | dci B x mi | nu, mu, quad B each | alphas B x K | ray out B x K]
+    DevBuf<double> b_solve_buf;           // scratch of solve_batched / kkt_matvec_batched / rcond_batched (outside the workspace, grown on demand):
+                                          // the staged mask, staged host columns, the residual / correction of a refinement step, the
+                                          // iteration vectors and running estimates of the condition estimate
+    DevBuf<int> b_form;                   // [batch]: which factor each problem holds -- 0 full, 1 condensed (k_b_begin writes it), -1 none yet
+    bool b_any_cond = false;              // some step of this handle ran condensed: a problem may hold a condensed factor
     int device = 0;
     hipStream_t stream = nullptr;         // the caller's: not owned
     Stream side;                          // panel lookahead stream (created on first factor)

@@ -690,15 +690,19 @@ __global__ __launch_bounds__(1024) void k_sumsq2(double* __restrict__ out, const
 }
 
 // Deterministic pseudo-random start vector in [-1, 1) for the eigenvalue estimates (zero in the pad).
-__global__ __launch_bounds__(256) void k_hash_vector(double* __restrict__ out, int64_t N, int64_t Npad, unsigned long long seed)
+__device__ __forceinline__ double hash_entry(int64_t i, unsigned long long seed)
 {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= Npad) return;
     unsigned long long z = (unsigned long long)i + seed * 0x9E3779B97F4A7C15ull + 0x9E3779B97F4A7C15ull;   // splitmix64
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     z ^= z >> 31;
-    out[i] = (i < N) ? (double)(z >> 11) * (2.0 / 9007199254740992.0) - 1.0 : 0.0;
+    return (double)(z >> 11) * (2.0 / 9007199254740992.0) - 1.0;
+}
+__global__ __launch_bounds__(256) void k_hash_vector(double* __restrict__ out, int64_t N, int64_t Npad, unsigned long long seed)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= Npad) return;
+    out[i] = (i < N) ? hash_entry(i, seed) : 0.0;
 }
 
 // out = alpha * in

@@ -38,7 +38,7 @@ struct BatchEach {
 // First launch of every batched step (grid ceil(B / 256)): the activity flags, and for the problems that take part their
 // parameters and the reset of their anorm words.  A problem that sits out keeps all of it -- mu, shifts, the scale of its
 // static pivots: the values of the last step it took part in.
-__global__ __launch_bounds__(256) void k_b_begin(BatchPtrs bp, BatchEach in, int B)
+__global__ __launch_bounds__(256) void k_b_begin(BatchPtrs bp, BatchEach in, int B, int* __restrict__ form, int cond)
 {
     const int b = (int)(blockIdx.x * 256 + threadIdx.x);
     if (b >= B) return;
@@ -49,6 +49,7 @@ __global__ __launch_bounds__(256) void k_b_begin(BatchPtrs bp, BatchEach in, int
     bp.pdelta[b] = in.delta ? in.delta[b] : in.delta0;
     bp.pdelta_c[b] = in.delta_c ? in.delta_c[b] : in.delta_c0;
     bp.anorm[2 * b] = 0ull; bp.anorm[2 * b + 1] = 0ull;
+    form[b] = cond;                                      // which factor the problem holds from now on (k_b_solve_many): 0 full, 1 condensed
 }
 
 // The condensed form of a batched step (round 5; the big path's option, DESIGN section 7b, per problem): inequalities with
@@ -463,67 +464,132 @@ __global__ __launch_bounds__(128 * NX) void k_bc_assemble_p(BatchPtrs bp, Geo g,
                 if (idx % (2 * NX) == wave) bc_store_strip(bp, g, bc, b, rt, ct, sw, zero, eps, delta, delta_c, na);
 }
 
+// Hc_b applied to NC vectors at once from the KKT blocks (never the factor): the full 4-block matrix with the problem's own shifts
+// (bp.pdelta / pdelta_c: those of the last step it took part in) and Sigma = lda / (s + eps) of the staged vectors.  The ONE
+// statement of this arithmetic: k_b_berr (NC = 1) and k_b_kkt_matvec (kernels_bsolve.hpp) both run it.  By a workgroup of 256
+// threads; d[c]: vector c, [x | s | lambda_e | lambda_i] (FLIPPED: the multiplier blocks carry the sign flip of a direction, which
+// is undone here).  One pass over the blocks for the NC vectors; a vector's sums never see another vector, and their
+// partitions and order depend on the sizes alone.  The rows are handed out as they are formed:
+//   emit_x(j, c, v)        row j of the x block, from lane 0 of the wave that formed it
+//   emit_si(k, c, vs, vi)  rows n + k (slack) and n + mi + me + k (lambda_i), from thread k mod 256
+//   emit_e(a, c, v)        row n + mi + a (lambda_e), from thread a mod 256
+template <int NC, bool FLIPPED, class EmitX, class EmitSI, class EmitE>
+__device__ __forceinline__ void b_kkt_rows(const BatchPtrs& bp, const Geo& g, int64_t b, double eps, const double* const (&d)[NC],
+                                           EmitX emit_x, EmitSI emit_si, EmitE emit_e)
+{
+    const double delta = bp.pdelta[b], delta_c = bp.pdelta_c[b];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t n = g.n, me = g.me, mi = g.mi;
+    const double* d2L = bp.d2L + b * bp.sH;
+    const double* s = bp.s + b * mi;
+    const double* lda = bp.lda + b * (me + mi);
+    for (int64_t j0 = (int64_t)wave * 4; j0 < n; j0 += 16) {    // x rows, four per trip: sym(triu(d2L)) x + delta x + Je le + Ji li
+        double acc[NC][4];
+        #pragma unroll
+        for (int c = 0; c < NC; ++c) { acc[c][0] = 0.0; acc[c][1] = 0.0; acc[c][2] = 0.0; acc[c][3] = 0.0; }
+        for (int64_t i = lane; i < n; i += 64) {
+            double xi[NC];
+            #pragma unroll
+            for (int c = 0; c < NC; ++c) xi[c] = d[c][i];
+            #pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int64_t j = j0 + q;
+                if (j < n) {
+                    const double h = (i >= j ? d2L[j * bp.ldh + i] : d2L[i * bp.ldh + j]);
+                    #pragma unroll
+                    for (int c = 0; c < NC; ++c) acc[c][q] += h * xi[c];
+                }
+            }
+        }
+        for (int64_t a = lane; a < me; a += 64) {
+            double v[NC];
+            #pragma unroll
+            for (int c = 0; c < NC; ++c) v[c] = FLIPPED ? -d[c][n + mi + a] : d[c][n + mi + a];
+            #pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (j0 + q < n) {
+                    const double e = bp.Je[b * bp.sJe + (j0 + q) * bp.ldje + a];
+                    #pragma unroll
+                    for (int c = 0; c < NC; ++c) acc[c][q] += e * v[c];
+                }
+        }
+        for (int64_t a = lane; a < mi; a += 64) {
+            double v[NC];
+            #pragma unroll
+            for (int c = 0; c < NC; ++c) v[c] = FLIPPED ? -d[c][n + mi + me + a] : d[c][n + mi + me + a];
+            #pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (j0 + q < n) {
+                    const double e = bp.Ji[b * bp.sJi + (j0 + q) * bp.ldji + a];
+                    #pragma unroll
+                    for (int c = 0; c < NC; ++c) acc[c][q] += e * v[c];
+                }
+        }
+        #pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t j = j0 + q;
+            #pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const double a_ = wave_sum(acc[c][q]);
+                if (lane == 0 && j < n) emit_x(j, c, a_ + delta * d[c][j]);
+            }
+        }
+    }
+    for (int64_t k = tid; k < mi; k += 256) {                // s rows and lambda_i rows
+        double u[NC];
+        #pragma unroll
+        for (int c = 0; c < NC; ++c) u[c] = 0.0;
+        const double* col = bp.Ji + b * bp.sJi + k;
+        for (int64_t j = 0; j < n; ++j) {
+            const double e = col[j * bp.ldji];
+            #pragma unroll
+            for (int c = 0; c < NC; ++c) u[c] += e * d[c][j];
+        }
+        #pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const double li = FLIPPED ? -d[c][n + mi + me + k] : d[c][n + mi + me + k];
+            emit_si(k, c, lda[me + k] / (s[k] + eps) * d[c][n + k] - li, u[c] - d[c][n + k]);
+        }
+    }
+    for (int64_t a = tid; a < me; a += 256) {                // lambda_e rows
+        double u[NC];
+        #pragma unroll
+        for (int c = 0; c < NC; ++c) u[c] = 0.0;
+        const double* col = bp.Je + b * bp.sJe + a;
+        for (int64_t j = 0; j < n; ++j) {
+            const double e = col[j * bp.ldje];
+            #pragma unroll
+            for (int c = 0; c < NC; ++c) u[c] += e * d[c][j];
+        }
+        #pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const double le = FLIPPED ? -d[c][n + mi + a] : d[c][n + mi + a];
+            emit_e(a, c, u[c] - delta_c * le);
+        }
+    }
+}
+
 // Backward error of a batch of directions against the KKT blocks (never the factor): out[b] = |g - Hc raw| / |g| with raw the
-// direction with the multiplier flip undone, Hc the full 4-block matrix with each problem's own shifts (bp.pdelta / pdelta_c:
-// those of the last step it took part in).  grid B, 256
+// direction with the multiplier flip undone, Hc the full 4-block matrix with each problem's own shifts (b_kkt_rows).  grid B, 256
 // threads; g = -grad must be in bp.rhs (every batched step leaves it there).  The guard of the condensed form, and a check
 // any caller can afford: O(N^2) per problem.
 __global__ __launch_bounds__(256) void k_b_berr(BatchPtrs bp, Geo g, const double* __restrict__ dz, double eps, double* __restrict__ out)
 {
     __shared__ double red[2][4];
     const int64_t b = blockIdx.x;
-    const double delta = bp.pdelta[b], delta_c = bp.pdelta_c[b];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t n = g.n, me = g.me, mi = g.mi;
-    const double* d = dz + b * g.N;
     const double* gr = bp.rhs + b * bp.sV;
-    const double* d2L = bp.d2L + b * bp.sH;
-    const double* s = bp.s + b * mi;
-    const double* lda = bp.lda + b * (me + mi);
-    const double* dx = d; const double* ds = d + n; const double* dle = d + n + mi; const double* dli = d + n + mi + me;   // (flipped)
+    const double* const cols[1] = {dz + b * g.N};
     double rr = 0.0, gg = 0.0;
-    for (int64_t j0 = (int64_t)wave * 4; j0 < n; j0 += 16) {    // x rows, four per trip: sym(triu(d2L)) dx + delta dx + Je dle + Ji dli
-        double acc[4] = {0.0, 0.0, 0.0, 0.0};
-        for (int64_t i = lane; i < n; i += 64) {
-            const double xi = dx[i];
-            #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int64_t j = j0 + q;
-                if (j < n) acc[q] += (i >= j ? d2L[j * bp.ldh + i] : d2L[i * bp.ldh + j]) * xi;
-            }
-        }
-        for (int64_t a = lane; a < me; a += 64) {
-            const double v = dle[a];
-            #pragma unroll
-            for (int q = 0; q < 4; ++q) if (j0 + q < n) acc[q] -= bp.Je[b * bp.sJe + (j0 + q) * bp.ldje + a] * v;
-        }
-        for (int64_t a = lane; a < mi; a += 64) {
-            const double v = dli[a];
-            #pragma unroll
-            for (int q = 0; q < 4; ++q) if (j0 + q < n) acc[q] -= bp.Ji[b * bp.sJi + (j0 + q) * bp.ldji + a] * v;
-        }
-        #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const double a_ = wave_sum(acc[q]);
-            const int64_t j = j0 + q;
-            if (lane == 0 && j < n) { const double r = gr[j] - (a_ + delta * dx[j]); rr += r * r; gg += gr[j] * gr[j]; }
-        }
-    }
-    for (int64_t k = tid; k < mi; k += 256) {                // s rows and lambda_i rows
-        double u = 0.0;
-        const double* col = bp.Ji + b * bp.sJi + k;
-        for (int64_t j = 0; j < n; ++j) u += col[j * bp.ldji] * dx[j];
-        const double r1 = gr[n + k] - (lda[me + k] / (s[k] + eps) * ds[k] + dli[k]);
-        const double r2 = gr[n + mi + me + k] - (u - ds[k]);
-        rr += r1 * r1 + r2 * r2; gg += gr[n + k] * gr[n + k] + gr[n + mi + me + k] * gr[n + mi + me + k];
-    }
-    for (int64_t a = tid; a < me; a += 256) {                // lambda_e rows
-        double u = 0.0;
-        const double* col = bp.Je + b * bp.sJe + a;
-        for (int64_t j = 0; j < n; ++j) u += col[j * bp.ldje] * dx[j];
-        const double r = gr[n + mi + a] - (u + delta_c * dle[a]);
-        rr += r * r; gg += gr[n + mi + a] * gr[n + mi + a];
-    }
+    b_kkt_rows<1, true>(bp, g, b, eps, cols,
+        [&](int64_t j, int, double v) { const double r = gr[j] - v; rr += r * r; gg += gr[j] * gr[j]; },
+        [&](int64_t k, int, double vs, double vi) {
+            const double r1 = gr[n + k] - vs;
+            const double r2 = gr[n + mi + me + k] - vi;
+            rr += r1 * r1 + r2 * r2; gg += gr[n + k] * gr[n + k] + gr[n + mi + me + k] * gr[n + mi + me + k];
+        },
+        [&](int64_t a, int, double v) { const double r = gr[n + mi + a] - v; rr += r * r; gg += gr[n + mi + a] * gr[n + mi + a]; });
     rr = wave_sum(rr); gg = wave_sum(gg);
     if (lane == 0) { red[0][wave] = rr; red[1][wave] = gg; }
     __syncthreads();
@@ -1093,3 +1159,5 @@ __global__ __launch_bounds__(256) void k_b_merit_ray(double* __restrict__ out, c
 }
 
 }  // namespace pyipm
+
+#include "kernels_bsolve.hpp"

@@ -2685,8 +2685,13 @@ static int step_batched_enqueue(Ctx* ctx, const BatchEach& in, double* dz, int m
     BatchCond bc = batch_cond(ctx);
     const int cond = (ctx->condensed && g.mi > 0) ? 1 : 0;
     ctx->held.step_batched_begun(cond != 0);
+    if (ctx->b_form.capacity() < (size_t)B) {               // first step of the handle: no problem holds a factor yet
+        PYIPM_HIP(ctx->b_form.reserve((size_t)B));
+        PYIPM_HIP(hipMemsetAsync(ctx->b_form, 0xFF, (size_t)B * sizeof(int), ctx->stream));
+    }
+    if (cond) ctx->b_any_cond = true;
     PYIPM_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
-    hipLaunchKernelGGL(k_b_begin, grid1(B), dim3(256), 0, ctx->stream, bp, in, B);
+    hipLaunchKernelGGL(k_b_begin, grid1(B), dim3(256), 0, ctx->stream, bp, in, B, ctx->b_form.get(), cond);
     PYIPM_KCHECK();
     if (cond) {
         // condensed form: per problem n + me + |A| columns instead of n + 2 mi + me (config 5: 256 instead of 768) -- the
@@ -2914,6 +2919,232 @@ int pyipm_newton_merit_ray_batched(pyipm_newton_ctx* h, const double* dz, const 
     PYIPM_KCHECK();
     if (host) {
         PYIPM_HIP(hipMemcpyAsync(out, dev, B * (size_t)K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        PYIPM_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return PYIPM_OK;
+} PYIPM_CATCH_H(h)
+
+// ---- the kept factors of a batch as a solver (kernels_bsolve.hpp) ----------------------------------------
+// Scratch of the three entries below, the library's own buffer outside the workspace (as b_merit_buf): `count` doubles behind
+// the staged mask.  Growing drops the contents: nothing in it outlives a call.
+static int batch_solve_scratch(Ctx* ctx, size_t count, int** mask, double** p) {
+    const size_t B = (size_t)ctx->batch, head = (B * sizeof(int) + sizeof(double) - 1) / sizeof(double), need = head + count;
+    if (ctx->b_solve_buf.capacity() < need) {
+        PYIPM_HIP(ctx->b_solve_buf.reserve(need));
+        if (getenv("PYIPM_POISON_WORKSPACE")) PYIPM_HIP(hipMemsetAsync(ctx->b_solve_buf, 0xFF, need * sizeof(double), ctx->stream));   // as the workspace
+    }
+    *mask = reinterpret_cast<int*>(ctx->b_solve_buf.get());
+    *p = ctx->b_solve_buf.get() + head;
+    return 0;
+}
+// the mask as the kernels read it: the caller's device array, or the host one staged
+static int batch_mask(Ctx* ctx, const int32_t* active, int memkind, int* stage, const int** out) {
+    *out = nullptr;
+    if (!active) return 0;
+    if (memkind == PYIPM_MEM_HOST) {
+        PYIPM_HIP(hipMemcpyAsync(stage, active, (size_t)ctx->batch * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        *out = stage;
+    } else *out = (const int*)active;
+    return 0;
+}
+static int batch_solve_launch(Ctx* ctx, const BSolveIO& io) {
+    const Geo& g = ctx->g;
+    const int64_t rows = g.Npad + (ctx->b_any_cond ? TB : 0);        // (a condensed problem keeps its Ji-sided vector behind the sweep's rows)
+    const dim3 grid((unsigned)ctx->batch, (unsigned)((io.k + BS_W - 1) / BS_W)), block(64 * BS_NW);
+    const BatchPtrs bp = batch_ptrs(ctx);
+    const BatchCond bc = batch_cond(ctx);
+    if (rows <= 320)      hipLaunchKernelGGL((k_b_solve_many<320>), grid, block, 0, ctx->stream, bp, g, ctx->block_refine, io, bc, ctx->eps);
+    else if (rows <= 576) hipLaunchKernelGGL((k_b_solve_many<576>), grid, block, 0, ctx->stream, bp, g, ctx->block_refine, io, bc, ctx->eps);
+    else if (rows <= 832) hipLaunchKernelGGL((k_b_solve_many<832>), grid, block, 0, ctx->stream, bp, g, ctx->block_refine, io, bc, ctx->eps);
+    else                  hipLaunchKernelGGL((k_b_solve_many<1088>), grid, block, 0, ctx->stream, bp, g, ctx->block_refine, io, bc, ctx->eps);
+    PYIPM_KCHECK();
+    return 0;
+}
+static int batch_matvec_launch(Ctx* ctx, const BMatvecIO& io) {
+    const dim3 grid((unsigned)ctx->batch, (unsigned)((io.k + BMV_NC - 1) / BMV_NC));
+    hipLaunchKernelGGL(k_b_kkt_matvec, grid, dim3(256), 0, ctx->stream, batch_ptrs(ctx), ctx->g, ctx->eps, io);
+    PYIPM_KCHECK();
+    return 0;
+}
+// k columns of every problem between caller memory (leading dimension ld, batch stride) and a packed device block ([B][k][N])
+static int batch_cols_copy(Ctx* ctx, double* dst, const double* src, int64_t k, int64_t ld, int64_t stride, bool to_device,
+                           const int32_t* active_host) {
+    const size_t N = (size_t)ctx->g.N;
+    for (int b = 0; b < ctx->batch; ++b) {
+        if (active_host && !active_host[b]) continue;
+        if (to_device)
+            PYIPM_HIP(hipMemcpy2DAsync(dst + (size_t)b * (size_t)k * N, N * sizeof(double), src + (size_t)b * (size_t)stride, (size_t)ld * sizeof(double),
+                                       N * sizeof(double), (size_t)k, hipMemcpyHostToDevice, ctx->stream));
+        else
+            PYIPM_HIP(hipMemcpy2DAsync(dst + (size_t)b * (size_t)stride, (size_t)ld * sizeof(double), src + (size_t)b * (size_t)k * N, N * sizeof(double),
+                                       N * sizeof(double), (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return 0;
+}
+
+int pyipm_newton_solve_batched(pyipm_newton_ctx* h, int64_t k, const double* rhs, int64_t ld_rhs, int64_t stride_rhs,
+                               double* x, int64_t ld_x, int64_t stride_x, const int32_t* active, int flip, int refine, int memkind) try {
+    PYIPM_ENTER("solve_batched", G_BATCHED | G_DEVICE) const Geo& g = ctx->g;
+    if (k < 0) { ctx->err = "solve_batched: k < 0"; return PYIPM_E_BADARG; }
+    if (refine < 0) { ctx->err = "solve_batched: refine < 0 (no adaptive counts on a batched handle: a column's bits never depend on its neighbours)"; return PYIPM_E_BADARG; }
+    if (memkind != PYIPM_MEM_DEVICE && memkind != PYIPM_MEM_HOST) { ctx->err = "solve_batched: bad memkind"; return PYIPM_E_BADARG; }
+    if (k == 0) return PYIPM_OK;
+    if (k > 65535) { ctx->err = "solve_batched: k > 65535"; return PYIPM_E_BADARG; }
+    if (!ctx->held.batch_stepped) { ctx->err = "solve_batched: no step yet (the factors are a step's)"; return PYIPM_E_BADARG; }
+    if (!rhs || !x) { ctx->err = "solve_batched: null right-hand side or output"; return PYIPM_E_BADARG; }
+    if (ld_rhs < g.N || ld_x < g.N) { ctx->err = "solve_batched: leading dimension below N"; return PYIPM_E_BADARG; }
+    const size_t B = (size_t)ctx->batch, blk = B * (size_t)k * (size_t)g.N;
+    const bool host = memkind == PYIPM_MEM_HOST;
+    // device pointers: x may BE rhs (same ld and stride -- a refined solve then keeps a copy of the right-hand sides for its
+    // residuals); any other overlap of the two blocks is refused
+    bool inplace = false;
+    if (!host) {
+        const double* r1 = rhs + (B - 1) * (size_t)stride_rhs + (size_t)(k - 1) * (size_t)ld_rhs + (size_t)g.N;
+        const double* x1 = x + (B - 1) * (size_t)stride_x + (size_t)(k - 1) * (size_t)ld_x + (size_t)g.N;
+        inplace = rhs == x && ld_rhs == ld_x && stride_rhs == stride_x;
+        if (!inplace && rhs < x1 && x < r1) { ctx->err = "solve_batched: x overlaps rhs (it may only BE rhs, with the same ld and stride)"; return PYIPM_E_BADARG; }
+    }
+    const bool keep_b = inplace && refine > 0;
+    int* mstage; double* buf;
+    { int rc = batch_solve_scratch(ctx, (host ? 2 * blk : 0) + (refine ? blk : 0) + (keep_b ? blk : 0), &mstage, &buf); if (rc) return rc; }
+    const int* act;
+    { int rc = batch_mask(ctx, active, memkind, mstage, &act); if (rc) return rc; }
+    const int64_t kN = k * g.N;
+    BSolveIO io = {rhs, ld_rhs, stride_rhs, x, ld_x, stride_x, k, act, ctx->b_form.get(), flip ? 1 : 0};
+    double* r = buf;                                      // the residual of a refinement step, solved in place
+    if (host) {
+        double* rd = buf; double* xd = buf + blk; r = buf + 2 * blk;
+        { int rc = batch_cols_copy(ctx, rd, rhs, k, ld_rhs, stride_rhs, true, active); if (rc) return rc; }
+        io.rhs = rd; io.ld_rhs = g.N; io.stride_rhs = kN; io.x = xd; io.ld_x = g.N; io.stride_x = kN;
+    }
+    const dim3 gcols((unsigned)B, (unsigned)k, (unsigned)((g.N + 255) / 256));
+    const double* bsub = io.rhs; int64_t ld_b = io.ld_rhs, stride_b = io.stride_rhs;     // B of the residuals
+    if (keep_b) {
+        double* keep = buf + blk;
+        hipLaunchKernelGGL(k_b_copy_cols, gcols, dim3(256), 0, ctx->stream, keep, rhs, ld_rhs, stride_rhs, g.N);
+        PYIPM_KCHECK();
+        bsub = keep; ld_b = g.N; stride_b = kN;
+    }
+    // refinement works on the raw solution: the flip of the multiplier rows is the last thing done to x
+    const int flip_last = io.flip;
+    if (refine) io.flip = 0;
+    { int rc = batch_solve_launch(ctx, io); if (rc) return rc; }
+    for (int it = 0; it < refine; ++it) {
+        // R = B - Hc X from the blocks;  X += solve(R)
+        const BMatvecIO mv = {io.x, io.ld_x, io.stride_x, r, g.N, kN, bsub, ld_b, stride_b, k, act};
+        { int rc = batch_matvec_launch(ctx, mv); if (rc) return rc; }
+        const BSolveIO cor = {r, g.N, kN, r, g.N, kN, k, act, ctx->b_form.get(), 0};
+        { int rc = batch_solve_launch(ctx, cor); if (rc) return rc; }
+        hipLaunchKernelGGL(k_b_add_cols, gcols, dim3(256), 0, ctx->stream,
+                           io.x, io.ld_x, io.stride_x, r, g.N, kN, g.N, act, it + 1 == refine ? flip_last : 0, g.n + g.mi);
+        PYIPM_KCHECK();
+    }
+    if (host) {
+        { int rc = batch_cols_copy(ctx, x, io.x, k, ld_x, stride_x, false, active); if (rc) return rc; }
+        PYIPM_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return PYIPM_OK;
+} PYIPM_CATCH_H(h)
+
+int pyipm_newton_kkt_matvec_batched(pyipm_newton_ctx* h, int64_t k, const double* v, int64_t ld_v, int64_t stride_v,
+                                    double* y, int64_t ld_y, int64_t stride_y, int memkind) try {
+    PYIPM_ENTER("kkt_matvec_batched", G_BATCHED | G_DEVICE) const Geo& g = ctx->g;
+    if (k < 0) { ctx->err = "kkt_matvec_batched: k < 0"; return PYIPM_E_BADARG; }
+    if (memkind != PYIPM_MEM_DEVICE && memkind != PYIPM_MEM_HOST) { ctx->err = "kkt_matvec_batched: bad memkind"; return PYIPM_E_BADARG; }
+    if (k == 0) return PYIPM_OK;
+    if (k > 65535) { ctx->err = "kkt_matvec_batched: k > 65535"; return PYIPM_E_BADARG; }
+    if (!ctx->held.have_blocks || !ctx->held.have_vectors || !ctx->held.batch_stepped) {
+        ctx->err = "kkt_matvec_batched: stage blocks and vectors and take a step first (the step supplies the shifts)"; return PYIPM_E_BADARG; }
+    if (!v || !y) { ctx->err = "kkt_matvec_batched: null v or y"; return PYIPM_E_BADARG; }
+    if (ld_v < g.N || ld_y < g.N) { ctx->err = "kkt_matvec_batched: leading dimension below N"; return PYIPM_E_BADARG; }
+    const size_t B = (size_t)ctx->batch, blk = B * (size_t)k * (size_t)g.N;
+    const bool host = memkind == PYIPM_MEM_HOST;
+    const int64_t kN = k * g.N;
+    BMatvecIO io = {v, ld_v, stride_v, y, ld_y, stride_y, nullptr, 0, 0, k, nullptr};
+    if (host) {
+        int* mstage; double* buf;
+        { int rc = batch_solve_scratch(ctx, 2 * blk, &mstage, &buf); if (rc) return rc; }
+        { int rc = batch_cols_copy(ctx, buf, v, k, ld_v, stride_v, true, nullptr); if (rc) return rc; }
+        io.v = buf; io.ld_v = g.N; io.stride_v = kN; io.y = buf + blk; io.ld_y = g.N; io.stride_y = kN;
+    }
+    { int rc = batch_matvec_launch(ctx, io); if (rc) return rc; }
+    if (host) {
+        { int rc = batch_cols_copy(ctx, y, io.y, k, ld_y, stride_y, false, nullptr); if (rc) return rc; }
+        PYIPM_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return PYIPM_OK;
+} PYIPM_CATCH_H(h)
+
+// The quantities of pyipm_newton_rcond for every problem, the iterations of the whole batch in lockstep: every launch below
+// takes all problems through one step of theirs, nothing comes back to the host in between.
+int pyipm_newton_rcond_batched(pyipm_newton_ctx* h, int it_inv, int it_pow, const int32_t* active, double* out, int memkind) try {
+    PYIPM_ENTER("rcond_batched", G_BATCHED | G_DEVICE) const Geo& g = ctx->g;
+    if (!out) { ctx->err = "rcond_batched: null output"; return PYIPM_E_BADARG; }
+    if (it_inv < 0 || it_pow < 0) { ctx->err = "rcond_batched: negative (adaptive) iteration counts are not part of the batched estimate"; return PYIPM_E_BADARG; }
+    if (memkind != PYIPM_MEM_DEVICE && memkind != PYIPM_MEM_HOST) { ctx->err = "rcond_batched: bad memkind"; return PYIPM_E_BADARG; }
+    if (!ctx->held.have_blocks || !ctx->held.have_vectors || !ctx->held.batch_stepped) {
+        ctx->err = "rcond_batched: stage blocks and vectors and take a step first"; return PYIPM_E_BADARG; }
+    if (ctx->held.cond_active) {
+        ctx->err = "rcond_batched: the last step was condensed -- the estimate works on the factor of the full form only"; return PYIPM_E_BADARG; }
+    if (it_inv < 1) it_inv = 3;
+    if (it_pow < 1) it_pow = 6;
+    const int B = ctx->batch;
+    const size_t BN = (size_t)B * (size_t)g.N;
+    int* mstage; double* buf;
+    { int rc = batch_solve_scratch(ctx, 2 * BN + 9 * (size_t)B, &mstage, &buf); if (rc) return rc; }
+    const int* act;
+    { int rc = batch_mask(ctx, active, memkind, mstage, &act); if (rc) return rc; }
+    double *wa = buf, *wb = buf + BN, *est = buf + 2 * BN, *alive = est + 2 * B, *res = alive + B;    // est: [2][B] (power, inverse); res: [B][4]
+    double* fix = res + 4 * B;                               // [B]: the corrected min|w| estimate of the problems with static pivots
+    int* mask2 = reinterpret_cast<int*>(fix + B);            // [B]: those problems
+    const dim3 gstart((unsigned)B, (unsigned)((g.N + 255) / 256)), gwave((unsigned)((B + 3) / 4));
+    for (int phase = 0; phase < 2; ++phase) {
+        double* e = est + (size_t)phase * B;
+        hipLaunchKernelGGL(k_b_rc_start, gstart, dim3(256), 0, ctx->stream, wb, e, alive, g.N, (unsigned long long)(17 + phase));
+        PYIPM_KCHECK();
+        hipLaunchKernelGGL(k_b_rc_norm, gwave, dim3(256), 0, ctx->stream, wb, wa, e, alive, act, g.N, B, 0);
+        PYIPM_KCHECK();
+        const int its = phase == 0 ? it_pow : it_inv;
+        for (int it = 0; it < its; ++it) {
+            if (phase == 0) {                                 // wb = Hc (v / |v|)
+                const BMatvecIO mv = {wa, g.N, g.N, wb, g.N, g.N, nullptr, 0, 0, 1, act};
+                int rc = batch_matvec_launch(ctx, mv); if (rc) return rc;
+            } else {                                          // wb = inv(factored) (v / |v|)
+                const BSolveIO io = {wa, g.N, g.N, wb, g.N, g.N, 1, act, ctx->b_form.get(), 0};
+                int rc = batch_solve_launch(ctx, io); if (rc) return rc;
+            }
+            hipLaunchKernelGGL(k_b_rc_norm, gwave, dim3(256), 0, ctx->stream, wb, it + 1 < its ? wa : (double*)nullptr, e, alive, act, g.N, B, 1);
+            PYIPM_KCHECK();
+        }
+    }
+    {   // static pivots: the last inverse iterate (wb) taken back to the unperturbed matrix (k_b_rc_fix_begin, kernels_bsolve.hpp)
+        hipLaunchKernelGGL(k_b_rc_fix_begin, grid1(B), dim3(256), 0, ctx->stream, mask2, fix, alive, act, ctx->b_form.get(), ctx->dstats, B);
+        PYIPM_KCHECK();
+        const BMatvecIO mv = {wa, g.N, g.N, wb, g.N, g.N, nullptr, 0, 0, 1, mask2};
+        const BSolveIO sv = {wb, g.N, g.N, wb, g.N, g.N, 1, mask2, ctx->b_form.get(), 0};
+        hipLaunchKernelGGL(k_b_rc_norm, gwave, dim3(256), 0, ctx->stream, wb, wa, fix, alive, mask2, g.N, B, 0);      // wa = x / |x|
+        PYIPM_KCHECK();
+        { int rc = batch_matvec_launch(ctx, mv); if (rc) return rc; }                                                 // wb = Hc wa
+        { int rc = batch_solve_launch(ctx, sv); if (rc) return rc; }                                                  // wb = inv(factored) wb
+        hipLaunchKernelGGL(k_b_rc_sub, gstart, dim3(256), 0, ctx->stream, wb, wa, mask2, g.N);                        // wb = x'
+        PYIPM_KCHECK();
+        hipLaunchKernelGGL(k_b_rc_norm, gwave, dim3(256), 0, ctx->stream, wb, wa, fix, alive, mask2, g.N, B, 0);      // wa = x' / |x'|
+        PYIPM_KCHECK();
+        { int rc = batch_matvec_launch(ctx, mv); if (rc) return rc; }
+        hipLaunchKernelGGL(k_b_rc_norm, gwave, dim3(256), 0, ctx->stream, wb, (double*)nullptr, fix, alive, mask2, g.N, B, 1);   // fix = |Hc x'| / |x'|
+        PYIPM_KCHECK();
+    }
+    double* dev = (memkind == PYIPM_MEM_DEVICE) ? out : res;
+    hipLaunchKernelGGL(k_b_rc_finish, grid1(B), dim3(256), 0, ctx->stream, dev, est, est + B, fix, ctx->anorm, act, ctx->b_form.get(), B);
+    PYIPM_KCHECK();
+    if (memkind == PYIPM_MEM_HOST) {
+        for (int b0 = 0; b0 < B;) {                           // only the rows of the problems that took part, run by run
+            if (active && !active[b0]) { ++b0; continue; }
+            int b1 = b0 + 1;
+            while (b1 < B && (!active || active[b1])) ++b1;
+            PYIPM_HIP(hipMemcpyAsync(out + 4 * (size_t)b0, res + 4 * (size_t)b0, (size_t)(b1 - b0) * 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            b0 = b1;
+        }
         PYIPM_HIP(hipStreamSynchronize(ctx->stream));
     }
     return PYIPM_OK;
