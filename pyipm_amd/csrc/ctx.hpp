@@ -13,18 +13,18 @@
 #include <vector>
 #include "../../include/pyipm_newton.h"
 #include "owned.hpp"
+#include "step_plan.hpp"
 
 namespace pyipm {
 
 constexpr int TB = PYIPM_TILE;      // 64: block-pivot tile
+static_assert(TB == PLAN_TB, "step_plan.hpp states the tile on its own");
 constexpr int PADG = PYIPM_PAD;     // 128: Npad granularity = row tile of the MFMA update
 constexpr int BM = 128;             // MFMA update tile rows (i)
 constexpr int BKU = 16;             // MFMA update k-stage
 constexpr int ROWCHUNK = 2048;      // rows per block in the backward column dots
 
 // Tuning numbers of the schedules (measured on MI355X; constants, not per-handle state)
-constexpr int64_t TAIL_COLS = 24576;          // groups of tail_group panels once at most this many columns remain: there the panel chain
-                                              // outlasts the bulk update, and shorter groups move in-group update work off the chain
 constexpr int BULK_WAVES = 8;                 // waves per block of the BULK update tiles (8: 128 VGPRs each, 4 waves per SIMD;
                                               // 4: 241 VGPRs, 2 per SIMD: 1.5 % slower); the short side-stream launches keep 4
 constexpr int HEAD_WAVES = 4;                 // waves per block of a lookahead head launched on the chain's stream (4: k_update<128,true,4>,
@@ -43,7 +43,6 @@ constexpr int64_t BULK_BN_ROWS = 20480;       // 128 x 256 tiles only for launch
                                               // block per CU, every register) its kernels wait twice as long for a slot -- exposed panel 6.0
                                               // instead of 5.3 ms with the threshold at persist_rows, the step 0.8 % slower
 constexpr int BULK_BN_MIN_K = 512;            // ... and with at least this K (shorter ones keep 128 x 128: twice the blocks)
-constexpr int PX_HDR = 32;                    // doubles in front of the prefix snapshot: DevStats, then the assembly's maximum
 constexpr int TILE_FREE_CUS = 64;             // k_tile_step8: CUs assumed free beside a persistent bulk launch (units per block: 1 while the launch fits)
 
 // Block-cyclic 1D column distribution by panels of width nb.
@@ -59,6 +58,7 @@ struct Geo {
     }
     __host__ __device__ int owner(int64_t p) const { return (int)(p % world); }
     __host__ __device__ int64_t local_c0(int64_t p) const { return (p / world) * (int64_t)nb; }
+    operator PlanGeo() const { return PlanGeo{n, me, mi, Npad, nb, npanels}; }
 };
 
 // Panels aggregated per bulk trailing update (K = group * nb).  Grouping needs the group's panels on
@@ -112,25 +112,6 @@ struct ChainGeo {
 };
 constexpr int CHAIN_DBG_WORDS = 256 + 64 * 4 * 32;
 
-// The group schedule of the single-rank driver as one value: which panels form a group (one bulk trailing update per group) and
-// what the KKT structure says about each group.  plan_groups (pyipm_newton.hip) builds it for one geometry.  The accessors hold
-// the fallback for a panel WITHOUT a schedule (per-panel phases, distributed driver): uniform groups of G panels, dense panels.
-struct GroupSched {
-    std::vector<int> of_, off_;           // per panel: group id and offset inside the group
-    std::vector<int64_t> first_;          // per group: first panel (+ one past the last group)
-    std::vector<char> fast_;              // per group: every panel of it lies inside the slack block: closed-form elimination (k_s_panel)
-    std::vector<char> in_x_;              // per group: lies inside the x block (its chain kernels may skip the slack rows)
-    bool active() const { return !of_.empty(); }
-    void clear() { of_.clear(); off_.clear(); first_.clear(); fast_.clear(); in_x_.clear(); }   // the only way into per-panel mode
-    bool has(int64_t p) const { return (size_t)p < of_.size(); }
-    int64_t group_of(int64_t p, int64_t G) const { return has(p) ? of_[(size_t)p] : p / G; }
-    int64_t offset_of(int64_t p, int64_t G) const { return has(p) ? off_[(size_t)p] : p % G; }
-    bool fast_panel(int64_t p) const { return has(p) && fast(of_[(size_t)p]); }     bool in_x_panel(int64_t p) const { return has(p) && in_x(of_[(size_t)p]); }
-    int64_t ngroups() const { return (int64_t)fast_.size(); }
-    int64_t first(int64_t grp) const { return first_[(size_t)grp]; }      int64_t size(int64_t grp) const { return first(grp + 1) - first(grp); }
-    bool fast(int64_t grp) const { return fast_[(size_t)grp] != 0; }      bool in_x(int64_t grp) const { return in_x_[(size_t)grp] != 0; }
-};
-
 // What a handle currently holds, as one record: which staged data, matrix, factor and work vectors are valid.  Fields are read
 // anywhere and written only by the transitions below, one per event; each carries the one statement of why it invalidates
 // what it invalidates (DESIGN.md section 1 has the table, with the work vector every entry borrows).
@@ -152,29 +133,23 @@ struct Held {
                                           // so every assembly is a full one until set_option("keep_zeros") is called again
     bool rc_warm_valid[2] = {false, false};   // rc_warm[k] holds the vector the last adaptive condition estimate ended with
     bool ev_assemble_valid = false, ev_solve_valid = false;   // events 2-3 / 4-5 have been recorded (last_timings)
-    // The reusable x-block prefix: columns [0, cB) of the storage hold L of the groups inside the x block,
-    // the tile inverses and flags of those columns are theirs, and the handle's snapshot holds the columns behind them as
-    // they were when the last of those groups had been applied -- all of it a function of the staged blocks, delta and delta_c.
+    // The reusable x-block prefix: columns [0, cB) of the storage hold L of the groups inside the x block, and
+    // the snapshot holds the columns behind them as those groups left them -- a function of the staged blocks, delta and delta_c.
     bool px_valid = false;
     double px_delta = 0.0, px_delta_c = 0.0;   // ... the shifts it was recorded with
-    int64_t px_groups = 0, px_cB = 0;          // ... and the schedule: groups of the prefix, first column behind them
-    // The second level: the groups [px_gS, px_gE) wholly inside the lambda_e columns are kept as well (their L, tile inverses, saved
-    // tiles and flags in place; their W rows below the boundary and the state of everything behind them in the second snapshot).
-    // Only ever consulted together with px_valid and written by every recording step: whatever drops the prefix drops it too.
-    bool px_e_valid = false;
-    int64_t px_gS = 0, px_gE = 0;
+    // ... and the plan of the step that recorded it: gB, cB and, the second level (e.ok), the lambda_e groups kept as well (their
+    // L in place, their W rows and everything behind them in the second snapshot).  Only ever consulted together with px_valid.
+    StepPlan px_rec;
     // The recording policy: whoever restages the blocks before any step reused them is an NLP loop and stops paying for
     // snapshots; a second step on the same blocks starts them again.
     bool px_record = true;
     int px_steps = 0;                          // fused steps since the blocks were staged
     bool px_reused = false;                    // ... one of them reused the prefix
     double px_last_delta = 0.0, px_last_delta_c = 0.0;   // shifts of the last factorisation (a shift loop changes them every time: no snapshot)
-    // What the last assembly decided for the factorisation that follows it (0 full, 1 recording, 2 reusing) and its boundary.
-    // 2 with `assembled`: the storage holds L of the prefix in columns [0, cB), the matrix behind them -- whoever looks at the
-    // storage as a matrix first has it completed (storage_whole).
-    int px_plan = 0; int64_t px_plan_groups = 0, px_plan_cB = 0;
-    bool px_plan_e = false; int64_t px_plan_gS = 0, px_plan_gE = 0;   // ... with the lambda_e groups [gS, gE) recorded / kept as well
-    bool partial() const { return assembled && px_plan == 2; }
+    // What the last assembly decided for the factorisation that follows it (step_plan.hpp).  Reusing with `assembled`: the storage
+    // holds L of the prefix in columns [0, cB) -- whoever looks at the storage as a matrix first has it completed (storage_whole).
+    StepPlan plan;
+    bool partial() const { return assembled && plan.kind == PX_REUSE; }
 
     enum : unsigned { V0 = 1, V1 = 2, V2 = 4, VLOC = 8 };
     // Somebody writes work vectors of the handle.  v0 / v1 carry a pending fused forward pass and its right-hand side, vloc the
@@ -201,24 +176,18 @@ struct Held {
     // Assembly, in two halves around its launches.  The condensed system lives in the same storage with another layout, so the
     // zeros are gone as soon as it starts.
     // A whole assembly overwrites the x columns: the prefix is gone.
-    void assemble_begun(bool condensed) { if (condensed) zeros_clean = false; else cond_active = false; px_valid = false; px_plan = 0; }
-    void assembly_planned(int plan, int64_t groups, int64_t cB, bool e, int64_t gS, int64_t gE) {
-        px_plan = plan; px_plan_groups = groups; px_plan_cB = cB;
-        px_plan_e = plan != 0 && e; px_plan_gS = gS; px_plan_gE = gE;
-    }
+    void assemble_begun(bool condensed) { if (condensed) zeros_clean = false; else cond_active = false; px_valid = false; plan = StepPlan(); }
+    void assembly_planned(const StepPlan& p) { plan = p; }
     // The slack columns re-assembled and the snapshot restored behind a valid prefix: a matrix again, its zeros as they were.
     void prefix_reassembled() { assembled = true; factored = false; forward_pending = false; }
     // Anything that may change the schedule or the order on the stream (set_option, set_stream), and a step that failed.
-    void prefix_dropped() { px_valid = false; px_e_valid = false; if (px_plan == 1) px_plan = 0; }
+    void prefix_dropped() { px_valid = false; px_rec = StepPlan(); if (plan.kind == PX_RECORD) plan = StepPlan(); }
     // An assembly of a step starts / its factorisation is done.  A second one on the same blocks: the caller is no NLP loop.
     void step_begun() { if (px_steps >= 1) px_record = true; }
-    void step_factored(bool recorded, bool reused, double delta, double delta_c, int64_t groups, int64_t cB) {
-        ++px_steps; px_last_delta = delta; px_last_delta_c = delta_c; px_plan = 0;
-        if (reused) px_reused = true;
-        if (recorded) {
-            px_valid = true; px_delta = delta; px_delta_c = delta_c; px_groups = groups; px_cB = cB;
-            px_e_valid = px_plan_e; px_gS = px_plan_gS; px_gE = px_plan_gE;
-        }
+    void step_factored(const StepPlan& done, double delta, double delta_c) {
+        ++px_steps; px_last_delta = delta; px_last_delta_c = delta_c; plan = StepPlan();
+        if (done.kind == PX_REUSE) px_reused = true;
+        if (done.kind == PX_RECORD) { px_valid = true; px_delta = delta; px_delta_c = delta_c; px_rec = done; }
     }
 
     // The zeros of a full single-rank assembly survive a factorisation of finite numbers (every update that reaches them adds an
@@ -229,7 +198,7 @@ struct Held {
     }
     void assemble_timed() { ev_assemble_valid = true; }
     // The owner of the storage wrote a matrix into it (the L-BFGS Gram system): full layout, no residual of this handle's.
-    void matrix_written() { px_valid = false; px_plan = 0; assembled = true; factored = false; have_rhs = false; forward_pending = false; cond_active = false; }
+    void matrix_written() { px_valid = false; plan = StepPlan(); assembled = true; factored = false; have_rhs = false; forward_pending = false; cond_active = false; }
     void step_batched_begun(bool condensed) { cond_active = condensed; }
     // rhs = g of every problem (backward_error_batched reads it).  v2 is the staging copy of a HOST output: the directions of the
     // problems that took part (step_lengths_batched with dz = NULL reads it); a device output is the caller's tensor alone.

@@ -1276,10 +1276,10 @@ int solve_plain(Ctx* ctx, double* v, bool forward_done, int nrhs, int64_t vstrid
 // `stream`, in place of P0 x (k_fwd_diag, k_fwd_gemv, k_diag_apply): the same bits.  Applies where solve_plain's one-launch sweeps
 // do; the caller keeps the per-panel loop otherwise.  The words are this launch's own (a solve may still be running on the main
 // stream with ctx->sweep_words): flags and a progress word per chunk, zeroed on the same stream in front of every launch.
-static bool fwd_prefix_applies(const Ctx* ctx, int64_t P0) {
+// (the plan adds what depends on the prefix: at least one panel, all of them inside the x block)
+static bool fwd_prefix_applies(const Ctx* ctx) {
     const Geo& g = ctx->g;
-    return ctx->fwd_prefix && sweeps_in_one_launch(ctx) && P0 >= 1 && g.nb % (2 * TB) == 0 && sub_width(ctx, (int)g.nb) == (int)g.nb &&
-           P0 * g.nb <= g.n;
+    return ctx->fwd_prefix && sweeps_in_one_launch(ctx) && g.nb % (2 * TB) == 0 && sub_width(ctx, (int)g.nb) == (int)g.nb;
 }
 static int fwd_prefix(Ctx* ctx, int64_t P0, double* v, hipStream_t stream) {
     const Geo& g = ctx->g;
@@ -1737,272 +1737,8 @@ int assemble_dev(Ctx* ctx, double delta, double delta_c) {
     return 0;
 }
 
-// ---- single-rank factorisation: the plan (plan_groups, plan_step), then the enqueue (factor_all) ------------------------------
-// Three-level hierarchy: 64-wide block pivots inside nb-wide panels inside groups of `group` panels.  Panels of a
-// group are factored left-looking against the group's earlier panels; the trailing matrix is updated ONCE per group
-// with K = group*nb, which divides the C-tile read-modify-write traffic (the HBM bound of the rank-nb update) by `group`.
-// Group schedule: `group` panels per bulk update while the bulk update outlasts the panel chain; once at most
-// TAIL_COLS columns remain the chain is the critical path and shorter groups (less in-group update work on
-// the chain, more in the cheap bulk launches) end the factorisation sooner.  A pure function of its arguments.
-GroupSched plan_groups(const Geo& g, int group, int tail_group, bool tail_group_user, bool skip_zeros, int lookahead) {
-    GroupSched s;
-    const int64_t np = g.npanels;
-    const bool closed_form = skip_zeros && g.mi > 0;   // groups inside the slack block: closed-form elimination (k_s_panel)
-    s.of_.assign((size_t)np, 0); s.off_.assign((size_t)np, 0);
-    for (int64_t p = 0; p < np;) {
-        const int64_t remaining = g.Npad - g.panel_c0(p);
-        // (round 6: systems of at most 8192 rows take groups of 8 in the tail too -- with the chain of a group as ONE launch a group
-        //  boundary costs more than the in-group updates of the longer group: config 2 2.25 against 2.29 ms; N = 32768: 104.9
-        //  against 102.4 ms, config 3 185.4 against 183.2: 4 stays there)
-        const int tg = (!tail_group_user && g.Npad <= 8192) ? 8 : tail_group;
-        int64_t G = (tg > 0 && remaining <= TAIL_COLS) ? tg : group;
-        if (G > group) G = group;
-        if (p + G > np) G = np - p;
-        // (round 5) the panels inside the slack block as ONE group: their kernels run up front (enqueue_slack_first) and what is left of
-        // a slack group in the loop of factor_all is a head, a k_s_schur launch and four stream hops -- 56 us per group of four
-        // panels between the x block's last bulk update and the multiplier block's first chain (N = 32768: six groups)
-        if (closed_form && lookahead && p > 0 && g.panel_c0(p) >= g.n && g.panel_c0(p + G - 1) + g.panel_w(p + G - 1) <= g.n + g.mi)
-            while (p + G < np && g.panel_c0(p + G) + g.panel_w(p + G) <= g.n + g.mi) ++G;
-        const int64_t ca = g.panel_c0(p), cb = g.panel_c0(p + G - 1) + g.panel_w(p + G - 1);      // the group's columns [ca, cb)
-        for (int64_t q = 0; q < G; ++q) { s.of_[(size_t)(p + q)] = (int)s.first_.size(); s.off_[(size_t)(p + q)] = (int)q; }
-        s.first_.push_back(p);
-        s.in_x_.push_back(cb <= g.n ? 1 : 0);
-        s.fast_.push_back((closed_form && ca >= g.n && cb <= g.n + g.mi) ? 1 : 0);
-        p += G;
-    }
-    s.first_.push_back(np);
-    return s;
-}
-
-// ---- the reusable x-block prefix -------------------------------------------------------------------------
-// The x-block panels hold d2L + delta I, Je', Ji': what stage_blocks staged and delta, nothing of s, lda or mu.  Groups [0, gB)
-// -- gB the first group that does not lie inside the x block -- are the prefix; once all of their contributions have reached
-// the columns [cB, Npad) behind them and nothing else has, those columns are a function of the blocks, delta, delta_c and the
-// geometry (minus the panels wholly inside the slack block: no x column reaches them, they are re-assembled).  A RECORDING step
-// is a full factorisation that copies them, the statistics and the assembly's maximum as they stand at that point into the
-// snapshot; a REUSING step re-assembles the slack columns, restores the rest from the snapshot, seeds the statistics and
-// factors from group gB on.  Only pyipm_newton_step does either: nobody can look at the matrix between its phases.
-enum { PX_FULL = 0, PX_RECORD = 1, PX_REUSE = 2 };
-static int64_t prefix_groups(const GroupSched& sc) {
-    int64_t gB = 0;
-    while (gB < sc.ngroups() && sc.in_x(gB)) ++gB;
-    return gB;
-}
-// The column ranges of the snapshot, [c0, c1) each with the rows [c0, Npad): what lies behind column cB except the panels wholly
-// inside the slack block.  Returns the snapshot's doubles (header included).
-struct PxRange { int64_t c0, c1, off; };
-static size_t prefix_ranges(const Geo& g, int64_t cB, PxRange out[2], int* count) {
-    int64_t s0 = 0, s1 = 0;                                  // the panels wholly inside the slack block: columns [s0, s1)
-    if (g.mi > 0) {
-        s0 = (g.n + g.nb - 1) / g.nb * g.nb; if (s0 < cB) s0 = cB;
-        s1 = (g.n + g.mi) / g.nb * g.nb;
-    }
-    const int64_t cut[2][2] = {{cB, s1 > s0 ? s0 : g.Npad}, {s1 > s0 ? s1 : g.Npad, g.Npad}};
-    size_t tot = PX_HDR; *count = 0;
-    for (int k = 0; k < 2; ++k) {
-        if (cut[k][1] <= cut[k][0]) continue;
-        out[*count] = PxRange{cut[k][0], cut[k][1], (int64_t)tot};
-        tot += (size_t)(cut[k][1] - cut[k][0]) * (size_t)(g.Npad - cut[k][0]);
-        ++*count;
-    }
-    return tot;
-}
-static_assert(sizeof(DevStats) <= 16 * sizeof(double) && PX_HDR > 16, "the snapshot's header holds DevStats, then the maximum");
-// (c_end > 0, restoring: only the columns in front of c_end -- a step that keeps the lambda_e groups too)
-static int prefix_copy(Ctx* ctx, int64_t cB, bool save, int64_t c_end = 0) {
-    const Geo& g = ctx->g;
-    PxRange r[2]; int nr = 0;
-    const size_t tot = prefix_ranges(g, cB, r, &nr);
-    if (tot > ctx->snap.capacity()) { ctx->err = "prefix snapshot: buffer too small"; return PYIPM_E_BADARG; }
-    double* hdr = ctx->snap.get();
-    const hipMemcpyKind dd = hipMemcpyDeviceToDevice;
-    if (save) {
-        PYIPM_HIP(hipMemcpyAsync(hdr, ctx->dstats, sizeof(DevStats), dd, ctx->stream));
-        PYIPM_HIP(hipMemcpyAsync(hdr + 16, ctx->anorm, sizeof(unsigned long long), dd, ctx->stream));
-    } else {
-        PYIPM_HIP(hipMemcpyAsync(ctx->anorm, hdr + 16, sizeof(unsigned long long), dd, ctx->stream));
-    }
-    for (int k = 0; k < nr; ++k) {
-        const int64_t rows = g.Npad - r[k].c0, cols = (c_end > 0 && c_end < r[k].c1 ? c_end : r[k].c1) - r[k].c0;
-        if (cols <= 0) continue;
-        double* a = ctx->A + r[k].c0 + r[k].c0 * g.Npad;       // (single rank: local = global columns)
-        double* b = ctx->snap.get() + r[k].off;
-        const dim3 grid((unsigned)cols, (unsigned)((rows + 2047) / 2048));
-        if (save) hipLaunchKernelGGL(k_copy_cols, grid, dim3(256), 0, ctx->stream, b, rows, (const double*)a, g.Npad, rows, cols);
-        else      hipLaunchKernelGGL(k_copy_cols, grid, dim3(256), 0, ctx->stream, a, g.Npad, (const double*)b, rows, rows, cols);
-        PYIPM_KCHECK();
-    }
-    return 0;
-}
-// ---- the second level: the lambda_e groups -----------------------------------------------------------------
-// The slack columns couple to lambda_i only, so behind the x groups the lambda_e columns depend on the staged blocks, delta and
-// delta_c alone: the groups [gS, gE) that lie wholly inside the columns [n + mi, n + mi + me) are kept like the prefix.  gS is the
-// first group behind the slack block, gE the first one that does not lie wholly inside lambda_e, cS / cE their first columns; a
-// group that straddles either border is factored.  What changes behind cE from step to step are the diagonal entries of the
-// lambda_i block (the slack term), and an FMA chain rounds by its running value: a reusing step takes the 128-row diagonal blocks
-// behind cE as the prefix left them (first snapshot), lets the groups it factors in front of gS and the slack kernels apply
-// their terms, applies the kept groups with k_update over a list of those blocks alone (diag_update; the saved W), in group
-// order -- the products every entry of a block received in the recording step, in that order -- and takes everything else behind cE
-// from the second snapshot.
-struct LamE { bool ok = false; int64_t gS = 0, gE = 0, cS = 0, cE = 0; };
-static LamE lam_e_groups(const Geo& g, const GroupSched& sc, int64_t gB) {
-    LamE e;
-    const int64_t ng = sc.ngroups(), e0 = g.n + g.mi, e1 = e0 + g.me;
-    if (g.me <= 0 || g.mi <= 0 || gB <= 0 || gB >= ng) return e;
-    auto c0 = [&](int64_t grp) { return grp >= ng ? g.Npad : g.panel_c0(sc.first(grp)); };
-    int64_t gS = gB; while (gS < ng && c0(gS) < e0) ++gS;
-    int64_t gE = gS; while (gE < ng && c0(gE + 1) <= e1) ++gE;
-    if (gE == gS || gE >= ng) return e;                       // no whole group inside lambda_e, or none behind it
-    e.ok = true; e.gS = gS; e.gE = gE; e.cS = c0(gS); e.cE = c0(gE);
-    return e;
-}
-// The second snapshot: PX_HDR doubles, W of the columns [cS, cE) in the rows [cE, Npad) (leading dimension Npad - cE), the square.
-static size_t lam_e_doubles(const Geo& g, const LamE& e) {
-    const size_t rows = (size_t)(g.Npad - e.cE);
-    return PX_HDR + rows * (size_t)(e.cE - e.cS) + rows * rows;
-}
-static double* lam_e_w(const Ctx* ctx, const LamE& e, int64_t c) { return ctx->snap_e.get() + PX_HDR + (c - e.cS) * (ctx->g.Npad - e.cE); }
-static double* lam_e_square(const Ctx* ctx, const LamE& e) { return lam_e_w(ctx, e, e.cE); }
-// K source columns from global column src_c0 on (L at Lop; -S at W, whose first row is global row w_row0 <= cE: row r of column
-// k at W[(r - w_row0) + k ldw]) applied to the 128-row diagonal blocks of the columns [cE, Npad): k_update<64> (the instance of
-// the narrow bulk launches) over a list of those tiles.  k_update addresses its W operand by global row; the address of "row 0"
-// it is handed is computed on integers (a pointer in front of the buffer is never formed; no tile of the list reads there).
-static int diag_update(Ctx* ctx, hipStream_t st, const double* Lop, const double* W, int64_t w_row0, int64_t ldw, int K, int64_t src_c0,
-                       int64_t cE) {
-    const double* const Wop = reinterpret_cast<const double*>(reinterpret_cast<uintptr_t>(W) - (uintptr_t)w_row0 * sizeof(double));
-    const Geo& g = ctx->g;
-    const int64_t nrt = (g.Npad - cE) / BM;
-    if (nrt <= 0 || K <= 0) return 0;
-    if (ctx->diag_tiles_n != nrt) {
-        ctx->diag_tiles_host.clear();
-        for (int64_t r = 0; r < nrt; ++r) for (int h = 0; h < BM / 64; ++h)
-            ctx->diag_tiles_host.push_back((unsigned)r | ((unsigned)(r * (BM / 64) + h) << 16));
-        PYIPM_HIP(ctx->diag_tiles.reserve(ctx->diag_tiles_host.size()));
-        PYIPM_HIP(hipMemcpyAsync(ctx->diag_tiles.get(), ctx->diag_tiles_host.data(), ctx->diag_tiles_host.size() * sizeof(unsigned),
-                                 hipMemcpyHostToDevice, st));
-        ctx->diag_tiles_n = nrt;
-    }
-    UpdGeo u;
-    u.row_begin = cE; u.Npad = g.Npad; u.first_lp = cE / g.nb; u.sub0 = 0;
-    u.nb = g.nb; u.world = 1; u.rank = 0; u.nrt = (int)nrt; u.nct = (int)(nrt * (BM / 64));
-    u.prio = 0; u.rt_min0 = 0; u.rt_step = 0; u.dbg = ctx->dbg_buf; u.ks_cstride = 0;
-    active_ranges(ctx, src_c0, src_c0 + K, &u.a0, &u.a1, &u.b0, &u.b1);
-    u.tiles = ctx->diag_tiles.get();
-    hipLaunchKernelGGL((k_update<64, true, 8>), dim3((unsigned)ctx->diag_tiles_host.size()), dim3(512), 0, st, ctx->A, g.Npad, Lop, g.Npad,
-                       Wop, ldw, K, u);
-    PYIPM_KCHECK();
-    return 0;
-}
-
-// What kind of step the fused entry point runs now.  Reuse applies to the full form on one rank with a lookahead schedule and at
-// least one group inside the x block; everything else is a full step, as it always was.
-static int prefix_mode(Ctx* ctx, double delta, double delta_c, int64_t* gB_out, int64_t* cB_out, LamE* e_out) {
-    const Geo& g = ctx->g;
-    Held& h = ctx->held;
-    *gB_out = 0; *cB_out = 0; *e_out = LamE();
-    if (!ctx->reuse_x || g.world != 1 || ctx->batched || ctx->provider_only || (ctx->condensed && g.mi > 0) || !ctx->lookahead ||
-        h.storage_exported) return PX_FULL;                    // (a holder of the storage pointer may write into the x columns at any time)
-    const GroupSched sc = plan_groups(g, ctx->group, ctx->tail_group, ctx->tail_group_user, ctx->skip_zeros != 0, ctx->lookahead);
-    const int64_t gB = prefix_groups(sc);
-    if (gB == 0 || gB >= sc.ngroups()) return PX_FULL;
-    const int64_t cB = g.panel_c0(sc.first(gB));
-    *gB_out = gB; *cB_out = cB;
-    const LamE le = ctx->reuse_lam_e ? lam_e_groups(g, sc, gB) : LamE();
-    if (h.px_valid && delta == h.px_delta && delta_c == h.px_delta_c && gB == h.px_groups && cB == h.px_cB && ctx->snap) {
-        if (le.ok && h.px_e_valid && le.gS == h.px_gS && le.gE == h.px_gE && ctx->snap_e.capacity() >= lam_e_doubles(g, le)) *e_out = le;
-        return PX_REUSE;
-    }
-    // the first factorisation of these blocks records; a later one only with the shifts of the one before it (a shift loop
-    // changes them every time and never gets as far as reusing)
-    if (!h.px_record || (h.px_steps > 0 && (delta != h.px_last_delta || delta_c != h.px_last_delta_c))) return PX_FULL;
-    PxRange r[2]; int nr = 0;
-    const size_t tot = prefix_ranges(g, cB, r, &nr);
-    if (ctx->snap.capacity() < tot) {
-        if (ctx->snap.reserve(tot) != hipSuccess) {              // no room for it: the handle goes on without the feature
-            (void)hipGetLastError();
-            ctx->reuse_x = 0;
-            return PX_FULL;
-        }
-        if (getenv("PYIPM_POISON_WORKSPACE")) (void)hipMemsetAsync(ctx->snap, 0xFF, tot * sizeof(double), ctx->stream);
-    }
-    if (le.ok) {
-        const size_t tot_e = lam_e_doubles(g, le);
-        if (ctx->snap_e.capacity() < tot_e) {
-            if (ctx->snap_e.reserve(tot_e) != hipSuccess) {          // no room for the second one: the first level alone
-                (void)hipGetLastError();
-                ctx->reuse_lam_e = 0;
-                return PX_RECORD;
-            }
-            if (getenv("PYIPM_POISON_WORKSPACE")) (void)hipMemsetAsync(ctx->snap_e, 0xFF, tot_e * sizeof(double), ctx->stream);
-        }
-        *e_out = le;
-    }
-    return PX_RECORD;
-}
-// The assembly of a reusing step (events 2 and 3 around it): the slack columns -- Sigma, -I -- from the staged vectors, the
-// columns of the snapshot from the snapshot.  Columns [0, cB) keep L of the prefix.
-// With the lambda_e groups kept (e.ok): of the first snapshot the columns in front of cS and the diagonal blocks behind cE as the
-// prefix left them, of the second one everything else behind cE; the columns [cS, cE) keep L.
-static int reassemble_slack(Ctx* ctx, int64_t cB, const LamE& e) {
-    const Geo& g = ctx->g;
-    PYIPM_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
-    int rc = prefix_copy(ctx, cB, false, e.ok ? e.cS : 0); if (rc) return rc;
-    if (e.ok) {
-        PxRange r[2]; int nr = 0;
-        (void)prefix_ranges(g, cB, r, &nr);
-        if (nr < 1 || r[nr - 1].c0 > e.cE || r[nr - 1].c1 != g.Npad) { ctx->err = "prefix snapshot: the lambda_i columns are not in its last range"; return PYIPM_E_BADARG; }
-        const int64_t ne = g.Npad - e.cE, s0 = r[nr - 1].c0;
-        hipLaunchKernelGGL(k_copy_diag_blocks, dim3((unsigned)ne), dim3(64), 0, ctx->stream, ctx->A, g.Npad,
-                           (const double*)(ctx->snap.get() + r[nr - 1].off), g.Npad - s0, s0, e.cE, ne);
-        PYIPM_KCHECK();
-        hipLaunchKernelGGL(k_copy_square, dim3((unsigned)ne, (unsigned)((ne + 2047) / 2048)), dim3(256), 0, ctx->stream, ctx->A, g.Npad,
-                           lam_e_square(ctx, e), ne, e.cE, 0);
-        PYIPM_KCHECK();
-    }
-    if (g.mi > 0) {
-        const int zip = (ctx->keep_zeros && !ctx->held.storage_exported && ctx->held.zeros_clean) ? 1 : 0;
-        const int64_t lc0 = g.n / 16 * 16;
-        const dim3 grid((unsigned)((g.Npad + 511) / 512), (unsigned)((g.n + g.mi - lc0 + 15) / 16));
-        hipLaunchKernelGGL(k_assemble, grid, dim3(256), 0, ctx->stream, ctx->A, g.Npad, g, ctx->d2L, ctx->ld_d2L,
-                           ctx->Je, ctx->ld_Je, ctx->Ji, ctx->ld_Ji, ctx->s, ctx->lda, ctx->eps, ctx->delta, ctx->delta_c, ctx->anorm, 0, 0,
-                           zip, lc0, 0, g.n, g.n + g.mi);
-        PYIPM_KCHECK();
-    }
-    PYIPM_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
-    ctx->held.prefix_reassembled();
-    ctx->held.assemble_timed();
-    return 0;
-}
-
-// The assembly of a step or of pyipm_newton_assemble, with the decision what the factorisation behind it does (Held::px_plan).
-// The separate phases take part: between a reusing assembly and its factorisation the storage holds L of the prefix in the x
-// columns, and every entry point that looks at the storage as a matrix completes it first (G_STORAGE, storage_whole).
-int assemble_planned(Ctx* ctx, double delta, double delta_c) {
-    if (!ctx->held.have_blocks || !ctx->held.have_vectors || ctx->provider_only) return assemble_timed(ctx, delta, delta_c);   // (its refusals)
-    ctx->held.step_begun();
-    int64_t gB = 0, cB = 0; LamE le;
-    const int px = prefix_mode(ctx, delta, delta_c, &gB, &cB, &le);
-    const int rc = px == PX_REUSE ? reassemble_slack(ctx, cB, le) : assemble_timed(ctx, delta, delta_c);
-    if (rc) return rc;
-    ctx->held.assembly_planned(ctx->held.cond_active ? (int)PX_FULL : px, gB, cB, le.ok, le.gS, le.gE);
-    return 0;
-}
-// ... and its factorisation, with the bookkeeping of what was recorded or reused.
-int factor_planned(Ctx* ctx, pyipm_factor_stats* stats, bool fuse) {
-    const int px = ctx->held.assembled ? ctx->held.px_plan : (int)PX_FULL;
-    const int64_t gB = ctx->held.px_plan_groups, cB = ctx->held.px_plan_cB;
-    const double delta = ctx->delta, delta_c = ctx->delta_c;
-    const int rc = factor_dispatch(ctx, stats, fuse, px);
-    if (rc) { ctx->held.prefix_dropped(); ctx->held.px_plan = 0; return rc; }       // a failed factorisation: the next one runs in full
-    ctx->held.step_factored(px == PX_RECORD, px == PX_REUSE, delta, delta_c, gB, cB);
-    ctx->last_step_kind = px; ctx->n_recorded += px == PX_RECORD; ctx->n_reused += px == PX_REUSE;
-    return 0;
-}
-int storage_whole(Ctx* ctx) {
-    if (ctx->held.partial()) { const int rc = assemble_timed(ctx, ctx->delta, ctx->delta_c); if (rc) return rc; }
-    ctx->held.prefix_dropped();
-    return 0;
-}
+// ---- single-rank factorisation: the plan (step_plan.hpp: plan_groups, make_step_plan; plan_step), then the enqueue (factor_all) ---
+#include "reuse_impl.hpp"
 
 // diagnostics (PYIPM_GROUP_TRACE=1): where each group's chain, head and bulk update begin and end on the device, without a
 // tracer's per-call cost on the host (tools/group_trace.py)
@@ -2028,38 +1764,35 @@ struct GroupTrace {
 };
 
 // does group grp run as a tile chain (factor_group)?
-static bool chain_group(const Ctx* ctx, int64_t grp) {
-    return ctx->group_chain && !ctx->sched.fast(grp) && ctx->sched.size(grp) * (ctx->g.nb / TB) <= 32 && ctx->g.nb % 128 == 0;
+static bool chain_group(const Ctx* ctx, int64_t grp) { return pyipm::chain_group(ctx->g, ctx->sched, ctx->group_chain != 0, grp); }
+
+struct FactorRun {                     // one whole factorisation: its plan, and what the plan does not hold
+    const StepPlan plan;
+    unsigned fr_blocks = 0;            // workgroups of the range launch over the plan's [frA, frB) (fwd_range_grid); 0: the fallback owners
+    GroupTrace tr;
+    bool across_prev = false;          // the lookahead loop: the iteration before this one looked across the slack block
+    bool done_early(const Ctx* ctx, int64_t q) const { return plan.slack_first && ctx->sched.fast_panel(q); }   // panel q was enqueued up front
+};
+// the forward substitution of the panels [q0, q1), whose L is complete on the forward stream, there
+static int fwd_panels(Ctx* ctx, int64_t q0, int64_t q1) {
+    int rc = 0;
+    for (int64_t q = q0; q < q1 && !rc; ++q) { rc = fwd_panel(ctx, q, ctx->fwd_vec, ctx->fwd); if (!rc) rc = diag_panel(ctx, q, ctx->fwd_vec, ctx->fwd); }
+    return rc;
 }
 
-struct FactorRun {                     // what holds for one whole factorisation: decided by factor_all before the first launch
-    bool fuse_forward;                 // y_p only needs panel p factored: the forward pass of the step's right-hand side trails on ctx->fwd
-    bool early0;                       // group 0 goes to the columns beyond it panel by panel (panel_done)
-    bool slack_first;                  // the closed-form panels of the slack block were enqueued up front (enqueue_slack_first) ...
-    bool done_early(const Ctx* ctx, int64_t q) const { return slack_first && ctx->sched.fast_panel(q); }   // ... panel q was
-    int64_t fr_a = 0, fr_b = 0;        // panels [fr_a, fr_b): their forward substitution runs in one launch of its own (fwd_range), not here
-};
-
 // Panel q of group grp is complete once `used` reaches this point.  The fused forward substitution takes it up.
-// Group 0 right-looking panel by panel (round 6, lookahead = 2): a system whose x block is ONE group followed by the slack
-// block (config 2).  Nothing runs beside the first group's chain, the slack group is no work, and the x group's bulk
-// update -- a launch of a hundred-odd tiles -- is what the multiplier block's chain waits for in full (272 us of 2.22 ms).
-// Here every panel of group 0 goes to the columns beyond the group as soon as it is complete: a K = nb launch on the side
-// stream (idle until the next chain) behind the panel's event, under the chain of the panels that follow; neither a head
-// nor a bulk update is left for group 0.  Every entry receives the same products in the same order.  Measured
-// (tools/r06_early.sh): config 2 2.225 -> 2.165 ms -- the chain itself slows from 880 to 970 us beside the pieces (its
-// round trips to memory share the fabric with their operands), the next chain starts 140 us earlier.  Where the next group
-// is an ordinary one the one-group lookahead already hides the bulk update under that group's chain and the pieces lose
-// (n, me, mi = 3072, 512, 1024: 2.99 -> 3.08 ms): not applied there.  Fewer, persistent blocks per piece (64 ... 192
-// of them) only made the last piece longer.
+// Group 0 right-looking panel by panel (early0): where the x block is ONE group followed by the slack block
+// every panel of group 0 goes to the columns beyond the group as soon as it is complete -- a K = nb launch on the side stream
+// behind the panel's event, under the chain of the panels that follow; neither a head nor a bulk update is left for group 0.
+// Every entry receives the same products in the same order.  Measured (tools/r06_early.sh): config 2 2.225 -> 2.165 ms; where
+// the next group is an ordinary one the lookahead already hides the bulk update and the pieces lose: not applied there.
 static int panel_done(Ctx* ctx, const FactorRun& run, int64_t grp, int64_t q, hipStream_t used) {
-    if (run.fuse_forward && !(q >= run.fr_a && q < run.fr_b)) {
+    if (run.plan.fuse_forward && run.plan.fwd_owner(q, run.fr_blocks != 0) == FwdOwner::PanelDone) {
         if (!run.done_early(ctx, q)) PYIPM_HIP(hipEventRecord(ctx->ev_done[q], used));      // (else: recorded behind its kernel)
         PYIPM_HIP(hipStreamWaitEvent(ctx->fwd, ctx->ev_done[q], 0));
-        int r2 = fwd_panel(ctx, q, ctx->fwd_vec, ctx->fwd); if (r2) return r2;
-        r2 = diag_panel(ctx, q, ctx->fwd_vec, ctx->fwd); if (r2) return r2;
+        const int r2 = fwd_panels(ctx, q, q + 1); if (r2) return r2;
     }
-    if (!(run.early0 && grp == 0)) return 0;
+    if (!(run.plan.early0 && grp == 0)) return 0;
     const int64_t p1 = ctx->sched.first(1);
     PYIPM_HIP(hipEventRecord(ctx->ev_early, used));
     PYIPM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_early, 0));
@@ -2078,16 +1811,9 @@ static int run_group(Ctx* ctx, const FactorRun& run, int64_t grp, hipStream_t S)
     return 0;
 }
 
-// (round 5) The closed-form panels of the slack block depend on nothing but the assembly -- no x-block update
-// reaches their columns -- and used to sit, one 7 us launch after the other, between the x block's last chain and the
-// multiplier block's first (config 2: 0.15 of 2.7 ms, plus the last x group's bulk update queued behind them on the same
-// stream).  They are enqueued up front on the rows stream; what READS them (k_s_schur on the update stream, the forward
-// sweep) keeps its place and waits for one event.  Statistics are atomic sums / minima / maxima: the same numbers.
-static bool slack_first_applies(const Ctx* ctx) {
-    if (!ctx->lookahead || ctx->sched.fast(0)) return false;
-    for (int64_t gi = 1; gi < ctx->sched.ngroups(); ++gi) if (ctx->sched.fast(gi)) return true;
-    return false;
-}
+// (round 5) The closed-form panels of the slack block depend on nothing but the assembly: they are enqueued
+// up front on the rows stream; what READS them (k_s_schur on the update stream, the forward sweep) keeps its place and waits
+// for one event.  Statistics are atomic sums / minima / maxima: the same numbers.
 static int enqueue_slack_first(Ctx* ctx, const FactorRun& run, hipStream_t after) {
     { int r0 = ensure_rest_stream(ctx); if (r0) return r0; }
     PYIPM_HIP(hipEventRecord(ctx->ev_sfast, after));                  // the assembly and the reset of the statistics
@@ -2095,7 +1821,7 @@ static int enqueue_slack_first(Ctx* ctx, const FactorRun& run, hipStream_t after
     for (int64_t q = 0; q < ctx->g.npanels; ++q) {
         if (!ctx->sched.fast_panel(q)) continue;
         int r2 = factor_panel(ctx, q, ctx->rest, true); if (r2) return r2;
-        if (run.fuse_forward) PYIPM_HIP(hipEventRecord(ctx->ev_done[q], ctx->rest));
+        if (run.plan.fuse_forward) PYIPM_HIP(hipEventRecord(ctx->ev_done[q], ctx->rest));
     }
     PYIPM_HIP(hipEventRecord(ctx->ev_sfast, ctx->rest));              // every closed-form panel is done
     return 0;
@@ -2153,23 +1879,18 @@ static GroupStep plan_step(const Ctx* ctx, const FactorRun& run, int64_t grp) {
     // microsecond launches (closed form) that stay on the main stream, head included (sending them through the side
     // stream cost two stream crossings per group, 50-240 us each time for 30 us of work; config 2: 0.6 of 3.6 ms).
     st.cs = st.nxt_fast ? ctx->stream : ctx->side;
-    // (round 5) Lookahead ACROSS the slack block.  With its panels run up front the slack group between the last x group
-    // and the first multiplier group is no work at all -- but that multiplier group's columns used to get this group's
-    // contribution from its BULK update, and its chain started behind the whole launch and the slack group's hops
-    // (N = 32768: 1.6 + 0.3 ms with nothing else on the chain's path; config 2: 0.14 ms).  The group after the slack group
-    // is treated as the lookahead target: a head (split: its diagonal block on the chain's stream, the rows below on the
-    // rows stream) applies this group's contribution to its columns, the bulk update starts beyond them.  The same
-    // products in the same order per entry (x groups in order, then the slack block's diagonal update).
-    st.across = run.slack_first && st.nxt_fast && !st.fast_src && grp > 0 && grp + 2 < sc.ngroups() &&
+    // (round 5) Lookahead ACROSS the slack block, whose panels ran up front: the group after the slack group is
+    // the lookahead target -- a split head applies this group's contribution to its columns, the bulk update starts beyond them
+    // (its chain used to wait for the whole bulk launch: 1.6 + 0.3 ms at N = 32768).  The same products in the same order per entry.
+    st.across = run.plan.slack_first && st.nxt_fast && !st.fast_src && grp > 0 && grp + 2 < sc.ngroups() &&
                 !sc.fast(grp + 2) && chain_group(ctx, grp + 2);
     st.pT = sc.first(grp + (st.across ? 2 : 1)); st.nT = sc.size(grp + (st.across ? 2 : 1));
-    // The head runs on hs: the stream of the chain it follows, i.e. the side stream for every group but the first, so
-    // that chain -> head -> next chain never cross streams.  There it waits for ev_main: the bulk update of
-    // the group before (and the early heads) touched its columns on the main stream -- normally long complete.
-    // (the FIRST head stays on the main stream also when group 0 ran on the chain's stream: nothing runs beside it either
-    //  way, and as a main-stream launch it takes the bulk instance and is part of the trailing figures, as in rounds 1-3)
+    // The head runs on hs: the stream of the chain it follows, i.e. the side stream for every group but the first, so that
+    // chain -> head -> next chain never cross streams.  There it waits for ev_main: the bulk update of the group before touched
+    // its columns on the main stream.  (The FIRST head stays on the main stream: nothing runs beside it either way, and as a
+    // main-stream launch it takes the bulk instance and is part of the trailing figures, as in rounds 1-3.)
     st.hs = (grp > 0 && (st.cs == ctx->side || st.across)) ? ctx->side : ctx->stream;
-    st.pieces = run.early0 && grp == 0;
+    st.pieces = run.plan.early0 && grp == 0;
     // (a head INTO the slack block is structurally empty: no x column reaches an s column, and a slack column's only
     //  update is a diagonal entry of the multiplier block -- no launch, 10-15 us of the chain's path each)
     st.head = !st.pieces && (st.across || !st.nxt_fast);
@@ -2177,20 +1898,10 @@ static GroupStep plan_step(const Ctx* ctx, const FactorRun& run, int64_t grp) {
     return st;
 }
 
-// The enqueue, in this order: the schedule (plan_groups, FactorRun); the closed-form panels of the slack block up front
-// (enqueue_slack_first); group 0 on the main stream; then per group grp, as plan_step decided: head (group grp -> the lookahead
-// target) on hs, group grp + 1 on cs, bulk update (group grp -> everything behind the target) on the main stream beside it --
-// one-group lookahead.  lookahead = 0: bulk update, then the next group, all on the main stream.
-// px (pyipm_newton_step only): PX_RECORD -- neither of the two shortcuts that blur the point where the prefix is complete (the slack
-// panels up front, the lookahead across the slack block; nor group 0 panel by panel): the last prefix group's bulk update covers
-// every column behind it, the snapshot follows on the main stream, group gB after it.  PX_REUSE -- the loop starts at group gB,
-// the forward substitution runs over the prefix panels first.  The same products in the same order per entry: the same bits.
-int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false, int px = PX_FULL) {
-    const Geo& g = ctx->g;
-    if (g.world != 1) { ctx->err = "factor(): single-rank entry point; use the per-panel phases when world > 1"; return PYIPM_E_BADARG; }
-    if (!ctx->held.assembled) { ctx->err = "factor: assemble first"; return PYIPM_E_BADARG; }
-    const auto t_host0 = std::chrono::steady_clock::now();
-    int rc = 0;
+// ---- the phases of the enqueue: each carries out its part of the plan (run.plan) and is empty where the plan has none -------------
+// begin: streams and events, the forward stream behind the right-hand side's copy, the statistics reset or (reusing) seeded
+static int enqueue_begin(Ctx* ctx, FactorRun& run) {
+    const StepPlan& plan = run.plan;
     if (!ctx->side) {
         // panel kernels are latency-critical and tiny: highest dispatch priority, so they take the first
         // CU slot a retiring bulk-update block frees instead of queueing behind the whole bulk grid
@@ -2199,161 +1910,112 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false, i
         PYIPM_HIP(ctx->side.ensure_highest(hipStreamNonBlocking));
     }
     PYIPM_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
-    ctx->sched = plan_groups(g, ctx->group, ctx->tail_group, ctx->tail_group_user, ctx->skip_zeros != 0, ctx->lookahead);
-    const GroupSched& sc = ctx->sched;
-    const int64_t np = g.npanels, ngroups = sc.ngroups();
-    const bool rec = px == PX_RECORD, reuse = px == PX_REUSE;
-    const int64_t gB = px ? prefix_groups(sc) : 0;
-    if (px && (gB == 0 || gB >= ngroups || !ctx->lookahead)) { ctx->err = "factor: no reusable prefix in this schedule"; return PYIPM_E_BADARG; }
-    // the second level (what the assembly planned): the lambda_e groups [gS, gE) are recorded / kept as well
-    const LamE le = (px && ctx->held.px_plan_e) ? lam_e_groups(g, sc, gB) : LamE();
-    if (px && ctx->held.px_plan_e && !(le.ok && le.gS == ctx->held.px_plan_gS && le.gE == ctx->held.px_plan_gE && ctx->snap_e)) {
-        ctx->err = "factor: the schedule changed behind the assembly of a step that keeps the lambda_e groups"; return PYIPM_E_BADARG;
-    }
-    const int64_t g0 = reuse ? (le.ok ? le.gE : gB) : 0;                           // g0: the first group of the lookahead loop
-    // (second snapshot's header: the record in front of the lambda_e groups, then their own; gS > gB always -- group gB begins in
-    //  front of column n + mi)
-    DevStats* const st_before = le.ok ? (DevStats*)ctx->snap_e.get() : nullptr;
-    DevStats* const st_lam_e = le.ok ? (DevStats*)(ctx->snap_e.get() + 16) : nullptr;
-    FactorRun run{fuse_forward, !px && ctx->lookahead >= 2 && ngroups > 2 && chain_group(ctx, 0) && sc.fast(1),
-                  !rec && slack_first_applies(ctx)};
-    // The kept panels behind the prefix in one launch (fwd_range): the slack panels and the lambda_e groups where every group in
-    // [gB, gS) is closed-form and was enqueued up front, the lambda_e groups alone where one of them is factored this step.
-    int64_t frA = 0, frB = 0; unsigned fr_blocks = 0; bool fr_slack = false;
-    if (reuse && fuse_forward && le.ok && fwd_prefix_applies(ctx, sc.first(gB))) {
-        fr_slack = run.slack_first;
-        for (int64_t grp = gB; grp < le.gS; ++grp) fr_slack = fr_slack && sc.fast(grp);
-        frA = sc.first(fr_slack ? gB : le.gS); frB = sc.first(le.gE);
-        fr_blocks = fwd_range_grid(ctx, frA, frB);
-        if (fr_blocks) { run.fr_a = frA; run.fr_b = frB; }
-    }
-    GroupTrace tr;
-    if (tr.on()) {
-        fprintf(stderr, "[pyipm group trace] %s step%s\n", rec ? "recording" : reuse ? "reusing" : "full",
-                reuse ? ": the x-block prefix is kept" : "");
-        if (px) fprintf(stderr, "[pyipm group trace] %s %lld groups: x prefix [0, %lld), lambda_e [%lld, %lld)\n", rec ? "records" : "keeps",
-                        (long long)(gB + (le.ok ? le.gE - le.gS : 0)), (long long)gB, (long long)le.gS, (long long)le.gE);
-    }
     ctx->held.factor_begun();
-    if (fuse_forward) {
+    if (plan.fuse_forward) {
         PYIPM_HIP(ctx->fwd.ensure(hipStreamNonBlocking));
-        PYIPM_HIP(ensure_events(ctx->ev_done, (size_t)np, hipEventDisableTiming));
+        PYIPM_HIP(ensure_events(ctx->ev_done, (size_t)ctx->g.npanels, hipEventDisableTiming));
         PYIPM_HIP(hipEventRecord(ctx->ev_head, ctx->stream));          // v0 = rhs copy was enqueued on the main stream
         PYIPM_HIP(hipStreamWaitEvent(ctx->fwd, ctx->ev_head, 0));
     }
-    if (reuse) {                            // the statistics as the prefix left them, not zero
-        PYIPM_HIP(hipMemcpyAsync(ctx->dstats, ctx->snap.get(), sizeof(DevStats), hipMemcpyDeviceToDevice, ctx->stream));
-        if (le.ok) { hipLaunchKernelGGL(k_merge_stats, dim3(1), dim3(64), 0, ctx->stream, ctx->dstats, (const DevStats*)st_lam_e); PYIPM_KCHECK(); }
-        ctx->n_trailing = 0; ctx->trailing_flops = 0.0; ctx->trailing_area = 0.0;
+    if (plan.kind != PX_REUSE) return factor_begin(ctx);
+    const SnapHeaders hdr = snap_headers(ctx);                          // the statistics as the prefix left them, not zero
+    PYIPM_HIP(hipMemcpyAsync(ctx->dstats, hdr.at_boundary, sizeof(DevStats), hipMemcpyDeviceToDevice, ctx->stream));
+    if (plan.e.ok) { hipLaunchKernelGGL(k_merge_stats, dim3(1), dim3(64), 0, ctx->stream, ctx->dstats, (const DevStats*)hdr.of_lam_e); PYIPM_KCHECK(); }
+    ctx->n_trailing = 0; ctx->trailing_flops = 0.0; ctx->trailing_area = 0.0;
+    return 0;
+}
+// the new right-hand side through the prefix panels (reusing, fused) in one launch (k_fwd_prefix) or panel by panel; the range
+// launch follows at once where it takes the slack panels (complete at ev_sfast) with the kept lambda_e groups
+static int enqueue_fwd_kept(Ctx* ctx, FactorRun& run) {
+    const StepPlan& plan = run.plan;
+    if (plan.kind != PX_REUSE || !plan.fuse_forward) return 0;
+    int rc = plan.fwd_prefix_launch ? fwd_prefix(ctx, plan.pB, ctx->fwd_vec, ctx->fwd) : fwd_panels(ctx, 0, plan.pB); if (rc) return rc;
+    run.tr.mark("fwd prefix end (before group)", plan.gB, ctx->fwd);
+    if (!(run.fr_blocks && plan.fr_slack)) return 0;
+    PYIPM_HIP(hipStreamWaitEvent(ctx->fwd, ctx->ev_sfast, 0));
+    rc = fwd_range(ctx, plan.frA, plan.frB, run.fr_blocks, ctx->fwd_vec, ctx->fwd); if (rc) return rc;
+    run.tr.mark("fwd kept range end", plan.gB, ctx->fwd);
+    return 0;
+}
+// The groups between the prefix and the kept lambda_e groups (the slack group, a group that straddles a border) on the main stream.
+// What they reach behind themselves that this step still needs: the columns in front of cS and the diagonal blocks behind cE.
+static int enqueue_between(Ctx* ctx, FactorRun& run) {
+    const StepPlan& plan = run.plan; const GroupSched& sc = ctx->sched;
+    if (plan.kind != PX_REUSE || !plan.e.ok) return 0;
+    for (int64_t grp = plan.gB; grp < plan.e.gS; ++grp) {
+        const int64_t p0 = sc.first(grp), n0 = sc.size(grp);
+        if (plan.slack_first && sc.fast(grp)) PYIPM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_sfast, 0));
+        run.tr.mark("chain+rows begin", grp, ctx->stream);
+        int rc = run_group(ctx, run, grp, ctx->stream); if (rc) return rc;
+        run.tr.mark("chain+rows end", grp, ctx->stream);
+        if (sc.fast(grp)) { rc = timed_update(ctx, p0, n0, p0 + n0, ctx->g.npanels - (p0 + n0)); if (rc) return rc; continue; }   // (k_s_schur: diagonal entries)
+        for (int64_t t = grp + 1; t < plan.e.gS; ++t)
+            if (!sc.fast(t)) { rc = timed_update(ctx, p0, n0, sc.first(t), sc.size(t)); if (rc) return rc; }
+        rc = diag_update_group(ctx, grp, wbuf(ctx, p0), 0, ctx->g.Npad, plan.e.cE); if (rc) return rc;
+    }
+    return 0;
+}
+// ... the kept groups: their forward substitution waits for nothing, their products go to the diagonal blocks
+static int enqueue_kept_diag(Ctx* ctx, FactorRun& run) {
+    const StepPlan& plan = run.plan; const LamE& le = plan.e;
+    if (plan.kind != PX_REUSE || !le.ok) return 0;
+    run.tr.mark("diagonal blocks begin", le.gS, ctx->stream);
+    if (run.fr_blocks && !plan.fr_slack) {
+        const int rc = fwd_range(ctx, plan.frA, plan.frB, run.fr_blocks, ctx->fwd_vec, ctx->fwd); if (rc) return rc;
+        run.tr.mark("fwd kept range end", le.gS, ctx->fwd);
+    }
+    for (int64_t grp = le.gS; grp < le.gE; ++grp) {
+        const int64_t p0 = ctx->sched.first(grp);
+        const bool mine = plan.fuse_forward && plan.fwd_owner(p0, run.fr_blocks != 0) == FwdOwner::Kept;
+        int rc = mine ? fwd_panels(ctx, p0, ctx->sched.first(grp + 1)) : 0; if (rc) return rc;
+        rc = diag_update_group(ctx, grp, lam_e_w(ctx, le, ctx->g.panel_c0(p0)), le.cE, ctx->g.Npad - le.cE, le.cE); if (rc) return rc;
+    }
+    run.tr.mark("diagonal blocks end", le.gE, ctx->stream);
+    return 0;
+}
+// A recording step, group grp complete on the main stream.  A lambda_e group: its W in the rows behind cE goes to the second
+// snapshot before the buffer is recycled.  which = 1, the last group of the prefix, or 2, the last lambda_e group: no lookahead
+// -- one update of everything behind the group, the snapshot, then the next group, all on the main stream.  0: no boundary.
+static int record_behind(Ctx* ctx, FactorRun& run, int64_t grp, int which) {
+    const Geo& g = ctx->g; const StepPlan& plan = run.plan; const LamE& le = plan.e;
+    const int64_t p0 = ctx->sched.first(grp), n0 = ctx->sched.size(grp); int rc = 0;
+    if (plan.kind == PX_RECORD && le.ok && grp >= le.gS && grp < le.gE) {
+        const int64_t c0 = g.panel_c0(p0), rows = g.Npad - le.cE;
+        rc = copy_cols(ctx, lam_e_w(ctx, le, c0), rows, wbuf(ctx, p0) + le.cE, g.Npad, rows, g.panel_c0(p0 + n0) - c0); if (rc) return rc;
+    }
+    if (!which) return 0;
+    run.tr.mark("bulk begin", grp, ctx->stream);
+    rc = timed_update(ctx, p0, n0, p0 + n0, g.npanels - (p0 + n0)); if (rc) return rc;
+    run.tr.mark("bulk end", grp, ctx->stream);
+    if (which == 2) {
+        const SnapHeaders hdr = snap_headers(ctx);
+        PYIPM_HIP(hipMemcpyAsync(hdr.of_lam_e, ctx->dstats, sizeof(DevStats), hipMemcpyDeviceToDevice, ctx->stream));
+        hipLaunchKernelGGL(k_merge_stats, dim3(1), dim3(64), 0, ctx->stream, ctx->dstats, (const DevStats*)hdr.before_lam_e); PYIPM_KCHECK();
+        rc = copy_square(ctx, lam_e_square(ctx, le), le.cE, true); if (rc) return rc;
     } else {
-        rc = factor_begin(ctx); if (rc) return rc;
+        rc = prefix_copy(ctx, plan, true); if (rc) return rc;
     }
-    if (run.slack_first) { rc = enqueue_slack_first(ctx, run, ctx->stream); if (rc) return rc; }
-    if (reuse && fuse_forward) {            // the new right-hand side through the prefix panels: L and the tile inverses are there
-        const int64_t P0 = sc.first(gB);
-        if (fwd_prefix_applies(ctx, P0)) {  // ... in one launch (k_fwd_prefix), or panel by panel
-            rc = fwd_prefix(ctx, P0, ctx->fwd_vec, ctx->fwd); if (rc) return rc;
-        } else {
-            for (int64_t q = 0; q < P0; ++q) {
-                rc = fwd_panel(ctx, q, ctx->fwd_vec, ctx->fwd); if (rc) return rc;
-                rc = diag_panel(ctx, q, ctx->fwd_vec, ctx->fwd); if (rc) return rc;
-            }
-        }
-        tr.mark("fwd prefix end (before group)", gB, ctx->fwd);
-        if (fr_blocks && fr_slack) {        // ... and on through the slack panels (complete at ev_sfast) and the kept lambda_e groups
-            PYIPM_HIP(hipStreamWaitEvent(ctx->fwd, ctx->ev_sfast, 0));
-            rc = fwd_range(ctx, frA, frB, fr_blocks, ctx->fwd_vec, ctx->fwd); if (rc) return rc;
-            tr.mark("fwd kept range end", gB, ctx->fwd);
-        }
-    }
-    if (reuse && le.ok) {
-        // The groups between the prefix and the kept lambda_e groups (the slack group, a group that straddles a border), one after
-        // the other on the main stream.  What they reach behind themselves that this step still needs: the columns in front of cS
-        // (none inside the slack block: a slack column takes nothing from the columns before it) and the diagonal blocks behind cE.
-        for (int64_t grp = gB; grp < le.gS; ++grp) {
-            const int64_t p0 = sc.first(grp), n0 = sc.size(grp);
-            if (run.slack_first && sc.fast(grp)) PYIPM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_sfast, 0));
-            tr.mark("chain+rows begin", grp, ctx->stream);
-            rc = run_group(ctx, run, grp, ctx->stream); if (rc) return rc;
-            tr.mark("chain+rows end", grp, ctx->stream);
-            if (sc.fast(grp)) { rc = timed_update(ctx, p0, n0, p0 + n0, np - (p0 + n0)); if (rc) return rc; continue; }   // (k_s_schur: diagonal entries)
-            for (int64_t t = grp + 1; t < le.gS; ++t)
-                if (!sc.fast(t)) { rc = timed_update(ctx, p0, n0, sc.first(t), sc.size(t)); if (rc) return rc; }
-            int K = 0; for (int64_t q = p0; q < p0 + n0; ++q) K += (int)g.panel_w(q);
-            rc = diag_update(ctx, ctx->stream, ctx->A + g.local_c0(p0) * g.Npad, wbuf(ctx, p0), 0, g.Npad, K, g.panel_c0(p0), le.cE); if (rc) return rc;
-        }
-        // ... the kept groups: their forward substitution waits for nothing, their products go to the diagonal blocks
-        tr.mark("diagonal blocks begin", le.gS, ctx->stream);
-        if (fr_blocks && !fr_slack) {       // (one launch behind the panels of [gB, gS), which went panel by panel)
-            rc = fwd_range(ctx, frA, frB, fr_blocks, ctx->fwd_vec, ctx->fwd); if (rc) return rc;
-            tr.mark("fwd kept range end", le.gS, ctx->fwd);
-        }
-        for (int64_t grp = le.gS; grp < le.gE; ++grp) {
-            const int64_t p0 = sc.first(grp), n0 = sc.size(grp), c0 = g.panel_c0(p0);
-            if (fuse_forward && !fr_blocks)
-                for (int64_t q = p0; q < p0 + n0; ++q) {
-                    rc = fwd_panel(ctx, q, ctx->fwd_vec, ctx->fwd); if (rc) return rc;
-                    rc = diag_panel(ctx, q, ctx->fwd_vec, ctx->fwd); if (rc) return rc;
-                }
-            rc = diag_update(ctx, ctx->stream, ctx->A + g.local_c0(p0) * g.Npad, lam_e_w(ctx, le, c0), le.cE, g.Npad - le.cE,
-                             (int)(g.panel_c0(sc.first(grp + 1)) - c0), c0, le.cE); if (rc) return rc;
-        }
-        tr.mark("diagonal blocks end", le.gE, ctx->stream);
-    }
-    if (reuse && run.slack_first && sc.fast(g0)) PYIPM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_sfast, 0));   // (as in front of any slack group)
+    run.tr.mark(which == 2 ? "second snapshot end" : "snapshot end", grp, ctx->stream);
+    rc = run_group(ctx, run, grp + 1, ctx->stream); if (rc) return rc;
+    PYIPM_HIP(hipEventRecord(ctx->ev_main, ctx->stream));
+    run.across_prev = false; return 0;
+}
+// The lookahead loop: group g0 on the main stream; then per group grp, as plan_step decided: head (grp -> the lookahead target) on
+// hs, group grp + 1 on cs, bulk update (grp -> everything behind the target) on the main stream beside it.  lookahead = 0: all on it.
+static int enqueue_groups(Ctx* ctx, FactorRun& run) {
+    const StepPlan& plan = run.plan; const GroupSched& sc = ctx->sched; GroupTrace& tr = run.tr;
+    const int64_t np = ctx->g.npanels, ngroups = sc.ngroups(), g0 = plan.g0; const bool reuse = plan.kind == PX_REUSE;
+    if (reuse && plan.slack_first && sc.fast(g0)) PYIPM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_sfast, 0));   // (as in front of any slack group)
     tr.mark("chain+rows begin", g0, ctx->stream);
-    rc = run_group(ctx, run, g0, ctx->stream); if (rc) return rc;
+    int rc = run_group(ctx, run, g0, ctx->stream); if (rc) return rc;
     tr.mark("chain+rows end", g0, ctx->stream);
-    if (reuse) PYIPM_HIP(hipEventRecord(ctx->ev_main, ctx->stream));      // group g0 ran on the main stream: its head on the side stream waits for this
+    if (reuse) PYIPM_HIP(hipEventRecord(ctx->ev_main, ctx->stream));       // group g0 ran on the main stream: its head on the side stream waits for this
     if (tr.on()) fprintf(stderr, "[pyipm group trace] %lld groups\n", (long long)ngroups);
-    // A recording step isolates the lambda_e groups' own statistics: the record so far is set aside and reset in front of group gS
-    // (on the stream that group runs on, behind everything that came before it), merged back behind group gE - 1.
-    auto stats_aside = [&](hipStream_t S) -> int {
-        PYIPM_HIP(hipMemcpyAsync(st_before, ctx->dstats, sizeof(DevStats), hipMemcpyDeviceToDevice, S));
-        hipLaunchKernelGGL(k_init_stats, dim3(1), dim3(64), 0, S, ctx->dstats); PYIPM_KCHECK();
-        return 0;
-    };
-    bool across_prev = false;
     for (int64_t grp = g0; grp + 1 < ngroups; ++grp) {
         const int64_t p0 = sc.first(grp), n0 = sc.size(grp);            // the source: its contribution goes to everything behind it
-        if (rec && le.ok && grp >= le.gS && grp < le.gE) {
-            // a lambda_e group, complete on the main stream: its W in the rows behind cE, before the buffer is recycled
-            const int64_t c0 = g.panel_c0(p0), rows = g.Npad - le.cE, cols = g.panel_c0(sc.first(grp + 1)) - c0;
-            hipLaunchKernelGGL(k_copy_cols, dim3((unsigned)cols, (unsigned)((rows + 2047) / 2048)), dim3(256), 0, ctx->stream,
-                               lam_e_w(ctx, le, c0), rows, (const double*)(wbuf(ctx, p0) + le.cE), g.Npad, rows, cols);
-            PYIPM_KCHECK();
-        }
-        if (rec && le.ok && grp + 1 == le.gE) {
-            // the last lambda_e group: as behind the prefix -- one update of everything behind it, the groups' own record, the
-            // second snapshot, then group gE, all on the main stream
-            tr.mark("bulk begin", grp, ctx->stream);
-            rc = timed_update(ctx, p0, n0, p0 + n0, np - (p0 + n0)); if (rc) return rc;
-            tr.mark("bulk end", grp, ctx->stream);
-            PYIPM_HIP(hipMemcpyAsync(st_lam_e, ctx->dstats, sizeof(DevStats), hipMemcpyDeviceToDevice, ctx->stream));
-            hipLaunchKernelGGL(k_merge_stats, dim3(1), dim3(64), 0, ctx->stream, ctx->dstats, (const DevStats*)st_before); PYIPM_KCHECK();
-            const int64_t ne = g.Npad - le.cE;
-            hipLaunchKernelGGL(k_copy_square, dim3((unsigned)ne, (unsigned)((ne + 2047) / 2048)), dim3(256), 0, ctx->stream, ctx->A, g.Npad,
-                               lam_e_square(ctx, le), ne, le.cE, 1);
-            PYIPM_KCHECK();
-            tr.mark("second snapshot end", grp, ctx->stream);
-            rc = run_group(ctx, run, le.gE, ctx->stream); if (rc) return rc;
-            PYIPM_HIP(hipEventRecord(ctx->ev_main, ctx->stream));
-            across_prev = false;
-            continue;
-        }
-        if (rec && grp + 1 == gB) {
-            // the last group of the prefix (complete on the main stream: group 0 ran there, every later one was joined behind its
-            // chain): one update of everything behind it, the snapshot, then group gB -- all on the main stream, no lookahead
-            tr.mark("bulk begin", grp, ctx->stream);
-            rc = timed_update(ctx, p0, n0, p0 + n0, np - (p0 + n0)); if (rc) return rc;
-            tr.mark("bulk end", grp, ctx->stream);
-            rc = prefix_copy(ctx, g.panel_c0(sc.first(gB)), true); if (rc) return rc;
-            tr.mark("snapshot end", grp, ctx->stream);
-            rc = run_group(ctx, run, gB, ctx->stream); if (rc) return rc;
-            PYIPM_HIP(hipEventRecord(ctx->ev_main, ctx->stream));
-            across_prev = false;
-            continue;
-        }
+        const int snapshot = plan.snapshot_behind(grp);
+        rc = record_behind(ctx, run, grp, snapshot); if (rc) return rc;
+        if (snapshot) continue;
         if (!ctx->lookahead) {
             rc = timed_update(ctx, p0, n0, p0 + n0, np - (p0 + n0)); if (rc) return rc;
             rc = run_group(ctx, run, grp + 1, ctx->stream); if (rc) return rc;
@@ -2364,8 +2026,8 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false, i
             // (recorded at the end of the iteration before.  Behind an `across` iteration the source is the slack group: its
             //  head is the diagonal update of the target's columns, ordered behind the x group's head on this stream, and the
             //  x group's bulk update -- what the event would wait for -- no longer touches those columns)
-            if (!across_prev) PYIPM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_main, 0));
-            if (run.slack_first && st.fast_src) PYIPM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_sfast, 0));   // (k_s_schur reads the slack columns)
+            if (!run.across_prev) PYIPM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_main, 0));
+            if (plan.slack_first && st.fast_src) PYIPM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_sfast, 0));   // (k_s_schur reads the slack columns)
         }
         if (st.pieces) {
             PYIPM_HIP(hipEventRecord(ctx->ev_early, ctx->side));          // the last piece
@@ -2381,9 +2043,12 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false, i
             PYIPM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_head, 0));
         }
         tr.mark("chain+rows begin", grp + 1, st.cs);
-        if (run.slack_first && st.nxt_fast)                              // its kernels ran up front: whoever follows on cs (= the main
+        if (plan.slack_first && st.nxt_fast)                             // its kernels ran up front: whoever follows on cs (= the main
             PYIPM_HIP(hipStreamWaitEvent(st.cs, ctx->ev_sfast, 0));      // stream: k_s_schur too) is ordered behind them
-        if (rec && le.ok && grp + 1 == le.gS) { rc = stats_aside(st.cs); if (rc) return rc; }
+        if (plan.kind == PX_RECORD && plan.e.ok && grp + 1 == plan.e.gS) {   // stats_aside: the record so far is set aside and reset in
+            PYIPM_HIP(hipMemcpyAsync(snap_headers(ctx).before_lam_e, ctx->dstats, sizeof(DevStats), hipMemcpyDeviceToDevice, st.cs));   // front of
+            hipLaunchKernelGGL(k_init_stats, dim3(1), dim3(64), 0, st.cs, ctx->dstats); PYIPM_KCHECK();   // group gS, merged back behind gE - 1
+        }
         rc = run_group(ctx, run, grp + 1, st.cs); if (rc) return rc;
         tr.mark("chain+rows end", grp + 1, st.cs);
         PYIPM_HIP(hipEventRecord(ctx->ev_panel, st.cs));
@@ -2396,10 +2061,14 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false, i
         // two stream crossings for nothing)
         PYIPM_HIP(hipEventRecord(ctx->ev_main, ctx->stream));
         PYIPM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_panel, 0));
-        across_prev = st.across;
+        run.across_prev = st.across;
     }
-    if (fuse_forward) {                     // join: the main stream continues after the forward pass
-        tr.mark("fwd stream end (before group)", ngroups, ctx->fwd);
+    return 0;
+}
+// join: the main stream continues after the forward pass; the statistics come back, the timings are taken
+static int enqueue_end(Ctx* ctx, FactorRun& run, pyipm_factor_stats* stats, std::chrono::steady_clock::time_point t_host0) {
+    if (run.plan.fuse_forward) {
+        run.tr.mark("fwd stream end (before group)", ctx->sched.ngroups(), ctx->fwd);
         PYIPM_HIP(hipEventRecord(ctx->ev_fwd, ctx->fwd));
         PYIPM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_fwd, 0));
         ctx->held.forward_fused_under_factor();
@@ -2411,13 +2080,45 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false, i
         fprintf(stderr, "[pyipm] factor_all: host enqueue %.2f ms (tile lists built so far: %d in %.2f ms)\n", host_ms,
                 ctx->setup_lists_n, ctx->setup_lists_ms);
     }
-    rc = factor_end(ctx, stats);
+    const int rc = factor_end(ctx, stats);
     float ms = 0.f;
     PYIPM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    tr.report(ctx->ev[0], ctx->ev[1], ms);
+    run.tr.report(ctx->ev[0], ctx->ev[1], ms);
     ctx->t_factor = ms;
     ctx->t_panel = ctx->profile ? (ms - ctx->t_trailing_union) : 0.0;    // exposed panel time: no update launch running
     return rc;
+}
+
+// The enqueue: the schedule and the plan of this step (px: pyipm_newton_step and factor_planned alone pass one), which must be the
+// one its assembly decided; then the phases above in order.  The same products in the same order per entry: the same bits.
+int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false, int px = PX_FULL) {
+    const Geo& g = ctx->g;
+    if (g.world != 1) { ctx->err = "factor(): single-rank entry point; use the per-panel phases when world > 1"; return PYIPM_E_BADARG; }
+    if (!ctx->held.assembled) { ctx->err = "factor: assemble first"; return PYIPM_E_BADARG; }
+    const auto t_host0 = std::chrono::steady_clock::now();
+    const SchedOpts o = sched_opts(ctx); ctx->sched = plan_groups(g, o);
+    FactorRun run{make_step_plan(g, ctx->sched, o, px, px && ctx->held.plan.e.ok, fuse_forward, fwd_prefix_applies(ctx))};
+    const StepPlan& plan = run.plan;
+    if (px && plan.kind == PX_FULL) { ctx->err = "factor: no reusable prefix in this schedule"; return PYIPM_E_BADARG; }
+    if (px && !(plan == ctx->held.plan && (!plan.e.ok || ctx->snap_e))) {
+        const char* const what = plan.e.ok || ctx->held.plan.e.ok ? "lambda_e groups" : "x prefix";
+        ctx->err = "factor: the schedule changed behind the assembly of a step that keeps the " + std::string(what); return PYIPM_E_BADARG;
+    }
+    if (plan.frB > plan.frA) run.fr_blocks = fwd_range_grid(ctx, plan.frA, plan.frB);      // (0: the occupancy query says no -- the fallback owners)
+    if (run.tr.on()) {
+        const bool rec = plan.kind == PX_RECORD, reuse = plan.kind == PX_REUSE;
+        fprintf(stderr, "[pyipm group trace] %s step%s\n", rec ? "recording" : reuse ? "reusing" : "full",
+                reuse ? ": the x-block prefix is kept" : "");
+        if (px) fprintf(stderr, "[pyipm group trace] %s %lld groups: x prefix [0, %lld), lambda_e [%lld, %lld)\n", rec ? "records" : "keeps",
+                        (long long)(plan.gB + (plan.e.ok ? plan.e.gE - plan.e.gS : 0)), (long long)plan.gB, (long long)plan.e.gS, (long long)plan.e.gE);
+    }
+    int rc = enqueue_begin(ctx, run); if (rc) return rc;
+    if (plan.slack_first) { rc = enqueue_slack_first(ctx, run, ctx->stream); if (rc) return rc; }
+    rc = enqueue_fwd_kept(ctx, run); if (rc) return rc;
+    rc = enqueue_between(ctx, run); if (rc) return rc;
+    rc = enqueue_kept_diag(ctx, run); if (rc) return rc;
+    rc = enqueue_groups(ctx, run); if (rc) return rc;
+    return enqueue_end(ctx, run, stats, t_host0);
 }
 
 // factor_all on whichever system assemble() built; inertia reported for the FULL KKT matrix either way:
