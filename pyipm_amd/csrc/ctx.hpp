@@ -375,6 +375,8 @@ struct Ctx {
     PollWords fwdr_words{4096 + 8192,     // ... its own flags and progress words
                          "forward sweep over the kept slack and lambda_e panels (k_fwd_range): a poll timed out; the direction was NaN "
                          "(PYIPM_FWD_RANGE=0 runs it panel by panel)"};
+    int slack_one = 1;                    // the closed-form slack panels of a group schedule in one launch per contiguous run (k_s_panels);
+                                          // PYIPM_SLACK_ONE=0 at create time keeps a launch and an event per panel
     int last_step_kind = 0;               // 0 full, 1 recording, 2 reusing
     DevBuf<char> ws;                      // the workspace: the caller's (adopted) or the library's; capacity = the bytes the geometry needs
     // carved from workspace

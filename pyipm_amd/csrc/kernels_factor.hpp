@@ -709,8 +709,9 @@ __global__ __launch_bounds__(256) void k_panel_scale(
 // (1/d by division, the refinement recurrences of flagged tiles as fused multiply-adds), so the factor, the
 // statistics and the directions are bit for bit those of the dense path.
 // One block, 256 threads: wave w takes tiles w, w+4, ...; lane k owns column 64 t + k of the panel.
+// s_panel_dev is that block's work; k_s_panel runs it for one panel, k_s_panels for every panel of a contiguous range.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_s_panel(
+__device__ __forceinline__ void s_panel_dev(
     double* __restrict__ A, int64_t ld, int64_t c0, int64_t lc0, int nt,       // global / local first column of the panel
     double* __restrict__ Tinv, double* __restrict__ Tsave, double* __restrict__ Tflag,     // of the panel's first tile
     double refine_cond, int nref, DevStats* __restrict__ st, int64_t s0, int64_t i0, double pivtol_rel,
@@ -774,6 +775,30 @@ __global__ __launch_bounds__(256) void k_s_panel(
         stats_add(st, n, z, 0, (long long)nt * TB - n, b, mn, mx);                               // static pivots are positive
         atomicMax(&st->growth_bits, (unsigned long long)__double_as_longlong(gm));
     }
+}
+__global__ __launch_bounds__(256) void k_s_panel(
+    double* __restrict__ A, int64_t ld, int64_t c0, int64_t lc0, int nt,
+    double* __restrict__ Tinv, double* __restrict__ Tsave, double* __restrict__ Tflag,
+    double refine_cond, int nref, DevStats* __restrict__ st, int64_t s0, int64_t i0, double pivtol_rel,
+    const unsigned long long* __restrict__ anorm_bits)
+{
+    s_panel_dev(A, ld, c0, lc0, nt, Tinv, Tsave, Tflag, refine_cond, nref, st, s0, i0, pivtol_rel, anorm_bits);
+}
+// Panels [p0, p0 + gridDim.x) of the single-rank group schedule (local = global columns, ld = Npad), all inside the slack block:
+// workgroup b does for panel p0 + b exactly what one k_s_panel launch does.  The panels touch disjoint columns, tiles and flags;
+// the statistics are atomic integer sums, minima and maxima, so no order among the workgroups shows in any result.
+// Dinv, Tsv, Tflag: of tile 0 of the matrix.
+__global__ __launch_bounds__(256) void k_s_panels(
+    double* __restrict__ A, int64_t ld, int64_t p0, int nb,
+    double* __restrict__ Dinv, double* __restrict__ Tsv, double* __restrict__ Tflag,
+    double refine_cond, int nref, DevStats* __restrict__ st, int64_t s0, int64_t i0, double pivtol_rel,
+    const unsigned long long* __restrict__ anorm_bits)
+{
+    const int64_t c0 = (p0 + (int64_t)blockIdx.x) * nb;
+    const int64_t w = ld - c0 < nb ? ld - c0 : nb;                  // (Geo::panel_w)
+    const int64_t t0 = c0 / TB;
+    s_panel_dev(A, ld, c0, c0, (int)(w / TB), Dinv + t0 * (int64_t)(TB * TB), Tsv + t0 * (int64_t)(TB * TB), Tflag + t0,
+                refine_cond, nref, st, s0, i0, pivtol_rel, anorm_bits);
 }
 
 // The trailing update of slack-block source columns [c0, c0+ncols): column c touches exactly one entry, the

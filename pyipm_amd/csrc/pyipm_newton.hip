@@ -1788,8 +1788,9 @@ static int fwd_panels(Ctx* ctx, int64_t q0, int64_t q1) {
 // the next group is an ordinary one the lookahead already hides the bulk update and the pieces lose: not applied there.
 static int panel_done(Ctx* ctx, const FactorRun& run, int64_t grp, int64_t q, hipStream_t used) {
     if (run.plan.fuse_forward && run.plan.fwd_owner(q, run.fr_blocks != 0) == FwdOwner::PanelDone) {
-        if (!run.done_early(ctx, q)) PYIPM_HIP(hipEventRecord(ctx->ev_done[q], used));      // (else: recorded behind its kernel)
-        PYIPM_HIP(hipStreamWaitEvent(ctx->fwd, ctx->ev_done[q], 0));
+        const bool early = run.done_early(ctx, q);                     // its kernel ran up front: complete at ev_sfast, or (per-panel
+        if (!early) PYIPM_HIP(hipEventRecord(ctx->ev_done[q], used));  // launches) at the record behind its own kernel
+        PYIPM_HIP(hipStreamWaitEvent(ctx->fwd, early && ctx->slack_one ? ctx->ev_sfast : ctx->ev_done[q], 0));
         const int r2 = fwd_panels(ctx, q, q + 1); if (r2) return r2;
     }
     if (!(run.plan.early0 && grp == 0)) return 0;
@@ -1818,10 +1819,24 @@ static int enqueue_slack_first(Ctx* ctx, const FactorRun& run, hipStream_t after
     { int r0 = ensure_rest_stream(ctx); if (r0) return r0; }
     PYIPM_HIP(hipEventRecord(ctx->ev_sfast, after));                  // the assembly and the reset of the statistics
     PYIPM_HIP(hipStreamWaitEvent(ctx->rest, ctx->ev_sfast, 0));
-    for (int64_t q = 0; q < ctx->g.npanels; ++q) {
+    const Geo& g = ctx->g;
+    for (int64_t q = 0; q < g.npanels; ++q) {
         if (!ctx->sched.fast_panel(q)) continue;
-        int r2 = factor_panel(ctx, q, ctx->rest, true); if (r2) return r2;
-        if (run.plan.fuse_forward) PYIPM_HIP(hipEventRecord(ctx->ev_done[q], ctx->rest));
+        if (!ctx->slack_one) {                                        // (PYIPM_SLACK_ONE=0) a launch and an event per panel
+            int r2 = factor_panel(ctx, q, ctx->rest, true); if (r2) return r2;
+            if (run.plan.fuse_forward) PYIPM_HIP(hipEventRecord(ctx->ev_done[q], ctx->rest));
+            continue;
+        }
+        // One launch per contiguous run of them (k_s_panels: a workgroup per panel, each what factor_panel's k_s_panel launch
+        // does): 24 launches with a record behind each were 0.43 ms in front of a reusing step's first chain at N = 32768.
+        // Their forward substitution waits for ev_sfast (panel_done).
+        int64_t q1 = q + 1;
+        while (q1 < g.npanels && ctx->sched.fast_panel(q1)) ++q1;
+        hipLaunchKernelGGL(k_s_panels, dim3((unsigned)(q1 - q)), dim3(256), 0, ctx->rest, ctx->A, g.Npad, q, g.nb, ctx->Dinv, ctx->Tsv,
+                           ctx->Tflag, ctx->refine_cond, ctx->block_refine, ctx->dstats, g.n, g.n + g.mi + g.me, ctx->pivtol_rel,
+                           ctx->anorm);
+        PYIPM_KCHECK();
+        q = q1 - 1;
     }
     PYIPM_HIP(hipEventRecord(ctx->ev_sfast, ctx->rest));              // every closed-form panel is done
     return 0;
@@ -2299,6 +2314,7 @@ static int create_impl(pyipm_newton_ctx** out, int64_t n, int64_t me, int64_t mi
             { const char* e = getenv("PYIPM_REUSE_LAM_E"); if (e && e[0] == '0') ctx->reuse_lam_e = 0; }
             { const char* e = getenv("PYIPM_FWD_PREFIX"); if (e) { const int w = atoi(e); if (w <= 0) ctx->fwd_prefix = 0; else if (w >= 2) ctx->fwd_prefix_wgs = w; } }
             { const char* e = getenv("PYIPM_FWD_RANGE"); if (e) { const int w = atoi(e); if (w <= 0) ctx->fwd_range = 0; else if (w >= 2) ctx->fwd_range_wgs = w; } }
+            { const char* e = getenv("PYIPM_SLACK_ONE"); if (e && atoi(e) <= 0) ctx->slack_one = 0; }
         },
         [&](Ctx* ctx, char* base) { return carve_workspace(ctx, g, base, provider_only); },
         2 /* [0] max |entry|, [1] "assembly pending" */, true);
