@@ -575,7 +575,7 @@ int pyipm_newton_trailing_bytes(pyipm_newton_ctx* ctx, double out[4]);
  *   "condensed_sigma_max" (1e4): inequalities whose Sigma_k = lda_i/(s+eps) exceeds it are not folded into the x-x block but
  *                       kept as rows with -1/Sigma_k on the diagonal; "condensed_refine" (0): refinement steps against the
  *                       full blocks every condensed solve gets at least.
- *   "block_refine" 0..3 (2), "refine_cond" (1e3): refinement steps of the block solves L T = S / T z = y for diagonal tiles
+ *   "block_refine" 0..3 (2), "refine_cond" (1e2): refinement steps of the block solves L T = S / T z = y for diagonal tiles
  *                       whose pivot spread exceeds refine_cond (the tile inverses are explicit).
  *   "refine_target" (1e-14) / "refine_max" (8): adaptive refinement of solve(refine < 0): stop at this backward error or
  *                       after this many steps.

@@ -435,7 +435,10 @@ struct Ctx {
     int64_t tile8_rows = 12288;           // ... used by the single-rank schedule for the first group and where at most this many rows are left
     int bc_per_problem = 1;               // batched condensed form: the Gram part by one workgroup per problem where n = 64 .. 256 allows it
     int block_refine = 2;                 // refinement steps of L T = S in the panel scaling and of T z = y in the solves
-    double refine_cond = 1.0e3;           // ... applied to tiles whose pivot spread dmax/dmin exceeds this
+    double refine_cond = 1.0e2;           // ... applied to tiles whose pivot spread dmax/dmin exceeds this.  A heuristic: the spread is a cheap
+                                          // stand-in for cond(T), not a bound on it, and a dense tile below it can still want refining.  (1e3 until the factor was checked
+                                          // entrywise, tests/test_gpu_factor_entrywise.py: the spread underestimates cond(T) of a dense tile, and an
+                                          // unrefined block solve at a spread between 1e2 and 1e3 left Lb 37 eps |Lb| |T| from S -- 4.4 once refined)
     int profile = 0;
     int expert = 0;                       // set_option("expert", 1): the expert switches are accepted on this handle (else PYIPM_EXPERT=1)
     // timings of last calls (ms)

@@ -130,7 +130,7 @@ def test_static_pivots_in_the_slack_panels(reuse_x):
 
 @pytest.mark.parametrize("reuse_x", [True, False], ids=["reusing", "full"])
 def test_a_flagged_tile_takes_the_refinement_recurrence(reuse_x):
-    """Sigma = lambda_i / s spreads over 1e16 inside one 64-column tile, far beyond refine_cond = 1e3: the tile is flagged and L of its
+    """Sigma = lambda_i / s spreads over 1e16 inside one 64-column tile, far beyond refine_cond = 1e2: the tile is flagged and L of its
     columns goes through the refinement recurrence (block_refine = 2 steps)."""
     got, ref = _run(FIRST, True, reuse_x, "flagged_tile"), _ref(FIRST, reuse_x, "flagged_tile")
     _same(got, ref, ("flagged_tile", reuse_x))
