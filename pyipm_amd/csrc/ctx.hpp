@@ -316,6 +316,8 @@ struct Ctx {
     int sweep_max_blocks = 0;             // test hook: cap on the workgroups of the one-launch sweeps (0 = as many as the GPU holds)
     int occ_fwd_sweep = 0, occ_bwd_sweep = 0, occ_fwd_prefix = 0, occ_fwd_range = 0;   // resident workgroups per CU of the one-launch sweeps (occupancy query, cached)
     int sweep_persist = 1;                // single rank, one right-hand side: the backward sweep as ONE device-driven launch (k_bwd_sweep)
+    int bwd_slack = 1;                    // ... its chain leaves the closed-form slack panels out (bwd_chain_plan.hpp); PYIPM_BWD_SLACK=0 at create
+                                          // time keeps every panel on the chain
     DevBuf<double> sweep_buf;             // ... the near sums as the column owners hand them to workgroup 0 (Npad doubles, NaN = not there yet)
     DevBuf<double> ms_buf;                // solve_many: its column blocks, partials and refinement vectors (allocated on first use, grown on demand)
     PollWords sweep_words{3 * 4096,       // ... its flags and counters (at most 3 npanels words, zeroed before every sweep)

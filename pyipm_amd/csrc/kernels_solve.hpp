@@ -13,6 +13,7 @@
 #pragma once
 #include "ctx.hpp"
 #include "fwd_range_plan.hpp"
+#include "bwd_chain_plan.hpp"
 
 namespace pyipm {
 
@@ -280,6 +281,8 @@ __global__ __launch_bounds__(1024) void k_bwd_diag4(const double* __restrict__ A
 // nothing on 32 waves and cost bandwidth on 4080.  Ownership is static and every sum has a fixed order: deterministic.  Every poll carries a
 // timeout (a workgroup that is not resident would otherwise hang the GPU): on expiry *err is set, the sweep ends and
 // the vector is poisoned with NaN.
+// Workgroup 0 leaves the closed-form slack panels out of its walk (bwd_chain_plan.hpp): "panel t - 1" above reads pred(t), the
+// next CHAIN panel to the left, and the steps counted by the progress words are chain steps.
 struct SweepGeo {
     int64_t Npad, ld, n, mi, me;
     int nb, npanels, skip;              // skip: structural zeros of the KKT factor (active_ranges on the host)
@@ -305,7 +308,7 @@ __device__ __forceinline__ bool sweep_wait(const unsigned* p, unsigned want, uns
     }
 }
 
-__global__ __launch_bounds__(1024) void k_bwd_sweep(const double* __restrict__ A, SweepGeo sg, double* v, unsigned* sync,
+__global__ __launch_bounds__(1024) void k_bwd_sweep(const double* __restrict__ A, SweepGeo sg, BwdChain ch, double* v, unsigned* sync,
                                                     unsigned* err, unsigned long long timeout,
                                                     double* nearbuf,                    // Npad doubles, filled with NaN before the launch
                                                     unsigned long long* dbg)            // diagnostics (NULL normally): workgroup 0's phases, tools/sweep_clock.py
@@ -321,10 +324,14 @@ __global__ __launch_bounds__(1024) void k_bwd_sweep(const double* __restrict__ A
         const int k = tid & 255, q = tid >> 8;
         if (tid == 0) ok_s = 1;
         __syncthreads();
-        for (int s = P - 1; s >= 0; --s) {
+        // the chain panels only (bwd_chain_plan.hpp): a closed-form slack panel gets no tile loads, no poll, no store and no flag --
+        // v holds its x once the owners of its columns are through.  up: the chain panel resolved before s (P: none), whose
+        // step hands panel s its near sums
+        for (int s = P - 1, up = P; s >= 0; up = s, s = bwd_chain_pred(ch, s)) {
             const int64_t c0 = (int64_t)s * nb;
             int64_t w64 = sg.Npad - c0; if (w64 > nb) w64 = nb;
             const int nbw = (int)w64, nt = nbw / TB;
+            const int nxt = bwd_chain_pred(ch, s);             // the chain panel resolved next (-1: none)
             // tiles (u, t), t < u <= 3, of the panel's diagonal block: requested up front, coalesced (see k_bwd_diag4)
             double lt[6][4];
             {
@@ -341,17 +348,17 @@ __global__ __launch_bounds__(1024) void k_bwd_sweep(const double* __restrict__ A
             }
             if (dbg && tid == 0) dbg[4 * s + 0] = wall_clock64();
             if (tid < nbw) {
-                // y_s with every contribution but the one of panel s + 1, which arrives as values, not as a count: a column's
+                // y_s with every contribution but the one of chain panel `up`, which arrives as values, not as a count: a column's
                 // entry of nearbuf turns from NaN into its sum (one round trip instead of counter + load; should the sum BE
-                // NaN -- a broken factor -- the count near[s + 1] says so)
+                // NaN -- a broken factor -- the count near[up] says so)
                 const double yv = ld_agent(v + c0 + tid);
                 double nv = 0.0;
-                if (s + 1 < P) {
+                if (up < P) {
                     const unsigned long long t0 = wall_clock64();
                     for (;;) {
                         nv = ld_agent(nearbuf + c0 + tid);
                         if (nv == nv) break;
-                        if (__hip_atomic_load(nearc + s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= (unsigned)gpp) { nv = ld_agent(nearbuf + c0 + tid); break; }
+                        if (__hip_atomic_load(nearc + up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= (unsigned)gpp) { nv = ld_agent(nearbuf + c0 + tid); break; }
                         if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { ok_s = 0; break; }
                         if ((unsigned long long)wall_clock64() - t0 > timeout) { __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); ok_s = 0; break; }
                     }
@@ -390,16 +397,17 @@ __global__ __launch_bounds__(1024) void k_bwd_sweep(const double* __restrict__ A
             __syncthreads();
             if (dbg && tid == 0) dbg[4 * s + 3] = wall_clock64();
             if (tid == 0) __hip_atomic_store(flag + s, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            // for the NEXT panel (s - 1): the owners of ITS columns have finished step s + 1 -- thread j polls the progress word of
+            // for the NEXT chain panel nxt: the owners of ITS columns have finished every chain step before s (progress words count chain
+            // steps) -- thread j polls the progress word of
             // the wave that owns group j of that panel (ownership is static: group g -> wave g mod #waves).  Until round 5 this
             // waited for EVERY owner to finish the step (a progress word per workgroup): where the sweep is bandwidth-bound --
             // the first half at N = 32768: 64 ... 32 MB of far columns per step against 6.5 us of chain -- the chain then ran at
             // the pace of the slowest owner of columns it would not need for a hundred panels (3.1 us of this wait per panel
             // against 1.5 at N = 6144); now those owners fall behind and catch up while the chain is the bound.
             // (One counter per step took 4080 atomics on one address: 27 us a step.)
-            if (s + 1 < P && s >= 1 && tid < gpp) {
+            if (up < P && nxt >= 0 && tid < gpp) {
                 const int nwv_o = ((int)gridDim.x - 1 - (gpp + 15) / 16) * 16;
-                if (!sweep_wait(prog + ((s - 1) * gpp + tid) % nwv_o, (unsigned)(P - (s + 1)), err, timeout)) ok_s = 0;
+                if (!sweep_wait(prog + (nxt * gpp + tid) % nwv_o, bwd_chain_awaited(ch, s), err, timeout)) ok_s = 0;
             }
             __syncthreads();
             if (!ok_s) break;
@@ -416,8 +424,8 @@ __global__ __launch_bounds__(1024) void k_bwd_sweep(const double* __restrict__ A
     auto publish = [&](unsigned steps_done) {                   // (wave-uniform) this wave has completed that many steps
         if (lane == 0 && !specialist_) __hip_atomic_store(prog + gw_, steps_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     };
-    // The first `nearb` workgroups are NEAR specialists: wave j of theirs takes, at every step t, group j of the columns of
-    // panel t - 1 -- the sums workgroup 0 is waiting for -- and nothing else, so it is already polling flag[t] when it goes
+    // The first `nearb` workgroups are NEAR specialists: wave j of theirs takes, at every chain step t, group j of the columns of
+    // the chain panel q = pred(t) (t - 1 unless closed-form slack panels lie between) -- the sums workgroup 0 is waiting for -- and nothing else, so it is already polling flag[t] when it goes
     // up (as an ordinary owner it might still be on its far group of step t + 1: workgroup 0 waited 4.5 us per panel at
     // N = 32768 against 2.1 at N = 6144).  Their sums go to nearbuf, never into y: no conflict with the columns' owners.
     const int nearb = (gpp + 15) / 16;
@@ -429,19 +437,24 @@ __global__ __launch_bounds__(1024) void k_bwd_sweep(const double* __restrict__ A
         if (gw >= gpp) return;
     }
     typedef double d2_t __attribute__((ext_vector_type(2)));
-    for (int t = P - 1; t >= 1; --t) {
+    // chain steps only: step t of a closed-form slack panel reaches no column.  The columns of such panels are far columns of every
+    // step to their right, the one next to them included
+    for (int t = P - 1, q; (q = bwd_chain_pred(ch, t)) >= 0; t = q) {
         const int64_t r0 = (int64_t)t * nb;
         int64_t w64 = sg.Npad - r0; if (w64 > nb) w64 = nb;
         const int nbw = (int)w64;
         const int glim = t * gpp;                              // groups [0, glim) lie left of panel t
-        if (!specialist && gw >= glim - gpp) break;            // nothing left for this wave, now or later
-        // my groups left of panel t - 1, the highest first: g = gw + k nwv  (a specialist: the one group glim - gpp + gw)
-        int kmax = specialist ? 0 : (glim - gpp - 1 - gw) / nwv;
+        const int nlo = q * gpp, nhi = nlo + gpp;              // ... [nlo, nhi) are the specialists'; [nhi, glim): skipped slack panels
+        const int top = nhi == glim ? nlo : glim;              // an owner's groups lie below `top`
+        if (!specialist && gw >= top) break;                   // nothing left for this wave, now or later
+        // my groups left of panel t but for q's, the highest first: g = gw + k nwv  (a specialist: the one group nlo + gw)
+        int kmax = specialist ? 0 : (top - 1 - gw) / nwv;
         const bool in_rows = 4 * lane < nbw;
         bool have_x = false;
         double xr[4] = {0.0, 0.0, 0.0, 0.0};
         for (int kk = kmax; kk >= 0; --kk) {
-            const int g = specialist ? glim - gpp + gw : gw + kk * nwv;
+            const int g = specialist ? nlo + gw : gw + kk * nwv;
+            if (!specialist && g >= nlo && g < nhi) continue;  // (only where slack panels were skipped: top == glim)
             const int64_t j0 = (int64_t)g * 8;
             const int64_t cp = (j0 / nb) * nb;                 // panel of these columns
             const bool nearg = specialist;
@@ -502,7 +515,7 @@ __global__ __launch_bounds__(1024) void k_bwd_sweep(const double* __restrict__ A
             }
             if (nearg && lane == 0) __hip_atomic_fetch_add(nearc + t, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        if (!specialist) publish((unsigned)(P - t));
+        if (!specialist) publish(bwd_chain_published(ch, t));
     }
     if (!specialist) publish((unsigned)P);
 }

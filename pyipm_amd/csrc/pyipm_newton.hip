@@ -1250,7 +1250,10 @@ static int bwd_sweep(Ctx* ctx, double* v) {
     // inside the 4096 words zeroed above (on a part with more than 257 CUs the words beyond them would keep last sweep's
     // counts and workgroup 0 would stop waiting)
     const unsigned blocks = sweep_grid(ctx, 1 + nearb + (g.Npad / 8 + 15) / 16, 1, 2 + nearb, 1 + nearb + 4096 / 16);
-    hipLaunchKernelGGL(k_bwd_sweep, dim3(blocks), dim3(1024), 0, ctx->stream, ctx->A, sweep_geo(ctx), v, sw.buf.get(), sw.err(),
+    // workgroup 0 leaves the closed-form slack panels out of its walk (bwd_chain_plan.hpp)
+    const SweepGeo sg = sweep_geo(ctx);
+    const BwdChain ch = bwd_chain(BwdChainGeo{sg.Npad, sg.n, sg.mi, sg.nb, sg.npanels, sg.skip}, ctx->bwd_slack);
+    hipLaunchKernelGGL(k_bwd_sweep, dim3(blocks), dim3(1024), 0, ctx->stream, ctx->A, sg, ch, v, sw.buf.get(), sw.err(),
                        POLL_TIMEOUT, ctx->sweep_buf.get(), ctx->dbg_buf);
     PYIPM_KCHECK();
     sw.used = true;
@@ -2315,6 +2318,7 @@ static int create_impl(pyipm_newton_ctx** out, int64_t n, int64_t me, int64_t mi
             { const char* e = getenv("PYIPM_FWD_PREFIX"); if (e) { const int w = atoi(e); if (w <= 0) ctx->fwd_prefix = 0; else if (w >= 2) ctx->fwd_prefix_wgs = w; } }
             { const char* e = getenv("PYIPM_FWD_RANGE"); if (e) { const int w = atoi(e); if (w <= 0) ctx->fwd_range = 0; else if (w >= 2) ctx->fwd_range_wgs = w; } }
             { const char* e = getenv("PYIPM_SLACK_ONE"); if (e && atoi(e) <= 0) ctx->slack_one = 0; }
+            { const char* e = getenv("PYIPM_BWD_SLACK"); if (e && e[0] == '0') ctx->bwd_slack = 0; }
         },
         [&](Ctx* ctx, char* base) { return carve_workspace(ctx, g, base, provider_only); },
         2 /* [0] max |entry|, [1] "assembly pending" */, true);

@@ -20,6 +20,8 @@ core.set_option("debug_timeline_ptr", 0.0)
 d = buf.cpu().numpy()[:4 * P].reshape(P, 4).astype(np.float64) * 0.01      # us
 order = np.arange(P - 1, -1, -1)
 d = d[order]
+d = d[d[:, 0] != 0.0]       # the chain leaves the closed-form slack panels out (bwd_chain_plan.hpp): their slots stay zero
+print("chain panels %d of %d" % (d.shape[0], P))
 wait = d[:, 1] - d[:, 0]; inpanel = d[:, 2] - d[:, 1]; pub = d[:, 3] - d[:, 2]
 gap = d[1:, 0] - d[:-1, 3]
 print("panels %d, sweep %.1f us from first to last stamp" % (P, d[-1, 3] - d[0, 0]))
