@@ -528,6 +528,34 @@ int pyipm_newton_kkt_matvec_batched(pyipm_newton_ctx* ctx, int64_t k, const doub
                                     double* y, int64_t ld_y, int64_t stride_y, int memkind);
 int pyipm_newton_rcond_batched(pyipm_newton_ctx* ctx, int it_inv, int it_pow, const int32_t* active, double* out, int memkind);
 
+/* Adaptive refinement of a batch of directions, EVERY PROBLEM BY ITSELF: pyipm_newton_solve's refine < 0 for the batched handle
+ * (which solve_batched refuses: there a fixed count makes every problem pay for the worst one and cannot say who converged).
+ * dz_b -- N doubles at dz + b stride, device memory, ld >= N and stride >= N -- is a solution of problem b's kept system: the
+ * right-hand side is the residual g the last step kept, the matrix the staged blocks with that problem's own delta, delta_c
+ * and Sigma (kkt_matvec_batched's arithmetic: never the factor, always the full 4-block matrix).  flip != 0: rows n + mi ..
+ * are negated, as the step wrote them.  It is refined in place by the rule of solve(refine < 0), per visit of a problem:
+ * berr = |g - Hc x|_2 / |g|_2 is measured from the blocks before every step; the problem stops converged at berr <= target,
+ * after max_steps steps, or when a step gained less than 4x (berr > 0.25 prev); a step that made it worse, or not finite, is
+ * TAKEN BACK (the saved iterate restored, the step not counted); NaN / Inf at the first measurement: nothing is done.  The
+ * decision is refine_each_verdict of pyipm_amd/csrc/refine_each_plan.hpp, the one statement the kernel and the CPU replay
+ * compile.  A step is x += inv(factor_b) r through solve_batched's kernel: a problem whose last step was condensed is
+ * corrected through its condensed factor, its residual formed against the full blocks all the same.
+ * target <= 0 / max_steps < 0: the handle's "refine_target" / "refine_max" (1e-14 / 8).
+ * info[b][4] = {steps taken, berr before the first step, berr of the kept iterate, converged 0|1} -- the layout of
+ * pyipm_newton_solve_info -- in host (the call synchronises) or device memory per memkind, and active with it.  active: batch
+ * flags or NULL = every problem; for a problem with active[b] == 0 (or one no step has factored yet) neither its row of dz
+ * nor its row of info is written.
+ * Nothing returns to the host between the steps: max_steps + 1 rounds of plain launches are enqueued, a problem's state
+ * (going / stopped, the last error, its step count) lives in the library's own scratch outside the workspace (grown on
+ * demand; pyipm_newton_workspace_bytes_batched is unchanged), and the workgroups of a stopped problem return at once.  No
+ * atomics or waits between workgroups, every sum in an order the sizes alone decide: the bits of problem b, in dz and in
+ * info, depend neither on the batch size, nor on b's place, nor on which other problems take part or how many steps they
+ * take.  The factors, the statistics, the kept residual and solution, a kept host-output direction and the handle's
+ * record of its last step are left alone, as by solve_batched.
+ * PYIPM_E_BADARG: not a batched handle, no step since the blocks or vectors were staged, a NULL dz or info, ld or stride < N. */
+int pyipm_newton_refine_batched(pyipm_newton_ctx* ctx, double* dz, int64_t ld, int64_t stride, const int32_t* active, int flip,
+                                double target, int max_steps, double* info, int memkind);
+
 /* ---- introspection for tests / bench ------------------------------------------------------ */
 
 /* Device pointer + leading dimension of the local KKT storage (column-major lower).  The caller may write through the
@@ -645,8 +673,8 @@ int pyipm_newton_set_option(pyipm_newton_ctx* ctx, const char* name, double valu
  * device direction goes).  A binding checks pyipm_newton_abi_version() == PYIPM_NEWTON_ABI_VERSION of the header it was
  * written against before any other call (pyipm_amd/newton.py does).  7: step_batched_each, step_lengths_batched; the
  * workspace of a batched handle grew by the per-problem parameters.  8: block_products_batched, block_products_t_batched,
- * merit_info_batched, merit_ray_batched.  (Still 8: solve_batched, kkt_matvec_batched, rcond_batched -- entries added, no
- * argument list, layout or workspace size changed.) */
+ * merit_info_batched, merit_ray_batched.  (Still 8: solve_batched, kkt_matvec_batched, rcond_batched, then refine_batched -- entries
+ * added, no argument list, layout or workspace size changed.) */
 #define PYIPM_NEWTON_ABI_VERSION 8
 int pyipm_newton_abi_version(void);
 

@@ -352,18 +352,53 @@ class BatchedNewton(object):
         self._ck(self.lib.pyipm_newton_rcond_batched(self.h, int(it_inv), int(it_pow), ptr(pa), ptr(out), MEM_DEVICE))
         return out
 
+    REFINE_KEYS = ("steps", "backward_error0", "backward_error", "converged")     # columns of refine_all (NewtonCore.solve_info's four)
+
+    def refine_all(self, dz, active=None, flip=True, target=None, max_steps=None):
+        """Adaptive refinement of the directions ``dz`` IN PLACE, every problem by itself (``pyipm_newton_refine_batched``):
+        ``dz`` (B, ld >= N) float64 on the handle's device, rows of unit stride -- e.g. what the last step returned -- each a
+        solution of its problem's kept system (the residual of the last step, the blocks with that problem's own shifts and
+        Sigma); ``flip``: rows n + mi .. are negated, as the steps write them.  Per problem: the backward error against the
+        blocks is measured before every step, and the problem stops converged at ``target``, after ``max_steps`` steps or
+        when a step gained less than 4x; a step that made it worse is taken back (None: the handle's ``refine_target`` /
+        ``refine_max``, 1e-14 / 8).  Returns a device tensor (B, 4), columns as REFINE_KEYS; ``active`` ((B,) flags; None =
+        all): the rows of the other problems are NaN there and untouched in ``dz``.  Nothing returns to the host on the way."""
+        self._staged_handle("refine_all")
+        t = self.torch
+        if not isinstance(dz, t.Tensor) or dz.dim() != 2 or dz.shape[0] != self.batch or dz.dtype != t.float64 \
+                or dz.device != self.device or (dz.shape[1] > 1 and dz.stride(1) != 1):
+            raise NewtonError("refine_all: dz must be a float64 (B, ld) tensor on the handle's device with rows of unit stride")
+        pa = None if active is None else self._per_problem(active, t.int32)
+        info = t.full((self.batch, 4), float("nan"), dtype=t.float64, device=self.device)
+        self._ck(self.lib.pyipm_newton_refine_batched(self.h, ptr(dz), int(dz.shape[1]), int(dz.stride(0)), ptr(pa), int(bool(flip)),
+                                                      0.0 if target is None else float(target),
+                                                      -1 if max_steps is None else int(max_steps), ptr(info), MEM_DEVICE))
+        return info
+
     n_factor = 0                           # passes over the batch (direction_all)
     n_inertia_retries = 0                  # problem x shifted pass whose inertia was still wrong (delta *= 10, pyipm.py:1399-1403)
+    # direction_all(refine=True): HipNewtonBackend's bars and counters, per problem
+    suspect_spread = 1e-10                 # pivot spread d_min / d_max at or below which the condition estimate is consulted
+    berr_tol = 1e-11                       # backward error a refined direction must meet to count as converged
+    berr_fallback = float(np.sqrt(np.finfo(float).eps))     # the bar of the last resort (an inexact direction, n_inexact)
+    n_rcond = 0                            # problems a condition estimate was taken for
+    n_refined = 0                          # problems whose direction went through refine_all
+    n_static = 0                           # directions recovered from a statically pivoted factor
+    n_unconverged = 0                      # refined directions that missed berr_tol and were sent to the shift loop
+    n_inexact = 0                          # directions returned on berr_fallback
     _shift_info = None
 
     def shift_info(self):
         """What the last ``direction_all`` decided, per problem: ``failed`` (entered the shift loop), ``suspect`` (the
         pivot-level ``rcond <= eps`` trigger fired on pass 1), ``delta_c`` (what its retry passes were given), ``delta`` (the
-        shift its last pass ran with; 0 where none), ``passes`` (retry passes it took part in)."""
+        shift its last pass ran with; 0 where none), ``passes`` (retry passes it took part in).  After
+        ``direction_all(refine=True)`` also ``singular`` (the condition estimate, or a refinement that stalled, said so),
+        ``refined`` (its direction went through ``refine_all``) and ``backward_error`` (of the direction returned, against
+        the blocks; NaN where none was measured)."""
         return self._shift_info
 
     def direction_all(self, d2L, Je, Ji, df, ce, ci, s, lda, mu, delta=0.0, eta=1e-4, beta=0.4, reg_coef=None, delta0=None,
-                      max_shift_tries=60, active=None):
+                      max_shift_tries=60, active=None, refine=False):
         """``reghess`` + solve (pyipm.py:1373-1406, 1717-1725) per problem of the batch, in the order ``HipNewtonBackend.direction``
         uses; ``mu`` and ``delta`` (the delta each problem persists from its last call) are scalars or (B,).
         Pass 1: no shifts, every problem.  A problem fails when its inertia is wrong (n_neg != me + mi), a NaN / Inf was met, or
@@ -374,7 +409,12 @@ class BatchedNewton(object):
         the guard fails too, and the retry passes run in the full form.
         ``active`` ((B,) flags; None = all): only these problems take part -- the others sit every pass out (their rows of dz
         are NaN, their statistics those of their last step, their delta unchanged).
+        ``refine=True``: the decisions of ``HipNewtonBackend.direction`` per problem instead (``_direction_all_refined``): a
+        condition estimate for the suspect problems, adaptive refinement for those at risk, shifts only for the singular.
         Returns (dz, delta (B,) float64, list of statistics): delta as the reference persists it, unchanged without a shift."""
+        if refine:
+            return self._direction_all_refined(d2L, Je, Ji, df, ce, ci, s, lda, mu, delta, eta, beta, reg_coef, delta0,
+                                               max_shift_tries, active)
         torch = self.torch
         me, mi, need = self.me, self.mi, self.me + self.mi
         eps = float(np.finfo(np.float64).eps)
@@ -431,6 +471,170 @@ class BatchedNewton(object):
                 self._ck(self.lib.pyipm_newton_set_option(self.h, b"condensed", 1.0))
         self._shift_info = {"failed": failed.copy(), "suspect": sus, "delta_c": dc_v, "delta": np.where(failed, delta_v, 0.0),
                             "passes": passes}
+        return out, delta_v, stats
+
+    def _direction_all_refined(self, d2L, Je, Ji, df, ce, ci, s, lda, mu, delta, eta, beta, reg_coef, delta0, max_shift_tries,
+                               active):
+        """``HipNewtonBackend.direction`` (ipm.py) for every problem of the batch, each launch serving all problems that need it.
+        Pass 1: no shifts, every problem.  Wrong inertia / NaN: the shift loop.  Suspect (static pivots, or a pivot spread at
+        or below ``suspect_spread``): ONE ``rcond_all`` over them; singular iff ``rcond <= eps``, or static pivots and
+        ``w_min <= 100 static_pivot`` -- those enter the shift loop with ``delta_c`` (me > 0).  Not singular but at risk
+        (static pivots, 2x2 pivots, growth > 64): ONE ``refine_all`` over them; a problem whose final backward error is above
+        ``berr_tol`` enters the loop as a singular one.  Everybody else keeps the bits of pass 1 and costs no launch.
+        In the loop a problem whose inertia has come right is refined again if it is at risk, and gets ``delta *= 10`` while it
+        misses ``berr_tol`` -- under the rules of ipm.py, per problem: only solves count as stalled, the least shifted
+        direction at ``berr_fallback`` is returned when two solves in a row gained less than 10x or the budget is spent
+        (``n_inexact``), otherwise a ``RuntimeError`` names the problems.
+        With ``condensed`` pass 1 is condensed; problems that fail it, are suspect, at risk or miss the guard are first
+        re-stepped in the full form WITHOUT shifts and judged there (the condition estimate is the full form's)."""
+        torch = self.torch
+        me, mi, need = self.me, self.mi, self.me + self.mi
+        eps = float(np.finfo(np.float64).eps)
+        reg_coef = float(np.sqrt(eps)) if reg_coef is None else float(reg_coef)      # pyipm.py:353
+        delta0 = reg_coef if delta0 is None else float(delta0)                       # pyipm.py:372
+        B = self.stage(d2L, Je, Ji, df, ce, ci, s, lda, mu=float(np.asarray(mu, dtype=np.float64).reshape(-1)[0]), eps=eps)
+        mu_v = np.broadcast_to(np.asarray(mu, dtype=np.float64), (B,)).copy()
+        delta_v = np.broadcast_to(np.asarray(delta, dtype=np.float64), (B,)).copy()
+        dc_v, zero = np.zeros(B), np.zeros(B)
+        part = np.ones(B, dtype=bool) if active is None else np.asarray(active).astype(bool).reshape(B)
+        out, st = self.step_each(mu_v, zero, zero, None if active is None else part.astype(np.int32))
+        self.n_factor += 1
+        stats = list(st)
+
+        def wrong(x):
+            return x["n_neg"] != need or bool(x["nonfinite"])
+
+        def suspect(x):
+            return x["n_zero"] > 0 or (x["d_max"] > 0 and x["d_min"] / x["d_max"] <= self.suspect_spread)
+
+        def at_risk(x):
+            return x["n_zero"] > 0 or x["n_2x2"] > 0 or x["growth"] > 64.0
+
+        def mask(idx):
+            a = np.zeros(B, dtype=np.int32)
+            a[idx] = 1
+            return a
+
+        passes = np.zeros(B, dtype=np.int64)
+        berr = np.full(B, np.nan)
+        refined, singular = np.zeros(B, dtype=bool), np.zeros(B, dtype=bool)
+        best = {}                              # b -> (backward error, dz row, delta, statistics) of its best unconverged direction
+        cond = bool(self._opts_get("condensed")) and mi > 0
+        full = False                           # the handle has been switched to the full form for the rest of this call
+        try:
+            if cond:
+                redo = np.array([wrong(x) or suspect(x) or at_risk(x) for x in stats])
+                if self.guard:
+                    be = self.last_backward_errors = self.backward_errors(out)
+                    redo |= ((be > self.condensed_tol) | ~torch.isfinite(be)).cpu().numpy()
+                redo &= part
+                if redo.any():
+                    self.n_condensed_fallback += 1
+                    self._ck(self.lib.pyipm_newton_set_option(self.h, b"condensed", 0.0))
+                    full = True
+                    _, st = self.step_each(mu_v, zero, zero, mask(np.flatnonzero(redo)), out=out)
+                    self.n_factor += 1
+                    stats = list(st)
+                judged = redo
+            else:
+                judged = part
+            bad = np.array([wrong(x) for x in stats]) & judged
+            sus = np.array([suspect(x) for x in stats]) & judged
+            singular |= np.array([bool(x["nonfinite"]) for x in stats]) & judged
+            ask = np.flatnonzero(sus & ~singular)      # (whatever the inertia says: the estimate decides on delta_c)
+            if ask.size:
+                rc = self.rcond_all(active=mask(ask)).cpu().numpy()
+                self.n_rcond += int(ask.size)
+                for b in ask:
+                    w_min, _, rcond, static = rc[b]
+                    singular[b] = not (rcond > eps) or (stats[b]["n_zero"] > 0 and not (w_min > 100.0 * static))
+
+            def refine_group(idx, shifted):
+                """ONE refine_all over ``idx``; returns those that missed berr_tol (remembered as candidates of the last resort)."""
+                info = self.refine_all(out, active=mask(idx)).cpu().numpy()
+                self.n_refined += int(idx.size)
+                missed = []
+                for b in idx:
+                    refined[b], berr[b] = True, info[b, 2]
+                    if info[b, 2] >= 0.0 and info[b, 2] <= self.berr_tol:
+                        if stats[b]["n_zero"] > 0:
+                            self.n_static += 1     # reference: LU over the whole matrix, no shift (pyipm.py:1381 not taken)
+                        continue
+                    self.n_unconverged += 1
+                    missed.append(b)
+                    be_b = float(info[b, 2])
+                    # the LEAST shifted direction that meets berr_fallback is kept; below that bar, the most accurate one
+                    if be_b >= 0.0 and np.isfinite(be_b) and (b not in best or (best[b][0] > self.berr_fallback and be_b < best[b][0])):
+                        best[b] = (be_b, out[b].clone(), float(delta_v[b]) if shifted else 0.0, stats[b])
+                return np.array(missed, dtype=np.int64)
+
+            risk = np.flatnonzero(np.array([at_risk(x) for x in stats]) & judged & ~bad & ~singular)
+            if risk.size:
+                singular[refine_group(risk, False)] = True
+            failed = bad | singular
+            pending = np.flatnonzero(failed)
+            for b in pending:
+                dc_v[b] = reg_coef * eta * mu_v[b] ** beta if (singular[b] and me) else 0.0
+                delta_v[b] = delta0 if delta_v[b] == 0.0 else max(delta_v[b] / 2.0, delta0)
+            if pending.size and cond and not full:
+                self.n_condensed_fallback += 1
+                self._ck(self.lib.pyipm_newton_set_option(self.h, b"condensed", 0.0))
+                full = True
+            tries = np.zeros(B, dtype=np.int64)
+            stalled, prev_be = np.zeros(B, dtype=np.int64), np.full(B, np.nan)
+
+            def settle(b):
+                """The best direction seen for b, if it is berr_fallback-accurate: returned in place of the last solve."""
+                if b in best and best[b][0] <= self.berr_fallback:
+                    self.n_inexact += 1
+                    berr[b], delta_v[b], stats[b] = best[b][0], best[b][2], best[b][3]
+                    out[b].copy_(best[b][1])
+                    return True
+                return False
+
+            while pending.size:
+                act = mask(pending)
+                _, st = self.step_each(mu_v, np.where(act, delta_v, 0.0), np.where(act, dc_v, 0.0), act, out=out)
+                self.n_factor += 1
+                passes[pending] += 1
+                new = list(st)
+                for b in pending:
+                    stats[b] = new[b]
+                again, lost = [], []
+                inert = np.array([b for b in pending if wrong(stats[b])], dtype=np.int64)
+                for b in inert:                    # an inertia retry, not an unconverged solve: no part in the stall count
+                    tries[b] += 1
+                    self.n_inertia_retries += 1
+                    (lost if tries[b] > max_shift_tries else again).append(b)
+                if lost:
+                    raise RuntimeError("inertia not corrected after %d diagonal shifts: problems %s" % (max_shift_tries + 1, lost))
+                ok = np.array([b for b in pending if not wrong(stats[b])], dtype=np.int64)
+                berr[ok] = np.nan
+                rk = np.array([b for b in ok if at_risk(stats[b])], dtype=np.int64)
+                for b in (refine_group(rk, True) if rk.size else ()):
+                    be_b = berr[b]
+                    stalled[b] = stalled[b] + 1 if (np.isfinite(prev_be[b]) and be_b >= 0.0 and be_b >= 0.1 * prev_be[b]) else 0
+                    if be_b >= 0.0:
+                        prev_be[b] = be_b
+                    if stalled[b] >= 2 and settle(b):
+                        continue
+                    tries[b] += 1
+                    if tries[b] > max_shift_tries:
+                        if settle(b):
+                            continue
+                        lost.append(b)
+                        continue
+                    again.append(b)
+                if lost:
+                    raise RuntimeError("refined solve did not reach backward error %.1e after %d diagonal shifts: problems %s"
+                                       % (self.berr_tol, max_shift_tries + 1, lost))
+                pending = np.array(sorted(again), dtype=np.int64)
+                delta_v[pending] *= 10.0
+        finally:
+            if full:
+                self._ck(self.lib.pyipm_newton_set_option(self.h, b"condensed", 1.0))
+        self._shift_info = {"failed": failed.copy(), "suspect": sus, "delta_c": dc_v, "delta": np.where(failed, delta_v, 0.0),
+                            "passes": passes, "singular": singular, "refined": refined, "backward_error": berr}
         return out, delta_v, stats
 
     def _fetch_stats(self, step_id):

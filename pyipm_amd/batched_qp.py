@@ -33,11 +33,12 @@ class BatchedQPIPM(object):
     RAY_BATCH = 64                       # backtracking candidates alpha tau^k of every problem per launch of k_b_merit_ray
 
     def __init__(self, Q, c, A=None, b=None, G=None, h=None, x0=None, s0=None, lda0=None, mu=0.2, nu=10.0, rho=0.1, tau=0.995,
-                 eta=1.0E-4, beta=0.4, miter=20, niter=10, Ktol=1.0E-4, device=None, condensed=False, profile=False):
+                 eta=1.0E-4, beta=0.4, miter=20, niter=10, Ktol=1.0E-4, device=None, condensed=False, profile=False, refine=False):
         """Q (B, n, n), c (B, n), A (B, me, n), b (B, me), G (B, mi, n), h (B, mi): NumPy arrays or torch tensors; a block
         without the batch dimension is shared by every problem.  Starts x0 (B, n; default 0), s0 (B, mi; default
         max(G x0 - h, Ktol)), lda0 (B, me + mi; default lda_e = 0, lda_i = mu / s0).  ``profile``: synchronise around the
-        phases and keep their times in ``timings``."""
+        phases and keep their times in ``timings``.  ``refine``: ``direction_all(refine=True)`` -- a condition estimate
+        and adaptive refinement per problem instead of a shift for every suspect one (an LP is then not shifted at all)."""
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("BatchedQPIPM needs a GPU: the Newton-step core has no CPU fallback")
@@ -72,7 +73,7 @@ class BatchedQPIPM(object):
         self.eps = float(np.finfo(np.float64).eps)
         self.mu, self.nu, self.rho, self.tau, self.eta, self.beta = mu, nu, rho, tau, eta, beta
         self.miter, self.niter, self.Ktol = int(miter), int(niter), Ktol
-        self.profile = bool(profile)
+        self.profile, self.refine = bool(profile), bool(refine)
         self.core = BatchedNewton(n, me, mi, device=dev.index, condensed=condensed)
         # the constant blocks, and vectors of the right shapes so that the handle exists before the first product
         self.core.stage(self.Q, self.Je, self.Ji, self.c, z(me) if me else None, z(mi) + 1.0 if mi else None,
@@ -162,7 +163,8 @@ class BatchedQPIPM(object):
             t0 = self._tick()
             f, df, ce, ci = self._provider(x)
             dz, delta_new, _ = core.direction_all(self.Q, self.Je, self.Ji, df, ce, ci, s if mi else None,
-                                                  lda if (me or mi) else None, mu, delta, self.eta, self.beta, active=act)
+                                                  lda if (me or mi) else None, mu, delta, self.eta, self.beta, active=act,
+                                                  refine=self.refine)
             delta[act] = delta_new[act]
             info = core.merit_info_all(dz)
             al = core.step_lengths_all(self.tau, dz)

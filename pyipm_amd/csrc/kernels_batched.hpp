@@ -1161,3 +1161,4 @@ __global__ __launch_bounds__(256) void k_b_merit_ray(double* __restrict__ out, c
 }  // namespace pyipm
 
 #include "kernels_bsolve.hpp"
+#include "kernels_brefine.hpp"

@@ -2871,6 +2871,58 @@ int pyipm_newton_rcond_batched(pyipm_newton_ctx* h, int it_inv, int it_pow, cons
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
+// Adaptive refinement of a batch of directions, every problem by the rule of drv::refine_loop(refine < 0) applied to it alone
+// (refine_each_plan.hpp; kernels_brefine.hpp).  max_steps + 1 rounds are enqueued whatever the problems do: a problem that has
+// stopped costs workgroups that return at once.
+int pyipm_newton_refine_batched(pyipm_newton_ctx* h, double* dz, int64_t ld, int64_t stride, const int32_t* active, int flip,
+                                double target, int max_steps, double* info, int memkind) try {
+    PYIPM_ENTER("refine_batched", G_BATCHED | G_DEVICE) const Geo& g = ctx->g;
+    if (memkind != PYIPM_MEM_DEVICE && memkind != PYIPM_MEM_HOST) { ctx->err = "refine_batched: bad memkind"; return PYIPM_E_BADARG; }
+    if (!ctx->held.have_blocks || !ctx->held.have_vectors || !ctx->held.batch_stepped) {
+        ctx->err = "refine_batched: no step since the blocks / vectors were staged (the factors, the shifts and the residual are a step's)"; return PYIPM_E_BADARG; }
+    if (!dz || !info) { ctx->err = "refine_batched: null direction or info"; return PYIPM_E_BADARG; }
+    if (ld < g.N || (ctx->batch > 1 && stride < g.N)) { ctx->err = "refine_batched: leading dimension / batch stride below N"; return PYIPM_E_BADARG; }
+    if (!(target > 0.0)) target = ctx->refine_target;
+    if (max_steps < 0) max_steps = ctx->refine_max;
+    const int B = ctx->batch;
+    const size_t BN = (size_t)B * (size_t)g.N;
+    int* mstage; double* buf;
+    { int rc = batch_solve_scratch(ctx, 2 * BN + 7 * (size_t)B, &mstage, &buf); if (rc) return rc; }
+    const int* act;
+    { int rc = batch_mask(ctx, active, memkind, mstage, &act); if (rc) return rc; }
+    double* res = buf + 2 * BN;                              // [B][4]: info of a call with host output
+    double* prev = res + 4 * (size_t)B;                      // [B]
+    int* words = reinterpret_cast<int*>(prev + B);           // go [B], it [B]
+    const bool host = memkind == PYIPM_MEM_HOST;
+    const BRefine rf = {dz, stride, buf, buf + BN, words, words + B, prev, host ? res : info, max_steps, target};
+    const BatchPtrs bp = batch_ptrs(ctx);
+    const dim3 gadd((unsigned)B, (unsigned)((g.N + 255) / 256));
+    if (host) PYIPM_HIP(hipMemsetAsync(res, 0xFF, 4 * (size_t)B * sizeof(double), ctx->stream));     // (a problem without a factor: NaN)
+    hipLaunchKernelGGL(k_b_ref_begin, grid1(B), dim3(256), 0, ctx->stream, rf, act, ctx->b_form.get(), B);
+    PYIPM_KCHECK();
+    for (int round = 0; round <= max_steps; ++round) {
+        if (flip) hipLaunchKernelGGL((k_b_ref_round<true>), dim3((unsigned)B), dim3(256), 0, ctx->stream, bp, g, ctx->eps, rf);
+        else      hipLaunchKernelGGL((k_b_ref_round<false>), dim3((unsigned)B), dim3(256), 0, ctx->stream, bp, g, ctx->eps, rf);
+        PYIPM_KCHECK();
+        if (round == max_steps) break;                       // (a problem with max_steps steps behind it never goes on)
+        const BSolveIO cor = {rf.r, g.N, g.N, rf.r, g.N, g.N, 1, rf.go, ctx->b_form.get(), 0};
+        { int rc = batch_solve_launch(ctx, cor); if (rc) return rc; }
+        hipLaunchKernelGGL(k_b_ref_add, gadd, dim3(256), 0, ctx->stream, rf, g.N, flip ? 1 : 0, g.n + g.mi);
+        PYIPM_KCHECK();
+    }
+    if (host) {
+        for (int b0 = 0; b0 < B;) {                           // only the rows of the problems that took part, run by run
+            if (active && !active[b0]) { ++b0; continue; }
+            int b1 = b0 + 1;
+            while (b1 < B && (!active || active[b1])) ++b1;
+            PYIPM_HIP(hipMemcpyAsync(info + 4 * (size_t)b0, res + 4 * (size_t)b0, (size_t)(b1 - b0) * 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            b0 = b1;
+        }
+        PYIPM_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return PYIPM_OK;
+} PYIPM_CATCH_H(h)
+
 // Teardown is an order, not a list: stuck collectives aborted, every stream of the handle drained, the communicators gone --
 // after that nothing on the device refers to what the handle owns, and ~Ctx may release its members in any order.
 int pyipm_newton_destroy(pyipm_newton_ctx* h) try {

@@ -129,6 +129,8 @@ def load_library(path: str | None = None):
                                                c_int, c_int, c_int]),
         "pyipm_newton_kkt_matvec_batched": (c_int, [ctxp, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int]),
         "pyipm_newton_rcond_batched": (c_int, [ctxp, c_int, c_int, c_void_p, c_void_p, c_int]),
+        "pyipm_newton_refine_batched": (c_int, [ctxp, c_void_p, c_int64, c_int64, c_void_p, c_int, c_double, c_int, c_void_p,
+                                                c_int]),
         "pyipm_mfma_f64_peak": (c_int, [c_int, c_int, POINTER(c_double)]),
         "pyipm_newton_block_products": (c_int, [ctxp, c_void_p, c_void_p, c_void_p, c_void_p]),
         "pyipm_newton_block_products_t": (c_int, [ctxp, c_void_p, c_void_p, c_void_p]),
