@@ -195,6 +195,28 @@ int pyipm_newton_anorm(pyipm_newton_ctx* ctx, double** dev_ptr);
 /* y = Hc * v with Hc applied from the staged blocks (never from the factor): used by the
  * refinement step and by the parity tests (backward error). */
 int pyipm_newton_kkt_matvec(pyipm_newton_ctx* ctx, const double* v, double* y, int memkind);
+/* Y = Hc * V for k columns in one pass over the staged blocks: column j computes y_j = Hc v_j, v_j at v + j*ld_v, y_j at
+ * y + j*ld_y (ld_v, ld_y >= N; entries N .. ld_y-1 of each output column are not written).  Hc is exactly what
+ * pyipm_newton_kkt_matvec applies: the full four-block matrix of pyipm.py:824-842 from the staged blocks and the staged s,
+ * lda, eps with the handle's current delta / delta_c, raw sign (no flip), never the factor -- the full matrix on a
+ * condensed handle too.  Replaces k calls of pyipm_newton_kkt_matvec (residuals and backward errors of k solutions, the
+ * check of a solve_many): triu(d2L), Je and Ji are each read twice per 64 columns instead of once per column, and the
+ * products run on the fp64 matrix pipe.
+ *   Valid: a single-rank single-system handle (a provider-only one included) with blocks and vectors staged.
+ *   PYIPM_E_BADARG, each with a last_error text: a batched handle, world > 1, blocks or vectors not staged, NULL v or y,
+ *   ld_v or ld_y < N, k < 0, y overlapping v, a bad memkind.  k == 0 returns 0 and does nothing.
+ *   Column j is bit for bit independent of k, of its place among the columns and of what the other columns hold (a NaN
+ *   column stays in its column; no atomics, a summation order the geometry alone decides); two identical calls give
+ *   identical bits.  It equals pyipm_newton_kkt_matvec of that column to rounding, not to the bit.
+ *   The call writes no work vector and changes nothing the handle holds: the factor, the kept residual, the direction of the
+ *   last solve()/step() and a pending fused forward pass are left alone; solve() after it returns the bits it would without it.
+ *   Device pointers: asynchronous on the handle's stream, v and y used where they are.  PYIPM_MEM_HOST: staged through a
+ *   buffer the library allocates on first use and grows on demand (not part of pyipm_newton_workspace_bytes); the call
+ *   synchronises.
+ *   PYIPM_MS_MATVEC_MANY=1 in the environment at create time sends the residual product of pyipm_newton_solve_many's
+ *   refinement through this routine (one launch instead of k products); unset, solve_many is unchanged bit for bit. */
+int pyipm_newton_kkt_matvec_many(pyipm_newton_ctx* ctx, int64_t k, const double* v, int64_t ld_v,
+                                 double* y, int64_t ld_y, int memkind);
 
 /* Fused convenience: residual + assemble + factor + solve + flip = pyipm.py:1717-1725
  * without regularisation retries (the host loop re-issues assemble/factor with new shifts). */

@@ -320,6 +320,9 @@ struct Ctx {
                                           // time keeps every panel on the chain
     DevBuf<double> sweep_buf;             // ... the near sums as the column owners hand them to workgroup 0 (Npad doubles, NaN = not there yet)
     DevBuf<double> ms_buf;                // solve_many: its column blocks, partials and refinement vectors (allocated on first use, grown on demand)
+    DevBuf<double> km_buf;                // kkt_matvec_many: host operands and results pass through it (allocated on first use, grown on demand)
+    int ms_matvec_many = 0;               // solve_many's refinement forms Hc X through kkt_matvec_many (one launch for all columns);
+                                          // PYIPM_MS_MATVEC_MANY=1 at create time
     PollWords sweep_words{3 * 4096,       // ... its flags and counters (at most 3 npanels words, zeroed before every sweep)
                           "backward sweep (k_bwd_sweep): a poll timed out in an earlier solve; its result was NaN"};
     int dist_slices = 2;                  // distributed schedule: the two-message protocol (slices ahead of the panel message: the next owner's tile

@@ -9,6 +9,7 @@
 #include "kernels_chain.hpp"
 #include "kernels_solve.hpp"
 #include "kernels_msolve.hpp"
+#include "kernels_kmany.hpp"
 #include "kernels_batched.hpp"
 #include "kernels_merit.hpp"
 
@@ -1456,6 +1457,49 @@ int solve_many_inplace(Ctx* ctx, double* X, int64_t k, int64_t kpad, double* par
     return 0;
 }
 
+// Y = Hc V for k columns (column j at V + j * ldv, Y + j * ldy) from the staged blocks, the handle's current shifts, in ONE launch
+// (kernels_kmany.hpp); single rank.  Rows 0 .. N-1 of every column are written, with pad also rows N .. Npad-1 (y = v there, as
+// kkt_matvec_dev leaves them; ldv, ldy >= Npad then).  Writes nothing but Y: no work vector, nothing of Held.
+int kkt_matvec_many_dev(Ctx* ctx, int64_t k, const double* V, int64_t ldv, double* Y, int64_t ldy, bool pad) {
+    const Geo& g = ctx->g;
+    if (!ctx->held.have_blocks || !ctx->held.have_vectors) { ctx->err = "kkt_matvec_many: stage blocks and vectors first"; return PYIPM_E_BADARG; }
+    if (k <= 0) return 0;
+    KmArgs a;
+    a.U = ctx->d2L; a.ldu = ctx->ld_d2L; a.Je = ctx->Je; a.lde = ctx->ld_Je; a.Ji = ctx->Ji; a.ldi = ctx->ld_Ji;
+    a.s = ctx->s; a.lda = ctx->lda; a.eps = ctx->eps; a.delta = ctx->delta; a.delta_c = ctx->delta_c;
+    a.n = g.n; a.me = g.me; a.mi = g.mi; a.N = g.N; a.rows_out = pad ? g.Npad : g.N;
+    a.V = V; a.ldv = ldv; a.Y = Y; a.ldy = ldy; a.k = k;
+    a.tx = (int)((g.n + KM_TR - 1) / KM_TR); a.te = (int)((g.me + KM_TR - 1) / KM_TR); a.ti = (int)((g.mi + KM_TR - 1) / KM_TR);
+    a.ts = a.ti;
+    const int tiles = a.tx + a.te + a.ti + a.ts + (a.rows_out > a.N ? 1 : 0);
+    hipLaunchKernelGGL(k_kmany, dim3((unsigned)((k + KM_KB - 1) / KM_KB), (unsigned)tiles), dim3(256), 0, ctx->stream, a);
+    PYIPM_KCHECK();
+    return 0;
+}
+
+// The whole call after argument checks.  Device pointers: the launch reads v and writes y where they are.  Host pointers: packed
+// (ld = N) through ctx->km_buf, outside the workspace.
+int kkt_matvec_many(Ctx* ctx, int64_t k, const double* v, int64_t ld_v, double* y, int64_t ld_y, int memkind) {
+    const Geo& g = ctx->g;
+    const hipStream_t st = ctx->stream;
+    if (memkind == PYIPM_MEM_DEVICE) return kkt_matvec_many_dev(ctx, k, v, ld_v, y, ld_y, false);
+    const size_t col = (size_t)g.N * (size_t)k, need = 2 * col;
+    if (ctx->km_buf.capacity() < need) {
+        PYIPM_HIP(ctx->km_buf.reserve(need));
+        if (getenv("PYIPM_POISON_WORKSPACE")) PYIPM_HIP(hipMemsetAsync(ctx->km_buf, 0xFF, need * sizeof(double), st));   // as the workspace
+    }
+    double* Vd = ctx->km_buf;
+    double* Yd = Vd + col;
+    PYIPM_HIP(hipMemcpy2DAsync(Vd, (size_t)g.N * sizeof(double), v, (size_t)ld_v * sizeof(double), (size_t)g.N * sizeof(double),
+                               (size_t)k, hipMemcpyHostToDevice, st));
+    PYIPM_HIP(hipStreamSynchronize(st));                                     // host memory not retained
+    int rc = kkt_matvec_many_dev(ctx, k, Vd, g.N, Yd, g.N, false); if (rc) return rc;
+    PYIPM_HIP(hipMemcpy2DAsync(y, (size_t)ld_y * sizeof(double), Yd, (size_t)g.N * sizeof(double), (size_t)g.N * sizeof(double),
+                               (size_t)k, hipMemcpyDeviceToHost, st));
+    PYIPM_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
 // The whole call after argument checks: stage, solve, refine, flip, copy out.  Every vector lives in ctx->ms_buf: v0 - v3,
 // vc, the kept residual and the factor are not touched, so a pending fused forward pass and the last direction survive.
 int solve_many(Ctx* ctx, int64_t k, const double* rhs, int64_t ld_rhs, double* dz, int64_t ld_dz, int flip, int refine,
@@ -1497,7 +1541,8 @@ int solve_many(Ctx* ctx, int64_t k, const double* rhs, int64_t ld_rhs, double* d
     std::vector<double> ss(adaptive ? 2 * (size_t)k : 0);
     rc = refine_loop(ctx, refine,
         [&]() -> int {                                          // R = B - Hc X
-            for (int64_t j = 0; j < k; ++j) { int r2 = kkt_matvec_dev(ctx, X + j * Np, R + j * Np); if (r2) return r2; }
+            if (ctx->ms_matvec_many) { int r2 = kkt_matvec_many_dev(ctx, k, X, Np, R, Np, true); if (r2) return r2; }   // all columns in one launch
+            else for (int64_t j = 0; j < k; ++j) { int r2 = kkt_matvec_dev(ctx, X + j * Np, R + j * Np); if (r2) return r2; }
             hipLaunchKernelGGL(k_axpby, grid1((int64_t)col), dim3(256), 0, st, R, B, R, 1.0, -1.0, (int64_t)col);
             PYIPM_KCHECK();
             return 0;
@@ -2319,6 +2364,7 @@ static int create_impl(pyipm_newton_ctx** out, int64_t n, int64_t me, int64_t mi
             { const char* e = getenv("PYIPM_FWD_RANGE"); if (e) { const int w = atoi(e); if (w <= 0) ctx->fwd_range = 0; else if (w >= 2) ctx->fwd_range_wgs = w; } }
             { const char* e = getenv("PYIPM_SLACK_ONE"); if (e && atoi(e) <= 0) ctx->slack_one = 0; }
             { const char* e = getenv("PYIPM_BWD_SLACK"); if (e && e[0] == '0') ctx->bwd_slack = 0; }
+            { const char* e = getenv("PYIPM_MS_MATVEC_MANY"); if (e && atoi(e) > 0) ctx->ms_matvec_many = 1; }
         },
         [&](Ctx* ctx, char* base) { return carve_workspace(ctx, g, base, provider_only); },
         2 /* [0] max |entry|, [1] "assembly pending" */, true);
@@ -3024,6 +3070,23 @@ int pyipm_newton_kkt_matvec(pyipm_newton_ctx* h, const double* v, double* y, int
     PYIPM_ENTER("kkt_matvec", G_SINGLE | G_DEVICE)
     if (!v || !y) return PYIPM_E_BADARG;
     return kkt_matvec_io(ctx, kLocalOps, v, y, memkind);
+} PYIPM_CATCH_H(h)
+
+int pyipm_newton_kkt_matvec_many(pyipm_newton_ctx* h, int64_t k, const double* v, int64_t ld_v, double* y, int64_t ld_y,
+                                 int memkind) try {
+    PYIPM_ENTER("kkt_matvec_many", G_SINGLE | G_ONE_RANK) const Geo& g = ctx->g;
+    if (k < 0) { ctx->err = "kkt_matvec_many: k < 0"; return PYIPM_E_BADARG; }
+    if (memkind != PYIPM_MEM_DEVICE && memkind != PYIPM_MEM_HOST) { ctx->err = "kkt_matvec_many: bad memkind"; return PYIPM_E_BADARG; }
+    if (k == 0) return PYIPM_OK;
+    if (!ctx->held.have_blocks || !ctx->held.have_vectors) { ctx->err = "kkt_matvec_many: stage blocks and vectors first"; return PYIPM_E_BADARG; }
+    if (!v || !y) { ctx->err = "kkt_matvec_many: null v or y"; return PYIPM_E_BADARG; }
+    if (ld_v < g.N || ld_y < g.N) { ctx->err = "kkt_matvec_many: leading dimension below N"; return PYIPM_E_BADARG; }
+    {   // the launch reads v while it writes y
+        const double* v1 = v + (k - 1) * ld_v + g.N; const double* y1 = y + (k - 1) * ld_y + g.N;
+        if ((uintptr_t)v < (uintptr_t)y1 && (uintptr_t)y < (uintptr_t)v1) { ctx->err = "kkt_matvec_many: y overlaps v"; return PYIPM_E_BADARG; }
+    }
+    PYIPM_HIP(hipSetDevice(ctx->device));
+    return kkt_matvec_many(ctx, k, v, ld_v, y, ld_y, memkind);
 } PYIPM_CATCH_H(h)
 
 int pyipm_newton_solve_info(pyipm_newton_ctx* h, double out[4]) try {

@@ -88,6 +88,7 @@ def load_library(path: str | None = None):
         "pyipm_newton_anorm": (c_int, [ctxp, POINTER(c_void_p)]),
         "pyipm_newton_rcond": (c_int, [ctxp, c_int, c_int, POINTER(c_double)]),
         "pyipm_newton_kkt_matvec": (c_int, [ctxp, c_void_p, c_void_p, c_int]),
+        "pyipm_newton_kkt_matvec_many": (c_int, [ctxp, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int]),
         "pyipm_newton_step": (c_int, [ctxp, c_double, c_double, c_int, c_void_p, POINTER(FactorStats), c_int]),
         "pyipm_newton_reuse_info": (c_int, [ctxp, POINTER(c_int64)]),
         "pyipm_newton_step_lengths": (c_int, [ctxp, c_double, c_void_p, POINTER(c_double), POINTER(c_double)]),
@@ -392,6 +393,31 @@ class NewtonCore(object):
         y = self.torch.empty(self.N, dtype=self.torch.float64, device=self.device)
         self._ck(self.lib.pyipm_newton_kkt_matvec(self.h, self._ptr(v), self._ptr(y), MEM_DEVICE))
         return y
+
+    def kkt_matvec_many(self, V):
+        """``Hc @ V`` for ``V`` of shape (N, k) in one pass over the staged blocks (pyipm_newton_kkt_matvec_many).  A torch
+        tensor is taken on the device and an (N, k) fp64 device tensor comes back (the transposed view of a contiguous
+        (k, N) buffer); a NumPy array goes through the host entry and an (N, k) array comes back.  Column j is bitwise
+        independent of the other columns."""
+        torch = self.torch
+        host = not isinstance(V, torch.Tensor)
+        if host:
+            V = np.asarray(V, dtype=np.float64)
+        if V.ndim != 2 or V.shape[0] != self.N:
+            raise ValueError("kkt_matvec_many: V must have shape (N, k) with N = %d, got %s" % (self.N, tuple(V.shape)))
+        k = int(V.shape[1])
+        self._use_current_stream()
+        if host:
+            vin = np.ascontiguousarray(V.T)              # (k, N): column j of V at vin + j * N
+            out = np.empty((k, self.N), dtype=np.float64)
+            self._ck(self.lib.pyipm_newton_kkt_matvec_many(self.h, k, c_void_p(vin.ctypes.data), self.N,
+                                                           c_void_p(out.ctypes.data), self.N, MEM_HOST))
+            return out.T
+        vin = self._dev(V, contiguous=False).t().contiguous()
+        out = torch.empty((k, self.N), dtype=torch.float64, device=self.device)
+        self._ck(self.lib.pyipm_newton_kkt_matvec_many(self.h, k, self._ptr(vin), self.N, self._ptr(out), self.N, MEM_DEVICE))
+        self._keep_v_many = vin                          # (the library reads it on the stream, after this returns)
+        return out.t()
 
     def step(self, delta=0.0, delta_c=0.0, refine=0):
         """Fused residual + assemble + factor + solve + flip."""
