@@ -310,6 +310,11 @@ struct Ctx {
     Stream rest;                          // ... that stream (high priority, created on first use: ensure_rest_stream)
     std::vector<Event> ev_band;           // panel (by offset in its group): its tiles are inverted and applied inside the diagonal block
     Event ev_join, ev_main, ev_split, ev_sfast;
+    int tail_split = 1;                   // reusing step: a chain group hands over to the next chain behind its own launch and the diagonal block's
+                                          // share of the head (StepPlan::tail_split); PYIPM_TAIL_SPLIT=0 at create time keeps the old order
+    Event ev_rows, ev_head2, ev_chain_end;   // ... the source's rows kernels are through; the rest of the head is; the source's chain launch is
+    DevBuf<unsigned> tail_flag;           // ... one word: the token of the last head whose rest is through (releases the next chain's extra rows)
+    unsigned tail_token = 0;
     int keep_zeros = 1;                   // K1 does not store again the zeros nothing can fill in (k_assemble, zeros_in_place)
     int tile_step = 1;                    // stepped panel schedule (kernels_panel.hpp): one launch per diagonal tile (the rows inside the
                                           // diagonal block), one for the rows below it; panels of at most 4 tiles; same bits

@@ -611,11 +611,19 @@ int launch_tile_steps(Ctx* ctx, hipStream_t chain, int64_t gc0, int64_t glc0, in
 }
 
 struct SubPanel { int64_t c0, lc0; int nt; double* W; int64_t id; };
+// The tail split seen from one block (single-rank reusing step; StepPlan::tail_split, enqueue_groups decides):
+//   xrows > 0: the block hands over split -- its chain launch takes the `xrows` rows right below the diagonal block along (the
+//   next group's diagonal block; released by *xword reaching xwant, NULL: at once), the rows kernels start behind them and ALL of
+//   them run on ctx->rest, nothing follows the chain's launch on its stream; every panel is done (on_done) and ctx->ev_rows is
+//   recorded on ctx->rest once the chain's launch has ended too.
+//   rows_behind: the rows kernels wait for it (the rest of the head into this block's columns ran on another stream).
+struct TailHand { int64_t xrows = 0; const unsigned* xword = nullptr; unsigned xwant = 0; hipEvent_t rows_behind = nullptr; };
 struct BlockDesc {
     std::vector<SubPanel> sp;              // adjacent in global AND local columns; W adjacent too (sp[k].W = sp[0].W + (c0_k - c0_0) * Npad)
     bool wide = false;                     // sub-panels of local panel `lp` (column tiles addressed inside it) instead of whole panels
     int64_t lp = 0;                        // wide: the local panel index; else: sp[k].id is the (local = global) panel index
     int64_t hole0 = 0, hole1 = 0;          // rows of exact zeros the rows kernels skip (KKT structure)
+    TailHand hand;                         // the tail split's part in this block (none: all zero)
 };
 int factor_block(Ctx* ctx, const BlockDesc& bd, hipStream_t chain, const std::function<int(int64_t, hipStream_t)>& on_done) {
     const Geo& g = ctx->g;
@@ -646,14 +654,19 @@ int factor_block(Ctx* ctx, const BlockDesc& bd, hipStream_t chain, const std::fu
     // (k_tile_chain: the whole diagonal block is ONE launch; the rows of sub-panel q wait on their own stream for the chain's
     //  progress words instead -- k_chain_wait below)
     const bool one_launch = ctx->chain_whole && chain_applies(ctx, gc0, nT);
+    const bool hand = bd.hand.xrows > 0;
+    const int64_t rbeg = gend + bd.hand.xrows;          // the rows kernels' first row
+    if (hand && !one_launch) { ctx->err = "factor_block: the tail split needs the one-launch chain (group_extra_ok)"; return PYIPM_E_BADARG; }
+    if (bd.hand.rows_behind) PYIPM_HIP(hipStreamWaitEvent(ctx->rest, bd.hand.rows_behind, 0));
     ChainGeo cgw; memset(&cgw, 0, sizeof(cgw));
     if (one_launch) {
         // (the rows stream polls the chain's progress with a bounded wait: it must not start polling before the chain can start --
         //  behind a Gram launch of seconds, the condensed form at n = 65536, the bound ran out while the chain's stream was still busy)
         PYIPM_HIP(hipEventRecord(ctx->ev_band[0], chain));
         PYIPM_HIP(hipStreamWaitEvent(ctx->rest, ctx->ev_band[0], 0));
-        int r0 = launch_tile_steps(ctx, chain, gc0, glc0, nT, 0, nT, Wg, Dv, Ts); if (r0) return r0;
+        int r0 = launch_tile_steps(ctx, chain, gc0, glc0, nT, 0, nT, Wg, Dv, Ts, (int)(bd.hand.xrows / TB), bd.hand.xword, bd.hand.xwant); if (r0) return r0;
         cgw = ctx->chain_last;
+        if (hand) PYIPM_HIP(hipEventRecord(ctx->ev_chain_end, chain));
     }
     for (int kp = 1, ta = 0; kp <= n0 && !one_launch; ++kp) {
         const int tb = kp < n0 ? toff[(size_t)kp] + 1 : nT;
@@ -668,7 +681,8 @@ int factor_block(Ctx* ctx, const BlockDesc& bd, hipStream_t chain, const std::fu
         // the last sub-panel's rows are what the next block waits for: they stay on the chain's stream (a dependency across
         // streams costs 10-30 us when the waiting side is idle), behind the other sub-panels' work on ctx->rest
         hipStream_t rs = ctx->rest;
-        if (k + 1 == n0) {
+        // (the tail split: what the next block waits for left with the chain's launch; these rows go to ctx->rest like the others)
+        if (k + 1 == n0 && !hand) {
             PYIPM_HIP(hipEventRecord(ctx->ev_join, ctx->rest));
             PYIPM_HIP(hipStreamWaitEvent(chain, ctx->ev_join, 0));
             rs = chain;
@@ -685,14 +699,14 @@ int factor_block(Ctx* ctx, const BlockDesc& bd, hipStream_t chain, const std::fu
         // stages -- instead of one by one: half the read-modify-write passes over those rows and longer K per launch.
         // In the tail the one-by-one form keeps only the last sub-panel's stages behind the chain.  Same bits either way.
         const bool left = g.Npad - gend > PENDING_LEFT_ROWS;
-        if (g.Npad > gend && left && k > 0) {
+        if (g.Npad > rbeg && left && k > 0) {
             const int K = toff[(size_t)k] * TB;
-            int rc = upd(rs, ctx->A + glc0 * g.Npad, Wg, K, gend, k, 1, gc0);
+            int rc = upd(rs, ctx->A + glc0 * g.Npad, Wg, K, rbeg, k, 1, gc0);
             if (rc) return rc;
         }
-        if (g.Npad > gend) {
-            hipLaunchKernelGGL(k_panel_rest, dim3((unsigned)((g.Npad - gend) / TB)), dim3(256), 0, rs, ctx->A, g.Npad, c0, lc0, nt,
-                               gend, q.W, g.Npad, ctx->Dinv + (c0 / TB) * TT, ctx->Tsv + (c0 / TB) * TT, ctx->Tflag + c0 / TB,
+        if (g.Npad > rbeg) {
+            hipLaunchKernelGGL(k_panel_rest, dim3((unsigned)((g.Npad - rbeg) / TB)), dim3(256), 0, rs, ctx->A, g.Npad, c0, lc0, nt,
+                               rbeg, q.W, g.Npad, ctx->Dinv + (c0 / TB) * TT, ctx->Tsv + (c0 / TB) * TT, ctx->Tflag + c0 / TB,
                                ctx->block_refine, bd.hole0, bd.hole1, &ctx->dstats->growth_bits);
             PYIPM_KCHECK();
             if (k + 1 < n0 && !left) {
@@ -703,12 +717,12 @@ int factor_block(Ctx* ctx, const BlockDesc& bd, hipStream_t chain, const std::fu
                 if (g.Npad - tc0 <= PENDING32_ROWS) {
                     int64_t pa0, pa1, pb0, pb1;
                     active_ranges(ctx, c0, c0 + K, &pa0, &pa1, &pb0, &pb1);
-                    hipLaunchKernelGGL(k_inpanel_update, dim3((unsigned)((g.Npad - gend) / 32), (unsigned)(ncols / TB)), dim3(256), 0,
+                    hipLaunchKernelGGL(k_inpanel_update, dim3((unsigned)((g.Npad - rbeg) / 32), (unsigned)(ncols / TB)), dim3(256), 0,
                                        rs, ctx->A, g.Npad, nx.lc0, ctx->A + lc0 * g.Npad, g.Npad, q.W, g.Npad,
-                                       tc0, K, gend, g.Npad, pa0, pa1, pb0, pb1, SIDE_PRIO);
+                                       tc0, K, rbeg, g.Npad, pa0, pa1, pb0, pb1, SIDE_PRIO);
                     PYIPM_KCHECK();
                 } else {
-                    int rc = upd(rs, ctx->A + lc0 * g.Npad, q.W, K, gend, k + 1, n0 - 1 - k, c0);
+                    int rc = upd(rs, ctx->A + lc0 * g.Npad, q.W, K, rbeg, k + 1, n0 - 1 - k, c0);
                     if (rc) return rc;
                 }
             }
@@ -717,20 +731,27 @@ int factor_block(Ctx* ctx, const BlockDesc& bd, hipStream_t chain, const std::fu
         // inv(T)) is there.  Whoever reads panel q as a whole (the forward substitution that trails the factorisation) needs L of its
         // columns inside the diagonal block too, i.e. the state after the tile step of the next sub-panel's first tile (what an event
         // behind that launch used to say): a second wait, behind the rows kernels.  L, like W and inv(T), is written through.
-        if (one_launch && k + 1 < n0) {
+        if (one_launch && k + 1 < n0 && !hand) {
             const int tq = toff[(size_t)k + 1] + 1;
             hipLaunchKernelGGL(k_chain_wait, dim3(1), dim3(64), 0, ctx->rest, cgw, tq, tq, tq);
             PYIPM_KCHECK();
         }
+        if (hand) continue;
         int rc = on_done(q.id, rs); if (rc) return rc;
+    }
+    if (hand) {
+        // a panel as a whole -- L inside the diagonal block, the extra rows -- is there when the chain's launch has ended
+        PYIPM_HIP(hipStreamWaitEvent(ctx->rest, ctx->ev_chain_end, 0));
+        for (int64_t k = 0; k < n0; ++k) { int rc = on_done(bd.sp[(size_t)k].id, ctx->rest); if (rc) return rc; }
+        PYIPM_HIP(hipEventRecord(ctx->ev_rows, ctx->rest));
     }
     return 0;
 }
 
 // A group of panels of the single-rank schedule: panels [p0, p0 + n0).
-int factor_group(Ctx* ctx, int64_t p0, int64_t n0, hipStream_t chain, const std::function<int(int64_t, hipStream_t)>& on_done) {
+int factor_group(Ctx* ctx, int64_t p0, int64_t n0, hipStream_t chain, const std::function<int(int64_t, hipStream_t)>& on_done, const TailHand& hand = {}) {
     const Geo& g = ctx->g;
-    BlockDesc bd;
+    BlockDesc bd; bd.hand = hand;
     for (int64_t k = 0; k < n0; ++k) {
         const int64_t q = p0 + k;
         bd.sp.push_back(SubPanel{g.panel_c0(q), g.local_c0(q), (int)(g.panel_w(q) / TB), wbuf(ctx, q), q});
@@ -788,17 +809,29 @@ int panel_chain(Ctx* ctx, int64_t p, hipStream_t stream, int64_t xrows, const un
 // instead of panel_rows behind it)?  The one-launch chain, whole tiles -- at most 16 of them: a wide panel's (nb = 1024) rows for
 // the next owner are 16 row tiles of 16 stages each, units that keep the chain's pace like the block's own far rows --, none of
 // them inside the panel's hole of structural zeros (k_panel_rest leaves those alone), progress words enough.
-bool chain_extra_ok(const Ctx* ctx, int64_t p, int64_t xrows) {
+// (the diagonal block of nt tiles at column c0, its hole [h0, h1): a panel, or a group of the single-rank schedule seen as one block)
+static bool block_extra_ok(const Ctx* ctx, int64_t c0, int nt, int64_t xrows, int64_t h0, int64_t h1) {
     const Geo& g = ctx->g;
-    const int64_t c0 = g.panel_c0(p);
-    const int nbw = (int)g.panel_w(p), nt = nbw / TB;
+    const int64_t nbw = (int64_t)nt * TB;
     if (xrows <= 0 || xrows % TB != 0 || xrows / TB > 16 || c0 + nbw + xrows > g.Npad) return false;
     if (!(nt >= 2 && chain_applies(ctx, c0, nt))) return false;
     if (1 + 4 * (nt + (int)(xrows / TB)) > Ctx::CHAIN_WORDS) return false;
-    int64_t h0 = 0, h1 = 0;
-    panel_hole(ctx, p, &h0, &h1);
     const int64_t r0 = c0 + nbw, r1 = r0 + xrows;
     return !(h1 > h0 && r1 > h0 && r0 < h1);
+}
+bool chain_extra_ok(const Ctx* ctx, int64_t p, int64_t xrows) {
+    int64_t h0 = 0, h1 = 0;
+    panel_hole(ctx, p, &h0, &h1);
+    return block_extra_ok(ctx, ctx->g.panel_c0(p), (int)ctx->g.panel_w(p) / TB, xrows, h0, h1);
+}
+// ... and group grp of the single-rank schedule (the tail split, StepPlan::tail_split): the group's whole diagonal block is one launch
+static bool group_extra_ok(const Ctx* ctx, int64_t grp, int64_t xrows) {
+    const Geo& g = ctx->g;
+    const int64_t p0 = ctx->sched.first(grp), p1 = ctx->sched.first(grp + 1);
+    int64_t cols = 0, h0 = 0, h1 = 0;
+    for (int64_t q = p0; q < p1; ++q) cols += g.panel_w(q);
+    if (ctx->skip_zeros && g.mi > 0 && ctx->sched.in_x_panel(p0)) slack_hole(g, &h0, &h1);
+    return ctx->chain_whole && cols / TB <= 32 && block_extra_ok(ctx, g.panel_c0(p0), (int)(cols / TB), xrows, h0, h1);
 }
 // every stage of panel p for the rows [r0, r1) below its diagonal block (128-aligned), the chain complete on `stream` before
 int panel_rows(Ctx* ctx, int64_t p, int64_t r0, int64_t r1, hipStream_t stream) {
@@ -1849,10 +1882,10 @@ static int panel_done(Ctx* ctx, const FactorRun& run, int64_t grp, int64_t q, hi
 }
 
 // all panels of one group on stream S
-static int run_group(Ctx* ctx, const FactorRun& run, int64_t grp, hipStream_t S) {
+static int run_group(Ctx* ctx, const FactorRun& run, int64_t grp, hipStream_t S, const TailHand& hand = {}) {
     const int64_t pA = ctx->sched.first(grp), nA = ctx->sched.size(grp);
     auto done = [&](int64_t q, hipStream_t used) { return panel_done(ctx, run, grp, q, used); };
-    if (chain_group(ctx, grp)) return factor_group(ctx, pA, nA, S, done);
+    if (chain_group(ctx, grp)) return factor_group(ctx, pA, nA, S, done, hand);
     for (int64_t q = pA; q < pA + nA; ++q) {
         if (!run.done_early(ctx, q)) { int r2 = factor_panel(ctx, q, S, true); if (r2) return r2; }
         int r2 = done(q, S); if (r2) return r2;
@@ -1928,6 +1961,36 @@ static int head_from(Ctx* ctx, bool fast_src, int64_t q0, int64_t nq, int64_t tp
     return 0;
 }
 
+// The tail split's head (StepPlan::tail_split): the complete group of panels [q0, q0 + nq) applied to the columns
+// of panels [tp, tp + tn) in two k_update launches of the same K.  The target's diagonal block on ds, the next chain's stream, behind
+// the source's chain launch; the rows behind it on the main stream in front of the bulk update, behind the source's rows kernels
+// (ev_rows).  release: the flag word takes the next token behind the second launch -- the next chain's extra rows wait for it.
+// ev_head2: the second launch is through (the target's rows kernels wait for it).  Every entry is written by one launch.
+__global__ __launch_bounds__(64) void k_tail_mark(unsigned* p, unsigned v) { if (threadIdx.x == 0) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+static int head_split(Ctx* ctx, GroupTrace& tr, int64_t grp, int64_t q0, int64_t nq, int64_t tp, int64_t tn, hipStream_t ds, int64_t xnext) {
+    const Geo& g = ctx->g; const bool release = xnext > 0;
+    int K = 0; int64_t cols = 0;
+    for (int64_t q = q0; q < q0 + nq; ++q) K += (int)g.panel_w(q);
+    for (int64_t q = tp; q < tp + tn; ++q) cols += g.panel_w(q);
+    const int64_t tc0 = g.panel_c0(tp), tend = tc0 + cols, src = g.panel_c0(q0);
+    const double* Lop = ctx->A + g.local_c0(q0) * g.Npad;
+    // (36 tiles of 128 x 128 at the default sizes.  With the default options -- reserve_cus > 0, so no 128 x 256 tiles over so
+    //  few rows -- launch_update128 halves such a narrow launch into 128 x 64 tiles, k_update<64, true, 8>: the instance the
+    //  kernel statistics show and the one measured; as 128 x 128 tiles on four waves the step took 5.67 against 5.48 ms.  Any
+    //  instance gives the same bits.)
+    int rc = launch_update128(ctx, ds, Lop, g.Npad, wbuf(ctx, q0), K, tc0, tp, tn, {.row_end = tend, .src_c0 = src, .prio = SIDE_PRIO}); if (rc) return rc;
+    tr.mark("diag head end", grp, ds);
+    PYIPM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_rows, 0));
+    // (the rows the next chain takes along first, in a launch of their own: the word behind it releases them while the rest runs)
+    const int64_t xend = release ? tend + xnext : tend;
+    if (xend > tend) { rc = launch_update128(ctx, ctx->stream, Lop, g.Npad, wbuf(ctx, q0), K, tend, tp, tn, {.row_end = xend, .src_c0 = src}); if (rc) return rc; }
+    if (release) { hipLaunchKernelGGL(k_tail_mark, dim3(1), dim3(64), 0, ctx->stream, ctx->tail_flag.get(), ++ctx->tail_token); PYIPM_KCHECK(); }
+    if (xend < g.Npad) { rc = launch_update128(ctx, ctx->stream, Lop, g.Npad, wbuf(ctx, q0), K, xend, tp, tn, {.src_c0 = src}); if (rc) return rc; }
+    PYIPM_HIP(hipEventRecord(ctx->ev_head2, ctx->stream));
+    tr.mark("rest of head end", grp, ctx->stream);
+    return 0;
+}
+
 // One iteration of the lookahead loop, decided (group grp is complete, group grp + 1 runs next)
 struct GroupStep {
     bool fast_src, nxt_fast;      // group grp / group grp + 1 lies inside the slack block
@@ -1968,7 +2031,7 @@ static int enqueue_begin(Ctx* ctx, FactorRun& run) {
     if (!ctx->side) {
         // panel kernels are latency-critical and tiny: highest dispatch priority, so they take the first
         // CU slot a retiring bulk-update block frees instead of queueing behind the whole bulk grid
-        for (Event* e : {&ctx->ev_main, &ctx->ev_early, &ctx->ev_split, &ctx->ev_sfast})      // the events of the schedule below
+        for (Event* e : {&ctx->ev_main, &ctx->ev_early, &ctx->ev_split, &ctx->ev_sfast, &ctx->ev_rows, &ctx->ev_head2, &ctx->ev_chain_end})      // the events of the schedule below
             PYIPM_HIP(e->ensure(hipEventDisableTiming));
         PYIPM_HIP(ctx->side.ensure_highest(hipStreamNonBlocking));
     }
@@ -2069,8 +2132,16 @@ static int enqueue_groups(Ctx* ctx, FactorRun& run) {
     const StepPlan& plan = run.plan; const GroupSched& sc = ctx->sched; GroupTrace& tr = run.tr;
     const int64_t np = ctx->g.npanels, ngroups = sc.ngroups(), g0 = plan.g0; const bool reuse = plan.kind == PX_REUSE;
     if (reuse && plan.slack_first && sc.fast(g0)) PYIPM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_sfast, 0));   // (as in front of any slack group)
+    // The tail split, as the plan states it per hand-over.  What group h's block takes along and waits for:
+    // gated -- the head into h's columns is split too, its second launch releases the extra rows through the flag word.
+    auto hand_of = [&](int64_t h, bool gated) {
+        TailHand th;
+        if (plan.split(h)) { th.xrows = group_cols(ctx->g, sc, h + 1); if (gated) { th.xword = ctx->tail_flag.get(); th.xwant = ctx->tail_token; } }
+        if (gated) th.rows_behind = ctx->ev_head2;
+        return th;
+    };
     tr.mark("chain+rows begin", g0, ctx->stream);
-    int rc = run_group(ctx, run, g0, ctx->stream); if (rc) return rc;
+    int rc = run_group(ctx, run, g0, ctx->stream, hand_of(g0, false)); if (rc) return rc;     // (what its extra rows read is ordered on the main stream)
     tr.mark("chain+rows end", g0, ctx->stream);
     if (reuse) PYIPM_HIP(hipEventRecord(ctx->ev_main, ctx->stream));       // group g0 ran on the main stream: its head on the side stream waits for this
     if (tr.on()) fprintf(stderr, "[pyipm group trace] %lld groups\n", (long long)ngroups);
@@ -2096,10 +2167,17 @@ static int enqueue_groups(Ctx* ctx, FactorRun& run) {
             PYIPM_HIP(hipEventRecord(ctx->ev_early, ctx->side));          // the last piece
             PYIPM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_early, 0)); // (later updates of those columns; cs, if it is the main stream)
             if (ctx->rest) PYIPM_HIP(hipStreamWaitEvent(ctx->rest, ctx->ev_early, 0));
+        } else if (plan.split(grp)) {
+            tr.mark("head begin", grp, st.cs);
+            rc = head_split(ctx, tr, grp, p0, n0, st.pT, st.nT, st.cs, plan.split(grp + 1) ? group_cols(ctx->g, sc, grp + 2) : 0); if (rc) return rc;
         } else {
             tr.mark("head begin", grp, st.hs);
             if (st.head) { rc = head_from(ctx, st.fast_src, p0, n0, st.pT, st.nT, st.hs, st.split); if (rc) return rc; }
             tr.mark("head end (its first launch's stream)", grp, st.hs);
+            if (plan.split(grp + 1)) {        // the next chain's extra rows read the whole head: its second launch ran on ctx->rest
+                PYIPM_HIP(hipEventRecord(ctx->ev_head2, ctx->rest));
+                PYIPM_HIP(hipStreamWaitEvent(st.cs, ctx->ev_head2, 0));
+            }
         }
         if (st.hs == ctx->stream && st.cs == ctx->side) {
             PYIPM_HIP(hipEventRecord(ctx->ev_head, ctx->stream));
@@ -2112,17 +2190,25 @@ static int enqueue_groups(Ctx* ctx, FactorRun& run) {
             PYIPM_HIP(hipMemcpyAsync(snap_headers(ctx).before_lam_e, ctx->dstats, sizeof(DevStats), hipMemcpyDeviceToDevice, st.cs));   // front of
             hipLaunchKernelGGL(k_init_stats, dim3(1), dim3(64), 0, st.cs, ctx->dstats); PYIPM_KCHECK();   // group gS, merged back behind gE - 1
         }
-        rc = run_group(ctx, run, grp + 1, st.cs); if (rc) return rc;
+        rc = run_group(ctx, run, grp + 1, st.cs, hand_of(grp + 1, plan.split(grp))); if (rc) return rc;
         tr.mark("chain+rows end", grp + 1, st.cs);
         PYIPM_HIP(hipEventRecord(ctx->ev_panel, st.cs));
         tr.mark("bulk begin", grp, ctx->stream);
         // bulk (overlaps the side stream): everything behind the target, whose columns the head above took
-        if (!st.pieces) { rc = timed_update(ctx, p0, n0, st.pT + st.nT, np - (st.pT + st.nT)); if (rc) return rc; }
+        // (the tail split: the next head's columns -- group grp + 2's -- in a launch of their own, so that the head waits for them alone;
+        //  each entry still takes this group's products from one launch, behind the groups before it)
+        const int64_t nA = plan.split(grp) && grp + 2 < ngroups ? sc.size(grp + 2) : 0;
+        if (nA > 0) {
+            rc = timed_update(ctx, p0, n0, st.pT + st.nT, nA); if (rc) return rc;
+            PYIPM_HIP(hipEventRecord(ctx->ev_main, ctx->stream));
+            tr.mark("bulk, next head's columns end", grp, ctx->stream);
+        }
+        if (!st.pieces) { rc = timed_update(ctx, p0, n0, st.pT + st.nT + nA, np - (st.pT + st.nT + nA)); if (rc) return rc; }
         tr.mark("bulk end", grp, ctx->stream);
         // what the next head must not overtake on the main stream: this group's bulk update -- recorded
         // BEFORE the main stream starts waiting for the side stream (the head would otherwise wait for its own stream,
         // two stream crossings for nothing)
-        PYIPM_HIP(hipEventRecord(ctx->ev_main, ctx->stream));
+        if (nA == 0) PYIPM_HIP(hipEventRecord(ctx->ev_main, ctx->stream));
         PYIPM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_panel, 0));
         run.across_prev = st.across;
     }
@@ -2160,7 +2246,9 @@ int factor_all(Ctx* ctx, pyipm_factor_stats* stats, bool fuse_forward = false, i
     if (!ctx->held.assembled) { ctx->err = "factor: assemble first"; return PYIPM_E_BADARG; }
     const auto t_host0 = std::chrono::steady_clock::now();
     const SchedOpts o = sched_opts(ctx); ctx->sched = plan_groups(g, o);
-    FactorRun run{make_step_plan(g, ctx->sched, o, px, px && ctx->held.plan.e.ok, fuse_forward, fwd_prefix_applies(ctx))};
+    StepPlan decided = make_step_plan(g, ctx->sched, o, px, px && ctx->held.plan.e.ok, fuse_forward, fwd_prefix_applies(ctx));
+    plan_tail_split(decided, g, ctx->sched, o, ctx->tail_split != 0, HEAD32_ROWS, [&](int64_t grp, int64_t rows) { return group_extra_ok(ctx, grp, rows); });
+    FactorRun run{std::move(decided)};
     const StepPlan& plan = run.plan;
     if (px && plan.kind == PX_FULL) { ctx->err = "factor: no reusable prefix in this schedule"; return PYIPM_E_BADARG; }
     if (px && !(plan == ctx->held.plan && (!plan.e.ok || ctx->snap_e))) {
@@ -2338,6 +2426,10 @@ static int create_handle(pyipm_newton_ctx** out, bool args_ok, int device, void*
     carve(ctx.get(), ctx->ws.get());
     if (hipMemset(ctx->anorm, 0, anorm_words * sizeof(unsigned long long)) != hipSuccess) return PYIPM_E_HIP;
     for (Event& e : ctx->ev) if (e.ensure(hipEventDefault) != hipSuccess) return PYIPM_E_HIP;
+    if (ctx->tail_split) {            // the flag word of the tail split, zero before any stream can poll it (PollWords::zero_and_wait: why the wait)
+        if (ctx->tail_flag.reserve(1) != hipSuccess) return PYIPM_E_NOMEM;
+        if (hipMemset(ctx->tail_flag.get(), 0, sizeof(unsigned)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return PYIPM_E_HIP;
+    }
     if (schedule_events) {
         for (Event& e : ctx->ev_prov) if (e.ensure(hipEventDefault) != hipSuccess) return PYIPM_E_HIP;
         for (Event* e : {&ctx->ev_fwd, &ctx->ev_head, &ctx->ev_panel}) if (e->ensure(hipEventDisableTiming) != hipSuccess) return PYIPM_E_HIP;
@@ -2364,6 +2456,7 @@ static int create_impl(pyipm_newton_ctx** out, int64_t n, int64_t me, int64_t mi
             { const char* e = getenv("PYIPM_FWD_RANGE"); if (e) { const int w = atoi(e); if (w <= 0) ctx->fwd_range = 0; else if (w >= 2) ctx->fwd_range_wgs = w; } }
             { const char* e = getenv("PYIPM_SLACK_ONE"); if (e && atoi(e) <= 0) ctx->slack_one = 0; }
             { const char* e = getenv("PYIPM_BWD_SLACK"); if (e && e[0] == '0') ctx->bwd_slack = 0; }
+            { const char* e = getenv("PYIPM_TAIL_SPLIT"); if (e && e[0] == '0') ctx->tail_split = 0; }
             { const char* e = getenv("PYIPM_MS_MATVEC_MANY"); if (e && atoi(e) > 0) ctx->ms_matvec_many = 1; }
         },
         [&](Ctx* ctx, char* base) { return carve_workspace(ctx, g, base, provider_only); },

@@ -1,6 +1,6 @@
 // step_plan.hpp -- what one factorisation of the single-rank driver does, decided before its first launch: the group schedule
 // (plan_groups) and the one statement of what a step keeps, copies and skips (make_step_plan).  Plain C++, nothing of HIP or of
-// the handle: the assembly, the factorisation and a stand-alone replay (tests/test_step_plan.py) compile this one source.
+// the handle: the assembly, the factorisation and the stand-alone replays (tests/test_step_plan.py, tests/test_step_plan_split.py) compile this one source.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -133,6 +133,11 @@ struct StepPlan {
     PxRange ranges[2] = {}; int nranges = 0; size_t snap_doubles = 0, snap_e_doubles = 0;   // the first snapshot's ranges, both sizes
     bool fuse_forward = false, fwd_prefix_launch = false, fr_slack = false;
     int64_t pB = 0, pS = 0, pE = 0, frA = 0, frB = 0;   // first panels of the groups gB, gS, gE (pS = pE = pB without the level)
+    // The tail split (plan_tail_split; not part of ==, like the forward fields: the factorisation alone knows it).  Per group grp
+    // of the lookahead loop: group grp + 1's chain starts behind group grp's chain launch -- which takes the rows of the next
+    // diagonal block along -- and the diagonal block's share of the head; everything else of the hand-over runs beside it.
+    std::vector<char> tail_split;
+    bool split(int64_t grp) const { return grp >= 0 && (size_t)grp < tail_split.size() && tail_split[(size_t)grp] != 0; }
     bool operator==(const StepPlan& o) const {          // (what a step keeps: not the forward fields; the ranges follow from cB and the geometry)
         return kind == o.kind && gB == o.gB && cB == o.cB && e == o.e && g0 == o.g0 && early0 == o.early0 && slack_first == o.slack_first && snap_doubles == o.snap_doubles && snap_e_doubles == o.snap_e_doubles; }
     // a recording step, group grp complete: 1 -- the first snapshot follows it, 2 -- the second one, 0 -- neither
@@ -166,5 +171,105 @@ inline StepPlan make_step_plan(const PlanGeo& g, const GroupSched& sc, const Sch
         p.frA = p.fr_slack ? p.pB : p.pS; p.frB = p.pE;
     }
     return p;
+}
+
+// ---- the tail split of a reusing step ----------------------------------------------------------------------
+// Where the hand-over from group grp to group grp + 1 is split: a reusing step with lookahead, both groups tile chains, and the
+// chain of group grp may take the rows of group grp + 1's diagonal block along (extra_ok(grp, rows): chain_extra_ok for the group
+// seen as one block).  Recording and full steps, `pieces` (early0: full steps only) and `across` (the next group a slack group:
+// no chain group) never qualify.  `on`: the handle's switch (PYIPM_TAIL_SPLIT).  tail_rows: only where at most this many rows are
+// left from the next group's first column on (HEAD32_ROWS, ctx.hpp: where the chain is the bound) -- further up the moved head
+// and the bulk update outlast the chains and queue on the main stream (first level alone at N = 32768: 11.3 -> 11.9 ms without it).
+inline int64_t group_cols(const PlanGeo& g, const GroupSched& sc, int64_t grp) {
+    int64_t w = 0; for (int64_t q = sc.first(grp); q < sc.first(grp + 1); ++q) w += g.panel_w(q); return w;
+}
+template <class ExtraOk>
+inline void plan_tail_split(StepPlan& p, const PlanGeo& g, const GroupSched& sc, const SchedOpts& o, bool on, int64_t tail_rows, ExtraOk extra_ok) {
+    const int64_t ng = sc.ngroups();
+    p.tail_split.assign((size_t)ng, 0);
+    if (!on || p.kind != PX_REUSE || !o.lookahead || p.early0) return;
+    for (int64_t grp = p.g0; grp + 1 < ng; ++grp)
+        p.tail_split[(size_t)grp] = chain_group(g, sc, o.group_chain, grp) && chain_group(g, sc, o.group_chain, grp + 1) &&
+                                    g.Npad - g.panel_c0(sc.first(grp + 1)) <= tail_rows &&
+                                    extra_ok(grp, group_cols(g, sc, grp + 1));
+}
+// ---- the enqueue items of the lookahead loop and what each waits for, as data (tests/step_plan_split_replay.cpp replays it) -------
+// An item applies the columns of one source group `src` to rows [r0, r1) of the columns of one group `dst`: dst == src is the
+// group's own factorisation (a stage), dst > src its update by src.  R(h): the rows of group h's diagonal block.
+enum TailItem {
+    TI_CHAIN,        // src = dst = h: R(h), the tile chain's launch (a group that is no chain group: all its rows, factor_panel)
+    TI_XROWS,        // ... R(h + 1) in the same launch, where the hand-over h -> h + 1 is split
+    TI_ROWS,         // ... the rows behind, the rows kernels (ctx->rest; the last sub-panel's on the chain's stream where h is not split)
+    TI_HEAD_DIAG,    // src = h, dst = h + 1, split: R(h + 1) on the next chain's stream
+    TI_HEAD_XROWS,   // ... R(h + 2) on the main stream, where h + 1 -> h + 2 is split too: the flag word is set behind it
+    TI_HEAD_REST,    // ... the rows behind, on the main stream
+    TI_HEAD_OLD,     // src = h, dst = h + 1, not split: head_from, all rows
+    TI_BULK_NEXT,    // src = h, dst = h + 2, split: the next head's columns in a launch of their own (ev_main behind it)
+    TI_BULK_REST,    // src = h, dst > h + 2 (split) or dst >= h + 2: the bulk update
+    TI_COUNT
+};
+struct TailRegion { int item; int64_t src, dst, r0, r1; };
+// rel 0: the reader's operands (L and W of group src) come from the writer, an item of src's own factorisation;
+// rel 1: the writer is the stage before on the same entries (source src - 1, the same dst).
+struct TailDep { int reader, writer, rel; const char* by; };
+constexpr TailDep TAIL_DEPS[] = {
+    {TI_XROWS, TI_CHAIN, 0, "same launch: the chain's progress words"},
+    {TI_ROWS, TI_CHAIN, 0, "k_chain_wait on ctx->rest (pieces: ev_band); the last sub-panel where h is not split: ev_join"},
+    {TI_HEAD_DIAG, TI_XROWS, 0, "stream order behind the chain's launch; ev_main where the source ran on the main stream"},
+    {TI_HEAD_XROWS, TI_XROWS, 0, "ev_rows, recorded behind ev_chain_end"},
+    {TI_HEAD_XROWS, TI_ROWS, 0, "ev_rows"},
+    {TI_HEAD_REST, TI_XROWS, 0, "ev_rows, recorded behind ev_chain_end"},
+    {TI_HEAD_REST, TI_ROWS, 0, "ev_rows"},
+    {TI_HEAD_OLD, TI_ROWS, 0, "stream order: the last rows kernel runs on the chain's stream behind ev_join (ev_main behind group g0)"},
+    {TI_HEAD_OLD, TI_CHAIN, 0, "stream order (a source that is no chain group)"},
+    {TI_BULK_NEXT, TI_ROWS, 0, "ev_rows, then the main stream's order behind the head"},
+    {TI_BULK_REST, TI_ROWS, 0, "split: as TI_BULK_NEXT; else ev_panel of the iteration before (ev_main / stream order behind g0)"},
+    {TI_BULK_REST, TI_CHAIN, 0, "stream order / ev_panel (a source that is no chain group)"},
+    {TI_CHAIN, TI_HEAD_DIAG, 1, "stream order (the chain's stream)"},
+    {TI_CHAIN, TI_HEAD_OLD, 1, "stream order (the chain's stream; ev_head where the head ran on the main stream)"},
+    {TI_XROWS, TI_HEAD_XROWS, 1, "the flag word, set behind that launch and enqueued before the chain that polls it"},
+    {TI_XROWS, TI_HEAD_OLD, 1, "ev_head2 recorded on ctx->rest behind the old head, waited for by the chain's stream"},
+    {TI_ROWS, TI_HEAD_REST, 1, "ev_head2"},
+    {TI_ROWS, TI_HEAD_OLD, 1, "stream order on ctx->rest (ev_split), or the chain's stream"},
+    {TI_HEAD_DIAG, TI_BULK_NEXT, 1, "ev_main, recorded behind that launch"},
+    {TI_HEAD_DIAG, TI_BULK_REST, 1, "ev_main"},
+    {TI_HEAD_XROWS, TI_BULK_NEXT, 1, "the main stream's order"},
+    {TI_HEAD_XROWS, TI_BULK_REST, 1, "the main stream's order"},
+    {TI_HEAD_REST, TI_BULK_NEXT, 1, "the main stream's order"},
+    {TI_HEAD_REST, TI_BULK_REST, 1, "the main stream's order"},
+    {TI_HEAD_OLD, TI_BULK_NEXT, 1, "ev_main, recorded behind that launch"},
+    {TI_HEAD_OLD, TI_BULK_REST, 1, "ev_main"},
+    {TI_BULK_NEXT, TI_BULK_REST, 1, "the main stream's order"},
+    {TI_BULK_REST, TI_BULK_REST, 1, "the main stream's order"},
+};
+inline const TailDep* tail_dep(int reader, int writer, int rel) {
+    for (const TailDep& d : TAIL_DEPS) if (d.reader == reader && d.writer == writer && d.rel == rel) return &d;
+    return nullptr;
+}
+// The items of the groups [from, ngroups) as enqueue_groups, factor_block and head_split launch them for this plan (`from`: no
+// slack group at or behind it; a head into or out of a slack group has forms of its own).
+inline std::vector<TailRegion> tail_regions(const StepPlan& p, const PlanGeo& g, const GroupSched& sc, const SchedOpts& o, int64_t from) {
+    std::vector<TailRegion> v;
+    const int64_t ng = sc.ngroups();
+    auto c0 = [&](int64_t h) { return h >= ng ? g.Npad : g.panel_c0(sc.first(h)); };
+    for (int64_t h = from; h < ng; ++h) {
+        const int64_t a = c0(h), b = c0(h + 1), x = p.split(h) ? c0(h + 2) : b;
+        if (!chain_group(g, sc, o.group_chain, h)) { v.push_back({TI_CHAIN, h, h, a, g.Npad}); }
+        else {
+            v.push_back({TI_CHAIN, h, h, a, b});
+            if (x > b) v.push_back({TI_XROWS, h, h, b, x});
+            if (g.Npad > x) v.push_back({TI_ROWS, h, h, x, g.Npad});
+        }
+        if (h + 1 >= ng) continue;
+        if (p.split(h)) {
+            const int64_t t0 = b, t1 = c0(h + 2), xe = p.split(h + 1) ? c0(h + 3) : t1;
+            v.push_back({TI_HEAD_DIAG, h, h + 1, t0, t1});
+            if (xe > t1) v.push_back({TI_HEAD_XROWS, h, h + 1, t1, xe});
+            if (g.Npad > xe) v.push_back({TI_HEAD_REST, h, h + 1, xe, g.Npad});
+        } else v.push_back({TI_HEAD_OLD, h, h + 1, b, g.Npad});
+        for (int64_t c = h + 2; c < ng; ++c)
+            v.push_back({p.split(h) && c == h + 2 ? TI_BULK_NEXT : TI_BULK_REST, h, c, c0(c), g.Npad});
+    }
+    return v;
 }
 }  // namespace pyipm
