@@ -704,6 +704,43 @@ int pyipm_newton_abi_version(void);
  * Returns achieved TFLOP/s in *tflops. */
 int pyipm_mfma_f64_peak(int device, int iters, double* tflops);
 
+/* ===================================================================================================================
+ * L-BFGS pair store: lbfgs_init / lbfgs_update of the reference (pyipm.py:993-1005, 1282-1371) where the pairs live.
+ *
+ * A store owns S and Y (n x (memory + 1), DEVICE), the small arrays SS, L, D (HOST, O(memory^2)), zeta and the counter of
+ * skipped pairs.  An offer forms dx = x_new - x_old and dg = g_old - g_new on the device, takes their products against the
+ * stored pairs in ONE read pass (2 n m + 4 n doubles), brings the 2 (m + 1) + 2 products to the host in one copy, decides
+ * there -- accept iff dg.dx > sqrt(eps) and zeta_new = dg.dx / (den + eps) > sqrt(eps), den = dx.dx for a constrained
+ * problem and dg.dg otherwise; more than `memory` skips in a row empty a non-empty store -- and appends an accepted pair,
+ * dropping the oldest once the store holds memory + 1 (the reference lets the storage reach that, :1300).  Constrained:
+ * SS = S'S, L = strictly lower S'Y; unconstrained: SS = Y'Y, L = upper S'Y; D = diag(S'Y).  The view is the argument list
+ * of pyipm_lbfgs_direction(..., PYIPM_MEM_DEVICE) (include/pyipm_lbfgs.h) on a handle with max_pairs >= memory + 1.
+ *
+ * Streams: the kernels of an offer run on the store's stream; an offer synchronises it ONCE (the products).  The append of
+ * an accepted pair is left in flight on that stream: read S / Y on the same stream or synchronise it first.  The products
+ * are deterministic (fixed grid, fixed order of the partial sums, no floating-point atomics): the same offers give the
+ * same bits.  One store per problem; row-sharded use is not offered yet -- the products of an offer are kept in ONE device
+ * buffer so that an all-reduce callback like pyipm_lbfgs_set_allreduce can be added without a change of layout.
+ * Entries return PYIPM_E_BADARG for a NULL handle or pointer (pyipm_pairs_last_error says which) and leave the store as it was. */
+typedef struct pyipm_pairs pyipm_pairs;
+typedef struct pyipm_pairs_view {          /* valid until the next offer / reset / destroy */
+    int64_t m, ld;                         /* stored pairs; pitch of S and Y in doubles      */
+    const double *S, *Y;                   /* DEVICE, n x m row-major, oldest pair first      */
+    const double *SS, *L, *D;              /* HOST, m x m row-major, contiguous               */
+    double zeta; int64_t fail;
+} pyipm_pairs_view;
+
+size_t pyipm_pairs_workspace_bytes(int64_t n, int memory);                 /* 0: bad geometry; 1 <= memory <= 31 */
+int pyipm_pairs_create(pyipm_pairs** out, int64_t n, int memory, int constrained, double zeta0, int device, void* stream);
+int pyipm_pairs_destroy(pyipm_pairs* p);
+const char* pyipm_pairs_last_error(pyipm_pairs* p);
+int pyipm_pairs_set_stream(pyipm_pairs* p, void* stream);
+int pyipm_pairs_reset(pyipm_pairs* p);                                     /* lbfgs_init */
+/* lbfgs_update.  x_*: n; g_*: at least n (only the first n are read).  outcome: 1 accepted, 0 skipped, 2 reset. */
+int pyipm_pairs_offer(pyipm_pairs* p, const double* x_old, const double* x_new, const double* g_old,
+                      const double* g_new, double eps, int memkind, int* outcome);
+int pyipm_pairs_view_get(pyipm_pairs* p, pyipm_pairs_view* v);
+
 #ifdef __cplusplus
 }
 #endif

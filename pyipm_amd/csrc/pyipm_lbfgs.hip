@@ -5,4 +5,5 @@ using namespace pyipm::drv;
 #include "kernels_lbfgs.hpp"
 #pragma GCC visibility push(default)
 #include "lbfgs_impl.hpp"
+#include "pairs_impl.hpp"                  // the pair store that feeds it (include/pyipm_newton.h, "pair store")
 #pragma GCC visibility pop

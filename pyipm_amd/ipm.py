@@ -334,12 +334,14 @@ class HipLbfgsBackend(object):
         self.n, self.me, self.mi = n, me, mi
         self.linear_constraints = bool(linear_constraints)   # dce/dci do not depend on x: stage once, J'J is reused
         self.n_calls = self.n_staged = 0
+        self.pair_doubles_uploaded = 0         # S / Y entries that crossed from the host (none with a resident pair store)
 
     def shape(self):
         return (self.n, self.me, self.mi)
 
     def lbfgs_direction(self, Je, Ji, s, lda, g, zeta, S, Y, SS, L, D, reg, eps):
         self.n_calls += 1
+        self.pair_doubles_uploaded += sum(int(a.size) for a in (S, Y) if isinstance(a, np.ndarray))   # device tensors pass through
         if (self.me or self.mi) and not (self.linear_constraints and self.n_staged):
             self.core.stage_jacobian(Je, Ji)
             self.n_staged += 1
@@ -358,7 +360,7 @@ class IPM(BarrierLoop):
                  dci=None, d2ci=None, lda0=None, lambda_dev=None, s0=None, mu=0.2, nu=10.0, rho=0.1, tau=0.995,
                  eta=1.0E-4, beta=0.4, miter=20, niter=10, Xtol=None, Ktol=1.0E-4, Ftol=None, lbfgs=False,
                  lbfgs_zeta=None, float_dtype=np.float64, verbosity=1, backend=None, device=None, nb=256, refine=0,
-                 device_step=False, condensed=False, linear_constraints=False):
+                 device_step=False, condensed=False, linear_constraints=False, resident_pairs=False):
         self.x0, self.s0, self.lda0 = x0, s0, lda0
         self.x_dev, self.lambda_dev = x_dev, lambda_dev        # accepted for signature parity; unused
         self.f, self.df, self.d2f = f, df, d2f
@@ -381,6 +383,8 @@ class IPM(BarrierLoop):
         self._own_backend = backend is None
         self._backend_opts = dict(device=device, nb=nb, refine=refine, device_step=device_step, condensed=condensed)
         self.linear_constraints = linear_constraints       # L-BFGS mode: Jacobians staged once, J'J reused
+        self.resident_pairs = bool(resident_pairs)         # L-BFGS mode: S, Y in the library's pair store (pyipm_amd.lbfgs.PairStore)
+        self._pairs = None
         self.compiled = False
         self.signal = 0
 
@@ -609,6 +613,8 @@ class IPM(BarrierLoop):
     # ------------------------------------------------------------------ L-BFGS storage (host, O(n m))
     def lbfgs_init(self):
         """Empty displacement storage (pyipm.py:993-1005)."""
+        if self.resident_pairs:
+            return self._pair_store(reset=True).view()
         n, z = self.nvar, np.zeros
         return float(self.lbfgs_zeta), z((n, 0)), z((n, 0)), z((0, 0)), z((0, 0)), z((0, 0)), 0
 
@@ -617,6 +623,11 @@ class IPM(BarrierLoop):
         skipped and counted, too many skips in a row reset the storage (pyipm.py:1282-1371).  For constrained
         problems SS = S'S, L = strictly-lower(S'Y), zeta scales the Hessian; for unconstrained ones the same
         arrays hold Y'Y and the upper-triangular S'Y and zeta scales the inverse Hessian."""
+        if self.resident_pairs:                      # the same update as ONE offer to the device-resident store
+            store = self._pair_store()
+            if store.offer(x_old, x_new, g_old, g_new, self.eps) == 2 and self.verbosity > 2:
+                print('Max failures reached, resetting storage arrays.')
+            return store.view()
         n, con = self.nvar, bool(self.neq or self.nineq)
         dx = x_new - x_old
         dg = g_old[:n] - g_new[:n]
@@ -633,6 +644,18 @@ class IPM(BarrierLoop):
                 print('Max failures reached, resetting storage arrays.')
             return self.lbfgs_init()
         return zeta, S, Y, SS, L, D, lbfgs_fail
+
+    def _pair_store(self, reset=False):
+        """The store of this problem's shape, on the backend's device; created on first use."""
+        from .lbfgs import PairStore
+        key = (self.nvar, int(self.lbfgs), bool(self.neq or self.nineq), float(self.lbfgs_zeta))
+        if self._pairs is None or self._pairs[0] != key:
+            core = getattr(self.backend, "core", None)
+            dev = core.device.index if core is not None else self._backend_opts["device"]
+            self._pairs = (key, PairStore(key[0], key[1], key[2], zeta0=key[3], device=dev))
+        elif reset:
+            self._pairs[1].reset()
+        return self._pairs[1]
 
     def lbfgs_dir(self, x, s, lda, g, zeta, S, Y, SS, L, D):
         """Counterpart of pyipm.py:1184-1246: the host evaluates the constraint Jacobians, the backend forms

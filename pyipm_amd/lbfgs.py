@@ -4,6 +4,9 @@ Counterpart of the reference's compiled ``lbfgs_dir_func`` (``/root/reference/py
 ``lbfgs_builder`` ``:1007-1182``, called from ``lbfgs_dir`` ``:1184-1246``).  Same shared object and the
 same conventions as ``pyipm_amd.newton``; PyTorch owns tensors and the stream, every kernel is HIP.
 No CPU fallback: without the library or a GPU the constructor raises.
+
+``PairStore`` is the storage that feeds it: ``lbfgs_init`` / ``lbfgs_update`` (pyipm.py:993-1005, 1282-1371) behind the
+``pyipm_pairs_*`` entry points, which ``include/pyipm_newton.h`` declares and ``pyipm_amd.newton`` binds.
 """
 from __future__ import annotations
 
@@ -198,4 +201,103 @@ class LbfgsCore(object):
         return {k: out[i] for i, k in enumerate(keys)}
 
 
-__all__ = ["LbfgsCore", "LbfgsStats", "MEM_DEVICE", "MEM_HOST", "exported_symbols"]
+class PairsView(ctypes.Structure):
+    """Mirror of ``pyipm_pairs_view`` (``include/pyipm_newton.h``)."""
+    _fields_ = [("m", c_int64), ("ld", c_int64), ("S", c_void_p), ("Y", c_void_p), ("SS", POINTER(c_double)),
+                ("L", POINTER(c_double)), ("D", POINTER(c_double)), ("zeta", c_double), ("fail", c_int64)]
+
+
+ACCEPTED, SKIPPED, RESET = 1, 0, 2          # outcomes of an offer
+
+
+class PairStore(object):
+    """The L-BFGS storage where the pairs live: ``lbfgs_init`` / ``lbfgs_update`` of the reference (pyipm.py:993-1005,
+    1282-1371) behind ``pyipm_pairs_*`` of ``include/pyipm_newton.h``.  S and Y stay on the device, SS / L / D, zeta and
+    the skip counter on the host inside the library.  No CPU fallback.
+
+    ::
+
+        store = PairStore(n, memory, constrained)
+        outcome = store.offer(x_old, x_new, g_old, g_new, eps)          # 1 accepted, 0 skipped, 2 reset
+        zeta, S, Y, SS, L, D, fail = store.view()                       # straight into LbfgsCore.direction
+    """
+
+    def __init__(self, n, memory, constrained, zeta0=1.0, device=None):
+        import torch
+        self.torch = torch
+        self.lib = load_library()
+        if not torch.cuda.is_available():
+            raise NewtonError("no HIP device visible: the L-BFGS pair store has no CPU fallback")
+        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
+        self.n, self.memory, self.constrained = int(n), int(memory), bool(constrained)
+        if self.lib.pyipm_pairs_workspace_bytes(self.n, self.memory) == 0:
+            raise NewtonError("invalid pair-store geometry n=%d memory=%d (1 <= memory <= 31)" % (n, memory))
+        h = c_void_p()
+        with torch.cuda.device(self.device):
+            rc = self.lib.pyipm_pairs_create(ctypes.byref(h), self.n, self.memory, int(self.constrained), float(zeta0),
+                                             self.device.index, c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        if rc:
+            raise NewtonError("pyipm_pairs_create failed: %s" % ERRORS.get(rc, rc))
+        self.h = h
+        self.n_offers = 0
+
+    def _ck(self, rc):
+        if rc:
+            msg = self.lib.pyipm_pairs_last_error(self.h)
+            err = NewtonError("%s: %s" % (ERRORS.get(rc, rc), msg.decode() if msg else ""))
+            err.code = rc
+            raise err
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.pyipm_pairs_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        """lbfgs_init: the empty storage with zeta0."""
+        self._ck(self.lib.pyipm_pairs_reset(self.h))
+
+    def offer(self, x_old, x_new, g_old, g_new, eps=float(np.finfo(np.float64).eps)):
+        """lbfgs_update.  Four NumPy arrays (staged by the library) or four device tensors (read where they are);
+        ``g_old`` / ``g_new`` may be longer than n.  Returns ACCEPTED, SKIPPED or RESET."""
+        torch, n = self.torch, self.n
+        args = (x_old, x_new, g_old, g_new)
+        if all(isinstance(a, torch.Tensor) for a in args):
+            keep = [to_device(a.reshape(-1), self.device) for a in args]         # (no copy for a contiguous fp64 device tensor)
+            ptrs, kind = [ptr(t) for t in keep], MEM_DEVICE
+        else:
+            keep = [np.ascontiguousarray(a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a, dtype=np.float64),
+                                         dtype=np.float64).reshape(-1) for a in args]
+            ptrs, kind = [c_void_p(a.ctypes.data) for a in keep], MEM_HOST
+        if any(a.shape[0] < n for a in keep):
+            raise NewtonError("offer: x and g need at least n = %d entries" % n)
+        out = c_int(0)
+        self._ck(self.lib.pyipm_pairs_set_stream(self.h, c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        self._ck(self.lib.pyipm_pairs_offer(self.h, ptrs[0], ptrs[1], ptrs[2], ptrs[3], float(eps), kind, ctypes.byref(out)))
+        self.n_offers += 1
+        return out.value
+
+    def view(self):
+        """(zeta, S, Y, SS, L, D, fail): S and Y are (n, m) device tensors that ALIAS the store's memory, rows ``ld`` doubles
+        apart -- valid until the next offer or reset; SS, L, D are NumPy copies."""
+        torch, n = self.torch, self.n
+        v = PairsView()
+        self._ck(self.lib.pyipm_pairs_view_get(self.h, ctypes.byref(v)))
+        m, ld = int(v.m), int(v.ld)
+        if m:
+            span = (n - 1) * ld + m
+            S, Y = (torch.as_tensor(RawDeviceArray(p, span), device=self.device).as_strided((n, m), (ld, 1)) for p in (v.S, v.Y))
+            SS, L, D = (np.ctypeslib.as_array(p, shape=(m, m)).copy() for p in (v.SS, v.L, v.D))
+        else:
+            S, Y = (torch.zeros((n, 0), dtype=torch.float64, device=self.device) for _ in range(2))
+            SS, L, D = (np.zeros((0, 0)) for _ in range(3))
+        return float(v.zeta), S, Y, SS, L, D, int(v.fail)
+
+
+__all__ = ["LbfgsCore", "LbfgsStats", "PairStore", "PairsView", "MEM_DEVICE", "MEM_HOST", "exported_symbols"]

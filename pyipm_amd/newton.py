@@ -157,6 +157,15 @@ def load_library(path: str | None = None):
         "pyipm_newton_step_dist": (c_int, [ctxp, c_double, c_double, c_int, c_void_p, POINTER(FactorStats), c_int]),
         "pyipm_newton_dist_timings": (c_int, [ctxp, POINTER(c_double)]),
         "pyipm_newton_abi_version": (c_int, []),
+        # L-BFGS pair store (pairs_impl.hpp; the Python side is pyipm_amd.lbfgs.PairStore)
+        "pyipm_pairs_workspace_bytes": (c_size_t, [c_int64, c_int]),
+        "pyipm_pairs_create": (c_int, [POINTER(c_void_p), c_int64, c_int, c_int, c_double, c_int, c_void_p]),
+        "pyipm_pairs_destroy": (c_int, [c_void_p]),
+        "pyipm_pairs_last_error": (c_char_p, [c_void_p]),
+        "pyipm_pairs_set_stream": (c_int, [c_void_p, c_void_p]),
+        "pyipm_pairs_reset": (c_int, [c_void_p]),
+        "pyipm_pairs_offer": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_int, POINTER(c_int)]),
+        "pyipm_pairs_view_get": (c_int, [c_void_p, c_void_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch

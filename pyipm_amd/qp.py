@@ -27,6 +27,8 @@ itself is the HIP library.  No CPU fallback: constructing the solver without a G
 (S, Y) resident too: the direction is ``pyipm_lbfgs_direction`` on device tensors, the constraints are linear so
 the Jacobians are staged once and J'J is reused by every direction, and Q may then be given in the factored
 form ``("diag+lowrank", d, F)`` = diag(d) + F F' (a dense n x n Q is exactly what L-BFGS is for avoiding).
+``resident_pairs=True`` hands the storage to the library's pair store (``pyipm_amd.lbfgs.PairStore``): ``lbfgs_update`` is
+then one ``pyipm_pairs_offer`` -- one pass over S and Y, no ``torch.cat``, no vendor-library product on the iteration path.
 """
 from __future__ import annotations
 
@@ -43,7 +45,7 @@ class QPDeviceIPM(BarrierLoop):
     def __init__(self, Q, c, A=None, b=None, G=None, h=None, Je=None, Ji=None, x0=None, s0=None, lda0=None,
                  mu=0.2, nu=10.0, rho=0.1, tau=0.995, eta=1.0E-4, beta=0.4, miter=20, niter=10, Xtol=None,
                  Ktol=1.0E-4, Ftol=None, verbosity=1, device=None, nb=256, refine=0, condensed=False,
-                 lbfgs=False, lbfgs_zeta=None, warm=True):
+                 lbfgs=False, lbfgs_zeta=None, warm=True, resident_pairs=False):
         import torch
         from .ipm import HipNewtonBackend
         if not torch.cuda.is_available():
@@ -94,6 +96,11 @@ class QPDeviceIPM(BarrierLoop):
             self.core.stage_blocks(self.Q, self.Je, self.Ji)
             self.lb = LbfgsCore(n, me, mi, self.lbfgs + 1, device=dev.index, nb=nb)     # storage reaches lbfgs+1 pairs
             self.lb.stage_jacobian(self.Je, self.Ji)                                    # linear constraints: once
+            # resident_pairs: the storage lives in the library's pair store (lbfgs_update = one offer, no torch.cat, no GEMV)
+            self.pairs = None
+            if resident_pairs:
+                from .lbfgs import PairStore
+                self.pairs = PairStore(n, self.lbfgs, bool(me or mi), zeta0=self.lbfgs_zeta, device=dev.index)
         else:
             self.backend = HipNewtonBackend(n, me, mi, device=dev.index, nb=nb, refine=refine, device_step=True,
                                             condensed=condensed)
@@ -415,6 +422,9 @@ class QPDeviceIPM(BarrierLoop):
         return self._g[:self.nvar + 2 * self.nineq + self.neq].clone()
 
     def lbfgs_init(self):
+        if self.pairs is not None:
+            self.pairs.reset()
+            return self.pairs.view()
         t, n, dev = self.torch, self.nvar, self.device
         e = lambda r, c: t.zeros((r, c), dtype=t.float64, device=dev)       # noqa: E731
         z = np.zeros((0, 0))
@@ -422,6 +432,9 @@ class QPDeviceIPM(BarrierLoop):
 
     def lbfgs_update(self, x_old, x_new, g_old, g_new, zeta, S, Y, SS, L, D, fail):
         """pyipm.py:1282-1371 with S, Y on the device; only the O(m) inner products cross PCIe."""
+        if self.pairs is not None:               # one pass over the stored pairs inside the library (pyipm_pairs_offer)
+            self.pairs.offer(x_old, x_new, g_old, g_new, self.eps)
+            return self.pairs.view()
         t, n = self.torch, self.nvar
         con = bool(self.neq or self.nineq)
         dx = x_new - x_old

@@ -8,6 +8,12 @@ of positive curvature).  The check is size-independent: the direction must satis
 H = Z - U inv(M) U' (the matrix of pyipm.py:1036-1052), applied matrix-free with torch as the checker.
 The CPU comparison (the reference's arithmetic, oracle/lbfgs_oracle.py) lives in bench.py --extras: tools do not touch oracle/.
 Prints one JSON line.
+
+    python tools/bench_lbfgs.py --update --n 262144 --memories 8,31
+
+times the OTHER half of the mode, lbfgs_update (pyipm.py:1282-1371), as one accepted offer to a FULL device-resident pair store
+(pyipm_pairs_offer, include/pyipm_newton.h) and, in the same process on the same inputs, as the torch body of
+QPDeviceIPM.lbfgs_update without the store (two torch.cat, the products through rocBLAS, two .contiguous()).
 """
 import argparse
 import json
@@ -39,6 +45,76 @@ def storage(n, m, seed, constrained=True):
     return zeta, S, Y, SS, L, D
 
 
+HBM_PEAK_BPS = 8.0e12          # MI355X HBM3E, specification peak: what "fraction of the read floor" is taken against
+
+
+def torch_update(torch, memory, con, eps, x_old, x_new, g_old, g_new, zeta, S, Y, SS, L, D, fail):
+    """The body of QPDeviceIPM.lbfgs_update with the torch storage, as it stands (pyipm_amd/qp.py)."""
+    from pyipm_amd.loop import lbfgs_pair_update
+    t, n = torch, x_old.numel()
+    dx = x_new - x_old
+    dg = g_old[:n] - g_new[:n]
+    drop = S.shape[1] > memory
+    Sn = t.cat([S[:, 1:] if drop else S, dx[:, None]], dim=1)
+    Yn = t.cat([Y[:, 1:] if drop else Y, dg[:, None]], dim=1)
+    prods = t.cat([Sn.t() @ dx if con else Yn.t() @ dg, dx @ Yn if con else Sn.t() @ dg,
+                   t.stack([t.dot(dg, dx), t.dot(dx, dx) if con else t.dot(dg, dg)])]).tolist()
+    kk = Sn.shape[1]
+    accepted, reset, zeta, SS, L, D, fail = lbfgs_pair_update(
+        zeta, SS, L, D, fail, drop, np.array(prods[:kk]), np.array(prods[kk:2 * kk]), prods[-2], prods[-1], con, memory, eps)
+    if accepted:
+        S, Y = Sn.contiguous(), Yn.contiguous()
+    assert accepted and not reset
+    return zeta, S, Y, SS, L, D, fail
+
+
+def update_leg(a):
+    """One accepted offer on a full store, store against torch storage, per memory depth."""
+    import torch
+    from pyipm_amd.lbfgs import PairStore
+    n, eps, con = a.n, float(np.finfo(np.float64).eps), True
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev); gen.manual_seed(3)
+    rnd = lambda *shape: torch.randn(shape, generator=gen, dtype=torch.float64, device=dev)      # noqa: E731
+    Mq = rnd(n, 16) / 4.0
+    hv = lambda v: Mq @ (Mq.T @ v) + 0.5 * v                                                      # noqa: E731
+    rows = []
+    for memory in [int(k) for k in a.memories.split(",")]:
+        xs = [rnd(n)]
+        for _ in range(memory + 1 + a.reps + 1):
+            xs.append(xs[-1] + rnd(n) / np.sqrt(n))
+        gs = [torch.cat([-hv(x), rnd(5)]) for x in xs]                # g is longer than n, as the loop passes it
+        store = PairStore(n, memory, con, device=0)
+        state = (1.0, torch.zeros((n, 0), dtype=torch.float64, device=dev), torch.zeros((n, 0), dtype=torch.float64, device=dev),
+                 np.zeros((0, 0)), np.zeros((0, 0)), np.zeros((0, 0)), 0)
+        t_store, t_torch = [], []
+        for k in range(len(xs) - 1):
+            args = (xs[k], xs[k + 1], gs[k], gs[k + 1])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            assert store.offer(*args, eps) == 1
+            torch.cuda.synchronize()                                 # (the append of the accepted pair is left in flight)
+            t1 = time.perf_counter()
+            state = torch_update(torch, memory, con, eps, *args, *state)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            if k > memory + 1:                                       # full store, first full offer taken as warm-up
+                t_store.append((t1 - t0) * 1e3); t_torch.append((t2 - t1) * 1e3)
+        zeta, S, Y, SS, L, D, _ = store.view()
+        assert S.shape[1] == state[1].shape[1] == memory + 1 and torch.equal(S, state[1]) and torch.equal(Y, state[2])
+        floor_bytes = (2 * n * memory + 4 * n) * 8                   # the kept columns (the oldest one leaves) + x_old, x_new, g_old, g_new
+        ms = float(np.median(t_store))
+        rows.append({"memory": memory, "stored_pairs": memory + 1, "offer_ms": ms, "torch_update_ms": float(np.median(t_torch)),
+                     "offer_ms_all": t_store, "torch_update_ms_all": t_torch, "read_floor_bytes": floor_bytes,
+                     "fraction_of_read_floor": floor_bytes / HBM_PEAK_BPS / (ms * 1e-3),
+                     "zeta_rel_diff": abs(zeta - state[0]) / abs(state[0]),
+                     "SS_rel_diff": float(np.abs(SS - state[3]).max() / np.abs(state[3]).max())})
+        store.close()
+    print(json.dumps({"workload": "L-BFGS update (pyipm.py:1282-1371): one accepted offer on a full store, constrained", "n": n,
+                      "dtype": "f64", "hbm_peak_Bps": HBM_PEAK_BPS, "timing": "wall, device synchronised before and after, median of %d" % a.reps,
+                      "update": rows}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=262144)
@@ -47,7 +123,11 @@ def main():
     ap.add_argument("--m", type=int, default=8)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--cpu-n", type=int, default=0, help="ignored (kept for old command lines): the CPU leg is bench.py --extras")
+    ap.add_argument("--update", action="store_true", help="time lbfgs_update (pair store against torch storage) instead of the direction")
+    ap.add_argument("--memories", default="8,31", help="--update: memory depths, comma-separated")
     a = ap.parse_args()
+    if a.update:
+        return update_leg(a)
     import torch
     from pyipm_amd.lbfgs import LbfgsCore
     n, me, mi, m = a.n, a.me, a.mi, a.m
