@@ -13,6 +13,7 @@ from ctypes import c_void_p
 
 import numpy as np
 
+from . import reghess
 from ._device import alloc_workspace, ptr, rows_to_device, to_device
 from .newton import ERRORS, MEM_DEVICE, FactorStats, NewtonError, load_library
 
@@ -377,10 +378,9 @@ class BatchedNewton(object):
 
     n_factor = 0                           # passes over the batch (direction_all)
     n_inertia_retries = 0                  # problem x shifted pass whose inertia was still wrong (delta *= 10, pyipm.py:1399-1403)
-    # direction_all(refine=True): HipNewtonBackend's bars and counters, per problem
-    suspect_spread = 1e-10                 # pivot spread d_min / d_max at or below which the condition estimate is consulted
-    berr_tol = 1e-11                       # backward error a refined direction must meet to count as converged
-    berr_fallback = float(np.sqrt(np.finfo(float).eps))     # the bar of the last resort (an inexact direction, n_inexact)
+    # direction_all(refine=True): HipNewtonBackend's counters per problem, and the bars of the rule (reghess.py), which is
+    # given this instance's values
+    suspect_spread, berr_tol, berr_fallback = reghess.SUSPECT_SPREAD, reghess.BERR_TOL, reghess.BERR_FALLBACK
     n_rcond = 0                            # problems a condition estimate was taken for
     n_refined = 0                          # problems whose direction went through refine_all
     n_static = 0                           # directions recovered from a statically pivoted factor
@@ -399,22 +399,25 @@ class BatchedNewton(object):
 
     def direction_all(self, d2L, Je, Ji, df, ce, ci, s, lda, mu, delta=0.0, eta=1e-4, beta=0.4, reg_coef=None, delta0=None,
                       max_shift_tries=60, active=None, refine=False):
-        """``reghess`` + solve (pyipm.py:1373-1406, 1717-1725) per problem of the batch, in the order ``HipNewtonBackend.direction``
-        uses; ``mu`` and ``delta`` (the delta each problem persists from its last call) are scalars or (B,).
-        Pass 1: no shifts, every problem.  A problem fails when its inertia is wrong (n_neg != me + mi), a NaN / Inf was met, or
-        it is suspect singular (static pivots, or d_min / d_max <= eps on its block pivots: the pivot-level trigger for the
-        reference's rcond <= eps -- there is no condition estimate on this path).  Failing problems get delta_c (suspect and
-        me > 0) and delta0 / max(delta / 2, delta0), and are stepped again ALONE (``active``) with delta *= 10 until their
-        inertia is right; the others keep the bits of pass 1.  With ``condensed`` pass 1 is condensed, a problem that misses
-        the guard fails too, and the retry passes run in the full form.
+        """``reghess`` + solve (pyipm.py:1373-1406, 1717-1725) per problem of the batch: the rule of ``pyipm_amd/reghess.py``,
+        which ``HipNewtonBackend.direction`` follows too, with each launch serving all problems that need it.  ``mu`` and
+        ``delta`` (the delta each problem persists from its last call) are scalars or (B,).
+        Pass 1: no shifts, every problem.  ``refine=False``: a problem fails when it is ``wrong`` or ``suspect`` at the bar eps
+        -- the pivot-level trigger for the reference's rcond <= eps; there is no condition estimate and no refinement on this
+        path, suspect means singular, and members with static pivots (LPs) are shifted.  Failing problems are stepped again
+        ALONE (``reghess.first_shift``, ``reghess.delta_c``, then delta *= 10) until their inertia is right; the others keep
+        the bits of pass 1.  With ``condensed`` pass 1 is condensed, a problem that misses the guard fails too, and the retry
+        passes run in the full form.
+        ``refine=True``: the decisions of ``HipNewtonBackend.direction`` per problem.  ONE ``rcond_all`` over the suspect
+        (``suspect_spread``), ``reghess.singular`` on each estimate; ONE ``refine_all`` over those ``at_risk`` and not singular,
+        and a problem that misses ``berr_tol`` enters the loop as a singular one.  In the loop a problem whose inertia has come
+        right is refined again if it is at risk, and its ``reghess.ShiftLoop`` says whether it is shifted further, settles on
+        its best direction (``n_inexact``) or is lost (a ``RuntimeError`` names the problems).  With ``condensed``, problems that
+        fail pass 1, are suspect, at risk or miss the guard are first re-stepped in the full form WITHOUT shifts and judged
+        there (the condition estimate is the full form's).
         ``active`` ((B,) flags; None = all): only these problems take part -- the others sit every pass out (their rows of dz
         are NaN, their statistics those of their last step, their delta unchanged).
-        ``refine=True``: the decisions of ``HipNewtonBackend.direction`` per problem instead (``_direction_all_refined``): a
-        condition estimate for the suspect problems, adaptive refinement for those at risk, shifts only for the singular.
         Returns (dz, delta (B,) float64, list of statistics): delta as the reference persists it, unchanged without a shift."""
-        if refine:
-            return self._direction_all_refined(d2L, Je, Ji, df, ce, ci, s, lda, mu, delta, eta, beta, reg_coef, delta0,
-                                               max_shift_tries, active)
         torch = self.torch
         me, mi, need = self.me, self.mi, self.me + self.mi
         eps = float(np.finfo(np.float64).eps)
@@ -429,86 +432,8 @@ class BatchedNewton(object):
         self.n_factor += 1
         stats = list(st)
 
-        def wrong(x):
-            return x["n_neg"] != need or bool(x["nonfinite"])
-
-        def suspect(x):
-            return bool(x["nonfinite"]) or x["n_zero"] > 0 or (x["d_max"] > 0 and x["d_min"] / x["d_max"] <= eps)
-
-        sus = np.array([suspect(x) for x in stats])
-        failed = np.array([wrong(x) for x in stats]) | sus
-        cond = bool(self._opts_get("condensed")) and mi > 0
-        if cond and self.guard:
-            be = self.last_backward_errors = self.backward_errors(out)
-            failed |= ((be > self.condensed_tol) | ~torch.isfinite(be)).cpu().numpy()
-        failed &= part
-        passes = np.zeros(B, dtype=np.int64)
-        fail = np.flatnonzero(failed)
-        for b in fail:
-            dc_v[b] = reg_coef * eta * mu_v[b] ** beta if (sus[b] and me) else 0.0
-            delta_v[b] = delta0 if delta_v[b] == 0.0 else max(delta_v[b] / 2.0, delta0)
-        if fail.size and cond:
-            self.n_condensed_fallback += 1
-            self._ck(self.lib.pyipm_newton_set_option(self.h, b"condensed", 0.0))
-        try:
-            tries = 0
-            while fail.size:
-                act = np.zeros(B, dtype=np.int32)
-                act[fail] = 1
-                _, st = self.step_each(mu_v, np.where(act, delta_v, 0.0), np.where(act, dc_v, 0.0), act, out=out)
-                self.n_factor += 1
-                passes[fail] += 1
-                stats = list(st)
-                fail = np.array([b for b in fail if wrong(stats[b])], dtype=np.int64)
-                if fail.size:
-                    tries += 1
-                    self.n_inertia_retries += int(fail.size)
-                    if tries > max_shift_tries:
-                        raise RuntimeError("inertia not corrected after %d diagonal shifts: problems %s" % (tries, fail.tolist()))
-                    delta_v[fail] *= 10.0
-        finally:
-            if failed.any() and cond:
-                self._ck(self.lib.pyipm_newton_set_option(self.h, b"condensed", 1.0))
-        self._shift_info = {"failed": failed.copy(), "suspect": sus, "delta_c": dc_v, "delta": np.where(failed, delta_v, 0.0),
-                            "passes": passes}
-        return out, delta_v, stats
-
-    def _direction_all_refined(self, d2L, Je, Ji, df, ce, ci, s, lda, mu, delta, eta, beta, reg_coef, delta0, max_shift_tries,
-                               active):
-        """``HipNewtonBackend.direction`` (ipm.py) for every problem of the batch, each launch serving all problems that need it.
-        Pass 1: no shifts, every problem.  Wrong inertia / NaN: the shift loop.  Suspect (static pivots, or a pivot spread at
-        or below ``suspect_spread``): ONE ``rcond_all`` over them; singular iff ``rcond <= eps``, or static pivots and
-        ``w_min <= 100 static_pivot`` -- those enter the shift loop with ``delta_c`` (me > 0).  Not singular but at risk
-        (static pivots, 2x2 pivots, growth > 64): ONE ``refine_all`` over them; a problem whose final backward error is above
-        ``berr_tol`` enters the loop as a singular one.  Everybody else keeps the bits of pass 1 and costs no launch.
-        In the loop a problem whose inertia has come right is refined again if it is at risk, and gets ``delta *= 10`` while it
-        misses ``berr_tol`` -- under the rules of ipm.py, per problem: only solves count as stalled, the least shifted
-        direction at ``berr_fallback`` is returned when two solves in a row gained less than 10x or the budget is spent
-        (``n_inexact``), otherwise a ``RuntimeError`` names the problems.
-        With ``condensed`` pass 1 is condensed; problems that fail it, are suspect, at risk or miss the guard are first
-        re-stepped in the full form WITHOUT shifts and judged there (the condition estimate is the full form's)."""
-        torch = self.torch
-        me, mi, need = self.me, self.mi, self.me + self.mi
-        eps = float(np.finfo(np.float64).eps)
-        reg_coef = float(np.sqrt(eps)) if reg_coef is None else float(reg_coef)      # pyipm.py:353
-        delta0 = reg_coef if delta0 is None else float(delta0)                       # pyipm.py:372
-        B = self.stage(d2L, Je, Ji, df, ce, ci, s, lda, mu=float(np.asarray(mu, dtype=np.float64).reshape(-1)[0]), eps=eps)
-        mu_v = np.broadcast_to(np.asarray(mu, dtype=np.float64), (B,)).copy()
-        delta_v = np.broadcast_to(np.asarray(delta, dtype=np.float64), (B,)).copy()
-        dc_v, zero = np.zeros(B), np.zeros(B)
-        part = np.ones(B, dtype=bool) if active is None else np.asarray(active).astype(bool).reshape(B)
-        out, st = self.step_each(mu_v, zero, zero, None if active is None else part.astype(np.int32))
-        self.n_factor += 1
-        stats = list(st)
-
-        def wrong(x):
-            return x["n_neg"] != need or bool(x["nonfinite"])
-
-        def suspect(x):
-            return x["n_zero"] > 0 or (x["d_max"] > 0 and x["d_min"] / x["d_max"] <= self.suspect_spread)
-
-        def at_risk(x):
-            return x["n_zero"] > 0 or x["n_2x2"] > 0 or x["growth"] > 64.0
+        def flags(pred, *args):
+            return np.array([bool(pred(x, *args)) for x in stats])
 
         def mask(idx):
             a = np.zeros(B, dtype=np.int32)
@@ -517,124 +442,114 @@ class BatchedNewton(object):
 
         passes = np.zeros(B, dtype=np.int64)
         berr = np.full(B, np.nan)
-        refined, singular = np.zeros(B, dtype=bool), np.zeros(B, dtype=bool)
-        best = {}                              # b -> (backward error, dz row, delta, statistics) of its best unconverged direction
+        refined, guard_miss = np.zeros(B, dtype=bool), np.zeros(B, dtype=bool)
+        loops = {}                             # b -> the reghess.ShiftLoop of a problem that missed berr_tol or is being shifted
         cond = bool(self._opts_get("condensed")) and mi > 0
         full = False                           # the handle has been switched to the full form for the rest of this call
-        try:
-            if cond:
-                redo = np.array([wrong(x) or suspect(x) or at_risk(x) for x in stats])
-                if self.guard:
-                    be = self.last_backward_errors = self.backward_errors(out)
-                    redo |= ((be > self.condensed_tol) | ~torch.isfinite(be)).cpu().numpy()
-                redo &= part
-                if redo.any():
-                    self.n_condensed_fallback += 1
-                    self._ck(self.lib.pyipm_newton_set_option(self.h, b"condensed", 0.0))
-                    full = True
-                    _, st = self.step_each(mu_v, zero, zero, mask(np.flatnonzero(redo)), out=out)
-                    self.n_factor += 1
-                    stats = list(st)
-                judged = redo
-            else:
-                judged = part
-            bad = np.array([wrong(x) for x in stats]) & judged
-            sus = np.array([suspect(x) for x in stats]) & judged
-            singular |= np.array([bool(x["nonfinite"]) for x in stats]) & judged
-            ask = np.flatnonzero(sus & ~singular)      # (whatever the inertia says: the estimate decides on delta_c)
-            if ask.size:
-                rc = self.rcond_all(active=mask(ask)).cpu().numpy()
-                self.n_rcond += int(ask.size)
-                for b in ask:
-                    w_min, _, rcond, static = rc[b]
-                    singular[b] = not (rcond > eps) or (stats[b]["n_zero"] > 0 and not (w_min > 100.0 * static))
 
-            def refine_group(idx, shifted):
-                """ONE refine_all over ``idx``; returns those that missed berr_tol (remembered as candidates of the last resort)."""
-                info = self.refine_all(out, active=mask(idx)).cpu().numpy()
-                self.n_refined += int(idx.size)
-                missed = []
-                for b in idx:
-                    refined[b], berr[b] = True, info[b, 2]
-                    if info[b, 2] >= 0.0 and info[b, 2] <= self.berr_tol:
-                        if stats[b]["n_zero"] > 0:
-                            self.n_static += 1     # reference: LU over the whole matrix, no shift (pyipm.py:1381 not taken)
-                        continue
-                    self.n_unconverged += 1
-                    missed.append(b)
-                    be_b = float(info[b, 2])
-                    # the LEAST shifted direction that meets berr_fallback is kept; below that bar, the most accurate one
-                    if be_b >= 0.0 and np.isfinite(be_b) and (b not in best or (best[b][0] > self.berr_fallback and be_b < best[b][0])):
-                        best[b] = (be_b, out[b].clone(), float(delta_v[b]) if shifted else 0.0, stats[b])
-                return np.array(missed, dtype=np.int64)
-
-            risk = np.flatnonzero(np.array([at_risk(x) for x in stats]) & judged & ~bad & ~singular)
-            if risk.size:
-                singular[refine_group(risk, False)] = True
-            failed = bad | singular
-            pending = np.flatnonzero(failed)
-            for b in pending:
-                dc_v[b] = reg_coef * eta * mu_v[b] ** beta if (singular[b] and me) else 0.0
-                delta_v[b] = delta0 if delta_v[b] == 0.0 else max(delta_v[b] / 2.0, delta0)
-            if pending.size and cond and not full:
+        def go_full():
+            nonlocal full
+            if cond and not full:
                 self.n_condensed_fallback += 1
                 self._ck(self.lib.pyipm_newton_set_option(self.h, b"condensed", 0.0))
                 full = True
-            tries = np.zeros(B, dtype=np.int64)
-            stalled, prev_be = np.zeros(B, dtype=np.int64), np.full(B, np.nan)
 
-            def settle(b):
-                """The best direction seen for b, if it is berr_fallback-accurate: returned in place of the last solve."""
-                if b in best and best[b][0] <= self.berr_fallback:
-                    self.n_inexact += 1
-                    berr[b], delta_v[b], stats[b] = best[b][0], best[b][2], best[b][3]
-                    out[b].copy_(best[b][1])
-                    return True
-                return False
+        def loop_of(b):
+            if b not in loops:
+                loops[b] = reghess.ShiftLoop(max_shift_tries, self.berr_fallback)
+            return loops[b]
 
+        def refine_group(idx):
+            """ONE refine_all over ``idx``; returns those that missed berr_tol."""
+            info = self.refine_all(out, active=mask(idx)).cpu().numpy()
+            self.n_refined += int(idx.size)
+            missed = []
+            for b in idx:
+                refined[b], berr[b] = True, info[b, 2]
+                if info[b, 2] >= 0.0 and info[b, 2] <= self.berr_tol:
+                    if stats[b]["n_zero"] > 0:     # reference: LU over the whole matrix, no shift (pyipm.py:1381 not taken);
+                        self.n_static += 1         # counted for a shifted solve too, which HipNewtonBackend does not do
+                    continue
+                self.n_unconverged += 1
+                missed.append(b)
+            return missed
+
+        try:
+            if cond and self.guard:
+                be = self.last_backward_errors = self.backward_errors(out)
+                guard_miss = ((be > self.condensed_tol) | ~torch.isfinite(be)).cpu().numpy()
+            judged = part
+            if cond and refine:
+                judged = (flags(reghess.wrong, need) | flags(reghess.suspect, self.suspect_spread) | flags(reghess.at_risk)
+                          | guard_miss) & part
+                if judged.any():
+                    go_full()
+                    _, st = self.step_each(mu_v, zero, zero, mask(np.flatnonzero(judged)), out=out)
+                    self.n_factor += 1
+                    stats = list(st)
+            bad = flags(reghess.wrong, need) & judged
+            nonfinite = flags(lambda x: x["nonfinite"])
+            if refine:
+                sus = flags(reghess.suspect, self.suspect_spread) & judged
+                singular = nonfinite & judged
+                ask = np.flatnonzero(sus & ~singular)      # (whatever the inertia says: the estimate decides on delta_c)
+                if ask.size:
+                    rc = self.rcond_all(active=mask(ask)).cpu().numpy()
+                    self.n_rcond += int(ask.size)
+                    for b in ask:
+                        singular[b] = reghess.singular(rc[b], stats[b], eps, nan_singular=True)
+                risk = np.flatnonzero(flags(reghess.at_risk) & judged & ~bad & ~singular)
+                for b in (refine_group(risk) if risk.size else ()):
+                    loop_of(b).remember(float(berr[b]), out[b].clone, 0.0, stats[b])
+                    singular[b] = True
+                failed = bad | singular
+            else:
+                sus = singular = nonfinite | flags(reghess.suspect, eps)
+                failed = (bad | sus | guard_miss) & part
+            pending = np.flatnonzero(failed)
+            for b in pending:
+                dc_v[b] = reghess.delta_c(singular[b], me, reg_coef, eta, mu_v[b], beta)
+                delta_v[b] = reghess.first_shift(delta_v[b], delta0)
+            if pending.size:
+                go_full()
             while pending.size:
                 act = mask(pending)
                 _, st = self.step_each(mu_v, np.where(act, delta_v, 0.0), np.where(act, dc_v, 0.0), act, out=out)
                 self.n_factor += 1
                 passes[pending] += 1
                 new = list(st)
+                verdict = {}
                 for b in pending:
                     stats[b] = new[b]
-                again, lost = [], []
-                inert = np.array([b for b in pending if wrong(stats[b])], dtype=np.int64)
-                for b in inert:                    # an inertia retry, not an unconverged solve: no part in the stall count
-                    tries[b] += 1
-                    self.n_inertia_retries += 1
-                    (lost if tries[b] > max_shift_tries else again).append(b)
+                    if reghess.wrong(stats[b], need):  # an inertia retry, not an unconverged solve: no part in the stall count
+                        self.n_inertia_retries += 1
+                        verdict[b] = loop_of(b).inertia_retry()
+                lost = [b for b in verdict if verdict[b] != reghess.AGAIN]
                 if lost:
-                    raise RuntimeError("inertia not corrected after %d diagonal shifts: problems %s" % (max_shift_tries + 1, lost))
-                ok = np.array([b for b in pending if not wrong(stats[b])], dtype=np.int64)
+                    raise RuntimeError("inertia not corrected after %d diagonal shifts: problems %s"
+                                       % (max_shift_tries + 1, lost if refine else [int(b) for b in lost]))
+                ok = np.array([b for b in pending if b not in verdict], dtype=np.int64)
                 berr[ok] = np.nan
-                rk = np.array([b for b in ok if at_risk(stats[b])], dtype=np.int64)
-                for b in (refine_group(rk, True) if rk.size else ()):
-                    be_b = berr[b]
-                    stalled[b] = stalled[b] + 1 if (np.isfinite(prev_be[b]) and be_b >= 0.0 and be_b >= 0.1 * prev_be[b]) else 0
-                    if be_b >= 0.0:
-                        prev_be[b] = be_b
-                    if stalled[b] >= 2 and settle(b):
-                        continue
-                    tries[b] += 1
-                    if tries[b] > max_shift_tries:
-                        if settle(b):
-                            continue
-                        lost.append(b)
-                        continue
-                    again.append(b)
+                rk = np.array([b for b in ok if refine and reghess.at_risk(stats[b])], dtype=np.int64)
+                for b in (refine_group(rk) if rk.size else ()):
+                    verdict[b] = loop_of(b).miss(float(berr[b]), out[b].clone, delta_v[b], stats[b])
+                    if verdict[b] == reghess.SETTLE:       # the best direction seen, in place of the last solve
+                        self.n_inexact += 1
+                        berr[b], best, delta_v[b], stats[b] = loops[b].best
+                        out[b].copy_(best)
+                lost = [b for b in ok if verdict.get(b) == reghess.LOST_SOLVE]
                 if lost:
                     raise RuntimeError("refined solve did not reach backward error %.1e after %d diagonal shifts: problems %s"
                                        % (self.berr_tol, max_shift_tries + 1, lost))
-                pending = np.array(sorted(again), dtype=np.int64)
+                pending = np.array([b for b in pending if verdict.get(b) == reghess.AGAIN], dtype=np.int64)
                 delta_v[pending] *= 10.0
         finally:
             if full:
                 self._ck(self.lib.pyipm_newton_set_option(self.h, b"condensed", 1.0))
         self._shift_info = {"failed": failed.copy(), "suspect": sus, "delta_c": dc_v, "delta": np.where(failed, delta_v, 0.0),
-                            "passes": passes, "singular": singular, "refined": refined, "backward_error": berr}
+                            "passes": passes}
+        if refine:
+            self._shift_info.update(singular=singular, refined=refined, backward_error=berr)
         return out, delta_v, stats
 
     def _fetch_stats(self, step_id):

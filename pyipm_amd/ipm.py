@@ -29,6 +29,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import reghess
 from .loop import BarrierLoop, lbfgs_pair_update
 
 
@@ -81,11 +82,8 @@ class HipNewtonBackend(object):
       detects (pyipm.py:1379-1381): the same delta / delta_c branch is taken.
     * Without static pivots the "rcond <= eps" trigger is "d_min/d_max <= eps" on the block pivots."""
 
-    berr_tol = 1e-11                       # backward error a refined direction must meet to count as converged
-    berr_fallback = float(np.sqrt(np.finfo(float).eps))   # ... and the bar of the LAST resort: when no shift within the budget
-                                           # yields a converged direction, the best one seen is returned if it meets this (the
-                                           # reference returns its LU direction whatever its accuracy, pyipm.py:1720-1721) and
-                                           # counted in n_inexact; only beyond it the backend gives up (ADVICE r3)
+    # the bars of the rule (reghess.py); the rule is given this instance's values
+    suspect_spread, berr_tol, berr_fallback = reghess.SUSPECT_SPREAD, reghess.BERR_TOL, reghess.BERR_FALLBACK
 
     def __init__(self, n, me, mi, device=None, nb=256, refine=0, max_shift_tries=60, device_step=False,
                  condensed=False):
@@ -133,14 +131,11 @@ class HipNewtonBackend(object):
                 raise
             return e.stats
 
-    suspect_spread = 1e-10                 # pivot spread d_min/d_max below which the condition estimate is consulted
-
     def _singular(self, st, eps):
         """The reference's ``rcond <= eps`` test (pyipm.py:1379-1381, rcond = min|w|/max|w| over the eigenvalues).
-        Block pivots of moderate spread cannot hide an eigenvalue ratio at the eps level; otherwise, and whenever
-        static pivots were placed, the ratio is ESTIMATED from the factor and the blocks (``core.rcond``: inverse /
-        power iterations).  With static pivots the factor is that of a perturbed matrix, whose smallest eigenvalue
-        sits at the perturbation level exactly when the unperturbed matrix is singular.
+        Block pivots of moderate spread cannot hide an eigenvalue ratio at the eps level (``reghess.suspect``); otherwise,
+        and whenever static pivots were placed, the ratio is ESTIMATED from the factor and the blocks (``core.rcond``:
+        inverse / power iterations) and judged by ``reghess.singular``.
 
         The estimate is taken with adaptive iteration counts (``core.rcond(-1, -1)``, include/pyipm_newton.h): late in an
         interior-point run the pivot spread stays below ``suspect_spread`` at EVERY iterate (Sigma = lda_i / s spans twenty
@@ -150,26 +145,19 @@ class HipNewtonBackend(object):
         self.last_rcond = None
         if st["nonfinite"]:
             return True
-        spread = st["d_min"] / st["d_max"] if st["d_max"] > 0 else 1.0
-        if st["n_zero"] == 0 and spread > self.suspect_spread:
+        if not reghess.suspect(st, self.suspect_spread):
             return False
         # adaptive iteration counts (include/pyipm_newton.h): the threshold decision of the fixed 3 + 6 iterations at a
         # third of their cost when the matrix is far from singular -- every suspect iterate of a convex QP
         est = self.last_rcond = self.core.rcond(-1, -1) if st["n_zero"] == 0 else self.core.rcond()
         self.n_rcond += 1
-        self.rcond_log.append((self.n_calls, est["rcond"], spread))
-        if st["n_zero"] > 0 and est["w_min"] <= 100.0 * est["static_pivot"]:
-            return True
-        return est["rcond"] <= eps
+        self.rcond_log.append((self.n_calls, est["rcond"], st["d_min"] / st["d_max"] if st["d_max"] > 0 else 1.0))
+        return reghess.singular((est["w_min"], est["w_max"], est["rcond"], est["static_pivot"]), st, eps, nan_singular=False)
 
     n_rcond = n_rcond_reused = 0
     rcond_log = []
 
-    @staticmethod
-    def _at_risk(st):
-        """Block pivots whose accuracy the tile-local pivot search does not guarantee: static pivots, 2x2 pivots
-        (indefinite tiles) or large entries of L.  Such a direction is checked against the blocks and refined."""
-        return st["n_zero"] > 0 or st["n_2x2"] > 0 or st["growth"] > 64.0
+    _at_risk = staticmethod(reghess.at_risk)
 
     def _solve(self, st):
         """Substitution for the current factor; (dz tensor, converged)."""
@@ -228,17 +216,13 @@ class HipNewtonBackend(object):
         st = self._factor()
         singular = self._singular(st, eps)
         dz = None
-        best = None                        # (backward error, dz, delta, stats) of the best unconverged direction so far
+        loop = reghess.ShiftLoop(self.max_shift_tries, self.berr_fallback, retry_overrun_as_miss=True, stall_on_inf=True)
 
-        def remember(dz_, delta_, st_):
-            nonlocal best
+        def missed():
+            """(backward error, how to copy the direction) of the solve that just missed berr_tol."""
+            self.n_unconverged += 1
             info = self.last_solve_info
-            be = info["backward_error"] if info else -1.0
-            # the LEAST shifted direction that meets berr_fallback is kept (the reference does not shift such a system at
-            # all); below that bar, the most accurate one
-            if dz_ is not None and be >= 0.0 and np.isfinite(be) and \
-                    (best is None or (best[0] > self.berr_fallback and be < best[0])):
-                best = (be, dz_.clone() if hasattr(dz_, "clone") else dz_, float(delta_), st_)
+            return (info["backward_error"] if info else -1.0), (lambda: dz.clone() if hasattr(dz, "clone") else dz)
 
         if not singular and st["n_neg"] == need:
             dz, converged = self._solve(st)
@@ -246,67 +230,37 @@ class HipNewtonBackend(object):
                 # a statically pivoted / 2x2 / high-growth factor whose refinement against the blocks stalls above
                 # berr_tol solves a nearby system, not this one: what the reference's LU would flag as rcond <= eps.
                 # Take the branch reghess takes then (pyipm.py:1379-1403) instead of returning the direction silently.
-                self.n_unconverged += 1
-                remember(dz, 0.0, st)
+                loop.remember(*missed(), 0.0, st)
                 dz, singular = None, True
             elif st["n_zero"] > 0:
                 self.n_static += 1         # reference: LU over the whole matrix, no shift (pyipm.py:1381 not taken)
         if dz is None:
-            delta_c = reg_coef * eta * (mu_host ** beta) if (singular and self.me) else 0.0
-            delta = delta0 if delta == 0.0 else max(delta / 2.0, delta0)
-            tries = 0
+            # the shift loop (reghess.ShiftLoop: the reference's delta *= 10 loop, :1399-1403, until the inertia is right AND
+            # the direction satisfies the blocks)
+            delta_c = reghess.delta_c(singular, self.me, reg_coef, eta, mu_host, beta)
+            delta = reghess.first_shift(delta, delta0)
             while True:
                 core.assemble(delta, delta_c)
                 st = self._factor()
-                if st["n_neg"] == need and not st["nonfinite"]:
-                    break
-                tries += 1
-                self.n_inertia_retries += 1
-                if tries > self.max_shift_tries:
-                    raise RuntimeError("inertia not corrected after %d diagonal shifts" % tries)
-                delta *= 10.0
-            dz, converged = self._solve(st)
-            stalled, prev_be = 0, None
-            solved = True                  # the loop head looks at a solve that really happened (not at an inertia retry)
-            while not converged:
-                # still no direction that satisfies the blocks: the shift has not made the factor trustworthy yet.
-                # Larger shift (the reference's delta *= 10 loop, :1399-1403); when the budget is spent, the best direction
-                # seen if it is at least berr_fallback-accurate (shifted or not), else give up loudly.
-                if solved:
-                    self.n_unconverged += 1
-                    remember(dz, delta, st)
-                    # ... or as soon as larger shifts have stopped helping: two SOLVES in a row whose backward error did not
-                    # fall tenfold with the tenfold shift, and a direction at berr_fallback in hand.  (Exactly dependent
-                    # equality constraints: no shift of the x block cures the multiplier block; waiting for delta ~ 1 to
-                    # dominate the system cost nine factorisations per iterate and returned a gradient-like step -- round 4.)
-                    # A factorisation whose inertia was wrong produced no direction: it takes no part in this bookkeeping
-                    # (two inertia retries used to count as "larger shifts stopped helping").
-                    be = self.last_solve_info["backward_error"] if self.last_solve_info else -1.0
-                    stalled = stalled + 1 if (prev_be is not None and be >= 0.0 and be >= 0.1 * prev_be) else 0
-                    prev_be = be if be >= 0.0 else prev_be
-                    if stalled >= 2 and best is not None and best[0] <= self.berr_fallback:
-                        self.n_inexact += 1
-                        dz, delta, st = best[1], best[2], best[3]
-                        self._dir_override = dz
-                        break
-                tries += 1
-                if tries > self.max_shift_tries:
-                    if best is not None and best[0] <= self.berr_fallback:
-                        self.n_inexact += 1
-                        dz, delta, st = best[1], best[2], best[3]
-                        self._dir_override = dz
-                        break
-                    raise RuntimeError("refined solve did not reach backward error %.1e after %d diagonal shifts (last: %s)"
-                                       % (self.berr_tol, tries, self.last_solve_info))
-                delta *= 10.0
-                core.assemble(delta, delta_c)
-                st = self._factor()
-                if st["n_neg"] != need or st["nonfinite"]:
+                if reghess.wrong(st, need):
                     self.n_inertia_retries += 1      # (an inertia retry, not an unconverged solve: counted on its own)
-                    solved = False
-                    continue
-                dz, converged = self._solve(st)
-                solved = True
+                    verdict = loop.inertia_retry()
+                else:
+                    dz, converged = self._solve(st)
+                    if converged:                    # (no n_static here: that counter is the UNshifted recoveries')
+                        break
+                    verdict = loop.miss(*missed(), delta, st)
+                if verdict == reghess.SETTLE:
+                    self.n_inexact += 1
+                    _, dz, delta, st = loop.best
+                    self._dir_override = dz
+                    break
+                if verdict == reghess.LOST_INERTIA:
+                    raise RuntimeError("inertia not corrected after %d diagonal shifts" % loop.tries)
+                if verdict == reghess.LOST_SOLVE:
+                    raise RuntimeError("refined solve did not reach backward error %.1e after %d diagonal shifts (last: %s)"
+                                       % (self.berr_tol, loop.tries, self.last_solve_info))
+                delta *= 10.0
         if not as_tensor:
             dz = dz.cpu().numpy()
         return dz, float(delta), st
