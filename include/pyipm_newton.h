@@ -695,7 +695,7 @@ int pyipm_newton_set_option(pyipm_newton_ctx* ctx, const char* name, double valu
  * device direction goes).  A binding checks pyipm_newton_abi_version() == PYIPM_NEWTON_ABI_VERSION of the header it was
  * written against before any other call (pyipm_amd/newton.py does).  7: step_batched_each, step_lengths_batched; the
  * workspace of a batched handle grew by the per-problem parameters.  8: block_products_batched, block_products_t_batched,
- * merit_info_batched, merit_ray_batched.  (Still 8: solve_batched, kkt_matvec_batched, rcond_batched, then refine_batched -- entries
+ * merit_info_batched, merit_ray_batched.  (Still 8: solve_batched, kkt_matvec_batched, rcond_batched, then refine_batched, pyipm_pairs_*, pyipm_qn_* -- entries
  * added, no argument list, layout or workspace size changed.) */
 #define PYIPM_NEWTON_ABI_VERSION 8
 int pyipm_newton_abi_version(void);
@@ -740,6 +740,51 @@ int pyipm_pairs_reset(pyipm_pairs* p);                                     /* lb
 int pyipm_pairs_offer(pyipm_pairs* p, const double* x_old, const double* x_new, const double* g_old,
                       const double* g_new, double eps, int memkind, int* outcome);
 int pyipm_pairs_view_get(pyipm_pairs* p, pyipm_pairs_view* v);
+
+/* ===================================================================================================================
+ * Quasi-Newton KKT operator of the last L-BFGS direction: product, kept-state solve, backward error, refinement.
+ *
+ * pyipm_lbfgs_direction (include/pyipm_lbfgs.h) solves, through the normal equations G = J'J/zeta + diag(0, 1/Sigma),
+ *
+ *   K dz = g ,   K = [ B_k   0      J        ]     B_k = zeta I - W inv(M) W',  W = [zeta S, Y],  M = [[zeta SS, L], [L', -D]]
+ *                    [ 0     Sigma  [0 | -I] ]     (no pairs: B_k = zeta I),   Sigma = lda_i / (s + eps),   J = [Je | Ji]
+ *                    [ J'    [0;-I]  0       ]     dz = [dz_x (n) | dz_s (mi) | dz_lambda (me + mi)]  -- the RAW direction
+ *
+ * (the system of the reference's general branch, pyipm.py:1099-1148), and so pays the squared conditioning of J and the
+ * whole spread of Sigma.  These four entries take the handle of a direction and work from what that call left in it: K is
+ * applied from the staged Jacobians, Sigma and the pairs -- never from a factor, and WITHOUT the regularisation the
+ * direction may have added to the equality block (stats.regularised): a regularised factor is the preconditioner of the
+ * refinement and nothing more.  One step of refinement against K recovers the digits the normal equations lost.
+ *
+ * Vectors are N = n + 2 mi + me doubles, host or device by memkind.  flip != 0: a vector of the SOLUTION space (v of
+ * matvec, dz of solve and refine) has its multiplier rows n + mi .. N-1 negated, as the direction writes them with flip;
+ * the entries undo that on read and apply it on write.  Right-hand sides (rhs, out of matvec) are never flipped.
+ * Every entry synchronises the handle's stream before it returns.  Sums run in an order the sizes alone decide (no
+ * floating-point atomics): equal calls give equal bits.
+ *
+ * PYIPM_E_BADARG, with a message in pyipm_lbfgs_last_error: a NULL handle or vector; no direction since the handle was
+ * created or since pyipm_lbfgs_stage_jacobian / pyipm_lbfgs_set_allreduce; me + mi = 0 (the unconstrained direction is an
+ * explicit formula: there is no system); a handle with an all-reduce callback installed -- a row-sharded handle is not
+ * supported here.  A direction after any of these calls returns the bits it would have returned without them. */
+typedef struct pyipm_lbfgs_ctx pyipm_lbfgs_ctx;
+/* out = K v: one pass over J for both J'v_x and J v_lambda. */
+int pyipm_qn_matvec(pyipm_lbfgs_ctx* h, const double* v, int flip, int memkind, double* out);
+/* K~ dz = rhs from the kept state alone (K~ = K, with the direction's regularisation where it regularised): the direction's
+ * arithmetic for one new column against the kept factor of zeta G, the kept 2m solved columns and the kept 2m x 2m system --
+ * no Gram launch, no factorisation.  rhs = the g of the last direction reproduces that direction bit for bit. */
+int pyipm_qn_solve(pyipm_lbfgs_ctx* h, const double* rhs, double* dz, int flip, int memkind);
+/* Refines dz in place as a solution of K dz = rhs (rhs == NULL: the g of the last direction).
+ *   refine > 0: that many steps  r = rhs - K dz ;  dz += qn_solve(r).
+ *   refine < 0: adaptive, the rule of pyipm_newton_solve: berr = |rhs - K dz|_2 / |rhs|_2 is measured before every step; stop
+ *               converged at berr <= "refine_target", after "refine_max" steps, or when a step gained less than 4x; a step that
+ *               made berr worse or not finite is taken back and the kept iterate returned.  Both options are set through
+ *               pyipm_lbfgs_set_option (1e-14 / 8).  The host sees one synchronisation per measured berr.
+ *   refine == 0: measures berr only; dz is not written. */
+int pyipm_qn_refine(pyipm_lbfgs_ctx* h, const double* rhs, double* dz, int flip, int refine, int memkind);
+/* Outcome of the last qn_refine, the layout of pyipm_newton_solve_info: out[0] = steps taken, out[1] = berr before the first
+ * step, out[2] = berr of the kept iterate, out[3] = 1 when berr met the target (out[1..2] = -1 after refine > 0, which does
+ * not measure). */
+int pyipm_qn_info(pyipm_lbfgs_ctx* h, double out[4]);
 
 #ifdef __cplusplus
 }

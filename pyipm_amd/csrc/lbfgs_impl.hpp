@@ -4,6 +4,7 @@
 #pragma once
 #include "../../include/pyipm_lbfgs.h"
 #include "kernels_lbfgs.hpp"
+#include "kernels_qn.hpp"
 
 namespace {
 
@@ -36,6 +37,15 @@ struct LbCtx {
     bool ev_valid = false;
     double gram_flops = 0;
     bool did[8] = {};
+    // ---- the quasi-Newton KKT operator of the last direction (qn_impl.hpp; include/pyipm_newton.h, pyipm_qn_*)
+    bool qn_valid = false;              // JT, sig, V, g, M2, Hs, the factor of zeta*G, P and R columns 1.. are those of ONE direction
+    int qn_m = 0; double qn_zeta = 0.0; // ... its pair count and zeta
+    double *qx = nullptr, *qsave = nullptr, *qb = nullptr, *qr = nullptr, *qd = nullptr;   // iterate, saved iterate, rhs, residual, correction (N each)
+    double *qJv = nullptr, *qJtv = nullptr;             // J v_l (n), J'v_x (p_pad)
+    double *qrow = nullptr;                             // row partials of k_qn_jpass: (p_pad / 64) x n
+    double *qHa = nullptr, *qHb = nullptr, *qHs = nullptr, *qt = nullptr, *qinfo = nullptr, *qnrm = nullptr;
+    bool qn_two_pass = false;           // measurement hook (tools/bench_lbfgs.py --refine): k_tall_tn + k_jvec instead of k_qn_jpass
+    double qn_info[4] = {0.0, -1.0, -1.0, 0.0};
     std::string err;
 };
 
@@ -123,7 +133,21 @@ size_t lb_carve(LbCtx* c, int64_t n, int64_t me, int64_t mi, int cap, int64_t p_
     const size_t oM2 = cv.take((size_t)(2 * cap) * (2 * cap) * D);
     const size_t ov = cv.take((size_t)(2 * cap + 8) * D);
     const size_t oi = cv.take(64);
+    // work vectors of pyipm_qn_* (behind everything a direction uses: its layout is unchanged)
+    size_t oq[5];
+    for (size_t& o : oq) o = cv.take((size_t)(N + 1) * D);
+    const size_t oqJv = cv.take((size_t)(n + 1) * D);
+    const size_t oqJtv = cv.take((size_t)(p_pad + 1) * D);
+    const size_t oqrow = cv.take(p > 0 ? (size_t)(p_pad / 64) * (size_t)n * D : 256);
+    const size_t oqsm = cv.take((size_t)(4 * 2 * cap + 8) * D);             // qHa | qHb | qHs | qt | qinfo
+    const size_t oqn = cv.take((size_t)(2 * QN_NBLK + 2) * D);
     if (base) {
+        c->qx = (double*)(base + oq[0]); c->qsave = (double*)(base + oq[1]); c->qb = (double*)(base + oq[2]);
+        c->qr = (double*)(base + oq[3]); c->qd = (double*)(base + oq[4]);
+        c->qJv = (double*)(base + oqJv); c->qJtv = (double*)(base + oqJtv); c->qrow = (double*)(base + oqrow);
+        c->qHa = (double*)(base + oqsm); c->qHb = c->qHa + 2 * cap; c->qHs = c->qHb + 2 * cap; c->qt = c->qHs + 2 * cap;
+        c->qinfo = c->qt + 2 * cap;
+        c->qnrm = (double*)(base + oqn);
         c->JT = (double*)(base + oJT); c->Cs = (double*)(base + oCs); c->Gc = (double*)(base + oGc); c->ksplit = ks; c->g = (double*)(base + og); c->s = (double*)(base + os);
         c->lda = (double*)(base + ol); c->sig = (double*)(base + osg); c->dz = (double*)(base + odz);
         c->S = (double*)(base + oS); c->Y = (double*)(base + oY); c->V = (double*)(base + oV);
@@ -247,6 +271,7 @@ int pyipm_lbfgs_create(pyipm_lbfgs_ctx** out, int64_t n, int64_t me, int64_t mi,
     lb->nsplit = lb_nsplit(n, lb->p_pad, lb->rrmax);
     const size_t ws_bytes = lb_carve(nullptr, n, me, mi, max_pairs, lb->p_pad, lb->n_pad, nullptr);
     if (lb->ws.reserve(ws_bytes) != hipSuccess) return PYIPM_E_NOMEM;
+    lb->qn_two_pass = getenv("PYIPM_QN_TWO_PASS") != nullptr;
     if (getenv("PYIPM_POISON_WORKSPACE")) hipMemset(lb->ws, 0xFF, ws_bytes);   // test hook (tests/conftest.py): NaN wherever nothing is written first
     lb_carve(lb.get(), n, me, mi, max_pairs, lb->p_pad, lb->n_pad, lb->ws);
     bool ok = true;
@@ -282,6 +307,7 @@ int pyipm_lbfgs_set_allreduce(pyipm_lbfgs_ctx* h, pyipm_lbfgs_allreduce_fn fn, v
     if (!h) return PYIPM_E_BADARG;
     LB(h)->allreduce = fn; LB(h)->allreduce_user = user;
     LB(h)->gram_valid = false;
+    LB(h)->qn_valid = false;
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
@@ -299,6 +325,7 @@ int pyipm_lbfgs_stage_jacobian(pyipm_lbfgs_ctx* h, const double* Je, int64_t ld_
     if (!h) return PYIPM_E_BADARG;
     LbCtx* lb = LB(h);
     if (lb->p == 0) return PYIPM_OK;
+    lb->qn_valid = false;                    // (whatever follows: JT is no longer the Jacobian of the last direction)
     LB_HIP(hipSetDevice(lb->device));
     int rc = lb_put2d(lb, lb->JT, lb->p_pad, Je, ld_Je, lb->n, lb->me, memkind); if (rc) return rc;
     rc = lb_put2d(lb, lb->JT + lb->me, lb->p_pad, Ji, ld_Ji, lb->n, lb->mi, memkind); if (rc) return rc;
@@ -324,6 +351,7 @@ int pyipm_lbfgs_direction(pyipm_lbfgs_ctx* h, const double* g, const double* s, 
     LB_HIP(hipSetDevice(lb->device));
     hipStream_t st = lb->stream;
     const int r = 2 * m, rr = r + 1;
+    lb->qn_valid = false;
     pyipm_lbfgs_stats out; memset(&out, 0, sizeof(out));
     out.m = m; out.small_pivot_min = 1.0e308;
     for (int i = 0; i < 8; ++i) lb->did[i] = false;
@@ -463,6 +491,7 @@ int pyipm_lbfgs_direction(pyipm_lbfgs_ctx* h, const double* g, const double* s, 
     out.small_pivot_min = info;
     lb->ev_valid = true;
     lb->did[0] = p > 0;
+    lb->qn_valid = p > 0; lb->qn_m = m; lb->qn_zeta = zeta;      // what pyipm_qn_* work from (qn_impl.hpp)
     if (stats) *stats = out;
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)

@@ -5,5 +5,6 @@ using namespace pyipm::drv;
 #include "kernels_lbfgs.hpp"
 #pragma GCC visibility push(default)
 #include "lbfgs_impl.hpp"
+#include "qn_impl.hpp"                     // its quasi-Newton KKT operator (include/pyipm_newton.h, pyipm_qn_*)
 #include "pairs_impl.hpp"                  // the pair store that feeds it (include/pyipm_newton.h, "pair store")
 #pragma GCC visibility pop

@@ -282,11 +282,13 @@ class HipLbfgsBackend(object):
     1184-1246).  The "rcond <= eps" trigger on the equality block (:1108-1113, an ``eigh`` in the
     reference) is taken from the block pivots of the factorisation, as in ``HipNewtonBackend``."""
 
-    def __init__(self, n, me, mi, memory, device=None, nb=256, linear_constraints=False):
+    def __init__(self, n, me, mi, memory, device=None, nb=256, linear_constraints=False, refine=0):
         from .lbfgs import LbfgsCore
         self.core = LbfgsCore(n, me, mi, int(memory) + 1, device=device, nb=nb)   # storage grows to memory+1 (:1300)
         self.n, self.me, self.mi = n, me, mi
         self.linear_constraints = bool(linear_constraints)   # dce/dci do not depend on x: stage once, J'J is reused
+        self.refine = int(refine)              # != 0: every constrained direction is refined against the quasi-Newton KKT operator
+        self.last_refine_info = None
         self.n_calls = self.n_staged = 0
         self.pair_doubles_uploaded = 0         # S / Y entries that crossed from the host (none with a resident pair store)
 
@@ -299,7 +301,10 @@ class HipLbfgsBackend(object):
         if (self.me or self.mi) and not (self.linear_constraints and self.n_staged):
             self.core.stage_jacobian(Je, Ji)
             self.n_staged += 1
-        dz, self.last_stats = self.core.direction(g, s, lda, zeta, S, Y, SS, L, D, reg=reg, eps=eps, flip=False)
+        dz, self.last_stats = self.core.direction(g, s, lda, zeta, S, Y, SS, L, D, reg=reg, eps=eps, flip=False,
+                                                  refine=self.refine)
+        if self.refine and (self.me or self.mi):
+            self.last_refine_info = self.core.refine_info()
         if S.shape[1] and self.last_stats["small_pivot_min"] == 0.0:
             # the reference's sym_solve raises on an exactly singular system (scipy.linalg.solve, pyipm.py:18-20)
             raise np.linalg.LinAlgError("L-BFGS: the 2m x 2m system is singular (zero pivot)")
@@ -314,7 +319,7 @@ class IPM(BarrierLoop):
                  dci=None, d2ci=None, lda0=None, lambda_dev=None, s0=None, mu=0.2, nu=10.0, rho=0.1, tau=0.995,
                  eta=1.0E-4, beta=0.4, miter=20, niter=10, Xtol=None, Ktol=1.0E-4, Ftol=None, lbfgs=False,
                  lbfgs_zeta=None, float_dtype=np.float64, verbosity=1, backend=None, device=None, nb=256, refine=0,
-                 device_step=False, condensed=False, linear_constraints=False, resident_pairs=False):
+                 device_step=False, condensed=False, linear_constraints=False, resident_pairs=False, lbfgs_refine=0):
         self.x0, self.s0, self.lda0 = x0, s0, lda0
         self.x_dev, self.lambda_dev = x_dev, lambda_dev        # accepted for signature parity; unused
         self.f, self.df, self.d2f = f, df, d2f
@@ -338,6 +343,7 @@ class IPM(BarrierLoop):
         self._backend_opts = dict(device=device, nb=nb, refine=refine, device_step=device_step, condensed=condensed)
         self.linear_constraints = linear_constraints       # L-BFGS mode: Jacobians staged once, J'J reused
         self.resident_pairs = bool(resident_pairs)         # L-BFGS mode: S, Y in the library's pair store (pyipm_amd.lbfgs.PairStore)
+        self.lbfgs_refine = int(lbfgs_refine)              # L-BFGS mode: refinement of every direction (LbfgsCore.refine); 0 = none
         self._pairs = None
         self.compiled = False
         self.signal = 0
@@ -386,7 +392,7 @@ class IPM(BarrierLoop):
             if self.lbfgs:
                 self.backend = HipLbfgsBackend(self.nvar, self.neq, self.nineq, self.lbfgs,
                                                device=self._backend_opts["device"], nb=self._backend_opts["nb"],
-                                               linear_constraints=self.linear_constraints)
+                                               linear_constraints=self.linear_constraints, refine=self.lbfgs_refine)
             else:
                 self.backend = HipNewtonBackend(self.nvar, self.neq, self.nineq, **self._backend_opts)
         self.compiled = True

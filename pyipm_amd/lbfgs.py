@@ -172,8 +172,52 @@ class LbfgsCore(object):
         self._ck(self.lib.pyipm_lbfgs_stage_jacobian(self.h, self._ptr(Je), lde, self._ptr(Ji), ldi, MEM_DEVICE))
         self.torch.cuda.current_stream(self.device).synchronize()      # Je / Ji temporaries may die now
 
-    def direction(self, g, s, lda, zeta, S, Y, SS, L, D, reg=0.0, eps=float(np.finfo(np.float64).eps), flip=False):
-        """Returns (dz device tensor of length n + 2 mi + me, stats dict)."""
+    def direction(self, g, s, lda, zeta, S, Y, SS, L, D, reg=0.0, eps=float(np.finfo(np.float64).eps), flip=False,
+                  refine=0):
+        """Returns (dz device tensor of length n + 2 mi + me, stats dict).  ``refine`` != 0 (constrained problems): the
+        direction is then refined against the quasi-Newton KKT operator (``refine``); ``refine_info()`` has the outcome."""
+        dz, st = self._direction(g, s, lda, zeta, S, Y, SS, L, D, reg, eps, flip)
+        if refine and (self.me or self.mi):
+            dz, _ = self.refine(dz, refine=refine, flip=flip)
+        return dz, st
+
+    # ---- the quasi-Newton KKT operator K of the last direction (include/pyipm_newton.h, pyipm_qn_*): K dz = g
+    def _stream(self):
+        torch = self.torch
+        self._ck(self.lib.pyipm_lbfgs_set_stream(self.h, c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+
+    def matvec(self, v, flip=False):
+        """K v (device tensor of N); ``flip``: v has its multiplier rows negated."""
+        v = self._dev(v, (self.N,))
+        out = self.torch.empty(self.N, dtype=self.torch.float64, device=self.device)
+        self._stream()
+        self._ck(self.lib.pyipm_qn_matvec(self.h, self._ptr(v), 1 if flip else 0, MEM_DEVICE, self._ptr(out)))
+        return out
+
+    def solve(self, rhs, flip=False):
+        """dz with K dz = rhs from the state the last direction kept (no Gram launch, no factorisation)."""
+        rhs = self._dev(rhs, (self.N,))
+        dz = self.torch.empty(self.N, dtype=self.torch.float64, device=self.device)
+        self._stream()
+        self._ck(self.lib.pyipm_qn_solve(self.h, self._ptr(rhs), self._ptr(dz), 1 if flip else 0, MEM_DEVICE))
+        return dz
+
+    def refine(self, dz, rhs=None, refine=-1, flip=False):
+        """Refines ``dz`` as a solution of K dz = rhs (None: the g of the last direction).  refine > 0: that many steps;
+        < 0: adaptive (options ``refine_target`` / ``refine_max``); 0: measures the backward error only.
+        Returns (a new device tensor, info dict)."""
+        dz = self._dev(dz, (self.N,)).clone()
+        rhs = None if rhs is None else self._dev(rhs, (self.N,))
+        self._stream()
+        self._ck(self.lib.pyipm_qn_refine(self.h, self._ptr(rhs), self._ptr(dz), 1 if flip else 0, int(refine), MEM_DEVICE))
+        return dz, self.refine_info()
+
+    def refine_info(self):
+        out = (c_double * 4)()
+        self._ck(self.lib.pyipm_qn_info(self.h, out))
+        return {"steps": int(out[0]), "berr0": out[1], "berr": out[2], "converged": bool(out[3])}
+
+    def _direction(self, g, s, lda, zeta, S, Y, SS, L, D, reg, eps, flip):
         torch = self.torch
         n, me, mi, N = self.n, self.me, self.mi, self.N
         m = 0 if S is None else int(S.shape[1])

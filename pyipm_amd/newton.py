@@ -166,6 +166,11 @@ def load_library(path: str | None = None):
         "pyipm_pairs_reset": (c_int, [c_void_p]),
         "pyipm_pairs_offer": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_int, POINTER(c_int)]),
         "pyipm_pairs_view_get": (c_int, [c_void_p, c_void_p]),
+        # quasi-Newton KKT operator of the last L-BFGS direction (qn_impl.hpp; the Python side is pyipm_amd.lbfgs.LbfgsCore)
+        "pyipm_qn_matvec": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+        "pyipm_qn_solve": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int]),
+        "pyipm_qn_refine": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int]),
+        "pyipm_qn_info": (c_int, [c_void_p, POINTER(c_double)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch

@@ -45,7 +45,7 @@ class QPDeviceIPM(BarrierLoop):
     def __init__(self, Q, c, A=None, b=None, G=None, h=None, Je=None, Ji=None, x0=None, s0=None, lda0=None,
                  mu=0.2, nu=10.0, rho=0.1, tau=0.995, eta=1.0E-4, beta=0.4, miter=20, niter=10, Xtol=None,
                  Ktol=1.0E-4, Ftol=None, verbosity=1, device=None, nb=256, refine=0, condensed=False,
-                 lbfgs=False, lbfgs_zeta=None, warm=True, resident_pairs=False):
+                 lbfgs=False, lbfgs_zeta=None, warm=True, resident_pairs=False, lbfgs_refine=0):
         import torch
         from .ipm import HipNewtonBackend
         if not torch.cuda.is_available():
@@ -83,6 +83,8 @@ class QPDeviceIPM(BarrierLoop):
         self.verbosity = verbosity
         self.lbfgs = int(lbfgs) if lbfgs else 0
         self.lbfgs_zeta = 1.0 if (lbfgs and lbfgs_zeta is None) else lbfgs_zeta
+        self.lbfgs_refine = int(lbfgs_refine)      # refinement of every L-BFGS direction (LbfgsCore.refine); 0 = none
+        self.last_refine_info = None
         if self.lbfgs:
             from .lbfgs import LbfgsCore
             if not 1 <= self.lbfgs <= 31:
@@ -458,7 +460,9 @@ class QPDeviceIPM(BarrierLoop):
         me, mi = self.neq, self.nineq
         reg = self.reg_coef * self.eta * (self.mu_host ** self.beta)
         dz, self.last_stats = self.lb.direction(g, s if mi else None, lda if (me or mi) else None, zeta,
-                                                S, Y, SS, L, D, reg=reg, eps=self.eps, flip=True)
+                                                S, Y, SS, L, D, reg=reg, eps=self.eps, flip=True, refine=self.lbfgs_refine)
+        if self.lbfgs_refine and (me or mi):
+            self.last_refine_info = self.lb.refine_info()
         return dz
 
     @staticmethod

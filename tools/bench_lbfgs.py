@@ -14,6 +14,13 @@ Prints one JSON line.
 times the OTHER half of the mode, lbfgs_update (pyipm.py:1282-1371), as one accepted offer to a FULL device-resident pair store
 (pyipm_pairs_offer, include/pyipm_newton.h) and, in the same process on the same inputs, as the torch body of
 QPDeviceIPM.lbfgs_update without the store (two torch.cat, the products through rocBLAS, two .contiguous()).
+
+    python tools/bench_lbfgs.py --refine --n 262144 --me 1024 --mi 3072 --m 8 --reps 20
+
+times what works from the state a direction keeps (pyipm_qn_*, include/pyipm_newton.h), Jacobians staged once: one direction, one
+K v, one kept-state solve, one adaptive refinement -- and, in the same process on the same inputs, K v through the two kernels
+the fused pass over J replaces (k_tall_tn with one column + k_jvec: a second handle created with PYIPM_QN_TWO_PASS set), the
+two alternating.  Kernel times come from a kernel trace of this command in a run of its own.
 """
 import argparse
 import json
@@ -115,6 +122,65 @@ def update_leg(a):
                       "update": rows}))
 
 
+def refine_leg(a):
+    import torch
+    from pyipm_amd.lbfgs import LbfgsCore
+    n, me, mi, m = a.n, a.me, a.mi, a.m
+    p, N = me + mi, n + 2 * mi + me
+    p_pad = (p + 127) // 128 * 128
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev); gen.manual_seed(0)
+    J = torch.randn((n, p), generator=gen, dtype=torch.float64, device=dev) / np.sqrt(n)
+    zeta, S, Y, SS, L, D = storage(n, m, 1, True)
+    rng = np.random.default_rng(2)
+    s = rng.uniform(0.5, 2.0, mi)
+    sig = np.exp(rng.uniform(np.log(10.0 ** -a.sigma_decades), np.log(10.0 ** a.sigma_decades), mi))   # the late-iteration spread
+    lda = np.concatenate([rng.standard_normal(me), sig * s])
+    td = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev)          # noqa: E731
+    gd, sd, ld, Sd, Yd, vd = td(rng.standard_normal(N)), td(s), td(lda), td(S), td(Y), td(rng.standard_normal(N))
+    cores = {}
+    for name, env in (("fused", None), ("two_kernels", "1")):
+        if env:
+            os.environ["PYIPM_QN_TWO_PASS"] = env
+        cores[name] = LbfgsCore(n, me, mi, max(m, 1), device=0)
+        os.environ.pop("PYIPM_QN_TWO_PASS", None)
+        cores[name].stage_jacobian(J[:, :me] if me else None, J[:, me:] if mi else None)
+    direct = lambda c: c.direction(gd, sd, ld, zeta, Sd, Yd, SS, L, D, reg=1e-12)      # noqa: E731
+    dz = {k: direct(c)[0] for k, c in cores.items()}
+    assert torch.equal(dz["fused"], dz["two_kernels"])
+    core = cores["fused"]
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    legs = {"direction_ms": lambda: direct(core), "matvec_ms": lambda: core.matvec(vd),
+            "matvec_two_kernels_ms": lambda: cores["two_kernels"].matvec(vd), "solve_ms": lambda: core.solve(gd),
+            "refine_adaptive_ms": lambda: core.refine(dz["fused"], refine=-1)}
+    rec = {k: [] for k in legs}
+    for it in range(a.reps + 2):                     # two warm-up rounds; the legs alternate inside a round
+        for k, fn in legs.items():
+            ms, out = wall(fn)
+            if it >= 2:
+                rec[k].append(ms)
+    kv = {k: c.matvec(vd) for k, c in cores.items()}
+    _, info = core.refine(dz["fused"], refine=-1)
+    launches = core.last_timings()["gram_launches"]
+    jbytes = n * p_pad * 8
+    med = {k: float(np.median(v)) for k, v in rec.items()}
+    print(json.dumps({"workload": "quasi-Newton KKT operator of an L-BFGS direction (pyipm_qn_*), QP-shaped synthetic, Jacobians staged once",
+                      "n": n, "me": me, "mi": mi, "m": m, "sigma_decades": a.sigma_decades, "dtype": "f64",
+                      "timing": "wall, device synchronised before and after, median of %d, legs alternating" % a.reps,
+                      "ms": med, "ms_all": rec, "refine_info": info, "gram_launches": launches,
+                      "matvec_fused_vs_two_kernels_rel_diff": float((kv["fused"] - kv["two_kernels"]).norm() / kv["fused"].norm()),
+                      "jacobian_bytes_padded": jbytes, "hbm_peak_Bps": HBM_PEAK_BPS,
+                      "matvec_call_fraction_of_one_read_floor": jbytes / HBM_PEAK_BPS / (med["matvec_ms"] * 1e-3),
+                      "matvec_two_kernels_call_fraction_of_two_read_floor": 2 * jbytes / HBM_PEAK_BPS / (med["matvec_two_kernels_ms"] * 1e-3)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=262144)
@@ -125,9 +191,13 @@ def main():
     ap.add_argument("--cpu-n", type=int, default=0, help="ignored (kept for old command lines): the CPU leg is bench.py --extras")
     ap.add_argument("--update", action="store_true", help="time lbfgs_update (pair store against torch storage) instead of the direction")
     ap.add_argument("--memories", default="8,31", help="--update: memory depths, comma-separated")
+    ap.add_argument("--refine", action="store_true", help="time K v, the kept-state solve and the refinement of a direction (pyipm_qn_*)")
+    ap.add_argument("--sigma-decades", type=float, default=6.0, help="--refine: Sigma spread, decades either side of 1")
     a = ap.parse_args()
     if a.update:
         return update_leg(a)
+    if a.refine:
+        return refine_leg(a)
     import torch
     from pyipm_amd.lbfgs import LbfgsCore
     n, me, mi, m = a.n, a.me, a.mi, a.m
