@@ -72,6 +72,9 @@ size_t pyipm_lbfgs_workspace_bytes(int64_t n, int64_t me, int64_t mi, int max_pa
 int pyipm_lbfgs_stage_jacobian(pyipm_lbfgs_ctx* h, const double* Je, int64_t ld_Je, const double* Ji,
                                int64_t ld_Ji, int memkind);
 
+/* Restaging only the columns of [Je | Ji] that changed, after one full staging: pyipm_lbfgs_stage_jacobian_columns, declared
+ * with the later additions to this handle (pyipm_qn_*) in pyipm_newton.h, section "partial restaging". */
+
 /* One search direction.  g: n + 2 mi + me (the NEGATED KKT residual, :1637, 1705-1710); s: mi; lda: me + mi;
  * S, Y: n x m row-major (ld_S, ld_Y >= m) — all flagged by memkind.  SS, L, D: m x m row-major, HOST memory
  * always (they are O(m^2) bookkeeping of lbfgs_update).  reg = reg_coef * eta * mu**beta (:1113).
@@ -84,8 +87,9 @@ int pyipm_lbfgs_direction(pyipm_lbfgs_ctx* h, const double* g, const double* s, 
 
 /* ms of the last direction call (HIP events on the handle's stream):
  * out[0] total, [1] Gram launch, [2] factorisation(s) of G, [3] the 2m+1 substitutions,
- * [4] the two passes over J, [5] small system + combination, [6] flop count of a Gram launch,
- * [7] Gram launches since create ([1] is ~0 for a direction that reused J'J). */
+ * [4] the two passes over J, [5] small system + combination, [6] flop count of the last Gram launch as executed
+ * (a partial launch after pyipm_lbfgs_stage_jacobian_columns: 2 * 128 * 128 * n_pad per recomputed tile),
+ * [7] Gram launches since create, partial ones included ([1] is ~0 for a direction that reused J'J). */
 int pyipm_lbfgs_last_timings(pyipm_lbfgs_ctx* h, double out[8]);
 
 /* Row-sharded use (one process per GPU; the direction shards by rows of J with three real exchanges).

@@ -763,7 +763,7 @@ int pyipm_pairs_view_get(pyipm_pairs* p, pyipm_pairs_view* v);
  * floating-point atomics): equal calls give equal bits.
  *
  * PYIPM_E_BADARG, with a message in pyipm_lbfgs_last_error: a NULL handle or vector; no direction since the handle was
- * created or since pyipm_lbfgs_stage_jacobian / pyipm_lbfgs_set_allreduce; me + mi = 0 (the unconstrained direction is an
+ * created or since pyipm_lbfgs_stage_jacobian / _stage_jacobian_columns / pyipm_lbfgs_set_allreduce; me + mi = 0 (the unconstrained direction is an
  * explicit formula: there is no system); a handle with an all-reduce callback installed -- a row-sharded handle is not
  * supported here.  A direction after any of these calls returns the bits it would have returned without them. */
 typedef struct pyipm_lbfgs_ctx pyipm_lbfgs_ctx;
@@ -785,6 +785,23 @@ int pyipm_qn_refine(pyipm_lbfgs_ctx* h, const double* rhs, double* dz, int flip,
  * step, out[2] = berr of the kept iterate, out[3] = 1 when berr met the target (out[1..2] = -1 after refine > 0, which does
  * not measure). */
 int pyipm_qn_info(pyipm_lbfgs_ctx* h, double out[4]);
+
+/* ---- L-BFGS direction: partial restaging of the Jacobians (the handle and its conventions: pyipm_lbfgs.h).
+ * Restage columns c0 .. c0 + count - 1 of J = [Je | Ji] alone (global column indices: 0 .. me - 1 is Je, me .. me + mi - 1
+ * is Ji) from Jc, n x count row-major with ld >= count: for problems where only some constraints are nonlinear.  A strided
+ * 2-D copy on the handle's stream like pyipm_lbfgs_stage_jacobian's; the padding columns stay zero.  The handle keeps the set of touched
+ * tile indices c / 128 (calls accumulate until the next direction), and that direction computes again only the 128 x 128
+ * lower-triangle tiles (i, j) of J'J with i or j in the set -- with the K partition, the tile arithmetic and the summation
+ * order of the full launch, so the direction is bit for bit the one a full pyipm_lbfgs_stage_jacobian of the same J gives.
+ * Tiles outside the set are neither read nor written; when every tile index is in it the full launch runs.
+ * A full pyipm_lbfgs_stage_jacobian must have come first.  PYIPM_E_BADARG, with the staged J and the cached J'J untouched
+ * and the handle usable, for: no full staging yet, c0 < 0, count < 0, c0 + count > me + mi, ld < count, Jc == NULL with
+ * count > 0, a bad memkind.  count == 0 returns PYIPM_OK and changes nothing (the only accepted form when me = mi = 0).
+ * Like a full staging the call ends the validity of the state pyipm_qn_* work from, until the next direction.
+ * Row-sharded handles (pyipm_lbfgs_set_allreduce) accept the call and copy the columns, but the next direction then
+ * computes and exchanges the whole of J'J: correct, nothing saved. */
+int pyipm_lbfgs_stage_jacobian_columns(pyipm_lbfgs_ctx* h, int64_t c0, int64_t count, const double* Jc, int64_t ld,
+                                       int memkind);
 
 #ifdef __cplusplus
 }

@@ -84,6 +84,8 @@ struct UpdLaunch {
                                  // (128 wide; the sub-panels of a wide panel, factor_block)
     int* used_bn = nullptr;      // out: the tile width of the instance that ran (64 / 128 / 256)
     int prio = -1;               // >= 0: wave priority flag of the launch whatever `bulk` says
+    const unsigned* tiles = nullptr;   // the caller's own tile list on the device (row tile | column tile << 16, 0xffffffff = none,
+    unsigned ntiles = 0;               // ntiles a multiple of 8): only these 128 x 128 tiles, whole column range (first_lp = sub0 = 0)
 };
 int launch_update128(Ctx* ctx, hipStream_t stream, const double* Lop, int64_t ldl, const double* Wop, int K,
                      int64_t row_begin, int64_t first_lp, int64_t n_lp, const UpdLaunch& o = {});

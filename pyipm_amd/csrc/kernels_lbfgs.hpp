@@ -335,6 +335,38 @@ __global__ __launch_bounds__(256) void k_lb_ksum(double* __restrict__ A, const d
     A[i] = t;
 }
 
+// Partial Gram launch (columns of J restaged, gram_tiles.hpp): the same two steps for the listed 128 x 128 tiles alone.
+// tiles[b] = row tile | column tile << 16, 0xffffffff = no tile; ld = p_pad; one workgroup per tile, a thread on two
+// rows of every fourth column (16-byte accesses, a wave on one contiguous 1 KB column).
+// Zero the listed tiles of the ns matrices C + y * stride: grid (entries, ns).
+__global__ __launch_bounds__(256) void k_lb_tiles_clear(double* __restrict__ C, int64_t ld, int64_t stride,
+                                                        const unsigned* __restrict__ tiles)
+{
+    const unsigned code = tiles[blockIdx.x];
+    if (code == 0xffffffffu) return;
+    double* t = C + (int64_t)blockIdx.y * stride + (int64_t)(code & 0xffffu) * 128 + (int64_t)(code >> 16) * 128 * ld;
+    const int r = (threadIdx.x & 63) * 2;
+    for (int j = threadIdx.x >> 6; j < 128; j += 4) *reinterpret_cast<double2*>(t + r + (int64_t)j * ld) = make_double2(0.0, 0.0);
+}
+
+// A = sum of the split-K partial matrices on the listed tiles, every entry summed as k_lb_ksum sums it: grid (entries).
+__global__ __launch_bounds__(256) void k_lb_tiles_ksum(double* __restrict__ A, const double* __restrict__ Cs, int64_t ld,
+                                                       int64_t count, int ns, const unsigned* __restrict__ tiles)
+{
+    const unsigned code = tiles[blockIdx.x];
+    if (code == 0xffffffffu) return;
+    const int64_t base = (int64_t)(code & 0xffffu) * 128 + (int64_t)(code >> 16) * 128 * ld + (threadIdx.x & 63) * 2;
+    for (int j = threadIdx.x >> 6; j < 128; j += 4) {
+        const int64_t i = base + (int64_t)j * ld;
+        double t0 = 0.0, t1 = 0.0;
+        for (int sp = 0; sp < ns; ++sp) {
+            const double2 v = *reinterpret_cast<const double2*>(Cs + (int64_t)sp * count + i);
+            t0 += v.x; t1 += v.y;
+        }
+        *reinterpret_cast<double2*>(A + i) = make_double2(t0, t1);
+    }
+}
+
 // Diagonal of zeta*G on top of the Gram launch; identity on the padding.
 __global__ __launch_bounds__(256) void k_lb_gram_diag(double* __restrict__ A, int64_t ld, int64_t p, int64_t me,
                                                       const double* __restrict__ sig, double zeta, double reg_e)

@@ -4,6 +4,7 @@
 #pragma once
 #include "../../include/pyipm_lbfgs.h"
 #include "kernels_lbfgs.hpp"
+#include "gram_tiles.hpp"
 #include "kernels_qn.hpp"
 
 namespace {
@@ -21,6 +22,9 @@ struct LbCtx {
     double *Cs = nullptr;               // ksplit partial Gram matrices, p_pad^2 each (ksplit > 1)
     double *Gc = nullptr;               // J'J of the staged Jacobians (p_pad^2): reused until they are staged again
     bool gram_valid = false;
+    GramTiles dirty;                    // tile indices whose columns were restaged since Gc was computed (stage_jacobian_columns)
+    std::vector<unsigned> tl_host;      // the partial Gram launch's tile list: host copy (kept until the direction has synchronised)
+    unsigned* tl_dev = nullptr;         // ... and on the device
     double *g = nullptr, *s = nullptr, *lda = nullptr, *sig = nullptr, *dz = nullptr;
     double *S = nullptr, *Y = nullptr;  // staging of host S, Y (n x cap, row-major)
     double *V = nullptr;                // n x rrmax row-major: [g_x | S-part | Y-part]
@@ -141,7 +145,9 @@ size_t lb_carve(LbCtx* c, int64_t n, int64_t me, int64_t mi, int cap, int64_t p_
     const size_t oqrow = cv.take(p > 0 ? (size_t)(p_pad / 64) * (size_t)n * D : 256);
     const size_t oqsm = cv.take((size_t)(4 * 2 * cap + 8) * D);             // qHa | qHb | qHs | qt | qinfo
     const size_t oqn = cv.take((size_t)(2 * QN_NBLK + 2) * D);
+    const size_t otl = cv.take(p > 0 ? (size_t)GramTiles::list_capacity(p_pad) * sizeof(unsigned) : 256);
     if (base) {
+        c->tl_dev = (unsigned*)(base + otl);
         c->qx = (double*)(base + oq[0]); c->qsave = (double*)(base + oq[1]); c->qb = (double*)(base + oq[2]);
         c->qr = (double*)(base + oq[3]); c->qd = (double*)(base + oq[4]);
         c->qJv = (double*)(base + oqJv); c->qJtv = (double*)(base + oqJtv); c->qrow = (double*)(base + oqrow);
@@ -187,6 +193,7 @@ int lb_factor_G(LbCtx* lb, double zeta, double reg_e, pyipm_factor_stats* st, bo
     const int64_t cnt = g.Npad * g.Npad;
     int rc;
     if (timed) LB_HIP(hipEventRecord(lb->ev[1], lb->stream));
+    if (lb->gram_valid && lb->dirty.all()) lb->gram_valid = false;      // every column tile restaged: the full launch
     if (!lb->gram_valid) {
         // J'J of the staged Jacobians -> Gc.  It depends on neither zeta nor Sigma (the factor is of zeta*G), so it is
         // computed once per stage_jacobian: every direction for linear constraints, and the regularised retry, reuse it.
@@ -213,6 +220,34 @@ int lb_factor_G(LbCtx* lb, double zeta, double reg_e, pyipm_factor_stats* st, bo
         }
         rc = lb_allreduce(lb, lb->Gc, cnt); if (rc) return rc;         // row-sharded: J'J = sum of the ranks' J_r'J_r
         lb->gram_valid = true;
+        lb->dirty.clear();
+        lb->gram_flops = 2.0 * (double)lb->n_pad * 0.5 * (double)g.Npad * (double)(g.Npad + 128);
+        lb->n_gram++;
+    } else if (lb->dirty.any()) {
+        // Columns restaged since (stage_jacobian_columns): the lower-triangle tiles with a dirty row or column index are
+        // computed again -- the K partition, the tile arithmetic and the order of the sum over the splits of the launch above --
+        // and nothing else of Cs or Gc is read or written.  (Never on a row-sharded handle: restaging clears gram_valid there.)
+        lb->gram_valid = false;                  // (until every step below is enqueued: a failed one leaves Gc half new)
+        lb->dirty.list(lb->tl_host);
+        const unsigned nent = (unsigned)lb->tl_host.size();
+        LB_HIP(hipMemcpyAsync(lb->tl_dev, lb->tl_host.data(), (size_t)nent * sizeof(unsigned), hipMemcpyHostToDevice, lb->stream));
+        double* keep = gc->A;
+        double* acc = ks > 1 ? lb->Cs : lb->Gc;
+        hipLaunchKernelGGL(k_lb_tiles_clear, dim3(nent, (unsigned)ks), dim3(256), 0, lb->stream, acc, g.Npad, cnt, lb->tl_dev);
+        LB_KCHECK();
+        gc->A = acc;
+        rc = launch_update128(gc, lb->stream, lb->JT, lb->p_pad, lb->JT, (int)(lb->n_pad / ks), 0, 0,
+                              (g.Npad + g.nb - 1) / g.nb,
+                              {.ldw = lb->p_pad, .ksplit = ks, .ks_cstride = ks > 1 ? cnt : 0, .tiles = lb->tl_dev, .ntiles = nent});
+        gc->A = keep;
+        if (rc) { lb->err = gc->err; return rc; }
+        if (ks > 1) {
+            hipLaunchKernelGGL(k_lb_tiles_ksum, dim3(nent), dim3(256), 0, lb->stream, lb->Gc, lb->Cs, g.Npad, cnt, ks, lb->tl_dev);
+            LB_KCHECK();
+        }
+        lb->gram_flops = 2.0 * 128.0 * 128.0 * (double)lb->n_pad * (double)lb->dirty.tile_count();
+        lb->gram_valid = true;
+        lb->dirty.clear();
         lb->n_gram++;
     }
     LB_HIP(hipMemcpyAsync(gc->A, lb->Gc, (size_t)cnt * sizeof(double), hipMemcpyDeviceToDevice, lb->stream));
@@ -267,6 +302,7 @@ int pyipm_lbfgs_create(pyipm_lbfgs_ctx** out, int64_t n, int64_t me, int64_t mi,
         if (rc) return rc;
         lb->gcx.reset(reinterpret_cast<Ctx*>(gh));
         lb->p_pad = lb->gcx->g.Npad;
+        lb->dirty.init(lb->p_pad);
     }
     lb->nsplit = lb_nsplit(n, lb->p_pad, lb->rrmax);
     const size_t ws_bytes = lb_carve(nullptr, n, me, mi, max_pairs, lb->p_pad, lb->n_pad, nullptr);
@@ -332,6 +368,26 @@ int pyipm_lbfgs_stage_jacobian(pyipm_lbfgs_ctx* h, const double* Je, int64_t ld_
     if (memkind == PYIPM_MEM_HOST) LB_HIP(hipStreamSynchronize(lb->stream));     // host memory is not retained
     lb->have_J = true;
     lb->gram_valid = false;
+    lb->dirty.clear();
+    return PYIPM_OK;
+} PYIPM_CATCH_H(h)
+
+int pyipm_lbfgs_stage_jacobian_columns(pyipm_lbfgs_ctx* h, int64_t c0, int64_t count, const double* Jc, int64_t ld,
+                                       int memkind) try {
+    if (!h) return PYIPM_E_BADARG;
+    LbCtx* lb = LB(h);
+    // every refusal comes before anything is touched: the staged J and the cached J'J stay what they were
+    if (c0 < 0 || count < 0 || c0 > lb->p || count > lb->p - c0) { lb->err = "stage_jacobian_columns: columns outside [0, me + mi)"; return PYIPM_E_BADARG; }
+    if (memkind != PYIPM_MEM_HOST && memkind != PYIPM_MEM_DEVICE) { lb->err = "stage_jacobian_columns: bad memkind"; return PYIPM_E_BADARG; }
+    if (count == 0) return PYIPM_OK;
+    if (!lb->have_J) { lb->err = "stage_jacobian_columns: stage the whole Jacobians first"; return PYIPM_E_BADARG; }
+    if (!Jc || ld < count) { lb->err = "stage_jacobian_columns: bad block pointer / leading dimension"; return PYIPM_E_BADARG; }
+    lb->qn_valid = false;                    // (whatever follows: JT is no longer the Jacobian of the last direction)
+    lb->dirty.mark(c0, count);
+    if (lb->allreduce) lb->gram_valid = false;      // row-sharded: the next direction computes and exchanges the whole of J'J
+    LB_HIP(hipSetDevice(lb->device));
+    int rc = lb_put2d(lb, lb->JT + c0, lb->p_pad, Jc, ld, lb->n, count, memkind); if (rc) return rc;
+    if (memkind == PYIPM_MEM_HOST) LB_HIP(hipStreamSynchronize(lb->stream));     // host memory is not retained
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)
 
@@ -426,7 +482,6 @@ int pyipm_lbfgs_direction(pyipm_lbfgs_ctx* h, const double* g, const double* s, 
         }
         LB_HIP(hipEventRecord(lb->ev[3], st));
         out.n_neg = fs.n_neg; out.n_zero = fs.n_zero; out.d_min = fs.d_min; out.d_max = fs.d_max;
-        lb->gram_flops = 2.0 * (double)lb->n_pad * 0.5 * (double)ldp * (double)(ldp + 128);
         // ---- pass 1 over J:  P = J' V
         {
             const int64_t kper = (n + lb->nsplit - 1) / lb->nsplit;

@@ -328,6 +328,17 @@ int launch_update128(Ctx* ctx, hipStream_t stream, const double* Lop, int64_t ld
     if (o.src_c0 >= 0) active_ranges(ctx, o.src_c0, o.src_c0 + K, &u.a0, &u.a1, &u.b0, &u.b1);
     else { u.a0 = 0; u.a1 = g.Npad; u.b0 = 0; u.b1 = 0; }
     const int use_waves = waves ? waves : BULK_WAVES;
+    if (o.tiles) {
+        // The partial Gram launch (lbfgs_impl.hpp): the tiles the caller lists, on the bulk 128 x 128 instance.  Whatever instance
+        // the full launch took, every entry receives its products k ascending in MFMA groups of 4: the same bits.
+        if (o.ntiles == 0) return 0;
+        if (o.ntiles % 8 != 0 || first_lp != 0 || o.sub0 != 0 || g.world != 1) { ctx->err = "bad caller tile list"; return PYIPM_E_BADARG; }
+        u.tiles = o.tiles;
+        if (ksplit > 1) u.ks_cstride = o.ks_cstride;
+        hipLaunchKernelGGL((k_update<128, true, 8>), dim3(o.ntiles, (unsigned)ksplit), dim3(512), 0, stream, ctx->A, g.Npad, Lop, ldl, Wop, ldw, K, u);
+        PYIPM_KCHECK();
+        return 0;
+    }
     // (col_end % 256: Npad is a multiple of 128 only -- a 256-wide tile at the last 128 columns would read and rewrite 128
     // columns past the storage, i.e. the first W slot, and W rows past Npad; such shapes keep 128 x 128 tiles)
     if (bulk && ctx->bulk_bn == 256 && use_waves == 8 && waves == 0 && ksplit == 1 && g.nb % 256 == 0 &&

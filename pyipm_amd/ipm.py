@@ -286,10 +286,23 @@ class HipLbfgsBackend(object):
         from .lbfgs import LbfgsCore
         self.core = LbfgsCore(n, me, mi, int(memory) + 1, device=device, nb=nb)   # storage grows to memory+1 (:1300)
         self.n, self.me, self.mi = n, me, mi
-        self.linear_constraints = bool(linear_constraints)   # dce/dci do not depend on x: stage once, J'J is reused
+        # linear_constraints: True = dce/dci do not depend on x (stage once, J'J is reused), False = they all may, or a boolean
+        # mask over the me + mi columns of [Je | Ji], True where a column does not: after the first direction only the runs of
+        # False columns are staged again, and only the tiles of J'J they reach are recomputed
+        self.column_runs = None                # [(c0, c1), ...]: the maximal runs of columns that depend on x (a mixed mask only)
+        if np.ndim(linear_constraints) > 0:
+            mask = np.asarray(linear_constraints, dtype=bool).reshape(-1)
+            if mask.size != me + mi:
+                raise ValueError("linear_constraints: a mask needs me + mi = %d entries, got %d" % (me + mi, mask.size))
+            linear_constraints = bool(mask.all())
+            if not linear_constraints and mask.any():
+                edges = np.flatnonzero(np.diff(np.concatenate([[True], mask, [True]]).astype(np.int8)))
+                self.column_runs = [(int(a), int(b)) for a, b in zip(edges[0::2], edges[1::2])]
+        self.linear_constraints = bool(linear_constraints)
         self.refine = int(refine)              # != 0: every constrained direction is refined against the quasi-Newton KKT operator
         self.last_refine_info = None
         self.n_calls = self.n_staged = 0
+        self.n_cols_staged = 0                 # columns of [Je | Ji] copied to the device so far (a full staging: me + mi)
         self.pair_doubles_uploaded = 0         # S / Y entries that crossed from the host (none with a resident pair store)
 
     def shape(self):
@@ -298,9 +311,16 @@ class HipLbfgsBackend(object):
     def lbfgs_direction(self, Je, Ji, s, lda, g, zeta, S, Y, SS, L, D, reg, eps):
         self.n_calls += 1
         self.pair_doubles_uploaded += sum(int(a.size) for a in (S, Y) if isinstance(a, np.ndarray))   # device tensors pass through
-        if (self.me or self.mi) and not (self.linear_constraints and self.n_staged):
+        if (self.me or self.mi) and self.n_staged and self.column_runs is not None:
+            me = self.me
+            for c0, c1 in self.column_runs:
+                parts = ([Je[:, c0:min(c1, me)]] if c0 < me else []) + ([Ji[:, max(c0, me) - me:c1 - me]] if c1 > me else [])
+                self.core.stage_jacobian_columns(c0, parts[0] if len(parts) == 1 else np.concatenate(parts, axis=1))
+                self.n_cols_staged += c1 - c0
+        elif (self.me or self.mi) and not (self.linear_constraints and self.n_staged):
             self.core.stage_jacobian(Je, Ji)
             self.n_staged += 1
+            self.n_cols_staged += self.me + self.mi
         dz, self.last_stats = self.core.direction(g, s, lda, zeta, S, Y, SS, L, D, reg=reg, eps=eps, flip=False,
                                                   refine=self.refine)
         if self.refine and (self.me or self.mi):
@@ -341,7 +361,8 @@ class IPM(BarrierLoop):
         self.backend = backend
         self._own_backend = backend is None
         self._backend_opts = dict(device=device, nb=nb, refine=refine, device_step=device_step, condensed=condensed)
-        self.linear_constraints = linear_constraints       # L-BFGS mode: Jacobians staged once, J'J reused
+        self.linear_constraints = linear_constraints       # L-BFGS mode: Jacobians staged once, J'J reused; or a boolean mask over
+                                                           # the me + mi columns of [Je | Ji] (HipLbfgsBackend): True = constant
         self.resident_pairs = bool(resident_pairs)         # L-BFGS mode: S, Y in the library's pair store (pyipm_amd.lbfgs.PairStore)
         self.lbfgs_refine = int(lbfgs_refine)              # L-BFGS mode: refinement of every direction (LbfgsCore.refine); 0 = none
         self._pairs = None

@@ -6,7 +6,8 @@ same conventions as ``pyipm_amd.newton``; PyTorch owns tensors and the stream, e
 No CPU fallback: without the library or a GPU the constructor raises.
 
 ``PairStore`` is the storage that feeds it: ``lbfgs_init`` / ``lbfgs_update`` (pyipm.py:993-1005, 1282-1371) behind the
-``pyipm_pairs_*`` entry points, which ``include/pyipm_newton.h`` declares and ``pyipm_amd.newton`` binds.
+``pyipm_pairs_*`` entry points, which ``include/pyipm_newton.h`` declares and ``pyipm_amd.newton`` binds, as they do the
+later additions to the direction's own handle (``pyipm_qn_*``, ``pyipm_lbfgs_stage_jacobian_columns``).
 """
 from __future__ import annotations
 
@@ -171,6 +172,15 @@ class LbfgsCore(object):
         Ji, ldi = self._rows(Ji if mi else None, (n, mi))
         self._ck(self.lib.pyipm_lbfgs_stage_jacobian(self.h, self._ptr(Je), lde, self._ptr(Ji), ldi, MEM_DEVICE))
         self.torch.cuda.current_stream(self.device).synchronize()      # Je / Ji temporaries may die now
+
+    def stage_jacobian_columns(self, c0, Jc):
+        """Jc (n, count), a NumPy array or a device tensor, replaces columns c0 .. c0 + count - 1 of [Je | Ji] (global column
+        indices); the next direction recomputes only the 128 x 128 tiles of J'J those columns reach.  After a full
+        ``stage_jacobian`` only."""
+        count = int(Jc.shape[1])
+        Jd, ld = self._rows(Jc if count else None, (self.n, count))
+        self._ck(self.lib.pyipm_lbfgs_stage_jacobian_columns(self.h, int(c0), count, self._ptr(Jd), ld, MEM_DEVICE))
+        self.torch.cuda.current_stream(self.device).synchronize()      # a temporary of Jc may die now
 
     def direction(self, g, s, lda, zeta, S, Y, SS, L, D, reg=0.0, eps=float(np.finfo(np.float64).eps), flip=False,
                   refine=0):

@@ -21,6 +21,13 @@ times what works from the state a direction keeps (pyipm_qn_*, include/pyipm_new
 K v, one kept-state solve, one adaptive refinement -- and, in the same process on the same inputs, K v through the two kernels
 the fused pass over J replaces (k_tall_tn with one column + k_jvec: a second handle created with PYIPM_QN_TWO_PASS set), the
 two alternating.  Kernel times come from a kernel trace of this command in a run of its own.
+
+    python tools/bench_lbfgs.py --columns --n 262144 --me 1024 --mi 3072 --m 8 --reps 20
+
+times one direction after restaging 128, 512 and p/2 columns of [Je | Ji] (pyipm_lbfgs_stage_jacobian_columns; tile-aligned and
+unaligned first columns, 128 columns once in Je and once in Ji), beside a direction after a full stage_jacobian, one that reuses
+J'J and one after restaging every column; per leg the restaging copy, the direction, its Gram launch, the tiles it computed and
+the launch's flop count.
 """
 import argparse
 import json
@@ -181,6 +188,81 @@ def refine_leg(a):
                       "matvec_two_kernels_call_fraction_of_two_read_floor": 2 * jbytes / HBM_PEAK_BPS / (med["matvec_two_kernels_ms"] * 1e-3)}))
 
 
+def columns_leg(a):
+    """One direction after restaging a run of columns (pyipm_lbfgs_stage_jacobian_columns), beside one after a full
+    stage_jacobian (the yardstick: that path is the one every earlier commit has) and one that reuses J'J."""
+    import torch
+    from pyipm_amd.lbfgs import LbfgsCore
+    n, me, mi, m = a.n, a.me, a.mi, a.m
+    p, N = me + mi, n + 2 * mi + me
+    p_pad = (p + 127) // 128 * 128
+    nt = p_pad // 128
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev); gen.manual_seed(0)
+    J = torch.randn((n, p), generator=gen, dtype=torch.float64, device=dev) / np.sqrt(n)
+    zeta, S, Y, SS, L, D = storage(n, m, 1, True)
+    rng = np.random.default_rng(2)
+    s = rng.uniform(0.5, 2.0, mi)
+    lda = np.concatenate([rng.standard_normal(me), rng.uniform(0.5, 2.0, mi)])
+    td = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev)          # noqa: E731
+    gd, sd, ld, Sd, Yd = td(rng.standard_normal(N)), td(s), td(lda), td(S), td(Y)
+    core = LbfgsCore(n, me, mi, max(m, 1), device=0)
+    full = lambda: core.stage_jacobian(J[:, :me] if me else None, J[:, me:] if mi else None)      # noqa: E731
+    full()
+    half = p_pad // 2
+    # (name, c0, count): c0 = None -> a full stage_jacobian, count = 0 -> nothing staged.  The sizes are for p = 4096, me = 1024.
+    legs = [("full_stage", None, p), ("reuse", 0, 0),
+            ("c128_aligned_Je", 128, 128), ("c128_aligned_Ji", (me + 127) // 128 * 128 + 128, 128), ("c128_unaligned", 200, 128),
+            ("c512_aligned", 1024, 512), ("c512_unaligned", 1100, 512),
+            ("c%d_aligned" % half, 1024, half), ("c%d_unaligned" % half, 1100, half),
+            ("all_columns", 0, p)]
+    legs = [g for g in legs if g[1] is None or g[1] + g[2] <= p]
+
+    def dirty_tiles(c0, count):
+        if c0 is None:
+            return nt * (nt + 1) // 2
+        if count == 0:
+            return 0
+        clean = nt - ((c0 + count - 1) // 128 - c0 // 128 + 1)
+        return nt * (nt + 1) // 2 - clean * (clean + 1) // 2
+
+    rec = {g[0]: [] for g in legs}
+    for it in range(a.reps + 2):                     # two warm-up rounds; the legs alternate inside a round
+        for name, c0, count in legs:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if c0 is None:
+                full()
+            elif count:
+                core.stage_jacobian_columns(c0, J[:, c0:c0 + count])         # a row-strided view: copied as it is
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            core.direction(gd, sd, ld, zeta, Sd, Yd, SS, L, D, reg=1e-12)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            if it >= 2:
+                tm = core.last_timings()
+                tm["stage_ms"], tm["wall_ms"] = (t1 - t0) * 1e3, (t2 - t1) * 1e3
+                rec[name].append(tm)
+    out = []
+    for name, c0, count in legs:
+        r = rec[name]
+        med = {k: float(np.median([x[k] for x in r])) for k in ("stage_ms", "wall_ms", "total_ms", "gram_ms", "factor_ms")}
+        launched = name != "reuse"
+        med.update(leg=name, c0=c0, columns=count, dirty_tiles=dirty_tiles(c0, count), tiles=nt * (nt + 1) // 2,
+                   gram_flops=r[-1]["gram_flops"] if launched else 0.0,
+                   gram_tflops=r[-1]["gram_flops"] / (med["gram_ms"] * 1e-3) / 1e12 if launched and med["gram_ms"] > 0 else None,
+                   wall_ms_all=[x["wall_ms"] for x in r], gram_ms_all=[x["gram_ms"] for x in r])
+        if launched:
+            assert r[-1]["gram_flops"] == 2.0 * 128 * 128 * ((n + 8191) // 8192 * 8192) * med["dirty_tiles"], name
+        out.append(med)
+    print(json.dumps({"workload": "L-BFGS direction after a partial restaging of the Jacobians, QP-shaped synthetic", "n": n, "me": me,
+                      "mi": mi, "m": m, "dtype": "f64", "jacobian_bytes_padded": n * p_pad * 8, "hbm_peak_Bps": HBM_PEAK_BPS,
+                      "timing": "wall, device synchronised before and after, median of %d, legs alternating; gram_ms from the "
+                                "library's events" % a.reps,
+                      "gram_launches": core.last_timings()["gram_launches"], "legs": out}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=262144)
@@ -193,7 +275,10 @@ def main():
     ap.add_argument("--memories", default="8,31", help="--update: memory depths, comma-separated")
     ap.add_argument("--refine", action="store_true", help="time K v, the kept-state solve and the refinement of a direction (pyipm_qn_*)")
     ap.add_argument("--sigma-decades", type=float, default=6.0, help="--refine: Sigma spread, decades either side of 1")
+    ap.add_argument("--columns", action="store_true", help="time a direction after restaging 128, 512 and p/2 columns (stage_jacobian_columns)")
     a = ap.parse_args()
+    if a.columns:
+        return columns_leg(a)
     if a.update:
         return update_leg(a)
     if a.refine:
