@@ -803,6 +803,39 @@ int pyipm_qn_info(pyipm_lbfgs_ctx* h, double out[4]);
 int pyipm_lbfgs_stage_jacobian_columns(pyipm_lbfgs_ctx* h, int64_t c0, int64_t count, const double* Jc, int64_t ld,
                                        int memkind);
 
+/* ---- The quasi-Newton KKT operator for k columns per call: what pyipm_newton_kkt_matvec_many and pyipm_newton_solve_many
+ * are to the exact-Hessian handle.  Column j of a block sits at base + j*ld, every ld >= N = n + 2 mi + me; entries
+ * N .. ld-1 of an output column are not written.  flip as in pyipm_qn_*: the solution-space blocks (v, dz) have their
+ * multiplier rows n + mi .. N-1 negated on read and on write; right-hand sides and products are never flipped.
+ *   Valid exactly where pyipm_qn_* are.  PYIPM_E_BADARG, each but the first with a pyipm_lbfgs_last_error text: a NULL handle,
+ *   no direction since the handle was created or the Jacobians were (re)staged, me + mi = 0, an all-reduce callback installed,
+ *   a NULL block, an ld below N, k < 0, out overlapping v, a bad memkind.  k == 0 returns PYIPM_OK and does nothing.
+ *   kkt_matvec_many: column j of out = K v_j with the K pyipm_qn_matvec applies -- from the staged Jacobians, the kept Sigma
+ *   and the kept pairs, never from the factor, without regularisation.
+ *   kkt_solve_many: column j of dz solves K~ dz_j = rhs_j from the kept state alone (the kept factor of zeta G, the kept 2m
+ *   solved columns, the kept J'W and the kept 2m x 2m system): no Gram launch, no factorisation; the arithmetic of
+ *   pyipm_qn_solve per column, the k substitutions as ONE block substitution (pyipm_newton_solve_many's, on the handle of
+ *   order me + mi).  refine as in pyipm_newton_solve_many: > 0 that many steps R = B - K X; X += solve_many(R) with the residual
+ *   formed by the many-column product; < 0 adaptive, stops when EVERY column meets "refine_target", after "refine_max" steps or
+ *   when the worst column gains less than 4x, and takes back a step that made the worst column worse or not finite
+ *   (pyipm_lbfgs_set_option reaches both options).  After refine != 0, pyipm_qn_info reports the step count and the worst
+ *   column's backward errors.
+ *   The two products with J run on the fp64 matrix pipe and read the staged J twice per 64 columns, where k calls of the
+ *   single-column entries read it k (matvec) and 2k (solve) times.
+ *   Column j of matvec_many, and of solve_many with refine >= 0, is bit for bit independent of k, of its place among the
+ *   columns and of what the other columns hold (a NaN column stays in its column; no floating-point atomics; every split of a
+ *   sum over n or me + mi is decided by the geometry alone); two identical calls give identical bits.  With refine < 0 the step
+ *   count follows the worst column.  A column equals pyipm_qn_matvec / pyipm_qn_solve of that column to rounding, not to the bit.
+ *   The calls write only buffers of their own and leave everything a direction left in the handle alone: a following
+ *   pyipm_lbfgs_direction and pyipm_qn_solve(rhs = g) return the bits they return without them.
+ *   Working memory for the column blocks is allocated by the library on first use and grown on demand (not part of
+ *   pyipm_lbfgs_workspace_bytes).  Device blocks are used where they are, asynchronously on the handle's stream apart from the
+ *   one synchronisation per measured backward error; PYIPM_MEM_HOST blocks are staged, and the call synchronises. */
+int pyipm_lbfgs_kkt_matvec_many(pyipm_lbfgs_ctx* h, int64_t k, const double* v, int64_t ld_v,
+                                double* out, int64_t ld_out, int flip, int memkind);
+int pyipm_lbfgs_kkt_solve_many(pyipm_lbfgs_ctx* h, int64_t k, const double* rhs, int64_t ld_rhs,
+                               double* dz, int64_t ld_dz, int flip, int refine, int memkind);
+
 #ifdef __cplusplus
 }
 #endif

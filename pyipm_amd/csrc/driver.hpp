@@ -102,6 +102,9 @@ int factor_begin(Ctx* ctx, hipStream_t st = nullptr);
 int solve_inplace(Ctx* ctx, double* v, bool forward_done = false);
 int solve_plain(Ctx* ctx, double* v, bool forward_done, int nrhs = 1, int64_t vstride = 0, double* part = nullptr,
                 int64_t pstride = 0);
+// V := M^{-1} V for kpad columns at stride ldv (kernels_msolve.hpp); kpad and the doubles of `part` from solve_many_sizes
+int solve_many_plain(Ctx* ctx, double* V, int64_t ldv, int64_t kpad, double* part);
+void solve_many_sizes(int64_t Npad, int64_t k, int64_t* kpad, size_t* part_doubles);
 int ensure_rest_stream(Ctx* ctx);
 bool panel_is_wide(const Ctx* ctx, int64_t p);
 bool panel_piecewise_ok(const Ctx* ctx, int64_t p);

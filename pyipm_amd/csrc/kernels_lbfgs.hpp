@@ -223,10 +223,11 @@ __global__ __launch_bounds__(256) void k_small_gram_reduce(double* __restrict__ 
 // gesv applies behind the reference's sym_solve (pyipm.py:18-20).  One wave; lane i owns row i.
 //   M[i][j] = (M1 ? M1[i*ld1 + off1 + j] : 0) + s2 * M2[i*r + j] ;   b[i] = B[i*ldb]
 // info[0] = smallest |pivot| (0: singular -> x = NaN).
-__global__ __launch_bounds__(64) void k_small_solve(double* __restrict__ x, double* __restrict__ info,
-                                                    const double* __restrict__ M1, int ld1, int off1,
-                                                    const double* __restrict__ M2, double s2,
-                                                    const double* __restrict__ B, int ldb, int r)
+// (the body apart: k_qm_small_solve of kernels_qnmany.hpp runs it once per column)
+__device__ __forceinline__ void small_solve_body(double* __restrict__ x, double* __restrict__ info,
+                                                 const double* __restrict__ M1, int ld1, int off1,
+                                                 const double* __restrict__ M2, double s2,
+                                                 const double* __restrict__ B, int ldb, int r)
 {
     __shared__ double a[64][65];
     __shared__ double b[64];
@@ -273,6 +274,13 @@ __global__ __launch_bounds__(64) void k_small_solve(double* __restrict__ x, doub
     }
     if (i < r) x[i] = b[i];
     if (i == 0) info[0] = pmin;
+}
+__global__ __launch_bounds__(64) void k_small_solve(double* __restrict__ x, double* __restrict__ info,
+                                                    const double* __restrict__ M1, int ld1, int off1,
+                                                    const double* __restrict__ M2, double s2,
+                                                    const double* __restrict__ B, int ldb, int r)
+{
+    small_solve_body(x, info, M1, ld1, off1, M2, s2, B, ldb, r);
 }
 
 // Hs = (W'V + sgn * P_w'R) / zeta, sgn = -1 on column 0, +1 elsewhere:

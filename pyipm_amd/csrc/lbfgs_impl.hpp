@@ -50,6 +50,7 @@ struct LbCtx {
     double *qHa = nullptr, *qHb = nullptr, *qHs = nullptr, *qt = nullptr, *qinfo = nullptr, *qnrm = nullptr;
     bool qn_two_pass = false;           // measurement hook (tools/bench_lbfgs.py --refine): k_tall_tn + k_jvec instead of k_qn_jpass
     double qn_info[4] = {0.0, -1.0, -1.0, 0.0};
+    DevBuf<double> qm_buf;              // column blocks of pyipm_lbfgs_kkt_*_many (qnmany_impl.hpp): allocated on first use, grown on demand
     std::string err;
 };
 

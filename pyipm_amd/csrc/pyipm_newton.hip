@@ -1440,6 +1440,10 @@ int solve_inplace(Ctx* ctx, double* v, bool forward_done) {
 // V := M^{-1} V in place for kpad columns at stride ldv (the current geometry's Npad), kpad a multiple of MS_KB, single
 // rank: the per-panel structure of solve_plain (wide_sub sub-panels, active_ranges) with every GEMV a product over
 // column blocks.  part: >= (ceil(Npad / MS_RCH) + 1) * kpad * MS_SUBW doubles (the partials, then their sums).
+void solve_many_sizes(int64_t Npad, int64_t k, int64_t* kpad, size_t* part_doubles) {
+    *kpad = (k + MS_KB - 1) / MS_KB * MS_KB;
+    *part_doubles = (size_t)((Npad + MS_RCH - 1) / MS_RCH + 1) * (size_t)*kpad * (size_t)MS_SUBW;      // partials + their sums
+}
 int solve_many_plain(Ctx* ctx, double* V, int64_t ldv, int64_t kpad, double* part) {
     const Geo& g = ctx->g;
     const hipStream_t st = ctx->stream;
@@ -1552,9 +1556,10 @@ int solve_many(Ctx* ctx, int64_t k, const double* rhs, int64_t ld_rhs, double* d
     const hipStream_t st = ctx->stream;
     refine = refine_steps(ctx, refine);                 // (the buffers below depend on it)
     const bool adaptive = refine < 0;
-    const int64_t kpad = (k + MS_KB - 1) / MS_KB * MS_KB, Np = g.Npad, Nc = ctx->held.cond_active ? ctx->gc.Npad : 0;
+    const int64_t Np = g.Npad, Nc = ctx->held.cond_active ? ctx->gc.Npad : 0;
+    int64_t kpad; size_t n_part;
+    solve_many_sizes(Np, k, &kpad, &n_part);
     const size_t col = (size_t)Np * (size_t)kpad;
-    const size_t n_part = (size_t)((Np + MS_RCH - 1) / MS_RCH + 1) * (size_t)kpad * (size_t)MS_SUBW;   // partials + their sums
     size_t need = col + (size_t)Nc * (size_t)kpad + n_part;                    // X, Xc, partials
     if (refine != 0) need += 2 * col;                                           // B, R
     if (adaptive) need += col + 2 * (size_t)kpad;                               // the spare iterate, per-column sums

@@ -227,6 +227,38 @@ class LbfgsCore(object):
         self._ck(self.lib.pyipm_qn_info(self.h, out))
         return {"steps": int(out[0]), "berr0": out[1], "berr": out[2], "converged": bool(out[3])}
 
+    def _columns(self, name, A):
+        """An (N, k) NumPy array or tensor as a contiguous (k, N) device buffer: column j at base + j * N."""
+        A = to_device(A, self.device, contiguous=False)
+        if A.dim() != 2 or A.shape[0] != self.N:
+            raise ValueError("%s: the block must have shape (N, k) with N = %d, got %s" % (name, self.N, tuple(A.shape)))
+        return A.t().contiguous()
+
+    def matvec_many(self, V, flip=False):
+        """K V for V of shape (N, k) in two passes over J per 64 columns (pyipm_lbfgs_kkt_matvec_many).  Returns an (N, k)
+        device tensor, the transposed view of a contiguous (k, N) buffer; column j is bitwise independent of the others."""
+        vin = self._columns("matvec_many", V)
+        k = int(vin.shape[0])
+        out = self.torch.empty((k, self.N), dtype=self.torch.float64, device=self.device)
+        self._stream()
+        self._ck(self.lib.pyipm_lbfgs_kkt_matvec_many(self.h, k, self._ptr(vin), self.N, self._ptr(out), self.N,
+                                                      1 if flip else 0, MEM_DEVICE))
+        self._keep_many = vin                            # (the library reads it on the stream, after this returns)
+        return out.t()
+
+    def solve_many(self, B, flip=False, refine=0):
+        """K dz_j = B[:, j] for B of shape (N, k) from the state the last direction kept (pyipm_lbfgs_kkt_solve_many);
+        ``refine`` as in ``NewtonCore.solve_many`` -- after ``refine != 0``, ``refine_info()`` reports the worst column.
+        Returns an (N, k) device tensor, the transposed view of a contiguous (k, N) buffer."""
+        rhs = self._columns("solve_many", B)
+        k = int(rhs.shape[0])
+        dz = self.torch.empty((k, self.N), dtype=self.torch.float64, device=self.device)
+        self._stream()
+        self._ck(self.lib.pyipm_lbfgs_kkt_solve_many(self.h, k, self._ptr(rhs), self.N, self._ptr(dz), self.N,
+                                                     1 if flip else 0, int(refine), MEM_DEVICE))
+        self._keep_many = rhs
+        return dz.t()
+
     def _direction(self, g, s, lda, zeta, S, Y, SS, L, D, reg, eps, flip):
         torch = self.torch
         n, me, mi, N = self.n, self.me, self.mi, self.N

@@ -28,6 +28,12 @@ times one direction after restaging 128, 512 and p/2 columns of [Je | Ji] (pyipm
 unaligned first columns, 128 columns once in Je and once in Ji), beside a direction after a full stage_jacobian, one that reuses
 J'J and one after restaging every column; per leg the restaging copy, the direction, its Gram launch, the tiles it computed and
 the launch's flop count.
+
+    python tools/bench_lbfgs.py --many 8,64 --n 262144 --me 1024 --mi 3072 --m 8 --reps 10
+
+times the many-column entries (pyipm_lbfgs_kkt_matvec_many / _solve_many) at each k against k calls of pyipm_qn_matvec /
+pyipm_qn_solve on the same handle, the legs alternating; with the flops 4 n p k of the two products with J over the call time as a
+share of the measured fp64 MFMA peak and the bytes of the staged J a call moves (profiles/qn_many_ab.json).
 """
 import argparse
 import json
@@ -188,6 +194,73 @@ def refine_leg(a):
                       "matvec_two_kernels_call_fraction_of_two_read_floor": 2 * jbytes / HBM_PEAK_BPS / (med["matvec_two_kernels_ms"] * 1e-3)}))
 
 
+MFMA_F64_VENDOR_TFLOPS = 78.6   # MI355X fp64 matrix peak, specification
+
+
+def many_leg(a):
+    """pyipm_lbfgs_kkt_matvec_many / _solve_many at k columns against k calls of pyipm_qn_matvec / pyipm_qn_solve on the same
+    handle (the yardstick: the single-column entries are what every earlier commit has), legs alternating inside a round."""
+    import torch
+    from pyipm_amd.lbfgs import LbfgsCore
+    from pyipm_amd.newton import mfma_f64_peak
+    n, me, mi, m = a.n, a.me, a.mi, a.m
+    p, N = me + mi, n + 2 * mi + me
+    p_pad = (p + 127) // 128 * 128
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev); gen.manual_seed(0)
+    J = torch.randn((n, p), generator=gen, dtype=torch.float64, device=dev) / np.sqrt(n)
+    zeta, S, Y, SS, L, D = storage(n, m, 1, True)
+    rng = np.random.default_rng(2)
+    s = rng.uniform(0.5, 2.0, mi)
+    lda = np.concatenate([rng.standard_normal(me), rng.uniform(0.5, 2.0, mi)])
+    td = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev)          # noqa: E731
+    gd, sd, ld, Sd, Yd = td(rng.standard_normal(N)), td(s), td(lda), td(S), td(Y)
+    core = LbfgsCore(n, me, mi, max(m, 1), device=0)
+    core.stage_jacobian(J[:, :me] if me else None, J[:, me:] if mi else None)
+    del J
+    core.direction(gd, sd, ld, zeta, Sd, Yd, SS, L, D, reg=1e-12)
+    peak = mfma_f64_peak(0)
+    rows = []
+    for k in [int(x) for x in a.many.split(",")]:
+        V = torch.randn((k, N), generator=gen, dtype=torch.float64, device=dev)          # (k, N): column j at V[j]
+        legs = {"matvec_many_ms": lambda: core.matvec_many(V.t()), "matvec_k_calls_ms": lambda: [core.matvec(V[j]) for j in range(k)],
+                "solve_many_ms": lambda: core.solve_many(V.t()), "solve_k_calls_ms": lambda: [core.solve(V[j]) for j in range(k)]}
+        rec = {name: [] for name in legs}
+        for it in range(a.reps + 2):                 # two warm-up rounds; the legs alternate inside a round
+            for name, fn in legs.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                if it >= 2:
+                    rec[name].append((time.perf_counter() - t0) * 1e3)
+        diff = {"matvec": float(max((core.matvec_many(V.t())[:, j] - core.matvec(V[j])).norm() / core.matvec(V[j]).norm() for j in (0, k - 1))),
+                "solve": float(max((core.solve_many(V.t())[:, j] - core.solve(V[j])).norm() / core.solve(V[j]).norm() for j in (0, k - 1)))}
+        med = {name: float(np.median(v)) for name, v in rec.items()}
+        spread = {name: float(max(v) - min(v)) for name, v in rec.items()}
+        flops = 4.0 * n * p * k                      # the two products with J
+        blocks = (k + 63) // 64
+        rows.append({"k": k, "ms": med, "ms_spread_max_minus_min": spread, "ms_all": rec,
+                     "matvec_speedup": med["matvec_k_calls_ms"] / med["matvec_many_ms"],
+                     "solve_speedup": med["solve_k_calls_ms"] / med["solve_many_ms"],
+                     "faster_by_more_than_the_yardsticks_spread": {
+                         "matvec": med["matvec_k_calls_ms"] - med["matvec_many_ms"] > spread["matvec_k_calls_ms"],
+                         "solve": med["solve_k_calls_ms"] - med["solve_many_ms"] > spread["solve_k_calls_ms"]},
+                     "many_vs_single_rel_diff_first_and_last_column": diff,
+                     "product_flops_4npk": flops, "jacobian_bytes_moved_per_call": 2 * 8 * n * p_pad * blocks,
+                     "matvec_many_call_tflops_on_4npk": flops / (med["matvec_many_ms"] * 1e-3) / 1e12,
+                     "matvec_many_call_share_of_measured_mfma_peak": flops / (med["matvec_many_ms"] * 1e-3) / 1e12 / peak,
+                     "solve_many_call_share_of_measured_mfma_peak": flops / (med["solve_many_ms"] * 1e-3) / 1e12 / peak,
+                     "matvec_many_call_jacobian_TBps": 2 * 8 * n * p_pad * blocks / (med["matvec_many_ms"] * 1e-3) / 1e12})
+    print(json.dumps({"workload": "quasi-Newton KKT operator for k columns per call (pyipm_lbfgs_kkt_*_many) against k single-column "
+                                  "calls (pyipm_qn_matvec / pyipm_qn_solve), QP-shaped synthetic, Jacobians staged once",
+                      "n": n, "me": me, "mi": mi, "m": m, "dtype": "f64",
+                      "timing": "wall, device synchronised before and after, median of %d, legs alternating; whole-call rates, not "
+                                "kernel rates" % a.reps,
+                      "mfma_f64_peak_measured_tflops": peak, "mfma_f64_peak_vendor_tflops": MFMA_F64_VENDOR_TFLOPS,
+                      "hbm_peak_Bps": HBM_PEAK_BPS, "gram_launches": core.last_timings()["gram_launches"], "many": rows}))
+
+
 def columns_leg(a):
     """One direction after restaging a run of columns (pyipm_lbfgs_stage_jacobian_columns), beside one after a full
     stage_jacobian (the yardstick: that path is the one every earlier commit has) and one that reuses J'J."""
@@ -276,7 +349,11 @@ def main():
     ap.add_argument("--refine", action="store_true", help="time K v, the kept-state solve and the refinement of a direction (pyipm_qn_*)")
     ap.add_argument("--sigma-decades", type=float, default=6.0, help="--refine: Sigma spread, decades either side of 1")
     ap.add_argument("--columns", action="store_true", help="time a direction after restaging 128, 512 and p/2 columns (stage_jacobian_columns)")
+    ap.add_argument("--many", default="", metavar="K", help="time pyipm_lbfgs_kkt_matvec_many / _solve_many at k = K (a comma-separated "
+                    "list: one handle, one process) against K calls of the single-column entries")
     a = ap.parse_args()
+    if a.many:
+        return many_leg(a)
     if a.columns:
         return columns_leg(a)
     if a.update:
