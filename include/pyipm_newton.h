@@ -803,6 +803,39 @@ int pyipm_qn_info(pyipm_lbfgs_ctx* h, double out[4]);
 int pyipm_lbfgs_stage_jacobian_columns(pyipm_lbfgs_ctx* h, int64_t c0, int64_t count, const double* Jc, int64_t ld,
                                        int memkind);
 
+/* ---- L-BFGS direction: simple bounds as structure, not as Jacobian columns.
+ * The mi inequalities of a direction split as mi = mg + mb: mg general ones, columns of Ji, then mb simple bounds.  Bound j
+ * acts on variable var[j] with sign[j]: +1 is a lower bound x_k - l >= 0 (the column +e_k), -1 an upper bound u - x_k >= 0
+ * (the column -e_k).  A bounded handle never sees those columns.  With k = var[j] the slack and the multiplier of bound j
+ * eliminate in closed form,
+ *     ds_j = sign_j dx_k - g_li,j ,   dlambda_j = Sigma_j ds_j - g_s,j ,
+ *     theta_k = zeta + sum_{var[j]=k} Sigma_j ,   ghat_x[k] = g_x[k] + sum_{var[j]=k} sign_j (Sigma_j g_li,j + g_s,j) ,
+ * and with omega_k = sqrt(zeta / theta_k) the system in (dx / omega, ds_g, dlambda_g) is the one pyipm_lbfgs_direction solves,
+ * with the same zeta and M, on diag(omega) [Je | Ji], diag(omega) W and omega ghat_x: order me + mg, whatever mb is.
+ *   The handle is a pyipm_lbfgs_ctx: destroy, last_error, set_stream, set_option, last_timings, stage_jacobian (Ji is n x mg),
+ * stage_jacobian_columns and direction work on it.  EVERY vector of a direction keeps the layout it would have with explicit
+ * columns: s has mg + mb entries, lda me + mg + mb, g and dz n + 2 (mg + mb) + me, the bounds in the last mb places of each
+ * inequality block.  stats describe the factorisation of the reduced G of order me + mg (me + mg = 0: bounds only -- the general
+ * branch with an empty J, no Gram matrix and no factorisation; all zero apart from m and small_pivot_min); the regularisation
+ * rule is pyipm_lbfgs_direction's on the equality block of the reduced G.
+ *   mb == 0 gives a plain handle: every call on it is the call on a handle from pyipm_lbfgs_create, to the bit.
+ *   mb > 0: the Gram matrix of the scaled operand depends on Sigma of the bounds, so the Gram launch runs in every direction
+ * (last_timings out[7] counts them; stage_jacobian_columns copies and saves nothing); pyipm_qn_matvec / _solve / _refine,
+ * pyipm_lbfgs_kkt_*_many and pyipm_lbfgs_set_allreduce return PYIPM_E_BADARG with a text that names the bounded handle.  Sums
+ * over a variable's bounds run in the order the bounds were given: equal calls give equal bits.
+ *   bounded_workspace_bytes answers without a GPU (0: bad geometry); against pyipm_lbfgs_workspace_bytes(n, me, mg, ...) it
+ * grows by O(n + mb) doubles and, where me + mg > 0, one more padded operand for the scaled copy -- never by mb^2.
+ *   bounded_create: geometry as pyipm_lbfgs_create with n >= 1, me, mg, mb >= 0, checked before any device is looked for.
+ *   bounded_stage: var and sign are HOST arrays of mb entries; the handle keeps a CSR by variable (a stable grouping: a
+ * variable may carry none, one, two or repeated bounds).  Stage again to change the bounds; a direction before the first staging
+ * on a handle with mb > 0 is PYIPM_E_BADARG.  PYIPM_E_BADARG with a last_error text and the bounds staged before untouched: a
+ * NULL pointer with mb > 0, an index outside 0 .. n-1, a sign that is not +-1, more than 64 bounds on one variable (the tail of a
+ * direction walks a variable's bounds once per bound of that variable). */
+size_t pyipm_lbfgs_bounded_workspace_bytes(int64_t n, int64_t me, int64_t mg, int64_t mb, int max_pairs, int nb);
+int pyipm_lbfgs_bounded_create(pyipm_lbfgs_ctx** out, int64_t n, int64_t me, int64_t mg, int64_t mb,
+                               int max_pairs, int nb, int device, void* stream);
+int pyipm_lbfgs_bounded_stage(pyipm_lbfgs_ctx* h, const int64_t* var, const double* sign);
+
 /* ---- The quasi-Newton KKT operator for k columns per call: what pyipm_newton_kkt_matvec_many and pyipm_newton_solve_many
  * are to the exact-Hessian handle.  Column j of a block sits at base + j*ld, every ld >= N = n + 2 mi + me; entries
  * N .. ld-1 of an output column are not written.  flip as in pyipm_qn_*: the solution-space blocks (v, dz) have their

@@ -5,6 +5,8 @@
 #include "../../include/pyipm_lbfgs.h"
 #include "kernels_lbfgs.hpp"
 #include "gram_tiles.hpp"
+#include "bounds_csr.hpp"
+#include "kernels_lbbounds.hpp"
 #include "kernels_qn.hpp"
 
 namespace {
@@ -50,6 +52,15 @@ struct LbCtx {
     double *qHa = nullptr, *qHb = nullptr, *qHs = nullptr, *qt = nullptr, *qinfo = nullptr, *qnrm = nullptr;
     bool qn_two_pass = false;           // measurement hook (tools/bench_lbfgs.py --refine): k_tall_tn + k_jvec instead of k_qn_jpass
     double qn_info[4] = {0.0, -1.0, -1.0, 0.0};
+    // ---- simple bounds as structure (pyipm_lbfgs_bounded_*; kernels_lbbounds.hpp).  mb > 0: me, mi = mg, p, N above are those
+    // of the REDUCED system the pipeline solves; the caller's vectors count mi + mb inequalities, the bounds last.
+    int64_t mb = 0;
+    bool bd_staged = false;
+    BoundsCsr bd;                       // host: the bounds by variable (O(mb) bookkeeping, like SS / L / D)
+    int64_t *bd_start = nullptr, *bd_ent = nullptr;     // ... and on the device
+    double *gF = nullptr, *dzF = nullptr;               // the caller's g and dz (n + 2 (mi + mb) + me)
+    double *om = nullptr;               // omega (n)
+    double *JTs = nullptr;              // diag(omega) J: the operand the Gram launch and the two passes read (p > 0)
     DevBuf<double> qm_buf;              // column blocks of pyipm_lbfgs_kkt_*_many (qnmany_impl.hpp): allocated on first use, grown on demand
     std::string err;
 };
@@ -65,6 +76,8 @@ struct LbCtx {
 #define LB_KCHECK() LB_HIP(hipGetLastError())
 
 inline LbCtx* LB(pyipm_lbfgs_ctx* h) { return reinterpret_cast<LbCtx*>(h); }
+// the Jacobian operand of a direction: the staged one, or its row-scaled copy on a bounded handle
+inline const double* lb_jop(const LbCtx* lb) { return lb->mb > 0 ? lb->JTs : lb->JT; }
 
 // sum over the ranks of a row-sharded problem (no-op without a callback)
 int lb_allreduce(LbCtx* lb, double* buf, int64_t count) {
@@ -106,7 +119,7 @@ int lb_nsplit(int64_t n, int64_t p_pad, int rrmax) {
 }
 
 // Device layout of a handle; returns total bytes, sets pointers when base != nullptr.
-size_t lb_carve(LbCtx* c, int64_t n, int64_t me, int64_t mi, int cap, int64_t p_pad, int64_t n_pad, char* base) {
+size_t lb_carve(LbCtx* c, int64_t n, int64_t me, int64_t mi, int64_t mb, int cap, int64_t p_pad, int64_t n_pad, char* base) {
     Carve cv;
     const size_t D = sizeof(double);
     const int64_t p = me + mi, N = n + 2 * mi + me;
@@ -117,9 +130,9 @@ size_t lb_carve(LbCtx* c, int64_t n, int64_t me, int64_t mi, int cap, int64_t p_
     const size_t oCs = cv.take(ks > 1 ? (size_t)ks * (size_t)p_pad * (size_t)p_pad * D : 256);
     const size_t oGc = cv.take(p > 0 ? (size_t)p_pad * (size_t)p_pad * D : 256);
     const size_t og = cv.take((size_t)(N + 1) * D);
-    const size_t os = cv.take((size_t)(mi + 1) * D);
-    const size_t ol = cv.take((size_t)(p + 1) * D);
-    const size_t osg = cv.take((size_t)(mi + 1) * D);
+    const size_t os = cv.take((size_t)(mi + mb + 1) * D);               // s, lda, Sigma: the bounds of a bounded handle behind the mi
+    const size_t ol = cv.take((size_t)(p + mb + 1) * D);
+    const size_t osg = cv.take((size_t)(mi + mb + 1) * D);
     const size_t odz = cv.take((size_t)(N + 1) * D);
     const size_t oS = cv.take((size_t)n * cap * D);
     const size_t oY = cv.take((size_t)n * cap * D);
@@ -147,6 +160,23 @@ size_t lb_carve(LbCtx* c, int64_t n, int64_t me, int64_t mi, int cap, int64_t p_
     const size_t oqsm = cv.take((size_t)(4 * 2 * cap + 8) * D);             // qHa | qHb | qHs | qt | qinfo
     const size_t oqn = cv.take((size_t)(2 * QN_NBLK + 2) * D);
     const size_t otl = cv.take(p > 0 ? (size_t)GramTiles::list_capacity(p_pad) * sizeof(unsigned) : 256);
+    if (mb > 0) {
+        // bounded handle, behind everything else: the caller's long g and dz, omega, the CSR
+        // and (with general constraints) the scaled operand.  O(n + mb) apart from that one operand.
+        const int64_t miF = mi + mb, NF = n + 2 * miF + me;
+        const size_t ogF = cv.take((size_t)(NF + 1) * D);
+        const size_t odF = cv.take((size_t)(NF + 1) * D);
+        const size_t oom = cv.take((size_t)(n + 1) * D);
+        const size_t obs = cv.take((size_t)(n + 1) * sizeof(int64_t));
+        const size_t obe = cv.take((size_t)mb * sizeof(int64_t));
+        const size_t oJs = p > 0 ? cv.take((size_t)p_pad * (size_t)n_pad * D) : 0;
+        if (base) {
+            c->gF = (double*)(base + ogF); c->dzF = (double*)(base + odF);
+            c->om = (double*)(base + oom);
+            c->bd_start = (int64_t*)(base + obs); c->bd_ent = (int64_t*)(base + obe);
+            c->JTs = p > 0 ? (double*)(base + oJs) : nullptr;
+        }
+    }
     if (base) {
         c->tl_dev = (unsigned*)(base + otl);
         c->qx = (double*)(base + oq[0]); c->qsave = (double*)(base + oq[1]); c->qb = (double*)(base + oq[2]);
@@ -155,8 +185,9 @@ size_t lb_carve(LbCtx* c, int64_t n, int64_t me, int64_t mi, int cap, int64_t p_
         c->qHa = (double*)(base + oqsm); c->qHb = c->qHa + 2 * cap; c->qHs = c->qHb + 2 * cap; c->qt = c->qHs + 2 * cap;
         c->qinfo = c->qt + 2 * cap;
         c->qnrm = (double*)(base + oqn);
-        c->JT = (double*)(base + oJT); c->Cs = (double*)(base + oCs); c->Gc = (double*)(base + oGc); c->ksplit = ks; c->g = (double*)(base + og); c->s = (double*)(base + os);
-        c->lda = (double*)(base + ol); c->sig = (double*)(base + osg); c->dz = (double*)(base + odz);
+        c->JT = (double*)(base + oJT); c->Cs = (double*)(base + oCs); c->Gc = (double*)(base + oGc); c->ksplit = ks; c->g = (double*)(base + og);
+        c->s = (double*)(base + os); c->lda = (double*)(base + ol); c->sig = (double*)(base + osg);
+        c->dz = (double*)(base + odz);
         c->S = (double*)(base + oS); c->Y = (double*)(base + oY); c->V = (double*)(base + oV);
         c->Ju = (double*)(base + oJu); c->u = (double*)(base + ou); c->P = (double*)(base + oP); c->R = (double*)(base + oR);
         c->part = (double*)(base + opart);
@@ -203,7 +234,7 @@ int lb_factor_G(LbCtx* lb, double zeta, double reg_e, pyipm_factor_stats* st, bo
             // split y of ONE launch accumulates columns [y K/ks, (y+1) K/ks) of JT into its own matrix Cs[y]; Gc = sum
             LB_HIP(hipMemsetAsync(lb->Cs, 0, (size_t)ks * (size_t)cnt * sizeof(double), lb->stream));
             gc->A = lb->Cs;
-            rc = launch_update128(gc, lb->stream, lb->JT, lb->p_pad, lb->JT, (int)(lb->n_pad / ks), 0, 0,
+            rc = launch_update128(gc, lb->stream, lb_jop(lb), lb->p_pad, lb_jop(lb), (int)(lb->n_pad / ks), 0, 0,
                                   (g.Npad + g.nb - 1) / g.nb,
                                   {.ldw = lb->p_pad, .ksplit = ks, .ks_cstride = cnt});
             gc->A = keep;
@@ -213,7 +244,7 @@ int lb_factor_G(LbCtx* lb, double zeta, double reg_e, pyipm_factor_stats* st, bo
         } else {
             LB_HIP(hipMemsetAsync(lb->Gc, 0, (size_t)cnt * sizeof(double), lb->stream));
             gc->A = lb->Gc;
-            rc = launch_update128(gc, lb->stream, lb->JT, lb->p_pad, lb->JT, (int)lb->n_pad, 0, 0,
+            rc = launch_update128(gc, lb->stream, lb_jop(lb), lb->p_pad, lb_jop(lb), (int)lb->n_pad, 0, 0,
                                   (g.Npad + g.nb - 1) / g.nb,
                                   {.ldw = lb->p_pad});
             gc->A = keep;
@@ -237,7 +268,7 @@ int lb_factor_G(LbCtx* lb, double zeta, double reg_e, pyipm_factor_stats* st, bo
         hipLaunchKernelGGL(k_lb_tiles_clear, dim3(nent, (unsigned)ks), dim3(256), 0, lb->stream, acc, g.Npad, cnt, lb->tl_dev);
         LB_KCHECK();
         gc->A = acc;
-        rc = launch_update128(gc, lb->stream, lb->JT, lb->p_pad, lb->JT, (int)(lb->n_pad / ks), 0, 0,
+        rc = launch_update128(gc, lb->stream, lb_jop(lb), lb->p_pad, lb_jop(lb), (int)(lb->n_pad / ks), 0, 0,
                               (g.Npad + g.nb - 1) / g.nb,
                               {.ldw = lb->p_pad, .ksplit = ks, .ks_cstride = ks > 1 ? cnt : 0, .tiles = lb->tl_dev, .ntiles = nent});
         gc->A = keep;
@@ -262,38 +293,32 @@ int lb_factor_G(LbCtx* lb, double zeta, double reg_e, pyipm_factor_stats* st, bo
     return rc;                               // (0 or nonfinite: factor_end has read it back, Held::factored)
 }
 
-}  // namespace
+bool lb_geometry_ok(int64_t n, int64_t me, int64_t mi, int64_t mb, int max_pairs, int* nb) {
+    if (n <= 0 || me < 0 || mi < 0 || mb < 0 || max_pairs < 1 || max_pairs > 32) return false;
+    if (*nb == 0) *nb = 256;
+    return *nb % 128 == 0 && *nb <= 1024;
+}
 
-#undef PYIPM_SETERR_NEWTON
-#undef PYIPM_CATCH_H
-#define PYIPM_SETERR_LBFGS(msg_) set_err_noexcept(reinterpret_cast<LbCtx*>(h), (msg_))
-#define PYIPM_CATCH_H(h_)  PYIPM_CATCH_CORE(PYIPM_SETERR_LBFGS, PYIPM_E_NOMEM, PYIPM_E_HIP)
-
-extern "C" {
-
-size_t pyipm_lbfgs_workspace_bytes(int64_t n, int64_t me, int64_t mi, int max_pairs, int nb) try {
-    if (n <= 0 || me < 0 || mi < 0 || max_pairs < 1 || max_pairs > 32) return 0;
-    if (nb == 0) nb = 256;
-    if (nb % 128 != 0 || nb > 1024) return 0;
+// mi: the inequalities that are Jacobian columns; mb: simple bounds on top (0: a plain handle)
+size_t lb_workspace_bytes(int64_t n, int64_t me, int64_t mi, int64_t mb, int max_pairs, int nb) {
+    if (!lb_geometry_ok(n, me, mi, mb, max_pairs, &nb)) return 0;
     const int64_t p = me + mi;
     const int64_t p_pad = p > 0 ? (p + PADG - 1) / PADG * PADG : 0, n_pad = (n + LB_KPAD - 1) / LB_KPAD * LB_KPAD;
-    size_t total = lb_carve(nullptr, n, me, mi, max_pairs, p_pad, n_pad, nullptr);
+    size_t total = lb_carve(nullptr, n, me, mi, mb, max_pairs, p_pad, n_pad, nullptr);
     if (p > 0) total += pyipm_newton_workspace_bytes(p, 0, 0, nb, 1, 0);
     return total;
-} PYIPM_CATCH_SIZE
+}
 
-int pyipm_lbfgs_create(pyipm_lbfgs_ctx** out, int64_t n, int64_t me, int64_t mi, int max_pairs, int nb,
-                       int device, void* stream) try {
+int lb_create(pyipm_lbfgs_ctx** out, int64_t n, int64_t me, int64_t mi, int64_t mb, int max_pairs, int nb, int device,
+              void* stream) {
     if (!out) return PYIPM_E_BADARG;
     *out = nullptr;
-    if (n <= 0 || me < 0 || mi < 0 || max_pairs < 1 || max_pairs > 32) return PYIPM_E_BADARG;
-    if (nb == 0) nb = 256;
-    if (nb % 128 != 0 || nb > 1024) return PYIPM_E_BADARG;
+    if (!lb_geometry_ok(n, me, mi, mb, max_pairs, &nb)) return PYIPM_E_BADARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return PYIPM_E_NODEVICE;
     if (hipSetDevice(device) != hipSuccess) return PYIPM_E_NODEVICE;
     std::unique_ptr<LbCtx> lb(new LbCtx());       // an early return releases what the handle owns by then (~LbCtx)
-    lb->n = n; lb->me = me; lb->mi = mi; lb->p = me + mi; lb->N = n + 2 * mi + me;
+    lb->n = n; lb->me = me; lb->mi = mi; lb->p = me + mi; lb->N = n + 2 * mi + me; lb->mb = mb;
     lb->cap = max_pairs; lb->rrmax = 2 * max_pairs + 1; lb->device = device; lb->nb = nb;
     lb->stream = (hipStream_t)stream;
     lb->n_pad = (n + LB_KPAD - 1) / LB_KPAD * LB_KPAD;
@@ -306,18 +331,63 @@ int pyipm_lbfgs_create(pyipm_lbfgs_ctx** out, int64_t n, int64_t me, int64_t mi,
         lb->dirty.init(lb->p_pad);
     }
     lb->nsplit = lb_nsplit(n, lb->p_pad, lb->rrmax);
-    const size_t ws_bytes = lb_carve(nullptr, n, me, mi, max_pairs, lb->p_pad, lb->n_pad, nullptr);
+    const size_t ws_bytes = lb_carve(nullptr, n, me, mi, mb, max_pairs, lb->p_pad, lb->n_pad, nullptr);
     if (lb->ws.reserve(ws_bytes) != hipSuccess) return PYIPM_E_NOMEM;
     lb->qn_two_pass = getenv("PYIPM_QN_TWO_PASS") != nullptr;
     if (getenv("PYIPM_POISON_WORKSPACE")) hipMemset(lb->ws, 0xFF, ws_bytes);   // test hook (tests/conftest.py): NaN wherever nothing is written first
-    lb_carve(lb.get(), n, me, mi, max_pairs, lb->p_pad, lb->n_pad, lb->ws);
+    lb_carve(lb.get(), n, me, mi, mb, max_pairs, lb->p_pad, lb->n_pad, lb->ws);
     bool ok = true;
-    if (lb->p > 0) ok = hipMemsetAsync(lb->JT, 0, (size_t)lb->p_pad * (size_t)lb->n_pad * sizeof(double), lb->stream) == hipSuccess;
+    const size_t opnd = (size_t)lb->p_pad * (size_t)lb->n_pad * sizeof(double);
+    if (lb->p > 0) ok = hipMemsetAsync(lb->JT, 0, opnd, lb->stream) == hipSuccess;
+    if (lb->JTs && ok) ok = hipMemsetAsync(lb->JTs, 0, opnd, lb->stream) == hipSuccess;     // (its padding is never written again)
     for (int i = 0; i < 9 && ok; ++i) ok = lb->ev[i].ensure(hipEventDefault) == hipSuccess;
     if (!ok) { hipStreamSynchronize(lb->stream); return PYIPM_E_HIP; }       // (the fill above may be in flight)
     *out = reinterpret_cast<pyipm_lbfgs_ctx*>(lb.release());
     return PYIPM_OK;
+}
+
+}  // namespace
+
+#undef PYIPM_SETERR_NEWTON
+#undef PYIPM_CATCH_H
+#define PYIPM_SETERR_LBFGS(msg_) set_err_noexcept(reinterpret_cast<LbCtx*>(h), (msg_))
+#define PYIPM_CATCH_H(h_)  PYIPM_CATCH_CORE(PYIPM_SETERR_LBFGS, PYIPM_E_NOMEM, PYIPM_E_HIP)
+
+extern "C" {
+
+size_t pyipm_lbfgs_workspace_bytes(int64_t n, int64_t me, int64_t mi, int max_pairs, int nb) try {
+    return lb_workspace_bytes(n, me, mi, 0, max_pairs, nb);
+} PYIPM_CATCH_SIZE
+
+int pyipm_lbfgs_create(pyipm_lbfgs_ctx** out, int64_t n, int64_t me, int64_t mi, int max_pairs, int nb,
+                       int device, void* stream) try {
+    return lb_create(out, n, me, mi, 0, max_pairs, nb, device, stream);
 } PYIPM_CATCH_NOH
+
+size_t pyipm_lbfgs_bounded_workspace_bytes(int64_t n, int64_t me, int64_t mg, int64_t mb, int max_pairs, int nb) try {
+    return lb_workspace_bytes(n, me, mg, mb, max_pairs, nb);
+} PYIPM_CATCH_SIZE
+
+int pyipm_lbfgs_bounded_create(pyipm_lbfgs_ctx** out, int64_t n, int64_t me, int64_t mg, int64_t mb, int max_pairs, int nb,
+                               int device, void* stream) try {
+    return lb_create(out, n, me, mg, mb, max_pairs, nb, device, stream);       // (mb == 0: a plain handle in every respect)
+} PYIPM_CATCH_NOH
+
+int pyipm_lbfgs_bounded_stage(pyipm_lbfgs_ctx* h, const int64_t* var, const double* sign) try {
+    if (!h) return PYIPM_E_BADARG;
+    LbCtx* lb = LB(h);
+    if (lb->mb == 0) return PYIPM_OK;                     // nothing to stage
+    // every refusal comes before anything is touched: the bounds staged before still hold
+    const char* why = lb->bd.build(lb->n, lb->mb, var, sign);
+    if (why) { lb->err = std::string("bounded_stage: ") + why; return PYIPM_E_BADARG; }
+    LB_HIP(hipSetDevice(lb->device));
+    lb->bd_staged = false;                                // (until both copies have landed)
+    LB_HIP(hipMemcpyAsync(lb->bd_start, lb->bd.start.data(), (size_t)(lb->n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, lb->stream));
+    LB_HIP(hipMemcpyAsync(lb->bd_ent, lb->bd.ent.data(), (size_t)lb->mb * sizeof(int64_t), hipMemcpyHostToDevice, lb->stream));
+    LB_HIP(hipStreamSynchronize(lb->stream));
+    lb->bd_staged = true;
+    return PYIPM_OK;
+} PYIPM_CATCH_H(h)
 
 int pyipm_lbfgs_destroy(pyipm_lbfgs_ctx* h) try {
     if (!h) return PYIPM_E_BADARG;
@@ -342,6 +412,7 @@ int pyipm_lbfgs_set_stream(pyipm_lbfgs_ctx* h, void* stream) try {
 
 int pyipm_lbfgs_set_allreduce(pyipm_lbfgs_ctx* h, pyipm_lbfgs_allreduce_fn fn, void* user) try {
     if (!h) return PYIPM_E_BADARG;
+    if (LB(h)->mb > 0) { LB(h)->err = "set_allreduce: a bounded handle cannot be row-sharded"; return PYIPM_E_BADARG; }
     LB(h)->allreduce = fn; LB(h)->allreduce_user = user;
     LB(h)->gram_valid = false;
     LB(h)->qn_valid = false;
@@ -399,7 +470,13 @@ int pyipm_lbfgs_direction(pyipm_lbfgs_ctx* h, const double* g, const double* s, 
     if (!h) return PYIPM_E_BADARG;
     LbCtx* lb = LB(h);
     const int64_t n = lb->n, me = lb->me, mi = lb->mi, p = lb->p, N = lb->N;
+    // a bounded handle: mb bounds behind the mi general inequalities in the caller's vectors; the pipeline below solves the
+    // reduced system of order p = me + mi on row-scaled operands (kernels_lbbounds.hpp)
+    const int64_t mb = lb->mb, miF = mi + mb, NF = n + 2 * miF + me;
+    const bool bounded = mb > 0;
     if (!g || !dz) { lb->err = "direction: null g / dz"; return PYIPM_E_BADARG; }
+    if (bounded && !lb->bd_staged) { lb->err = "direction: stage the bounds of the bounded handle first"; return PYIPM_E_BADARG; }
+    if (bounded && (!lda || !s)) { lb->err = "direction: null s / lda"; return PYIPM_E_BADARG; }
     if (m < 0 || m > lb->cap) { lb->err = "direction: m exceeds max_pairs of the handle"; return PYIPM_E_BADARG; }
     if (m > 0 && (!S || !Y || !SS || !L || !D || ld_S < m || ld_Y < m)) { lb->err = "direction: bad storage pointers"; return PYIPM_E_BADARG; }
     if (!(zeta > 0.0)) { lb->err = "direction: zeta must be positive"; return PYIPM_E_BADARG; }
@@ -415,10 +492,10 @@ int pyipm_lbfgs_direction(pyipm_lbfgs_ctx* h, const double* g, const double* s, 
     LB_HIP(hipEventRecord(lb->ev[0], st));
 
     // ---- inputs to the device; V = [g_x | S-part | Y-part]
-    int rc = lb_put(lb, lb->g, g, (size_t)N, memkind); if (rc) return rc;
-    if (p > 0) {
-        rc = lb_put(lb, lb->lda, lda, (size_t)p, memkind); if (rc) return rc;
-        rc = lb_put(lb, lb->s, s, (size_t)mi, memkind); if (rc) return rc;
+    int rc = lb_put(lb, bounded ? lb->gF : lb->g, g, (size_t)(bounded ? NF : N), memkind); if (rc) return rc;
+    if (p > 0 || bounded) {
+        rc = lb_put(lb, lb->lda, lda, (size_t)(me + miF), memkind); if (rc) return rc;
+        rc = lb_put(lb, lb->s, s, (size_t)miF, memkind); if (rc) return rc;
     }
     const double *dS = S, *dY = Y; int64_t ldS = ld_S, ldY = ld_Y;
     if (m > 0 && memkind == PYIPM_MEM_HOST) {
@@ -427,15 +504,36 @@ int pyipm_lbfgs_direction(pyipm_lbfgs_ctx* h, const double* g, const double* s, 
         dS = lb->S; dY = lb->Y; ldS = ldY = m;
     }
     // constrained: W = [zeta S, Y] scales the Hessian (:1127); unconstrained: W = [S, zeta Y] the inverse (:1167)
-    const double cS = p > 0 ? zeta : 1.0, cY = p > 0 ? 1.0 : zeta;
-    hipLaunchKernelGGL(k_lb_pack, grid1(n * rr), dim3(256), 0, st, lb->V, rr, lb->g, dS, ldS, dY, ldY, n, m, cS, cY);
-    LB_KCHECK();
+    const bool constrained = p > 0 || bounded;         // (bounds alone: the general branch with an empty J)
+    const double cS = constrained ? zeta : 1.0, cY = constrained ? 1.0 : zeta;
+    if (bounded) {
+        // Sigma of all mi + mb inequalities; omega and ghat_x from the variable's side; the reduced right-hand side;
+        // the scaled operand (the Gram matrix of it depends on Sigma of the bounds: computed in every direction)
+        hipLaunchKernelGGL(k_lb_sigma, grid1(miF), dim3(256), 0, st, lb->sig, lb->s, lb->lda + me, eps, miF);
+        LB_KCHECK();
+        hipLaunchKernelGGL(k_bd_weights, grid1(n), dim3(256), 0, st, lb->om, lb->g, lb->gF, lb->sig, lb->bd_start, lb->bd_ent,
+                           n, me, mi, mb, zeta);
+        LB_KCHECK();
+        if (p > 0) {
+            hipLaunchKernelGGL(k_bd_gather_g, grid1(2 * mi + me), dim3(256), 0, st, lb->g, lb->gF, n, me, mi, mb);
+            LB_KCHECK();
+            int64_t nblk = (n + 15) / 16; if (nblk > 16384) nblk = 16384;
+            hipLaunchKernelGGL(k_bd_scale, dim3((unsigned)nblk), dim3(256), 0, st, lb->JTs, lb->JT, lb->p_pad, lb->om, n);
+            LB_KCHECK();
+            lb->gram_valid = false;
+        }
+        hipLaunchKernelGGL(k_bd_pack, grid1(n * rr), dim3(256), 0, st, lb->V, rr, lb->g, dS, ldS, dY, ldY, n, m, cS, cY, lb->om);
+        LB_KCHECK();
+    } else {
+        hipLaunchKernelGGL(k_lb_pack, grid1(n * rr), dim3(256), 0, st, lb->V, rr, lb->g, dS, ldS, dY, ldY, n, m, cS, cY);
+        LB_KCHECK();
+    }
     if (m > 0) {                       // the O(m^2) bookkeeping of lbfgs_update -> the small system's constant part
         std::vector<double> M2((size_t)r * r, 0.0);
         for (int a = 0; a < m; ++a)
             for (int b = 0; b < m; ++b) {
                 const double ss = SS[a * m + b], l = L[a * m + b], lt = L[b * m + a], d = D[a * m + b];
-                if (p > 0) {           // Minv = [[zeta SS, L], [L', -D]]   (:1140-1143)
+                if (constrained) {     // Minv = [[zeta SS, L], [L', -D]]   (:1140-1143)
                     M2[(size_t)a * r + b] = zeta * ss;      M2[(size_t)a * r + m + b] = l;
                     M2[(size_t)(m + a) * r + b] = lt;       M2[(size_t)(m + a) * r + m + b] = -d;
                 } else {               // [[0, L], [L', D + zeta SS]]       (:1169-1171 as one system)
@@ -447,7 +545,24 @@ int pyipm_lbfgs_direction(pyipm_lbfgs_ctx* h, const double* g, const double* s, 
         LB_HIP(hipStreamSynchronize(st));          // M2 is a local
     }
 
-    if (p == 0) {
+    if (p == 0 && bounded) {
+        // ---------------- bounds only: the general branch with an empty J (no Gram matrix, no factorisation)
+        //   (W~'W~ / zeta - M) v11 = W~'g~_x / zeta ,   dx~ = (g~_x - W~ v11) / zeta   (the combination: k_bd_tail)
+        if (m > 0) {
+            hipLaunchKernelGGL(k_small_gram, dim3(LB_GBLK), dim3(256), (size_t)LB_GCH * (r + rr) * sizeof(double), st,
+                               lb->gpart, lb->V, (int64_t)rr, (int64_t)1, 1, lb->V, (int64_t)rr, (int64_t)1, rr, r, n);
+            LB_KCHECK();
+            hipLaunchKernelGGL(k_small_gram_reduce, grid1(r * rr), dim3(256), 0, st, lb->Ha, lb->gpart, r * rr, LB_GBLK);
+            LB_KCHECK();
+            LB_HIP(hipMemsetAsync(lb->Hb, 0, (size_t)r * rr * sizeof(double), st));       // P_w'R of an empty J
+            hipLaunchKernelGGL(k_lb_hs, grid1(r * rr), dim3(256), 0, st, lb->Hs, lb->Ha, lb->Hb, r, rr, zeta);
+            LB_KCHECK();
+            hipLaunchKernelGGL(k_small_solve, dim3(1), dim3(64), 0, st, lb->v11, lb->info, lb->Hs, rr, 1, lb->M2, -1.0,
+                               lb->Hs, rr, r);
+            LB_KCHECK();
+        }
+        LB_HIP(hipMemsetAsync(lb->Ju, 0, (size_t)n * sizeof(double), st));                 // J u of an empty J (k_bd_tail combines)
+    } else if (p == 0) {
         // ---------------- unconstrained: dz = zeta g - [S, zeta Y] c
         if (m > 0) {
             hipLaunchKernelGGL(k_small_gram, dim3(LB_GBLK), dim3(256), (size_t)LB_GCH * (r + 1) * sizeof(double), st,
@@ -465,7 +580,7 @@ int pyipm_lbfgs_direction(pyipm_lbfgs_ctx* h, const double* g, const double* s, 
     } else {
         const int64_t ldp = lb->p_pad;
         Ctx* gc = lb->gcx.get();
-        if (mi > 0) {
+        if (mi > 0 && !bounded) {
             hipLaunchKernelGGL(k_lb_sigma, grid1(mi), dim3(256), 0, st, lb->sig, lb->s, lb->lda + me, eps, mi);
             LB_KCHECK();
         }
@@ -487,7 +602,7 @@ int pyipm_lbfgs_direction(pyipm_lbfgs_ctx* h, const double* g, const double* s, 
         {
             const int64_t kper = (n + lb->nsplit - 1) / lb->nsplit;
             dim3 grid((unsigned)((ldp + 255) / 256), (unsigned)lb->nsplit, (unsigned)((rr + LB_CC - 1) / LB_CC));
-            hipLaunchKernelGGL(k_tall_tn, grid, dim3(256), 0, st, lb->part, ldp, lb->JT, ldp, lb->V, rr, n, kper);
+            hipLaunchKernelGGL(k_tall_tn, grid, dim3(256), 0, st, lb->part, ldp, lb_jop(lb), ldp, lb->V, rr, n, kper);
             LB_KCHECK();
             hipLaunchKernelGGL(k_tall_tn_reduce, dim3((unsigned)((ldp + 255) / 256), (unsigned)rr), dim3(256), 0, st,
                                lb->P, lb->part, ldp, rr, lb->nsplit);
@@ -530,16 +645,30 @@ int pyipm_lbfgs_direction(pyipm_lbfgs_ctx* h, const double* g, const double* s, 
         // ---- pass 2 over J: ONE vector.  dz_x = (g_x - W v11 - J u) / zeta
         {
             int64_t nblk = (n + 15) / 16; if (nblk > 16384) nblk = 16384;
-            hipLaunchKernelGGL(k_jvec, dim3((unsigned)nblk), dim3(256), 0, st, lb->Ju, lb->JT, ldp, lb->u, p, n);
+            hipLaunchKernelGGL(k_jvec, dim3((unsigned)nblk), dim3(256), 0, st, lb->Ju, lb_jop(lb), ldp, lb->u, p, n);
             LB_KCHECK();
         }
         LB_HIP(hipEventRecord(lb->ev[6], st));
-        hipLaunchKernelGGL(k_lb_comb_x, grid1(n), dim3(256), 0, st, lb->dz, lb->V, rr, n, lb->v11, r, 1.0 / zeta,
-                           (const double*)lb->Ju);
+        if (!bounded) {                         // (a bounded handle combines the x rows in k_bd_tail)
+            hipLaunchKernelGGL(k_lb_comb_x, grid1(n), dim3(256), 0, st, lb->dz, lb->V, rr, n, lb->v11, r, 1.0 / zeta,
+                               (const double*)lb->Ju);
+            LB_KCHECK();
+        }
+    }
+    if (bounded) {
+        // dx and the bounds' slack and multiplier rows in closed form from W~ v11 + J~ u (a nearly active bound would lose the
+        // digits of ds_j in omega dx~ - g_li,j: k_bd_tail), the general rows where the caller has them
+        hipLaunchKernelGGL(k_bd_tail, grid1(n), dim3(256), 0, st, lb->dzF, lb->V, rr, lb->v11, r, lb->Ju, lb->om, lb->gF, lb->sig,
+                           lb->bd_start, lb->bd_ent, n, me, mi, mb, zeta, flip ? -1.0 : 1.0);
         LB_KCHECK();
+        if (p > 0) {
+            hipLaunchKernelGGL(k_bd_scatter_dz, grid1(2 * mi + me), dim3(256), 0, st, lb->dzF, lb->dz, n, me, mi, mb);
+            LB_KCHECK();
+        }
+        lb->gram_valid = false;                 // never kept: Sigma of the bounds moves with every iteration
     }
     LB_HIP(hipEventRecord(lb->ev[7], st));
-    LB_HIP(hipMemcpyAsync(dz, lb->dz, (size_t)N * sizeof(double),
+    LB_HIP(hipMemcpyAsync(dz, bounded ? lb->dzF : lb->dz, (size_t)(bounded ? NF : N) * sizeof(double),
                           memkind == PYIPM_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
     double info = 1.0e308;
     if (m > 0) LB_HIP(hipMemcpyAsync(&info, lb->info, sizeof(double), hipMemcpyDeviceToHost, st));
@@ -547,7 +676,7 @@ int pyipm_lbfgs_direction(pyipm_lbfgs_ctx* h, const double* g, const double* s, 
     out.small_pivot_min = info;
     lb->ev_valid = true;
     lb->did[0] = p > 0;
-    lb->qn_valid = p > 0; lb->qn_m = m; lb->qn_zeta = zeta;      // what pyipm_qn_* work from (qn_impl.hpp)
+    lb->qn_valid = p > 0 && !bounded; lb->qn_m = m; lb->qn_zeta = zeta;      // what pyipm_qn_* work from (qn_impl.hpp)
     if (stats) *stats = out;
     return PYIPM_OK;
 } PYIPM_CATCH_H(h)

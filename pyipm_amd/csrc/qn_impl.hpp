@@ -9,6 +9,7 @@
 namespace {
 
 int qn_enter(LbCtx* lb, const char* name) {
+    if (lb->mb > 0) { lb->err = std::string(name) + ": not supported on a bounded handle (K would need the bound block)"; return PYIPM_E_BADARG; }
     if (lb->p == 0) { lb->err = std::string(name) + ": no constraints -- the unconstrained direction is an explicit formula, there is no system"; return PYIPM_E_BADARG; }
     if (lb->allreduce) { lb->err = std::string(name) + ": a row-sharded handle (all-reduce callback installed) is not supported"; return PYIPM_E_BADARG; }
     if (!lb->qn_valid) { lb->err = std::string(name) + ": no direction since the handle was created or the Jacobians were staged"; return PYIPM_E_BADARG; }

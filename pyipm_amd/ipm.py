@@ -33,12 +33,80 @@ from . import reghess
 from .loop import BarrierLoop, lbfgs_pair_update
 
 
+class BoundBlock(object):
+    """Simple bounds lb <= x <= ub as the LAST mb inequalities of ci: lower bounds first in ascending k (x_k - lb_k >= 0, the
+    column +e_k), then upper bounds (ub_k - x_k >= 0, the column -e_k).  -inf / +inf or None: no bound.  The columns are never
+    formed: every product with them is an index operation, O(n + mb)."""
+
+    def __init__(self, lb, ub, n):
+        lo = np.full(n, -np.inf) if lb is None else np.asarray(lb, dtype=np.float64).reshape(-1)
+        hi = np.full(n, np.inf) if ub is None else np.asarray(ub, dtype=np.float64).reshape(-1)
+        if lo.size != n or hi.size != n:
+            raise ValueError("bounds: lb and ub need n = %d entries" % n)
+        kl, ku = np.flatnonzero(np.isfinite(lo)), np.flatnonzero(np.isfinite(hi))
+        self.n, self.mb = n, int(kl.size + ku.size)
+        self.var = np.concatenate([kl, ku]).astype(np.int64)
+        self.sign = np.concatenate([np.ones(kl.size), -np.ones(ku.size)])
+        self.off = np.concatenate([-lo[kl], hi[ku]])
+        self.count = np.bincount(self.var, minlength=n).astype(np.float64)
+
+    def residual(self, x):
+        """The bounds' rows of ci(x)."""
+        return self.sign * x[self.var] + self.off
+
+    def dot(self, v):
+        """E v: the bound columns times mb multipliers (n)."""
+        return np.bincount(self.var, weights=self.sign * v, minlength=self.n)
+
+    def tdot(self, r):
+        """E' r (mb)."""
+        return self.sign * r[self.var]
+
+
+class BoundedJacobian(object):
+    """[Jd | E]: the dense columns [Je | Ji_general] and the bound block E of a BoundBlock, as the operator the host-side
+    least-squares problems need (first multiplier estimate, feasibility restoration)."""
+
+    def __init__(self, Jd, bb):
+        self.Jd, self.bb = Jd, bb
+        self.shape = (Jd.shape[0], Jd.shape[1] + bb.mb)
+
+    def dot(self, v):
+        pd = self.Jd.shape[1]
+        return self.Jd @ v[:pd] + self.bb.dot(v[pd:])
+
+    def tdot(self, r):
+        return np.concatenate([self.Jd.T @ r, self.bb.tdot(r)])
+
+    def gram(self, wide):
+        """J J' (n x n: E E' is the diagonal of the bounds per variable) or J'J (p x p, by index)."""
+        Jd, bb = self.Jd, self.bb
+        if wide:
+            G = Jd @ Jd.T
+            G[np.diag_indices_from(G)] += bb.count
+            return G
+        cross = Jd[bb.var, :].T * bb.sign                                  # Jd'E
+        same = (bb.var[:, None] == bb.var[None, :]) * np.outer(bb.sign, bb.sign)      # E'E (tall: mb < n)
+        return np.block([[Jd.T @ Jd, cross], [cross.T, same]])
+
+    def fro(self):
+        return float(np.sqrt(np.linalg.norm(self.Jd) ** 2 + self.bb.mb))
+
+    def dense(self):
+        """Only where a rank-deficient Jacobian sends the first multiplier estimate to the SVD."""
+        E = np.zeros((self.bb.n, self.bb.mb))
+        E[self.bb.var, np.arange(self.bb.mb)] = self.bb.sign
+        return np.concatenate([self.Jd, E], axis=1)
+
+
 def pinv_apply(J, g):
     """pinv(J) @ g -- the reference's first multiplier estimate (pyipm.py:726-730) -- without the SVD where J allows it: for a
     Jacobian of full rank and moderate condition the normal equations (Cholesky + one refinement step) give the same vector at
     a fraction of the cost (an SVD of a 1500 x 3600 Jacobian was half of a whole LP solve); rank-deficient or badly conditioned
     Jacobians (Cholesky fails or its diagonal spans more than three decades) take numpy.linalg.pinv as before."""
     import scipy.linalg
+    if isinstance(J, BoundedJacobian):             # the same steps with the bound block applied by index
+        return _pinv_apply_bounded(J, g)
     J = np.asarray(J, dtype=np.float64)
     n, m = J.shape
     wide = m >= n
@@ -65,6 +133,31 @@ def pinv_apply(J, g):
     except (np.linalg.LinAlgError, ValueError):
         pass
     return np.linalg.pinv(J) @ g
+
+
+def _pinv_apply_bounded(J, g):
+    import scipy.linalg
+    n, m = J.shape
+    wide = m >= n
+    try:
+        cf = scipy.linalg.cho_factor(J.gram(wide), lower=True, check_finite=False)
+        d = np.abs(np.diag(cf[0]))
+        if d.size and np.isfinite(d).all() and d.min() > 1.0e-3 * d.max():
+            def apply(r):
+                if wide:
+                    return J.tdot(scipy.linalg.cho_solve(cf, r, check_finite=False))
+                return scipy.linalg.cho_solve(cf, J.tdot(r), check_finite=False)
+            lam = apply(g)
+            lam = lam + apply(g - J.dot(lam))
+            r = g - J.dot(lam)
+            if not wide:
+                r = J.tdot(r)
+            scale = np.linalg.norm(g) if wide else J.fro() * np.linalg.norm(g)
+            if np.isfinite(lam).all() and np.linalg.norm(r) <= 1.0e-11 * max(scale, np.finfo(float).tiny):
+                return lam
+    except (np.linalg.LinAlgError, ValueError):
+        pass
+    return np.linalg.pinv(J.dense()) @ g
 
 
 class HipNewtonBackend(object):
@@ -282,10 +375,16 @@ class HipLbfgsBackend(object):
     1184-1246).  The "rcond <= eps" trigger on the equality block (:1108-1113, an ``eigh`` in the
     reference) is taken from the block pivots of the factorisation, as in ``HipNewtonBackend``."""
 
-    def __init__(self, n, me, mi, memory, device=None, nb=256, linear_constraints=False, refine=0):
+    def __init__(self, n, me, mi, memory, device=None, nb=256, linear_constraints=False, refine=0, bounds=None):
+        """``bounds=(var, sign)``: simple bounds BEHIND the mi general inequalities, on a bounded handle
+        (``LbfgsCore(bounds=...)``): Ji, the staged columns and a ``linear_constraints`` mask cover the me + mi general
+        columns alone; s, lda, g and the direction count mi + len(var) inequalities."""
         from .lbfgs import LbfgsCore
-        self.core = LbfgsCore(n, me, mi, int(memory) + 1, device=device, nb=nb)   # storage grows to memory+1 (:1300)
+        if bounds is not None and refine:
+            raise NotImplementedError("lbfgs_refine with bounds: the quasi-Newton KKT operator has no bound block")
+        self.core = LbfgsCore(n, me, mi, int(memory) + 1, device=device, nb=nb, bounds=bounds)   # storage grows to memory+1 (:1300)
         self.n, self.me, self.mi = n, me, mi
+        self.mb = self.core.mb
         # linear_constraints: True = dce/dci do not depend on x (stage once, J'J is reused), False = they all may, or a boolean
         # mask over the me + mi columns of [Je | Ji], True where a column does not: after the first direction only the runs of
         # False columns are staged again, and only the tiles of J'J they reach are recomputed
@@ -306,7 +405,7 @@ class HipLbfgsBackend(object):
         self.pair_doubles_uploaded = 0         # S / Y entries that crossed from the host (none with a resident pair store)
 
     def shape(self):
-        return (self.n, self.me, self.mi)
+        return (self.n, self.me, self.mi + self.mb)
 
     def lbfgs_direction(self, Je, Ji, s, lda, g, zeta, S, Y, SS, L, D, reg, eps):
         self.n_calls += 1
@@ -339,7 +438,16 @@ class IPM(BarrierLoop):
                  dci=None, d2ci=None, lda0=None, lambda_dev=None, s0=None, mu=0.2, nu=10.0, rho=0.1, tau=0.995,
                  eta=1.0E-4, beta=0.4, miter=20, niter=10, Xtol=None, Ktol=1.0E-4, Ftol=None, lbfgs=False,
                  lbfgs_zeta=None, float_dtype=np.float64, verbosity=1, backend=None, device=None, nb=256, refine=0,
-                 device_step=False, condensed=False, linear_constraints=False, resident_pairs=False, lbfgs_refine=0):
+                 device_step=False, condensed=False, linear_constraints=False, resident_pairs=False, lbfgs_refine=0,
+                 bounds=None):
+        """``bounds=(lb, ub)`` (L-BFGS mode): simple bounds on x, length n each, -inf / +inf or None where there is none.
+        They are the last inequalities -- lower bounds in ascending k, then upper bounds: ``nineq``, s and the returned
+        multipliers count them -- and are never written as columns of ``dci`` (``BoundBlock``)."""
+        if bounds is not None and not lbfgs:
+            raise NotImplementedError("bounds need lbfgs=m: the exact-Hessian handle takes bounds as rows of ci only")
+        if bounds is not None and lbfgs_refine:
+            raise NotImplementedError("lbfgs_refine with bounds: the quasi-Newton KKT operator has no bound block")
+        self.bounds, self._bb = bounds, None
         self.x0, self.s0, self.lda0 = x0, s0, lda0
         self.x_dev, self.lambda_dev = x_dev, lambda_dev        # accepted for signature parity; unused
         self.f, self.df, self.d2f = f, df, d2f
@@ -404,36 +512,63 @@ class IPM(BarrierLoop):
             self.nvar = nvar
         x0 = np.asarray(self.x0, dtype=np.float64)
         self.neq = int(np.size(self.ce(x0))) if (self.ce is not None and neq is None) else int(neq or 0)
-        self.nineq = int(np.size(self.ci(x0))) if (self.ci is not None and nineq is None) else int(nineq or 0)
+        if self.bounds is not None:
+            self._bb = BoundBlock(self.bounds[0], self.bounds[1], self.nvar)
+        mb = self._bb.mb if self._bb is not None else 0
+        self.nineq = (int(np.size(self.ci(x0))) if (self.ci is not None and nineq is None) else int(nineq or 0)) + mb
         if self.backend is not None and self._own_backend and hasattr(self.backend, "shape") and \
                 self.backend.shape() != (self.nvar, self.neq, self.nineq):
             self.backend = None            # force_recompile with another problem shape: the handle is per shape
         if self.backend is None:
             self._own_backend = True
             if self.lbfgs:
-                self.backend = HipLbfgsBackend(self.nvar, self.neq, self.nineq, self.lbfgs,
+                self.backend = HipLbfgsBackend(self.nvar, self.neq, self.nineq - mb, self.lbfgs,
                                                device=self._backend_opts["device"], nb=self._backend_opts["nb"],
-                                               linear_constraints=self.linear_constraints, refine=self.lbfgs_refine)
+                                               linear_constraints=self.linear_constraints, refine=self.lbfgs_refine,
+                                               bounds=(self._bb.var, self._bb.sign) if mb else None)
             else:
                 self.backend = HipNewtonBackend(self.nvar, self.neq, self.nineq, **self._backend_opts)
         self.compiled = True
 
     # ------------------------------------------------------------------ model pieces (host, O(n m))
+    # the inequalities: the caller's ci / dci for the general ones, then the bound block, applied by index
+    def _ci(self, x):
+        mg = self.nineq - (self._bb.mb if self._bb is not None else 0)
+        parts = [np.asarray(self.ci(x), dtype=np.float64).reshape(mg)] if mg else []
+        if self._bb is not None:
+            parts.append(self._bb.residual(np.asarray(x, dtype=np.float64)))
+        return np.concatenate(parts) if len(parts) != 1 else parts[0]
+
+    def _ji(self, x):
+        """The inequality columns that ARE columns: dci(x), n x mg (None without general inequalities)."""
+        mg = self.nineq - (self._bb.mb if self._bb is not None else 0)
+        return np.asarray(self.dci(x), dtype=np.float64).reshape(self.nvar, mg) if mg else None
+
+    def _ji_dot(self, x, v):
+        """Ji v over all nineq inequalities."""
+        Jg = self._ji(x)
+        mg = 0 if Jg is None else Jg.shape[1]
+        out = Jg @ v[:mg] if mg else np.zeros(self.nvar)
+        return out + self._bb.dot(v[mg:]) if self._bb is not None else out
+
     def _con(self, x, s):
         parts = []
         if self.neq:
             parts.append(np.asarray(self.ce(x), dtype=np.float64).reshape(self.neq))
         if self.nineq:
-            parts.append(np.asarray(self.ci(x), dtype=np.float64).reshape(self.nineq) - s)
+            parts.append(self._ci(x) - s)
         return np.concatenate(parts) if parts else np.zeros(0)
 
     def _jac_x(self, x):
+        """[Je | Ji]: a dense array, or with bounds the operator ``BoundedJacobian`` over the dense general columns."""
         cols = []
         if self.neq:
             cols.append(np.asarray(self.dce(x), dtype=np.float64).reshape(self.nvar, self.neq))
-        if self.nineq:
-            cols.append(np.asarray(self.dci(x), dtype=np.float64).reshape(self.nvar, self.nineq))
-        return np.concatenate(cols, axis=1)
+        Jg = self._ji(x) if self.nineq else None
+        if Jg is not None:
+            cols.append(Jg)
+        Jd = np.concatenate(cols, axis=1) if cols else np.zeros((self.nvar, 0))
+        return BoundedJacobian(Jd, self._bb) if self._bb is not None else Jd
 
     def _jaco(self, x):
         """(n+mi) x (me+mi) composite Jacobian [[Je, Ji],[0, -I]] (pyipm.py:582-607)."""
@@ -451,13 +586,13 @@ class IPM(BarrierLoop):
         if me:
             gx = gx - np.asarray(self.dce(x), dtype=np.float64).reshape(n, me) @ lda[:me]
         if mi:
-            gx = gx - np.asarray(self.dci(x), dtype=np.float64).reshape(n, mi) @ lda[me:]
+            gx = gx - self._ji_dot(x, lda[me:])
             out.append(lda[me:] - self.mu_host_dev / (s + self.eps))
         out[0] = gx
         if me:
             out.append(np.asarray(self.ce(x), dtype=np.float64).reshape(me))
         if mi:
-            out.append(np.asarray(self.ci(x), dtype=np.float64).reshape(mi) - s)
+            out.append(self._ci(x) - s)
         return np.concatenate(out)
 
     def KKT(self, x, s, lda):
@@ -476,7 +611,7 @@ class IPM(BarrierLoop):
         if self.neq:
             v += self.nu_host * np.sum(np.abs(self.ce(x)))
         if self.nineq:
-            v += self.nu_host * np.sum(np.abs(np.asarray(self.ci(x)).reshape(self.nineq) - s))
+            v += self.nu_host * np.sum(np.abs(self._ci(x) - s))
             v -= self.mu_host_dev * np.sum(np.log(s))
         return v
 
@@ -486,7 +621,7 @@ class IPM(BarrierLoop):
         if self.neq:
             v -= self.nu_host * np.sum(np.abs(self.ce(x)))
         if self.nineq:
-            v -= self.nu_host * np.sum(np.abs(np.asarray(self.ci(x)).reshape(self.nineq) - s))
+            v -= self.nu_host * np.sum(np.abs(self._ci(x) - s))
             v -= float(np.dot(self.mu_host_dev / (s + self.eps), dz[n:]))
         return v
 
@@ -522,6 +657,8 @@ class IPM(BarrierLoop):
         """Feasibility-restoration direction of the second-order correction (pyipm.py:1466-1477,
         1518-1529): a square solve when the Jacobian happens to be square, otherwise (the usual
         case) the minimum-norm least-squares solution."""
+        if self._bb is not None:
+            return self._restoration_bounded(x0, c_new)
         A = self._jaco(x0).T
         if A.shape[0] == A.shape[1]:
             try:
@@ -530,6 +667,23 @@ class IPM(BarrierLoop):
             except Exception:
                 pass
         return -np.linalg.lstsq(A, c_new, rcond=None)[0]
+
+    def _restoration_bounded(self, x0, c_new):
+        """The same minimum-norm solution of [J' | [0; -I]] d = c with the bound block eliminated by index: a bound's row
+        gives ds_b,j = sigma_j dx_k - c_b,j, so d minimises dx'D dx - 2 b'dx + |ds_g|^2 (D = I + bounds per variable,
+        b = E c_b) under the general rows alone -- order me + mg, O(n + mb) for the bounds."""
+        n, bb = self.nvar, self._bb
+        pg = self.neq + self.nineq - bb.mb
+        mg = self.nineq - bb.mb
+        cg, cb = c_new[:pg], c_new[pg:]
+        hinv = np.concatenate([1.0 / (1.0 + bb.count), np.ones(mg)])
+        h = np.concatenate([bb.dot(cb), np.zeros(mg)])
+        z = hinv * h
+        if pg:
+            A = np.concatenate([self._jac_x(x0).Jd, np.concatenate([np.zeros((mg, self.neq)), -np.eye(mg)], axis=1)], axis=0).T
+            nu = np.linalg.lstsq((A * hinv) @ A.T, cg - A @ z, rcond=None)[0]
+            z = z + hinv * (A.T @ nu)
+        return -np.concatenate([z, bb.tdot(z[:n]) - cb])
 
     def search(self, x0, s0, lda0, dz, alpha_smax, alpha_lmax, info=None):
         """Backtracking Armijo search on the merit function with an optional second-order
@@ -645,7 +799,7 @@ class IPM(BarrierLoop):
         same direction through inv(B) and, as written, cannot be compiled (duplicate input, :877-880)."""
         n, me, mi = self.nvar, self.neq, self.nineq
         Je = np.asarray(self.dce(x), dtype=np.float64).reshape(n, me) if me else None
-        Ji = np.asarray(self.dci(x), dtype=np.float64).reshape(n, mi) if mi else None
+        Ji = self._ji(x) if mi else None           # (the general columns alone: bounds are the handle's structure)
         reg = self.reg_coef * self.eta * (self.mu_host_dev ** self.beta)              # :1113
         return self.backend.lbfgs_direction(Je, Ji, s, lda, g, zeta, S, Y, SS, L, D, reg, self.eps)
 
@@ -707,7 +861,7 @@ class IPM(BarrierLoop):
         # initial point (pyipm.py:1597-1625)
         x = self.x0
         if mi:
-            s = (np.maximum(np.asarray(self.ci(x), dtype=np.float64).reshape(mi), self.Ktol)
+            s = (np.maximum(self._ci(x), self.Ktol)
                  if self.s0 is None else np.asarray(self.s0, dtype=np.float64))
             self._set_barrier(self.mu)
         else:

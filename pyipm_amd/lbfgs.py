@@ -7,7 +7,8 @@ No CPU fallback: without the library or a GPU the constructor raises.
 
 ``PairStore`` is the storage that feeds it: ``lbfgs_init`` / ``lbfgs_update`` (pyipm.py:993-1005, 1282-1371) behind the
 ``pyipm_pairs_*`` entry points, which ``include/pyipm_newton.h`` declares and ``pyipm_amd.newton`` binds, as they do the
-later additions to the direction's own handle (``pyipm_qn_*``, ``pyipm_lbfgs_stage_jacobian_columns``).
+later additions to the direction's own handle (``pyipm_qn_*``, ``pyipm_lbfgs_stage_jacobian_columns``,
+``pyipm_lbfgs_bounded_*``).
 """
 from __future__ import annotations
 
@@ -74,9 +75,16 @@ class LbfgsCore(object):
 
         core.stage_jacobian(Je, Ji)                               # dce(x), dci(x); once if the constraints are linear
         dz, st = core.direction(g, s, lda, zeta, S, Y, SS, L, D, reg=reg)     # RAW direction (flip=False), :1713
+
+    ``bounds=(var, sign)``: a bounded handle (``pyipm_lbfgs_bounded_*``).  ``mi`` then counts the general inequalities, the
+    columns of Ji, alone; bound j is ``sign[j] * x[var[j]] + const >= 0`` (+1 lower, -1 upper) and is never a column.  Every
+    vector of ``direction`` counts ``mi + len(var)`` inequalities, the bounds last.  The operator entries (``matvec``,
+    ``solve``, ``refine``, ``*_many``) and ``shard=True`` raise the library's refusal.
     """
 
-    def __init__(self, n, me, mi, max_pairs, device=None, nb=256, group=None, shard=False):
+    mb = 0                                       # simple bounds behind the mi general inequalities (a bounded handle)
+
+    def __init__(self, n, me, mi, max_pairs, device=None, nb=256, group=None, shard=False, bounds=None):
         """shard=True (or a process group): this handle holds ``n`` ROWS of a row-sharded problem; the three sums over
         the ranks (J'J, J'[g_x|W], W'[g_x|W]) go through ``torch.distributed.all_reduce`` on ``group`` — backend "nccl"
         (= RCCL) in place on the device buffers, "gloo" staged through the host (tests)."""
@@ -87,20 +95,33 @@ class LbfgsCore(object):
             raise NewtonError("no HIP device visible: the L-BFGS direction has no CPU fallback")
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
         self.n, self.me, self.mi, self.cap = int(n), int(me), int(mi), int(max_pairs)
-        self.N = self.n + 2 * self.mi + self.me
-        if self.lib.pyipm_lbfgs_workspace_bytes(self.n, self.me, self.mi, self.cap, int(nb)) == 0:
+        self.bounded = bounds is not None
+        self.mb = int(np.asarray(bounds[0]).shape[0]) if self.bounded else 0
+        self.mi_all = self.mi + self.mb                      # inequalities in the vectors of a direction
+        self.N = self.n + 2 * self.mi_all + self.me
+        if self.lib.pyipm_lbfgs_bounded_workspace_bytes(self.n, self.me, self.mi, self.mb, self.cap, int(nb)) == 0:
             raise NewtonError("invalid L-BFGS geometry n=%d me=%d mi=%d max_pairs=%d nb=%d" % (n, me, mi, max_pairs, nb))
         h = c_void_p()
         with torch.cuda.device(self.device):
-            rc = self.lib.pyipm_lbfgs_create(ctypes.byref(h), self.n, self.me, self.mi, self.cap, int(nb),
-                                             self.device.index,
-                                             c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+            stream = c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            if self.bounded:
+                rc = self.lib.pyipm_lbfgs_bounded_create(ctypes.byref(h), self.n, self.me, self.mi, self.mb, self.cap,
+                                                         int(nb), self.device.index, stream)
+            else:
+                rc = self.lib.pyipm_lbfgs_create(ctypes.byref(h), self.n, self.me, self.mi, self.cap, int(nb),
+                                                 self.device.index, stream)
         if rc:
             raise NewtonError("pyipm_lbfgs_create failed: %s" % ERRORS.get(rc, rc))
         self.h = h
         self.group, self.bytes_reduced, self._cb = group, 0, None
-        if shard or group is not None:
-            self._install_allreduce()
+        try:
+            if self.bounded:
+                self.stage_bounds(*bounds)
+            if shard or group is not None:
+                self._install_allreduce()
+        except Exception:
+            self.close()                                     # (a refusal here must not leave the handle to the finaliser)
+            raise
 
     def _install_allreduce(self):
         import torch.distributed as dist
@@ -173,6 +194,15 @@ class LbfgsCore(object):
         self._ck(self.lib.pyipm_lbfgs_stage_jacobian(self.h, self._ptr(Je), lde, self._ptr(Ji), ldi, MEM_DEVICE))
         self.torch.cuda.current_stream(self.device).synchronize()      # Je / Ji temporaries may die now
 
+    def stage_bounds(self, var, sign):
+        """The simple bounds of a bounded handle: ``var`` (integers in 0 .. n-1) and ``sign`` (+1 lower, -1 upper), as many
+        entries each as the handle was made for.  Host arrays; the library keeps a grouping by variable.  Again to change them."""
+        var = np.ascontiguousarray(np.asarray(var), dtype=np.int64).reshape(-1)
+        sign = np.ascontiguousarray(np.asarray(sign), dtype=np.float64).reshape(-1)
+        if not self.bounded or var.shape[0] != self.mb or sign.shape[0] != self.mb:
+            raise NewtonError("stage_bounds: the handle was made for %d bounds" % self.mb)
+        self._ck(self.lib.pyipm_lbfgs_bounded_stage(self.h, c_void_p(var.ctypes.data), c_void_p(sign.ctypes.data)))
+
     def stage_jacobian_columns(self, c0, Jc):
         """Jc (n, count), a NumPy array or a device tensor, replaces columns c0 .. c0 + count - 1 of [Je | Ji] (global column
         indices); the next direction recomputes only the 128 x 128 tiles of J'J those columns reach.  After a full
@@ -184,10 +214,10 @@ class LbfgsCore(object):
 
     def direction(self, g, s, lda, zeta, S, Y, SS, L, D, reg=0.0, eps=float(np.finfo(np.float64).eps), flip=False,
                   refine=0):
-        """Returns (dz device tensor of length n + 2 mi + me, stats dict).  ``refine`` != 0 (constrained problems): the
+        """Returns (dz device tensor of length n + 2 mi + me, with the bounds of a bounded handle counted in mi; stats dict).  ``refine`` != 0 (constrained problems): the
         direction is then refined against the quasi-Newton KKT operator (``refine``); ``refine_info()`` has the outcome."""
         dz, st = self._direction(g, s, lda, zeta, S, Y, SS, L, D, reg, eps, flip)
-        if refine and (self.me or self.mi):
+        if refine and (self.me or self.mi or self.mb):
             dz, _ = self.refine(dz, refine=refine, flip=flip)
         return dz, st
 
@@ -264,6 +294,7 @@ class LbfgsCore(object):
         n, me, mi, N = self.n, self.me, self.mi, self.N
         m = 0 if S is None else int(S.shape[1])
         g = self._dev(g, (N,))
+        mi += self.mb                                        # the bounds of a bounded handle count in s and lda
         s = self._dev(s, (mi,)) if mi else None
         lda = self._dev(lda, (me + mi,)) if (me + mi) else None
         Sd, lds = self._rows(S if m else None, (n, m))

@@ -172,6 +172,11 @@ def load_library(path: str | None = None):
         "pyipm_qn_refine": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int]),
         "pyipm_qn_info": (c_int, [c_void_p, POINTER(c_double)]),
         "pyipm_lbfgs_stage_jacobian_columns": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int]),
+        # simple bounds as structure (lbfgs_impl.hpp, kernels_lbbounds.hpp; LbfgsCore(bounds=...))
+        "pyipm_lbfgs_bounded_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int, c_int]),
+        "pyipm_lbfgs_bounded_create": (c_int, [POINTER(c_void_p), c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int,
+                                               c_void_p]),
+        "pyipm_lbfgs_bounded_stage": (c_int, [c_void_p, c_void_p, c_void_p]),
         # ... for k columns per call (qnmany_impl.hpp; LbfgsCore.matvec_many / solve_many)
         "pyipm_lbfgs_kkt_matvec_many": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int]),
         "pyipm_lbfgs_kkt_solve_many": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int]),

@@ -336,6 +336,84 @@ def columns_leg(a):
                       "gram_launches": core.last_timings()["gram_launches"], "legs": out}))
 
 
+def bounds_leg(a):
+    """A direction on a bounded handle (simple bounds eliminated in closed form, pyipm_lbfgs_bounded_*): a box on every variable,
+    mb = 2 n, beside the yardstick in the same process -- the plain handle's direction right after a full staging of the same J
+    without bounds -- and the bounds-only handle (me = mg = 0: no Gram launch at all) against the read floor of V."""
+    import torch
+    from pyipm_amd.lbfgs import LbfgsCore
+    n, me, mg, m = a.n, a.me, a.mi, a.m
+    p, mb = me + mg, 2 * a.n
+    mi = mg + mb
+    N = n + 2 * mi + me
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev); gen.manual_seed(0)
+    J = torch.randn((n, p), generator=gen, dtype=torch.float64, device=dev) / np.sqrt(n)
+    zeta, S, Y, SS, L, D = storage(n, m, 1, True)
+    rng = np.random.default_rng(2)
+    s = rng.uniform(0.5, 2.0, mi)
+    lda = np.concatenate([rng.standard_normal(me), rng.uniform(0.5, 2.0, mi)])
+    g = rng.standard_normal(N)
+    var = np.concatenate([np.arange(n), np.arange(n)])
+    sign = np.concatenate([np.ones(n), -np.ones(n)])
+    td = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev)          # noqa: E731
+    Sd, Yd = td(S), td(Y)
+    gen_rows = np.concatenate([np.arange(n + mg), n + mi + np.arange(me + mg)])                 # the rows without the bounds
+    only_rows = np.concatenate([np.arange(n), n + mg + np.arange(mb), n + mi + me + mg + np.arange(mb)])
+
+    def run(core, gv, sv, lv, restage):
+        gd, sd, ld = td(gv), td(sv), td(lv)
+        rec = []
+        for it in range(a.reps + 2):
+            if restage:
+                core.stage_jacobian(J[:, :me] if me else None, J[:, me:] if mg else None)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = core.direction(gd, sd, ld, zeta, Sd, Yd, SS, L, D, reg=1e-12)
+            torch.cuda.synchronize()
+            wall = (time.perf_counter() - t0) * 1e3
+            if it >= 2:
+                tm = core.last_timings(); tm["wall_ms"] = wall
+                rec.append(tm)
+        med = {k: float(np.median([r[k] for r in rec])) for k in rec[0]}
+        med["wall_ms_all"] = [r["wall_ms"] for r in rec]
+        return out[0], med
+
+    legs = {}
+    plain = LbfgsCore(n, me, mg, max(m, 1), device=0)
+    _, legs["plain_full_stage"] = run(plain, g[gen_rows], s[:mg], lda[:p], True)
+    plain.close()
+    bounded = LbfgsCore(n, me, mg, max(m, 1), device=0, bounds=(var, sign))
+    bounded.stage_jacobian(J[:, :me] if me else None, J[:, me:] if mg else None)
+    dz, legs["bounded"] = run(bounded, g, s, lda, False)
+    bounded.close()
+    # ---- checker: K dz = g with the bound columns applied by index, matrix-free
+    gd, sd, ld, vd, sgd = td(g), td(s), td(lda), td(var), td(sign)
+    x, ds, dl = dz[:n], dz[n:n + mi], dz[n + mi:]
+    W = torch.cat([zeta * Sd, Yd], dim=1)
+    Minv = td(np.block([[zeta * SS, L], [L.T, -D]]))
+    top = zeta * x - W @ torch.linalg.solve(Minv, W.T @ x) if m else zeta * x
+    top = top + J @ dl[:p]
+    top.index_add_(0, vd, sgd * dl[p:])
+    res = torch.empty_like(dz)
+    res[:n] = top
+    res[n:n + mi] = ld[me:] / (sd + np.finfo(float).eps) * ds - dl[me:]
+    low = torch.cat([J.T @ x, sgd * x[vd]])
+    low[me:] -= ds
+    res[n + mi:] = low
+    check = float((res - gd).norm() / gd.norm())
+    del J
+    only = LbfgsCore(n, 0, 0, max(m, 1), device=0, bounds=(var, sign))
+    _, legs["bounds_only"] = run(only, g[only_rows], s[mg:], lda[p:], False)
+    only.close()
+    p_pad = (p + 127) // 128 * 128
+    print(json.dumps({"workload": "L-BFGS direction with a box on every variable as structure, QP-shaped synthetic", "n": n, "me": me,
+                      "mg": mg, "mb": mb, "m": m, "dtype": "f64", "explicit_order_would_be": p + mb,
+                      "scale_pass_bytes": 2 * n * p_pad * 8, "v_bytes": n * (2 * m + 1) * 8, "hbm_peak_Bps": HBM_PEAK_BPS,
+                      "timing": "wall, device synchronised before and after, median of %d; gram_ms from the library's events" % a.reps,
+                      "residual_K_dz_minus_g_rel": check, "legs": legs}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=262144)
@@ -351,7 +429,11 @@ def main():
     ap.add_argument("--columns", action="store_true", help="time a direction after restaging 128, 512 and p/2 columns (stage_jacobian_columns)")
     ap.add_argument("--many", default="", metavar="K", help="time pyipm_lbfgs_kkt_matvec_many / _solve_many at k = K (a comma-separated "
                     "list: one handle, one process) against K calls of the single-column entries")
+    ap.add_argument("--bounds", action="store_true", help="time a direction with a box on every variable on a bounded handle "
+                    "(pyipm_lbfgs_bounded_*), the plain handle after a full staging beside it, and the bounds-only handle")
     a = ap.parse_args()
+    if a.bounds:
+        return bounds_leg(a)
     if a.many:
         return many_leg(a)
     if a.columns:
